@@ -4,7 +4,13 @@
 One "step" = one pass of the whole hot path over one batch of synthetic coded stills: CABAC parse -> dequantisation /
 inverse transforms -> intra reconstruction -> deblock -> SAO + crop -> fused YCbCr->RGB, all through the C ABI
 (include/heif_hipdec.h).  N=1 workload = BASELINE config 1 (3840x2160 4:2:0 8-bit stills, fused YCbCr->RGB24), `--batch`
-independent stills per step (throughput form).  Two timed regions are measured, W warm-up + K timed steps each:
+independent stills per step (throughput form).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) measures the headline only: it sets up, runs W warm-up and K timed steps of the
+from-host form below, writes the last step's outputs with `--dump-outputs DIR`, and prints the line.  Everything else described here
+runs with `--full`.  The synthetic inputs are cached on disk (tools/streamgen.py); build() codes those of a plain run.
+
+With `--full` two timed regions are measured, W warm-up + K timed steps each:
 
   value / ms_per_step   SURVEY.md 8(d)'s definition, "from compressed bytes in host memory to planes + RGB complete in HBM" (round 4: the
                         headline, as the round-3 review asked): every step pays hipdec_batch_create_recycling (host header parsing on
@@ -19,13 +25,13 @@ one 4K still; the 8K grid; Main10 4K with the PQ -> linear-RGB stage inside the 
 (`extra_workloads`), the drop-in form through the real libheif, and the CPU oracle on the host cores.
 
 With --gpus N (torch.distributed.run, one rank per GPU) every rank decodes its own batches (weak scaling, no data-path collective:
-independent stills exchange nothing), and the line carries `grid_sharded`: ONE 8K grid photo (BASELINE config 3) with its 48 tiles
+independent stills exchange nothing), and the `--full` line carries `grid_sharded`: ONE 8K grid photo (BASELINE config 3) with its 48 tiles
 sharded t mod N over the N GPUs, once through hipdec_grid_* (rank 0 drives all devices, strided peer-copy paste) and once through
 hipdec_grid_*_rccl (every rank decodes its tiles, grouped ncclSend / ncclRecv gather inside libheifhip.so), both checked against the
 one-GPU canvas, with the strong-scaling efficiency stated.  `--workload grid8k` makes that single photo the main measurement (strong
 scaling, as in rounds 1 - 2); `--workload grid8k_multi` gives every rank its own photos (weak).
 
-After the timed regions the run CHECKS results: planes and RGB24 of 32 stills spread over the batch are read back and compared with the
+After the timed regions a `--full` run CHECKS results: planes and RGB24 of 32 stills spread over the batch are read back and compared with the
 CPU oracle's decode of their streams (the cpu_baseline leg decodes them anyway); a mismatch fails the run.
 
 Prints ONE JSON line (rank 0).
@@ -51,11 +57,17 @@ KERNEL_NAMES = {"parse": "k_parse", "residual": "k_residual", "recon": "k_recon"
                 "sao_rgb": "k_sao_rgb"}
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="everything beside the headline as well: the resident form with per-kernel times and rooflines, "
+                    "config 5 over N GPUs, the batch curve, the single-still form, BASELINE's other configs and the extra workloads, sequence tracks, "
+                    "grid_sharded, the drop-in form, the CPU baseline and the check against the CPU oracle.  Without it a run sets up, warms up, "
+                    "times the headline's steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the headline's last step computed to "
+                    "DIR/<name>.npy (a fixed, seeded sample of the RGB outputs, float32 / float64)")
     ap.add_argument("--workload", default="still4k", choices=["still4k", "still1080", "main10_4k", "grid8k", "grid8k_multi"])
     ap.add_argument("--batch", type=int, default=0, help="independent stills per rank and step (0 = workload default)")
     ap.add_argument("--grid-single", action="store_true", help="(kept for old command lines: `--workload grid8k` IS the single-photo form again)")
@@ -74,7 +86,7 @@ def parse_args():
                     "holds every wave slot of the chip, the other kernels only start when it exits, and smaller batches parse less efficiently")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-procs", type=int, default=0, help="processes of the CPU baseline (0 = min(32, host cores))")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 GRID_VUI = dict(wpp=1, vui_primaries=1, vui_transfer=13, vui_matrix=6, vui_full_range=1)
@@ -96,7 +108,7 @@ def gen_streams(specs, rank=0, world=1):
     or starts RCCL.  With several ranks each one codes a share of the set and picks the rest up from the on-disk cache."""
     from tools import streamgen
     if world > 1:
-        streamgen.make_streams([sp for i, sp in enumerate(specs) if i % world == rank], workers=max(1, (os.cpu_count() or 2) // world))
+        streamgen.make_streams([sp for i, sp in enumerate(specs) if i % world == rank], workers=max(1, streamgen._usable_cpus() // world))
         deadline = time.time() + 900
         while True:
             missing = [sp for sp in specs if not os.path.exists(streamgen.stream_path(*sp))]
@@ -106,6 +118,60 @@ def gen_streams(specs, rank=0, world=1):
                 raise SystemExit("bench.py: synthetic streams of another rank did not appear")
             time.sleep(0.2)
     return streamgen.make_streams(specs)
+
+
+def main_specs(a):
+    """the synthetic inputs of the main measurement: (stream specs, items per rank and step)"""
+    w, h, def_batch, bit_depth, enc_cfg, _ = WORKLOADS[a.workload]
+    enc_cfg = dict(enc_cfg, qp=a.qp)
+    for kv in a.enc:
+        k, v = kv.split("=")
+        enc_cfg[k] = int(v)
+    if a.workload in ("grid8k", "grid8k_multi"):
+        return [(w, h, 2 + t, 8, enc_cfg) for t in range(48)], 48
+    nb = a.batch or def_batch
+    nd = max(1, min(a.distinct, nb))
+    return [(w, h, 1 + i, bit_depth, enc_cfg) for i in range(nd)], nb      # S2 / S4 / S5: seeds 1..nd (every rank cycles the same set, starting at its own offset)
+
+
+def prepare_inputs(argv=()):
+    """codes the main measurement's synthetic inputs into the on-disk cache (CPU only, no GPU): build() calls it, so that a benchmark run
+    does not spend its time in the test-only encoder"""
+    gen_streams(main_specs(parse_args(list(argv)))[0])
+
+
+def dump_outputs(path, images, n_items=16, n_pixels=1 << 18, seed=0):
+    """What the timed path delivered in its last step, as float arrays under `path`: a fixed, seeded sample of the output images (the same
+    items and pixel positions for the same arguments; < 64 MB) and the per-channel mean of every sampled image in full.
+    images: (count, read(i) -> interleaved rows (h, w * 3) of image i as uint8 / uint16)"""
+    import numpy as np
+    count, read = images
+    rng = np.random.default_rng(seed)
+    items = np.sort(rng.choice(count, size=min(n_items, count), replace=False))
+    samples, means, pixels = [], [], None
+    for i in items:
+        img = read(int(i))
+        img = img.reshape(img.shape[0], -1, 3)
+        if pixels is None:
+            pixels = np.sort(rng.integers(0, img.shape[0] * img.shape[1], size=min(n_pixels, img.shape[0] * img.shape[1])))
+        samples.append(img.reshape(-1, 3)[pixels].astype(np.float32))
+        means.append(img.sum(axis=0, dtype=np.uint64).sum(axis=0) / float(img.shape[0] * img.shape[1]))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rgb_sample.npy"), np.stack(samples))                    # [item][pixel][R, G, B]
+    np.save(os.path.join(path, "rgb_mean.npy"), np.stack(means))                        # [item][R, G, B] over the whole image
+    np.save(os.path.join(path, "sample_items.npy"), items.astype(np.float64))           # which images of the step
+    np.save(os.path.join(path, "sample_pixels.npy"), pixels.astype(np.float64))         # row-major pixel positions inside each image
+
+
+def rgb_rows(buf, stride, h, out_chroma):
+    """one image of interleaved output rows read back from device memory: uint8, or uint16 for the 16-bit-per-sample layouts"""
+    import numpy as np
+    a = buf.to_numpy((h, stride), np.uint8)
+    if out_chroma == 14:
+        return a.view("<u2")
+    if out_chroma == 12:
+        return a.view(">u2")
+    return a
 
 
 class Workload:
@@ -399,23 +465,13 @@ def main():
         libheif_amd.load_library()
         emit(json.dumps({"sequence_tracks": sequence_tracks()}))
         return
-    w, h, def_batch, bit_depth, enc_cfg, out_chroma = WORKLOADS[a.workload]
-    enc_cfg = dict(enc_cfg, qp=a.qp)
-    for kv in a.enc:
-        k, v = kv.split("=")
-        enc_cfg[k] = int(v)
+    w, h, _, bit_depth, _, out_chroma = WORKLOADS[a.workload]
     grid = a.workload in ("grid8k", "grid8k_multi")
     grid_single = a.workload == "grid8k"
-    extras_on = not (a.no_extras or a.only_main) and world == 1 and not grid
-    sharded_on = not (a.no_grid_sharded or a.only_main or grid)
-    if grid:
-        specs = [(w, h, 2 + t, 8, enc_cfg) for t in range(48)]
-        nb = 48
-    else:
-        nb = a.batch or def_batch
-        nd = max(1, min(a.distinct, nb))
-        specs = [(w, h, 1 + i, bit_depth, enc_cfg) for i in range(nd)]      # S2 / S4 / S5: seeds 1..nd (every rank cycles the same set,
-    distinct = gen_streams(specs, rank, world)                                 # starting at its own offset)
+    extras_on = a.full and not (a.no_extras or a.only_main) and world == 1 and not grid
+    sharded_on = a.full and not (a.no_grid_sharded or a.only_main or grid)
+    specs, nb = main_specs(a)
+    distinct = gen_streams(specs, rank, world)
     grid_specs = {}
     if sharded_on or extras_on:
         grid_specs["wpp"] = [(1024, 1024, 2 + t, 8, dict(GRID_VUI, qp=a.qp)) for t in range(48)]
@@ -437,7 +493,7 @@ def main():
         extra_streams = {k: gen_streams(v[1]) for k, v in extra_specs.items()}
     grid_streams = {k: gen_streams(v, rank, world) for k, v in grid_specs.items()}
     # BASELINE config 5 as written at N > 1: 1024 x 1080p stills interleaved over the GPUs (still i -> GPU i mod N; at N = 1 it is extra_workloads.c5_1080p_1024)
-    c5_on = (world > 1 or os.environ.get("HIPDEC_BENCH_C5")) and not (a.no_extras or a.only_main or grid) and a.workload == "still4k"   # (env: exercise the section on one GPU)
+    c5_on = a.full and (world > 1 or os.environ.get("HIPDEC_BENCH_C5")) and not (a.no_extras or a.only_main or grid) and a.workload == "still4k"   # (env: exercise the section on one GPU)
     c5_streams = gen_streams([(1920, 1080, 1000 + i, 8, dict(wpp=1, qp=a.qp)) for i in range(256)], rank, world) if c5_on else None
 
     dist = None
@@ -552,16 +608,28 @@ def main():
         n_items, px_rank, bs_bytes = wl.n, wl.px, wl.bs_bytes
         total_px = wl.px * world
         step = wl.step_resident
-    if batch is not None:
-        wl.timing_slots(max(1, a.steps))
-    elapsed = timed(step, a.steps, a.warmup, before_timed=(lambda: (wl.status() if a.warmup else None, wl.timing_slots(max(1, a.steps)))) if batch is not None else None)
-    if batch is not None:
-        wl.status()            # device-side decode errors are loud
-    elif gd is not None:
-        gd.wait()
-    ms_resident = elapsed / a.steps * 1e3
-    value_resident = total_px / (elapsed / a.steps) / 1e6
-    avg_us = kernel_times(wl.batches, a.steps) if not grid else None
+    # (the headline of a still workload is the from-host form further down: its plain run skips this region)
+    resident_on = grid or a.full or a.only_main
+    value_resident, ms_resident, avg_us = None, None, None
+    if resident_on:
+        if batch is not None:
+            wl.timing_slots(max(1, a.steps))
+        elapsed = timed(step, a.steps, a.warmup, before_timed=(lambda: (wl.status() if a.warmup else None, wl.timing_slots(max(1, a.steps)))) if batch is not None else None)
+        if batch is not None:
+            wl.status()            # device-side decode errors are loud
+        elif gd is not None:
+            gd.wait()
+        ms_resident = elapsed / a.steps * 1e3
+        value_resident = total_px / (elapsed / a.steps) / 1e6
+        avg_us = kernel_times(wl.batches, a.steps) if not grid else None
+        if a.dump_outputs and rank == 0 and (grid or a.only_main):      # the resident region is the headline: its last step's RGB
+            if grid:
+                if gd is not None:
+                    sync()
+                    dump_outputs(a.dump_outputs, (1, lambda i: rgb_out.cpu().numpy()))
+            else:
+                sync()
+                dump_outputs(a.dump_outputs, (n_items, lambda i: rgb_rows(*wl.batches[i % wl.parts]._rgb[i // wl.parts], out_chroma)))
 
     # config 5 over the job's GPUs: every rank decodes ITS stills (i mod N == rank) of the 1024 as one batch, no data-path collective; barrier + max over
     # ranks as the main measurement.  Total work is fixed: the line says "strong".  (A rank that cannot build its batch takes the others out of the
@@ -591,7 +659,7 @@ def main():
 
     # what the timed steps produced for stills spread over the batch (checked against the CPU oracle further down; outside every timed region)
     check_items = {}
-    verify_on = batch is not None and rank == 0 and not a.only_main and not a.no_cpu_baseline and a.parts == 1 and world == 1
+    verify_on = a.full and batch is not None and rank == 0 and not a.only_main and not a.no_cpu_baseline and a.parts == 1 and world == 1
     if verify_on:
         import hashlib
         nv = max(1, min(a.verify_stills, n_items))
@@ -610,8 +678,8 @@ def main():
         beta = bs_bytes / px_rank
         out = {
             "metric": "Mpixels/s HEIC 4:2:0 8-bit decode" if bit_depth == 8 else "Mpixels/s HEIC 4:2:0 %d-bit decode" % bit_depth,
-            "value": round(value_resident, 2), "unit": "Mpixel/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_resident, 3),
+            "value": round(value_resident, 2) if resident_on else None, "unit": "Mpixel/s",      # (a plain run of a still workload: the from-host form below)
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_resident, 3) if resident_on else None,
             "higher_is_better": True, "scaling": "strong" if grid_single and grid else "weak", "vs_baseline": None,
             "dtype": "u8" if bit_depth == 8 else "u16",
             "native_library": os.path.relpath(__import__("libheif_amd").library_path(), ROOT),   # (which build produced the numbers)
@@ -626,10 +694,11 @@ def main():
                        "stills_per_step_per_gpu": n_items, "distinct_contents": len(distinct), "bitstream_bytes_per_px": round(beta, 4),
                        "substreams_per_still": batch.info(0)["num_substreams"] if batch is not None else 16,
                        "parallelism": (("tiles sharded over %d GPUs, one process" % world) if grid_single else "independent photos, replicas x%d" % world) if grid else "replicas x%d" % world},
-            "value_resident": round(value_resident, 2),
-            "resident": {"value": round(value_resident, 2), "unit": "Mpixel/s", "ms_per_step": round(ms_resident, 3),
-                         "timed_region": "inputs resident in HBM when the timed region starts: hipdec_batch_run_rgb per step"},
         }
+        if resident_on:
+            out["value_resident"] = round(value_resident, 2)
+            out["resident"] = {"value": round(value_resident, 2), "unit": "Mpixel/s", "ms_per_step": round(ms_resident, 3),
+                               "timed_region": "inputs resident in HBM when the timed region starts: hipdec_batch_run_rgb per step"}
         if c5_line is not None:
             out["config5_interleaved"] = c5_line
         if avg_us is not None:
@@ -684,7 +753,8 @@ def main():
 
         for j, b0 in enumerate(wl.batches):
             rs = b0.rgb_state()
-            chains.append({"streams": wl.part_streams[j], "rgb": rs, "prev": b0, "next": create(wl.part_streams[j], b0, rs)})
+            # (b0 has run only where the resident region above was measured: a batch that never ran has no status to look at)
+            chains.append({"streams": wl.part_streams[j], "rgb": rs, "prev": b0, "prev_ran": resident_on, "next": create(wl.part_streams[j], b0, rs)})
         wl.batches = []
 
         def step_host():
@@ -692,18 +762,25 @@ def main():
                 cur = ch["next"]
                 cur.run_rgb()
                 ch["next"] = create(ch["streams"], cur, ch["rgb"])   # host work for the chain's next batch overlaps the kernels in flight
-                ch["prev"].status()             # (arena already handed on: the status word was copied back behind its kernels)
+                if ch["prev_ran"]:
+                    ch["prev"].status()         # (arena already handed on: the status word was copied back behind its kernels)
                 ch["prev"].free()
-                ch["prev"] = cur
+                ch["prev"], ch["prev_ran"] = cur, True
 
         def reset_counters():
             state["host_s"], state["creates"] = 0.0, 0
 
         el_h = timed(step_host, a.steps, a.warmup, before_timed=reset_counters)
         for ch in chains:
-            ch["prev"].status()
+            if ch["prev_ran"]:
+                ch["prev"].status()
             ch["prev"].free()
             ch["next"].free()
+        if a.dump_outputs and rank == 0:
+            # the last step's RGB rows are in the chains' output buffers (its planes went to the arena of the batch created behind it);
+            # still i of a step is item i // parts of part i % parts
+            check(lib.hipdec_stream_synchronize(None))
+            dump_outputs(a.dump_outputs, (n_items, lambda i: rgb_rows(*chains[i % len(chains)]["rgb"][0][i // len(chains)], out_chroma)))
         if rank == 0:
             v_h = total_px / (el_h / a.steps) / 1e6
             out["value"] = round(v_h, 2)                    # SURVEY 8(d)'s wall-clock definition is the headline
@@ -740,7 +817,7 @@ def main():
     # ------------------------------------------------------------------------------------------------------------------
     # single-still latency form (BASELINE config 2 as written), plugin life cycle
     # ------------------------------------------------------------------------------------------------------------------
-    if rank == 0 and not a.only_main and not grid:
+    if a.full and rank == 0 and not a.only_main and not grid:
         lib.hipdec_set_stage_overlap(0)
         first = distinct[0]
         single = Batch([first])
@@ -921,7 +998,7 @@ def main():
     # the drop-in form: T application threads x heif_decode_image() on distinct 4K HEIC files through the UNMODIFIED reference libheif
     # (oracle/_ref/libheif.so, the host application here, prebuilt) + the plugin, host to host (tools/dropin_throughput.py, C pthreads)
     # ------------------------------------------------------------------------------------------------------------------
-    if rank == 0 and not a.only_main and not a.no_dropin and not a.no_extras and world == 1 and not grid and a.workload == "still4k":
+    if a.full and rank == 0 and not a.only_main and not a.no_dropin and not a.no_extras and world == 1 and not grid and a.workload == "still4k":
         try:
             from tools import dropin_throughput
             # the thread counts the reference itself runs at (4 decoding threads per context, libheif/context.h:72; tests/test-race.go: 100) beside the
@@ -936,7 +1013,7 @@ def main():
         except Exception as e:   # the reference build is test infrastructure: its absence must not fail the bench
             out["dropin_through_libheif"] = {"error": repr(e)[:300]}
 
-    if rank == 0 and not a.no_cpu_baseline and not a.only_main and world == 1 and not grid:
+    if a.full and rank == 0 and not a.no_cpu_baseline and not a.only_main and world == 1 and not grid:
         contents = sorted(set(v["content"] for v in check_items.values())) or [0]
         out["cpu_baseline"] = cpu_baseline([rotated[c] for c in contents], w * h, a.cpu_seconds, a.cpu_procs, bit_depth)
         ref = dict(zip(contents, out["cpu_baseline"].pop("_hashes")))

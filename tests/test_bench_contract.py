@@ -1,5 +1,5 @@
 """The bench line contract (one JSON object with the driver's fields plus `roofline` and `cpu_baseline`), checked on the line
-bench.py printed on the MI355X at the end of the round (committed under profiles/ as r<NN>_final_bench.json)."""
+`bench.py --full` printed on the MI355X at the end of the round (committed under profiles/ as r<NN>_final_bench.json)."""
 import glob
 import json
 import os

@@ -190,7 +190,7 @@ def test_grid_rccl_entry_points_without_gpu_fail_loudly():
 def test_grid_rccl_world1_matches_oracle_and_the_one_process_form():
     """the GPU box has one GPU (RCCL refuses two ranks on one device), so this runs the whole SPMD path - communicator from
     hipdec_rccl_comm_create, the geometry all-reduce, decode, paste, colour stage - at world size 1; the N-rank sends / receives first run in
-    `bench.py --gpus N` (grid_sharded.rccl), which compares their canvas with this same one-GPU result"""
+    `bench.py --full --gpus N` (grid_sharded.rccl), which compares their canvas with this same one-GPU result"""
     import libheif_amd
     from libheif_amd.grid import GridDecoderC, GridDecoderRccl, GridLayout, RcclComm
     if not libheif_amd.load_library().hipdec_rccl_available():

@@ -19,7 +19,7 @@ def _psnr(a, b, hi):
     return 99.0 if m == 0 else 10 * np.log10(hi * hi / m)
 
 
-# ---- real fixtures of the reference (skipped where /root/reference is absent) -------------------
+# ---- real fixtures of the reference (stored under tests/golden/reference/) ----------------------
 def test_example_heic_decodes_with_exact_substream_termination(reference_dir):
     f = HeicFile(os.path.join(reference_dir, "examples", "example.heic"))
     items = f.hevc_items()

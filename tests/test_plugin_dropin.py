@@ -50,7 +50,7 @@ def test_decode_without_gpu_fails_loudly():
 
 
 @needs_ref
-def test_plugin_abi_matches_reference_headers(reference_dir):
+def test_plugin_abi_matches_reference_headers(reference_sources):
     """struct layouts restated in include/heif_plugin_abi.h against the real headers (compiled check)."""
     import os, subprocess, tempfile
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -80,7 +80,7 @@ int main() { return 0; }
         f = os.path.join(d, "abi.cc")
         open(f, "w").write(src)
         subprocess.check_call(["g++", "-std=c++20", "-fsyntax-only", "-I" + os.path.join(root, "include"),
-                               "-I" + os.path.join(root, "oracle", "_ref", "gen"), "-I" + os.path.join(reference_dir, "libheif", "api"), f])
+                               "-I" + os.path.join(root, "oracle", "_ref", "gen"), "-I" + os.path.join(reference_sources, "libheif", "api"), f])
 
 
 # ---------------------------------------------------------------------------------------------

@@ -127,7 +127,7 @@ def test_grid_rccl_path_with_three_ranks_over_a_toy_transport(tmp_path):
     """hipdec_grid_*_rccl, the one-process-per-GPU form, with THREE ranks: three processes, each with the emulated library on its own emulated
     device, and tests/emu/libfake_rccl.so (files in a directory) where librccl would be.  Every rank decodes its tiles t mod 3, the grouped send / receive
     gathers the packed tiles on rank 0, which pastes and converts; a damaged tile on rank 1 makes EVERY rank's wait fail; the communicator survives.  The
-    RCCL transport itself is not exercised (world size 1 on the GPU box, N ranks first in `bench.py --gpus N`)."""
+    RCCL transport itself is not exercised (world size 1 on the GPU box, N ranks first in `bench.py --full --gpus N`)."""
     from test_parse_emu import build_emu
     _build()
     build_emu("libfake_rccl.so")
