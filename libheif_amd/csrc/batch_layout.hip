@@ -323,7 +323,7 @@ int layout_core(BatchLayout& b, const size_t* sizes, std::string& err_out)
   // control words (zeroed before every run)
   b.off_ctrl = off;
   b.off_progress = off; off = align_up(off + sizeof(uint32_t) * nsubs, 256);
-  b.off_row_progress = off; off = align_up(off + sizeof(uint32_t) * nrows * 3, 256);   // per (CTB row, component)
+  b.off_row_progress = off; off = align_up(off + sizeof(uint32_t) * nrows * ROW_PROGRESS_SLOTS, 256);   // per (CTB row, slot: component or motion)
   b.off_waitneed = off; off = align_up(off + sizeof(uint32_t) * nsubs, 256);
   b.off_resume_k = off; off = align_up(off + sizeof(uint32_t) * nsubs, 256);
   b.queue_cap = 1; while (b.queue_cap < nsubs) b.queue_cap <<= 1;

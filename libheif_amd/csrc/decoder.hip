@@ -238,7 +238,6 @@ int launch_all(hipdec_batch& b, hipStream_t s, const void* fused_rgb_params = nu
   pa.general_chroma = 0;
   for (const PicParams& P : b.params) if (P.chroma_format_idc >= 2) pa.general_chroma = 1;
   pa.inter = b.any_inter ? 1 : 0;
-  if (pa.inter && pa.general_chroma) return set_error(HIPDEC_ERR_UNSUPPORTED, "a batch that mixes P pictures with 4:2:2 / 4:4:4 pictures");
   pa.pool = b.pool; pa.queue_cap = b.queue_cap; pa.num_subs = b.num_subs;
   pa.waitneed = (uint32_t*)(b.arena + b.off_waitneed); pa.resume_k = (uint32_t*)(b.arena + b.off_resume_k);
   pa.queue = (uint32_t*)(b.arena + b.off_queue); pa.qctl = (uint32_t*)(b.arena + b.off_qctl); pa.saved = (uint32_t*)(b.arena + b.off_saved);

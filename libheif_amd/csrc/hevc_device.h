@@ -75,6 +75,10 @@ static_assert(sizeof(SliceParams) == 64, "SliceParams layout");
 struct WeightTable { int16_t w[2][16][3]; int16_t o[2][16][3]; };   // o: before the << (BitDepth - 8)
 static_assert(sizeof(WeightTable) == 384, "WeightTable layout");
 
+// Words of the batch's row_progress array per CTB row: slot 0 the luma reconstruction wave, 1 the chroma one (the 4:2:0 / 4:2:2 pair; 4:4:4: Cb), 2 the
+// Cr wave of a 4:4:4 picture, 3 the motion wavefront of a P / B picture (k_motion) - a 4:4:4 P picture uses all four
+constexpr int ROW_PROGRESS_SLOTS = 4, ROW_PROGRESS_MOTION = 3;
+
 // a reference picture of a P / B picture: absolute device pointers (the planes live in an EARLIER batch's arena: decoded, deblocked, SAO applied,
 // coded size), strides in bytes; mf: that picture's motion field (MotionUnit per 4x4 unit, CTB-major z-order like the current picture's; 0 if it
 // was an intra picture), read by the temporal candidates

@@ -644,7 +644,6 @@ int parse_picture(const uint8_t* blob, size_t size, uint64_t max_pixels, ParsedP
         if (S.sao) { sl.sp.sao_luma = r.u(1); if (S.chroma_format_idc) sl.sp.sao_chroma = r.u(1); }
         if (slice_type != 2) {   // 7.3.6.1, P / B slice
           const bool is_b = slice_type == 0;
-          if (S.chroma_format_idc > 1) unsupported("P / B slices of a 4:2:2 / 4:4:4 picture");
           int num_ref[2] = {P.num_ref_idx_l0_default, is_b ? P.num_ref_idx_l1_default : 0};
           if (r.u(1)) {   // num_ref_idx_active_override_flag
             num_ref[0] = r.ue_max(14, "num_ref_idx_l0_active_minus1") + 1;

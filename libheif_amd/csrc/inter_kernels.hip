@@ -5,7 +5,8 @@
 // availability), 8.5.3.2.2 - 8.5.3.2.5 (merge mode: spatial, temporal, combined bi-predictive and zero candidates), 8.5.3.2.6 - 8.5.3.2.9 (motion
 // vector prediction: spatial candidates with scaling, the collocated candidate), 8.5.3.3.3 (fractional sample interpolation), 8.5.3.3.4.2 /
 // 8.5.3.3.4.3 (default and explicit weighted sample prediction, one or two lists).
-// Scope as the host front end enforces it: P and B slices, short-term and long-term reference pictures, 4:0:0 / 4:2:0.
+// Scope as the host front end enforces it: P and B slices, short-term and long-term reference pictures, 4:0:0 / 4:2:0 / 4:2:2 / 4:4:4 (8.5.3.2.10:
+// the chroma vector is mvLX * 2 / SubWidthC, / SubHeightC; chroma prediction blocks are nPbW / SubWidthC x nPbH / SubHeightC).
 //
 // MI355X mapping
 //   * the entropy decoder (parse_core.h, HIPDEC_PARSE_INTER build) only PARSES prediction units into MotionSyntax records: HEVC keeps parsing free
@@ -400,8 +401,8 @@ __global__ __launch_bounds__(64) void k_motion(MotionArgs A)
   const PicParams& P = A.pics[rd.pic];
   if (!P.is_inter) return;
   const int cy = (int)rd.row, ctb_w = P.ctb_w, log2_ctb = P.log2_ctb, units_log2 = P.units_per_ctb_log2, units = 1 << units_log2;
-  uint32_t* my_progress = A.row_progress + (size_t)(P.first_row + rd.row) * 3 + 2;   // slot 2 of the row: the reconstruction waves of a 4:2:0 picture use 0 and 1
-  const uint32_t* up_progress = my_progress - 3;
+  uint32_t* my_progress = A.row_progress + (size_t)(P.first_row + rd.row) * ROW_PROGRESS_SLOTS + ROW_PROGRESS_MOTION;   // (the reconstruction waves use 0 .. 2)
+  const uint32_t* up_progress = my_progress - ROW_PROGRESS_SLOTS;
   MotionUnit* field = (MotionUnit*)(A.arena + P.off_mf);
   const MotionSyntax* msyn_base = (const MotionSyntax*)(A.arena + P.off_msyn);
   const uint8_t* u_size = A.arena + P.off_u_size;
@@ -462,7 +463,7 @@ __global__ __launch_bounds__(64) void k_motion(MotionArgs A)
       // cy must be past CTB cx + 1.  Pictures of a chain thus follow each other at a 2-CTB distance instead of one launch per picture.
       const uint32_t col_row = C.reftab[C.slice->col_slot].progress_row;
       if (col_row) {
-        const uint32_t* col_progress = A.row_progress + (size_t)(col_row - 1 + (uint32_t)cy) * 3 + 2;
+        const uint32_t* col_progress = A.row_progress + (size_t)(col_row - 1 + (uint32_t)cy) * ROW_PROGRESS_SLOTS + ROW_PROGRESS_MOTION;
         uint32_t need = (uint32_t)(cx + 2);
         if (need > (uint32_t)ctb_w) need = (uint32_t)ctb_w;
         uint32_t spins = 0;
@@ -654,8 +655,10 @@ __global__ __launch_bounds__(256) void k_mc(FilterArgs A, int add_residual)
   const int W = plane ? P.cwidth : P.width, H = plane ? P.cheight : P.height;
   const int x = (int)(blockIdx.x * 16 + (threadIdx.x & 15)), y = (int)(blockIdx.y * 16 + (threadIdx.x >> 4));
   if (x >= W || y >= H) return;
-  const int sub = plane ? 1 : 0;                       // log2 subsampling (4:2:0 only)
-  const int xl = x << sub, yl = y << sub;              // the luma sample that decides which prediction unit the sample belongs to
+  // log2 SubWidthC / SubHeightC of this plane (6.2): 4:2:0 both, 4:2:2 horizontally only, 4:4:4 none (uniform per picture: the branches do not diverge)
+  const int cfi = P.chroma_format_idc;
+  const int sub_x = (plane && cfi != 3) ? 1 : 0, sub_y = (plane && cfi == 1) ? 1 : 0;
+  const int xl = x << sub_x, yl = y << sub_y;          // the luma sample that decides which prediction unit the sample belongs to
   const int log2_ctb = P.log2_ctb;
   const int cx = xl >> log2_ctb, cy = yl >> log2_ctb, m = (1 << (log2_ctb - 2)) - 1;
   const uint32_t z = mk_interleave((uint32_t)((xl >> 2) & m), (uint32_t)((yl >> 2) & m));
@@ -663,12 +666,14 @@ __global__ __launch_bounds__(256) void k_mc(FilterArgs A, int add_residual)
   if (mu.ref_idx[0] < 0 && mu.ref_idx[1] < 0) return;   // intra coded: k_recon predicts it
   const RefFrame* reftab = (const RefFrame*)(A.arena + P.off_reftab);
   const int bit_depth = plane ? P.bit_depth_chroma : P.bit_depth_luma;
+  // the vector in the plane's fractional units (luma: 1/4 sample; chroma: 1/8 sample, mvLX * 2 / SubWidthC and / SubHeightC, 8.5.3.2.10)
+  const int mvs_x = plane ? 2 >> sub_x : 1, mvs_y = plane ? 2 >> sub_y : 1;
   int pred[2] = {0, 0};
   for (int X = 0; X < 2; X++) {
     if (mu.ref_idx[X] < 0) continue;
     const RefFrame rf = reftab[mu.slot_pred[X] & 63u];
     pred[X] = mc_sample<Pix>((HIPDEC_GLOBAL const Pix*)(uintptr_t)rf.plane[plane],   // (an integer turned pointer is generic - FLAT loads - unless typed as global memory)
-                             rf.stride[plane] / sizeof(Pix), W, H, plane, bit_depth, x, y, mu.mv[X][0], mu.mv[X][1]);
+                             rf.stride[plane] / sizeof(Pix), W, H, plane, bit_depth, x, y, mu.mv[X][0] * mvs_x, mu.mv[X][1] * mvs_y);
   }
   const int bi = mu.ref_idx[0] >= 0 && mu.ref_idx[1] >= 0, one = mu.ref_idx[0] >= 0 ? 0 : 1;
   const int shift1 = 14 - bit_depth, maxv = (1 << bit_depth) - 1;   // (bit depth <= 12)
@@ -691,8 +696,10 @@ __global__ __launch_bounds__(256) void k_mc(FilterArgs A, int add_residual)
   v = mk_clip3(0, maxv, v);
   if (add_residual) {
     // the transform block that covers the sample: its size sits in the low nibble of the unit's size byte, its flags and its residual at its first unit
-    // (z order; the residual arrays hold a CTB's blocks one behind the other, each block in raster order: residual_kernel.hip).  4:2:0 chroma: a block of
-    // half the luma size - the 4x4 block of four 4x4 luma blocks hangs off the quad's 4th unit and sits at the quad's origin
+    // (z order; the residual arrays hold a CTB's blocks one behind the other, each block in raster order: residual_kernel.hip).  Chroma, in the layout
+    // of parse_core.h and k_residual: 4:4:4 a block of the luma block's size and place; 4:2:0 a block of half the luma size; 4:2:2 two such blocks one
+    // above the other, the lower one's coefficients behind the upper one's and its flags in unit z0 ^ 1.  The chroma of four 4x4 luma blocks (4:2:0,
+    // 4:2:2) hangs off the quad's 4th unit (4:2:2: the lower block's flags off its 3rd) and sits at the quad's origin
     const size_t ctb_rs = (size_t)(cy * P.ctb_w + cx), base = ctb_rs << P.units_per_ctb_log2;
     const uint8_t* u_size = A.arena + P.off_u_size + base;
     const uint8_t* u_flags = A.arena + P.off_u_flags + base;
@@ -705,14 +712,19 @@ __global__ __launch_bounds__(256) void k_mc(FilterArgs A, int add_residual)
       if (!plane) {
         if (u_flags[z0] & UF_CBF_LUMA) res = ((const int16_t*)(A.arena + P.off_coeff[0]))[ctb_rs * (size_t)ctb2 + z0 * 16u + (uint32_t)(((y & ((1 << tb) - 1)) << tb) + (x & ((1 << tb) - 1)))];
       } else {
-        const int16_t* coeff = (const int16_t*)(A.arena + P.off_coeff[plane]) + ctb_rs * (size_t)(ctb2 >> 2);
+        const int cc_shift = sub_x + sub_y, c_mult = 16 >> cc_shift;   // chroma samples per 4x4 luma unit
+        const int16_t* coeff = (const int16_t*)(A.arena + P.off_coeff[plane]) + ctb_rs * (size_t)(ctb2 >> cc_shift);
         const int bit = plane == 1 ? UF_CBF_CB : UF_CBF_CR;
-        if (tb > 2) {
-          const int lgc = tb - 1;
-          if (u_flags[z0] & bit) res = coeff[z0 * 4u + (uint32_t)(((y & ((1 << lgc) - 1)) << lgc) + (x & ((1 << lgc) - 1)))];
+        if (tb > 2 || !sub_x) {
+          const int lgc = tb - sub_x;                          // chroma block size (log2)
+          const int yt = y & ((1 << (tb - sub_y)) - 1);        // row inside the transform block's chroma area (4:2:2: two blocks tall)
+          const int low = yt >> lgc;                           // 4:2:2: the lower block (0 for the other formats)
+          if (u_flags[z0 ^ (uint32_t)low] & bit)
+            res = coeff[z0 * (uint32_t)c_mult + (uint32_t)(low << (2 * lgc)) + (uint32_t)(((yt & ((1 << lgc) - 1)) << lgc) + (x & ((1 << lgc) - 1)))];
         } else {
           const uint32_t zc = z & ~3u;
-          if (u_flags[zc | 3u] & bit) res = coeff[zc * 4u + (uint32_t)(((y & 3) << 2) + (x & 3))];
+          const int yt = y & ((8 >> sub_y) - 1), low = yt >> 2;   // 4:2:2: a 4x8 chroma area, two 4x4 blocks
+          if (u_flags[(zc | 3u) ^ (uint32_t)low] & bit) res = coeff[zc * (uint32_t)c_mult + (uint32_t)(low << 4) + (uint32_t)(((yt & 3) << 2) + (x & 3))];
         }
       }
       v = mk_clip3(0, maxv, v + res);

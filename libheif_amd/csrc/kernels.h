@@ -13,7 +13,7 @@ struct ReconArgs {
   const ReconWave* waves;
   uint32_t num_waves;
   uint8_t* arena;
-  uint32_t* row_progress;  // per (batch row, component): CTBs completed
+  uint32_t* row_progress;  // per (batch row, slot): CTBs completed (ROW_PROGRESS_SLOTS, hevc_device.h)
   uint32_t* ticket;
   int32_t* status;
   uint32_t inter_from_plane = 0;   // P / B pictures: k_mc has added the residuals of the inter coded units to its prediction (launch_mc(..., add_residual)): the rec
@@ -32,14 +32,15 @@ struct MotionArgs {
   const RowDesc* rows;
   uint32_t num_rows;
   uint8_t* arena;
-  uint32_t* row_progress;  // per (batch row, slot): slot 2 is the motion wavefront's
+  uint32_t* row_progress;  // per (batch row, slot): slot ROW_PROGRESS_MOTION is the motion wavefront's
   uint32_t* ticket;
   int32_t* status;
 };
 
 void launch_parse(const ParseArgs& a, hipStream_t s);
 void launch_parse_throughput(const ParseArgs& a, hipStream_t s);   // parse_kernel_tp.hip: k_parse_occ8, LDS-resident contexts (4:0:0 / 4:2:0 intra batches)
-void launch_parse_inter(const ParseArgs& a, hipStream_t s);   // parse_kernel_inter.hip: batches with P pictures (sequence tracks)
+void launch_parse_inter(const ParseArgs& a, hipStream_t s);   // parse_kernel_inter.hip: batches with P pictures (sequence tracks), 4:0:0 / 4:2:0 only
+void launch_parse_inter_general(const ParseArgs& a, hipStream_t s);   // parse_kernel_inter_general.hip: batches with P pictures and 4:2:2 / 4:4:4 pictures
 void launch_motion(const MotionArgs& a, hipStream_t s);       // P pictures: MotionSyntax -> motion field (merge / AMVP derivation)
 // motion-compensated prediction into the rec planes; add_residual: plus the residual of every inter coded sample (then k_recon runs with inter_from_plane)
 void launch_mc(const FilterArgs& a, int n_pics, int max_w, int max_h, bool wide, hipStream_t s, bool add_residual = false);

@@ -1059,10 +1059,13 @@ PC_DEV void inter_coding_unit(PS& s, int zb, int log2cb, int cu_skip, int16_t* c
     fill_tu_maps(s, zb, n_units, bypass, 1u, (uint32_t)((log2cb << 4) | (log2cb > 5 ? 5 : log2cb)));
   } else {
     // ---- transform tree of an inter coding unit (7.3.8.8): no IntraSplitFlag, interSplitFlag (7.4.9.8), cbf_luma inferred 1 at a root leaf
-    //      without chroma coefficients; chroma 4:2:0 / 4:0:0 only (the host refuses P slices of other formats)
+    //      without chroma coefficients.  ChromaArrayType 2 / 3 as in the intra tree below: chroma flags at 4x4 nodes too and chroma blocks of luma
+    //      size (4:4:4), a second flag and block for the lower chroma block (4:2:2); in a build without them (HIPDEC_PARSE_CHROMA_GENERAL 0) c444 and
+    //      c422 are constant 0 and the tree compiles to the 4:0:0 / 4:2:0 one, instruction for instruction
+    const int c444 = pc_is444(s), c422 = pc_is422(s);
     const int max_trafo_depth = s.max_th_depth_inter;
     const int inter_split = s.max_th_depth_inter == 0 && part_mode != PM_2Nx2N;
-    uint32_t cbf_cb_bits = 0, cbf_cr_bits = 0;
+    uint32_t cbf_cb_bits = 0, cbf_cr_bits = 0;   // bit d = cbf at trafoDepth d along the current path; 4:2:2: bit 8 + d = the flag of the lower chroma block
     int qn = 0;
     while (qn < n_units && !s.err) {
       int t;
@@ -1074,15 +1077,20 @@ PC_DEV void inter_coding_unit(PS& s, int zb, int log2cb, int cu_skip, int16_t* c
         else split = (t > s.log2_max_tb || (inter_split && depth == 0)) ? 1 : 0;
         if (s.chroma_format_idc) {
           const uint32_t bit = 1u << depth, pbit = depth ? (1u << (depth - 1)) : 0;
-          if (t > 2) {
-            int cb = 0, cr = 0;
-            if (depth == 0 || (cbf_cb_bits & pbit)) cb = decode_bin(s, s.ctxA, A_CBF_CHROMA + depth);
-            if (depth == 0 || (cbf_cr_bits & pbit)) cr = decode_bin(s, s.ctxA, A_CBF_CHROMA + depth);
-            cbf_cb_bits = (cbf_cb_bits & ~bit) | (cb ? bit : 0);
-            cbf_cr_bits = (cbf_cr_bits & ~bit) | (cr ? bit : 0);
-          } else {
-            cbf_cb_bits = (cbf_cb_bits & ~bit) | ((cbf_cb_bits & pbit) << 1);
-            cbf_cr_bits = (cbf_cr_bits & ~bit) | ((cbf_cr_bits & pbit) << 1);
+          const uint32_t both = c422 ? bit * 0x101u : bit, pboth = c422 ? pbit * 0x101u : pbit;   // 4:2:2: the upper and the lower block's flag
+          if (t > 2 || c444) {
+            int cb = 0, cr = 0, cb2 = 0, cr2 = 0;
+            // (the context index is written out at every call: a variable for it schedules k_parse_inter's 4:2:0 code differently)
+#define PC_CBF_CHROMA_CTX ((c444 && depth == 4) ? A_CBF_CHROMA4 : A_CBF_CHROMA + depth)   // depth 4 only occurs with ChromaArrayType 3
+            const int two = c422 && (!split || t == 3);   // 4:2:2: where the chroma is coded (a leaf, or the 8x8 node above four 4x4 leaves)
+            if (depth == 0 || (cbf_cb_bits & pbit)) { cb = decode_bin(s, s.ctxA, PC_CBF_CHROMA_CTX); if (two) cb2 = decode_bin(s, s.ctxA, PC_CBF_CHROMA_CTX); }
+            if (depth == 0 || (cbf_cr_bits & pbit)) { cr = decode_bin(s, s.ctxA, PC_CBF_CHROMA_CTX); if (two) cr2 = decode_bin(s, s.ctxA, PC_CBF_CHROMA_CTX); }
+#undef PC_CBF_CHROMA_CTX
+            cbf_cb_bits = (cbf_cb_bits & ~both) | (cb ? bit : 0) | (cb2 ? bit << 8 : 0);
+            cbf_cr_bits = (cbf_cr_bits & ~both) | (cr ? bit : 0) | (cr2 ? bit << 8 : 0);
+          } else {   // 4x4 luma: inherits the parent's flags (7.4.9.8)
+            cbf_cb_bits = (cbf_cb_bits & ~both) | ((cbf_cb_bits & pboth) << 1);
+            cbf_cr_bits = (cbf_cr_bits & ~both) | ((cbf_cr_bits & pboth) << 1);
           }
         }
         if (!split) break;
@@ -1092,28 +1100,43 @@ PC_DEV void inter_coding_unit(PS& s, int zb, int log2cb, int cu_skip, int16_t* c
       const int zu = zb + qn;
       const int tu_units = 1 << (2 * (t - 2));
       const int cbf_cb = (int)((cbf_cb_bits >> depth) & 1u), cbf_cr = (int)((cbf_cr_bits >> depth) & 1u);
+      const int cbf_cb2 = c422 ? (int)((cbf_cb_bits >> (8 + depth)) & 1u) : 0, cbf_cr2 = c422 ? (int)((cbf_cr_bits >> (8 + depth)) & 1u) : 0;
       int cbf_luma = 1;
-      if (depth != 0 || cbf_cb || cbf_cr) cbf_luma = decode_bin(s, s.ctxA, A_CBF_LUMA + (depth == 0 ? 1 : 0));
-      if ((cbf_luma | cbf_cb | cbf_cr) && (s.tools & TOOL_CUQPD) && !s.is_cu_qp_delta_coded) parse_cu_qp_delta(s);
+      if (depth != 0 || cbf_cb || cbf_cr || cbf_cb2 || cbf_cr2) cbf_luma = decode_bin(s, s.ctxA, A_CBF_LUMA + (depth == 0 ? 1 : 0));
+      if ((cbf_luma | cbf_cb | cbf_cr | cbf_cb2 | cbf_cr2) && (s.tools & TOOL_CUQPD) && !s.is_cu_qp_delta_coded) parse_cu_qp_delta(s);
       int do_chroma = 0, zc = zu, tc = t - 1;
-      if (s.chroma_format_idc) {
+      if (c444) { do_chroma = 1; tc = t; }   // chroma blocks coincide with the luma blocks
+      else if (s.chroma_format_idc) {
         if (t > 2) do_chroma = 1;
         else if ((qn & 3) == 3) { do_chroma = 1; zc = zb + (qn & ~3); tc = 2; }
       }
+      // luma, Cb, Cr - 4:2:2: luma, Cb upper, Cb lower, Cr upper, Cr lower (k = 3 / 4 are the lower blocks; their coefficients follow the upper
+      // block's) - into the layout of the intra tree, which k_residual and k_mc read
       uint32_t ts_bits = 0;
-      const uint32_t coded_bits = (uint32_t)cbf_luma | (do_chroma ? (uint32_t)(cbf_cb << 1) | (uint32_t)(cbf_cr << 2) : 0u);
+      const uint32_t coded_bits = (uint32_t)cbf_luma | (do_chroma ? (uint32_t)(cbf_cb << 1) | (uint32_t)(cbf_cr << 2) | (uint32_t)(cbf_cb2 << 3) | (uint32_t)(cbf_cr2 << 4) : 0u);
+      const int c_mult = c444 ? 16 : (c422 ? 8 : 4);    // chroma samples per 4x4 luma unit
 #pragma clang loop unroll(disable)
-      for (int k = 0; k < 3; k++) {
+      for (int k0 = 0; k0 < (c422 ? 5 : 3); k0++) {
+        const int k = c422 ? (k0 == 0 ? 0 : (k0 == 1 ? 1 : (k0 == 2 ? 3 : (k0 == 3 ? 2 : 4)))) : k0;   // coding order: both Cb blocks before the Cr blocks
         if (!((coded_bits >> k) & 1u)) continue;
-        const int lg = k == 0 ? t : tc;
-        int16_t* dst = k == 0 ? coef_y + zu * 16 : (k == 1 ? coef_cb : coef_cr) + zc * 4;
-        ts_bits |= (uint32_t)residual_coding(s, lg, k, 1 /* not intra: the up-right diagonal scan */) << k;
+        const int c = c422 ? (k == 0 ? 0 : 1 + ((k - 1) & 1)) : k, low = c422 && k >= 3;
+        const int lg = c == 0 ? t : tc;
+        int16_t* dst = c == 0 ? coef_y + zu * 16 : (c == 1 ? coef_cb : coef_cr) + zc * c_mult + (low << (2 * lg));
+        ts_bits |= (uint32_t)residual_coding(s, lg, c, 1 /* not intra: the up-right diagonal scan */) << k;
         flush_coef(s, dst, 1 << (2 * lg));
       }
       fill_tu_maps(s, zu, tu_units,
                    (uint32_t)((cbf_luma ? UF_CBF_LUMA : 0) | ((do_chroma && cbf_cb) ? UF_CBF_CB : 0) | ((do_chroma && cbf_cr) ? UF_CBF_CR : 0) | bypass |
                               ((ts_bits & 1u) ? UF_TS_LUMA : 0)),
                    (uint32_t)(1u | ((ts_bits & 2u) ? 64u : 0u) | ((ts_bits & 4u) ? 128u : 0u)), (uint32_t)((log2cb << 4) | t));
+      if (c422 && do_chroma) {
+        // 4:2:2: the lower chroma blocks' cbf and transform-skip bits go to unit index ^ 1, as in the intra tree
+        const int z2 = zu ^ 1;
+        const uint32_t f2 = (map_get(s.m_flags, z2) & ~(uint32_t)(UF_CBF_CB | UF_CBF_CR)) | (cbf_cb2 ? UF_CBF_CB : 0u) | (cbf_cr2 ? UF_CBF_CR : 0u);
+        const uint32_t m2 = (map_get(s.m_ipm, z2) & 63u) | (((ts_bits >> 3) & 1u) ? 64u : 0u) | (((ts_bits >> 4) & 1u) ? 128u : 0u);
+        map_fill(s.m_flags, z2, 1, f2);
+        map_fill(s.m_ipm, z2, 1, m2);
+      }
       qn += tu_units;
     }
   }

@@ -2,7 +2,8 @@
 // parse_core.h as parse_kernel.hip, compiled WITH the syntax a P slice adds (cu_skip_flag, pred_mode_flag, inter part_mode, prediction_unit,
 // mvd_coding, rqt_root_cbf, the inter transform tree; contexts of initType 1 / 2).  The throughput kernels of parse_kernel.hip are built without it:
 // the scalar pipe bounds the parser and stills never take these branches.  launch_parse() sends a batch here when the host found a P slice in it
-// (ParseArgs::inter).  4:0:0 / 4:2:0 only (the host refuses P slices of other chroma formats), one register budget (sequences are a latency path).
+// (ParseArgs::inter).  4:0:0 / 4:2:0 only: a batch that also holds 4:2:2 / 4:4:4 pictures goes to parse_kernel_inter_general.hip.  One register
+// budget (sequences are a latency path).
 #include <hip/hip_runtime.h>
 #include "hevc_device.h"
 #include "kernels.h"

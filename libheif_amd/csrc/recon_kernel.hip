@@ -727,8 +727,8 @@ __device__ __forceinline__ void recon_rows(const ReconArgs& A, const ReconWave& 
 
   for (int cy = (int)wd.first_row; cy < ctb_h && !err; cy += (int)wd.stride) {
   my_row = wd.base_row + (uint32_t)cy;     // batch row index
-  uint32_t* my_progress = A.row_progress + (size_t)my_row * 3 + c_idx;
-  const uint32_t* up_progress = my_progress - 3;
+  uint32_t* my_progress = A.row_progress + (size_t)my_row * ROW_PROGRESS_SLOTS + c_idx;
+  const uint32_t* up_progress = my_progress - ROW_PROGRESS_SLOTS;
   for (int cx = 0; cx < ctb_w && !err; cx++) {
     const int ctb_rs = cy * ctb_w + cx;
     const CtbInfo ci = ctb_info[ctb_rs];
@@ -857,8 +857,11 @@ __device__ __forceinline__ void recon_rows(const ReconArgs& A, const ReconWave& 
       if (INTER && (mode & 64) && from_plane) {   // a unit of an inter coded CU, complete in the plane and in the tile already
         if (!DUAL) mark_inter_available<Pix>(L, C, ux * 4, uy * 4, tb, 2, 2);
         else if (tb > 2 || (z & 3) == 3) {
-          const int quad = tb == 2;
-          mark_inter_available<Pix>(L, C, (quad ? (ux & ~1) : ux) * 2, (quad ? (uy & ~1) : uy) * 2, quad ? 2 : tb - 1, 1, 1);
+          // (4:2:2: the pair's blocks are two chroma blocks tall, the upper and the lower one)
+          const int quad = tb == 2, lgc = quad ? 2 : tb - 1, cuy = quad ? (uy & ~1) : uy;
+#pragma nounroll
+          for (int lower = 0; lower < (suby == 2 ? 1 : 2); lower++)
+            mark_inter_available<Pix>(L, C, (quad ? (ux & ~1) : ux) * 2, cuy * (4 / suby) + (lower << lgc), lgc, 1, C.ushy);
         }
       } else if (INTER && (mode & 64)) {   // the same with the residual added here: prediction from the plane + residual
         if (!DUAL) {
@@ -868,8 +871,15 @@ __device__ __forceinline__ void recon_rows(const ReconArgs& A, const ReconWave& 
           const int quad = tb == 2;
           const int zc = quad ? (z & ~3) : z, cux = quad ? (ux & ~1) : ux, cuy = quad ? (uy & ~1) : uy;
           const int lgc = quad ? 2 : tb - 1;
-          const Pix* pred = rec + (size_t)(y_ctb / 2 + cuy * 2) * stride + (size_t)(xc0 + cux * 2);
-          reconstruct_inter_block<Pix>(L, C, tile, pred, stride, cux * 2, cuy * 2, lgc, fl & cbf_bit, res_base + zc * 4, l, 32, 1, 1);
+          // 4:2:2: two blocks one above the other, the lower one's flags in unit z ^ 1 and its residual behind the upper one's
+          const int fl2 = suby == 2 ? 0 : (int)((L.m_unit[z ^ 1] >> 8) & 255u);
+#pragma nounroll
+          for (int lower = 0; lower < (suby == 2 ? 1 : 2); lower++) {
+            const int ycb = cuy * (4 / suby) + (lower << lgc);
+            const Pix* pred = rec + (size_t)(y_ctb / suby + ycb) * stride + (size_t)(xc0 + cux * 2);
+            reconstruct_inter_block<Pix>(L, C, tile, pred, stride, cux * 2, ycb, lgc, (lower ? fl2 : fl) & cbf_bit, res_base + zc * (8 / suby) + (lower << (2 * lgc)),
+                                         l, 32, 1, C.ushy);
+          }
         }
       } else if (!DUAL) {
         if (tb == 2) reconstruct_block_reg<Pix, 2>(L, C, top, ux * 4, uy * 4, mode, fl & (cbf_bit | UF_PCM), res_base + z * 16);

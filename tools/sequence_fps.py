@@ -1,7 +1,8 @@
 """Frames per second of sequence tracks through the decoder object, the way libheif drives it (one sample per push, polling for the next picture in
 output order; GPU box, dev tool): one 1280x720 track alone - every picture is one CABAC critical path, the instance has one sample at a time -
 and T tracks decoded side by side by T threads (their decodes coalesce into shared launch sets).
-usage: python tools/sequence_fps.py [frames] [tracks]"""
+usage: python tools/sequence_fps.py [frames] [tracks]
+SEQ_CHROMA=2 / 3: 4:2:2 / 4:4:4 tracks instead of 4:2:0 (chroma_format_idc)"""
 import os, sys, threading, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -13,7 +14,9 @@ from libheif_amd.decoder import HipDecoder
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 13
 tracks = int(sys.argv[2]) if len(sys.argv) > 2 else 16
 w, h = 1280, 720
-frames = make_frames(w, h, n)
+cfi = int(os.environ.get("SEQ_CHROMA", "1"))
+fmt = {1: "4:2:0", 2: "4:2:2", 3: "4:4:4"}[cfi]
+frames = make_frames(w, h, n, chroma_format_idc=cfi)
 kinds = {"intra only": None,
          "lowdelay (IPPP, 2 refs, TMVP, weighted)": dict(inter_num_refs=2, temporal_mvp=1, weighted_pred=1),
          "unrestricted (IBBP, TMVP)": dict(b_frames=2, inter_num_refs=2, temporal_mvp=1)}
@@ -56,6 +59,8 @@ for name, kw in kinds.items():
         if combo:
             set_sequence_pipeline(combo[0]); _ts._set_lookahead(combo[1])
             tag = "pipeline %d look-ahead %2d: " % combo
+        if cfi != 1:
+            tag += fmt + " "
         play(True)                                   # warm-up + correctness against the oracle
         t0 = time.perf_counter(); play(False); one = time.perf_counter() - t0
         before = chain_stats()
