@@ -5,10 +5,13 @@
  *
  *   cc -I include examples/decode_batch.c -L libheif_amd -lheifhip -Wl,-rpath,$PWD/libheif_amd -o decode_batch
  *   ./decode_batch item0.hevc item1.hevc ...          (files as written by tools/streamgen.py, or dumped from a HEIC's hvcC + item data)
+ *   ./decode_batch --thumb 256 item0.hevc ...         ends in ONE launch that turns every item into an RGB24 preview that fits into 256 x 256
+ *                                                     (the size rule of libheif's examples/heif_thumbnailer.cc:172-186, area-averaged on the device)
  */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include "heif_hipdec.h"
 
 static void* slurp(const char* path, size_t* size)
@@ -27,7 +30,14 @@ static void* slurp(const char* path, size_t* size)
 
 int main(int argc, char** argv)
 {
-  if (argc < 2) { fprintf(stderr, "usage: %s item.hevc [item.hevc ...]\n", argv[0]); return 2; }
+  const char* prog = argv[0];
+  int thumb = 0;
+  if (argc >= 2 && !strcmp(argv[1], "--thumb")) {
+    thumb = argc >= 3 ? atoi(argv[2]) : 0;
+    if (thumb < 1) argc = 0;                                       /* no or a bad N: usage */
+    else { argv += 2; argc -= 2; }
+  }
+  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N] item.hevc [item.hevc ...]\n", prog); return 2; }
   const int n = argc - 1;
   const void** data = (const void**)calloc((size_t)n, sizeof(void*));
   size_t* sizes = (size_t*)calloc((size_t)n, sizeof(size_t));
@@ -62,6 +72,40 @@ int main(int argc, char** argv)
     for (size_t k = 0; k < (size_t)info.width * info.height * es; k++) sum += y[k];
     printf("%s: %dx%d, %d bit, luma byte sum %llu\n", argv[1 + i], info.width, info.height, info.bit_depth_luma, sum);
     free(y);
+  }
+  if (thumb) {                                                     /* previews of all items as one launch: no full-size RGB exists anywhere, and of the colour stage only the previews cross to the host */
+    int* ws = (int*)calloc((size_t)n, sizeof(int));
+    int* hs = (int*)calloc((size_t)n, sizeof(int));
+    void** outs = (void**)calloc((size_t)n, sizeof(void*));
+    size_t* strides = (size_t*)calloc((size_t)n, sizeof(size_t));
+    for (int i = 0; i < n; i++) {
+      hipdec_image_info info;
+      hipdec_batch_info(prev, i, &info);
+      ws[i] = info.width; hs[i] = info.height;
+      if (info.width > thumb || info.height > thumb) {             /* heif_thumbnailer.cc:172-186 */
+        if (info.width > info.height) { hs[i] = (int)((long long)info.height * thumb / info.width); ws[i] = thumb; }
+        else { ws[i] = (int)((long long)info.width * thumb / info.height); hs[i] = thumb; }
+      }
+      if (ws[i] < 1 || hs[i] < 1) { fprintf(stderr, "%s: zero thumbnail output size\n", argv[1 + i]); return 1; }
+      strides[i] = (size_t)ws[i] * 3;
+      outs[i] = hipdec_malloc(strides[i] * (size_t)hs[i]);
+      if (!outs[i]) { fprintf(stderr, "%s\n", hipdec_last_error()); return 1; }
+    }
+    if (hipdec_batch_to_rgb_scaled_all(prev, 10, ws, hs, HIPDEC_SCALE_BOX, (void* const*)outs, strides, NULL) || hipdec_batch_status(prev)) {
+      fprintf(stderr, "%s\n", hipdec_last_error());
+      return 1;
+    }
+    for (int i = 0; i < n; i++) {
+      const size_t bytes = strides[i] * (size_t)hs[i];
+      uint8_t* rgb = (uint8_t*)malloc(bytes);
+      if (!rgb || hipdec_memcpy_d2h(rgb, outs[i], bytes)) { fprintf(stderr, "%s\n", hipdec_last_error()); return 1; }
+      unsigned long long sum = 0;
+      for (size_t k = 0; k < bytes; k++) sum += rgb[k];
+      printf("%s: preview %dx%d RGB24, byte sum %llu\n", argv[1 + i], ws[i], hs[i], sum);
+      free(rgb);
+      hipdec_free(outs[i]);
+    }
+    free(ws); free(hs); free(outs); free(strides);
   }
   hipdec_batch_free(prev);
   hipdec_shutdown();

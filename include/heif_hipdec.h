@@ -423,7 +423,45 @@ HIPDEC_API int hipdec_plane_mirror(const void* in, size_t in_stride, int w, int 
 HIPDEC_API int hipdec_plane_crop(const void* in, size_t in_stride, int w, int h, int bytes_per_sample, int left, int top, int out_w, int out_h, void* out,
                                  size_t out_stride, void* stream);
 
-/* counters since load: images through hipdec_image_transform, grid canvases handed out by hipdec_grid_read_plane_tracked */
+/* ---- scaled output (thumbnails) on the device -------------------------------------------------------------------------------------------------
+ * What applications do with heif_image_scale_image() right after heif_decode_image() (libheif/api/libheif/heif_image.cc:240; examples/heif_thumbnailer.cc:197),
+ * without the full-size picture leaving HBM.  Two filters:
+ *  HIPDEC_SCALE_NEAREST  HeifPixelImage::scale_nearest_neighbor (libheif/image/pixelimage.cc:1783-1972) bit for bit: output sample (x, y) of EVERY plane is
+ *                        input sample (x * in_width / out_width, y * in_height / out_height) of that plane (64-bit products), with the IMAGE's sizes also for
+ *                        the chroma planes; the output chroma planes have the subsampled size of the output image ((w + 1) / 2 ...).  Up-scaling is allowed.
+ *  HIPDEC_SCALE_BOX      area average (not in the reference), integer-exact.  A plane of pw x ph samples goes to qw x qh: output sample (ox, oy) is
+ *                        (S + n / 2) / n, S the sum of the input samples in [x0, x1) x [y0, y1), x0 = ox * pw / qw, x1 = (ox + 1) * pw / qw (x0 + 1 where that
+ *                        left the range empty), the same in y, n = (x1 - x0) * (y1 - y0); 64-bit products, integer division.  Each plane uses ITS OWN pw, ph. */
+typedef enum hipdec_scale_filter { HIPDEC_SCALE_NEAREST = 0, HIPDEC_SCALE_BOX = 1 } hipdec_scale_filter;
+/* Every plane of `in` (host or device pointers as `on_device` says; host planes the decoder handed over are found device-resident) to out_width x out_height,
+ * into the planes `out` brings (same on_device convention; NULL where `in` has none); out->width / height / chroma / bit_depth are filled in.  The chroma
+ * format is kept: chroma planes come out at the subsampled size of the output image. */
+HIPDEC_API int hipdec_image_scale(const hipdec_color_image* in, int out_width, int out_height, int filter, hipdec_color_image* out);
+/* counter since load: images through hipdec_image_scale */
+HIPDEC_API void hipdec_image_scale_stats(uint64_t* images);
+/* the plane kernel (device pointers; synchronises `stream`): a plane of in_w x in_h samples to out_w x out_h.  image_w / image_h -> image_out_w / image_out_h
+ * are the sizes of the IMAGE the plane belongs to, which the nearest-neighbour index uses (for a luma or a lone plane: the plane's own); the box filter
+ * only looks at the plane's sizes.  bytes_per_sample 1 or 2. */
+HIPDEC_API int hipdec_plane_scale(const void* in, size_t in_stride, int in_w, int in_h, int bytes_per_sample, int image_w, int image_h, int image_out_w,
+                                  int image_out_h, int out_w, int out_h, int filter, void* out, size_t out_stride, void* stream);
+/* hipdec_batch_to_rgb with a scaled result: interleaved rows of out_width x out_height pixels straight from item i's decoded planes, ONE fused kernel (no
+ * full-size RGB and no scaled planes in HBM).  Every out_chroma / bit depth / chroma format hipdec_batch_to_rgb takes, monochrome included.
+ *  nearest: the bytes of hipdec_batch_to_rgb at full size followed by the reference's interleaved scaling (pixelimage.cc:1876-1886):
+ *           out(x, y) = full(x * W / out_width, y * H / out_height); only the sampled pixels are read.
+ *  box:     the bytes of hipdec_color_convert (nearest-neighbour upsampling has nothing to do) on the three planes box-scaled to out_width x out_height each,
+ *           i.e. on a 4:4:4 image of the input's bit depth and VUI colour description.
+ * HIPDEC_ERR_LIMIT when the batch was created with max_image_size_pixels and out_width x out_height exceeds it.  Asynchronous on `stream`. */
+HIPDEC_API int hipdec_batch_to_rgb_scaled(hipdec_batch* b, int i, int out_chroma, int out_width, int out_height, int filter, void* out_dev, size_t out_stride,
+                                          void* stream);
+/* the same for ALL items as one launch, with per-item sizes (out_widths[i] x out_heights[i] into outs_dev[i] / out_strides[i]); the device time lands in
+ * slot [5] of hipdec_batch_slot_kernel_timing_us like hipdec_batch_to_rgb_all's */
+HIPDEC_API int hipdec_batch_to_rgb_scaled_all(hipdec_batch* b, int out_chroma, const int* out_widths, const int* out_heights, int filter, void* const* outs_dev,
+                                              const size_t* out_strides, void* stream);
+/* plane c of item i as hipdec_image_scale would hand it out for an image of out_width x out_height (c > 0: the subsampled size of that), into a host buffer */
+HIPDEC_API int hipdec_batch_read_plane_scaled(hipdec_batch* b, int i, int c, int out_width, int out_height, int filter, void* dst_host, size_t dst_stride);
+
+/* counters since load: images through hipdec_image_transform, grid canvases handed out by hipdec_grid_read_plane_tracked (hipdec_image_scale counts in
+ * hipdec_image_scale_stats) */
 HIPDEC_API void hipdec_image_ops_stats(uint64_t* transforms, uint64_t* grid_canvases);
 /* counters since load: conversions through hipdec_color_convert, input planes found device-resident, colour kernels launched */
 HIPDEC_API void hipdec_color_boundary_stats(uint64_t* conversions, uint64_t* resident_planes, uint64_t* kernel_launches);

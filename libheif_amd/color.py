@@ -82,6 +82,46 @@ def plan(bpp, chroma, nclx, target_chroma, upsampling=UPSAMPLING_BILINEAR, only_
     raise HipDecError(-4, "conversion outside the HEIC hot path")
 
 
+SCALE_NEAREST, SCALE_BOX = 0, 1   # hipdec_scale_filter
+
+
+class ColorImage(C.Structure):
+    """hipdec_color_image"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("chroma", C.c_int), ("bit_depth", C.c_int),
+                ("plane", C.c_void_p * 4), ("stride", C.c_size_t * 4), ("on_device", C.c_int)]
+
+
+def subsampled_size(width, height, chroma):
+    """get_subsampled_size (libheif/image/pixelimage.cc): the size of a chroma plane of a width x height image"""
+    return (width if chroma == CHROMA_444 else (width + 1) // 2), ((height + 1) // 2 if chroma == CHROMA_420 else height)
+
+
+def image_scale(planes, bpp, chroma, width, height, filter=SCALE_BOX, alpha=None):
+    """heif_image_scale_image() on the GPU (hipdec_image_scale).  planes: [Y] or [Y, Cb, Cr] NumPy arrays, alpha: an optional plane of the
+    luma size; chroma: 0 (monochrome) / CHROMA_420 / CHROMA_422 / CHROMA_444.  Returns the scaled planes in the same order (alpha last).
+    SCALE_NEAREST is the reference's arithmetic bit for bit, SCALE_BOX the area average defined in include/heif_hipdec.h."""
+    lib = load_library()
+    lib.hipdec_image_scale.argtypes = [C.POINTER(ColorImage), C.c_int, C.c_int, C.c_int, C.POINTER(ColorImage)]
+    dt = np.uint16 if bpp > 8 else np.uint8
+    src = [np.ascontiguousarray(p, dtype=dt) for p in planes]
+    h, w = src[0].shape
+    slots = [0] if len(src) == 1 else [0, 1, 2]
+    if alpha is not None:
+        src.append(np.ascontiguousarray(alpha, dtype=dt))
+        slots.append(3)
+    cw, ch = subsampled_size(width, height, chroma)
+    inp, out = ColorImage(), ColorImage()
+    inp.width, inp.height, inp.chroma, inp.bit_depth, inp.on_device = w, h, chroma, bpp, 0
+    res = []
+    for a, c in zip(src, slots):
+        o = np.empty((max(ch, 0), max(cw, 0)) if c in (1, 2) else (max(height, 0), max(width, 0)), dt)
+        inp.plane[c], inp.stride[c] = a.ctypes.data, a.strides[0]
+        out.plane[c], out.stride[c] = o.ctypes.data, o.shape[1] * o.itemsize
+        res.append(o)
+    check(lib.hipdec_image_scale(C.byref(inp), int(width), int(height), int(filter), C.byref(out)))
+    return res
+
+
 class DevicePlanes:
     """Decoded Y/Cb/Cr planes resident in HBM (tight strides)."""
 

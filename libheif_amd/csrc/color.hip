@@ -26,6 +26,70 @@ namespace {
 using namespace hipdec::colordev;
 
 
+// the store paths of a 4-pixel group of row yy starting at pixel x0 (npx of them inside the picture): one 12-byte store for RGB24, 16 bytes for RGBA32,
+// two 12-byte stores for RRGGBB, dwords per plane for the planar layout; byte stores where the group is cut or the destination is not aligned
+template <typename Pix, int LAYOUT>
+__device__ __forceinline__ void store_rgb4(const ColorParams& p, int x0, int yy, int npx, const int (&R)[4], const int (&G)[4], const int (&B)[4], const uint32_t (&A)[4])
+{
+  if (LAYOUT == LO_PLANAR) {
+    HIPDEC_GLOBAL Pix* r = (HIPDEC_GLOBAL Pix*)((HIPDEC_GLOBAL uint8_t*)p.o0 + (size_t)yy * p.os) + x0;
+    HIPDEC_GLOBAL Pix* g = (HIPDEC_GLOBAL Pix*)((HIPDEC_GLOBAL uint8_t*)p.o1 + (size_t)yy * p.os) + x0;
+    HIPDEC_GLOBAL Pix* b = (HIPDEC_GLOBAL Pix*)((HIPDEC_GLOBAL uint8_t*)p.o2 + (size_t)yy * p.os) + x0;
+    if (npx == 4 && sizeof(Pix) == 1 && ((p.os | (uintptr_t)p.o0 | (uintptr_t)p.o1 | (uintptr_t)p.o2) & 3) == 0) {
+      *(HIPDEC_GLOBAL uint32_t*)r = R[0] | (R[1] << 8) | (R[2] << 16) | ((uint32_t)R[3] << 24);
+      *(HIPDEC_GLOBAL uint32_t*)g = G[0] | (G[1] << 8) | (G[2] << 16) | ((uint32_t)G[3] << 24);
+      *(HIPDEC_GLOBAL uint32_t*)b = B[0] | (B[1] << 8) | (B[2] << 16) | ((uint32_t)B[3] << 24);
+    } else if (npx == 4 && sizeof(Pix) == 2 && ((p.os | (uintptr_t)p.o0 | (uintptr_t)p.o1 | (uintptr_t)p.o2) & 7) == 0) {
+      *(HIPDEC_GLOBAL uint2*)r = make_uint2(R[0] | (R[1] << 16), R[2] | (R[3] << 16));
+      *(HIPDEC_GLOBAL uint2*)g = make_uint2(G[0] | (G[1] << 16), G[2] | (G[3] << 16));
+      *(HIPDEC_GLOBAL uint2*)b = make_uint2(B[0] | (B[1] << 16), B[2] | (B[3] << 16));
+    } else {
+      for (int i = 0; i < npx; i++) { r[i] = (Pix)R[i]; g[i] = (Pix)G[i]; b[i] = (Pix)B[i]; }
+    }
+  } else if (LAYOUT == LO_RGB24) {
+    HIPDEC_GLOBAL uint8_t* o = (HIPDEC_GLOBAL uint8_t*)p.o0 + (size_t)yy * p.os + (size_t)x0 * 3;
+    if (npx == 4 && ((p.os | (uintptr_t)p.o0) & 3) == 0) {
+      U3 v;
+      v.a = R[0] | (G[0] << 8) | (B[0] << 16) | ((uint32_t)R[1] << 24);
+      v.b = G[1] | (B[1] << 8) | (R[2] << 16) | ((uint32_t)G[2] << 24);
+      v.c = B[2] | (R[3] << 8) | (G[3] << 16) | ((uint32_t)B[3] << 24);
+      *(HIPDEC_GLOBAL U3*)o = v;
+    } else {
+      for (int i = 0; i < npx; i++) { o[3 * i] = (uint8_t)R[i]; o[3 * i + 1] = (uint8_t)G[i]; o[3 * i + 2] = (uint8_t)B[i]; }
+    }
+  } else if (LAYOUT == LO_RGBA32) {
+    HIPDEC_GLOBAL uint8_t* o = (HIPDEC_GLOBAL uint8_t*)p.o0 + (size_t)yy * p.os + (size_t)x0 * 4;
+    if (npx == 4 && ((p.os | (uintptr_t)p.o0) & 15) == 0) {
+      uint4 v;
+      v.x = R[0] | (G[0] << 8) | (B[0] << 16) | (A[0] << 24);
+      v.y = R[1] | (G[1] << 8) | (B[1] << 16) | (A[1] << 24);
+      v.z = R[2] | (G[2] << 8) | (B[2] << 16) | (A[2] << 24);
+      v.w = R[3] | (G[3] << 8) | (B[3] << 16) | (A[3] << 24);
+      *(HIPDEC_GLOBAL uint4*)o = v;
+    } else {
+      for (int i = 0; i < npx; i++) { o[4 * i] = (uint8_t)R[i]; o[4 * i + 1] = (uint8_t)G[i]; o[4 * i + 2] = (uint8_t)B[i]; o[4 * i + 3] = (uint8_t)A[i]; }
+    }
+  } else {  // RRGGBB BE / LE, yuv2rgb.cc:717-723
+    HIPDEC_GLOBAL uint8_t* o = (HIPDEC_GLOBAL uint8_t*)p.o0 + (size_t)yy * p.os + (size_t)x0 * 6;
+    const bool le = LAYOUT == LO_RRGGBB_LE;
+    uint16_t s[12];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      int r = R[i], g = G[i], b = B[i];
+      if (!le) { r = ((r & 255) << 8) | (r >> 8); g = ((g & 255) << 8) | (g >> 8); b = ((b & 255) << 8) | (b >> 8); }
+      s[3 * i] = (uint16_t)r; s[3 * i + 1] = (uint16_t)g; s[3 * i + 2] = (uint16_t)b;
+    }
+    if (npx == 4 && ((p.os | (uintptr_t)p.o0) & 3) == 0) {
+      U3 v0, v1;
+      v0.a = s[0] | ((uint32_t)s[1] << 16); v0.b = s[2] | ((uint32_t)s[3] << 16); v0.c = s[4] | ((uint32_t)s[5] << 16);
+      v1.a = s[6] | ((uint32_t)s[7] << 16); v1.b = s[8] | ((uint32_t)s[9] << 16); v1.c = s[10] | ((uint32_t)s[11] << 16);
+      ((HIPDEC_GLOBAL U3*)o)[0] = v0; ((HIPDEC_GLOBAL U3*)o)[1] = v1;
+    } else {
+      for (int i = 0; i < npx * 3; i++) { o[2 * i] = (uint8_t)(s[i] & 255); o[2 * i + 1] = (uint8_t)(s[i] >> 8); }
+    }
+  }
+}
+
 template <typename Pix, int LAYOUT>
 __device__ __forceinline__ void rgb_block(const ColorParams& p)
 {
@@ -73,73 +137,17 @@ __device__ __forceinline__ void rgb_block(const ColorParams& p)
       } else convert_px(p, Y[i], CB[i], CR[i], R[i], G[i], B[i]);
     }
 
-    if (LAYOUT == LO_PLANAR) {
-      HIPDEC_GLOBAL Pix* r = (HIPDEC_GLOBAL Pix*)((HIPDEC_GLOBAL uint8_t*)p.o0 + (size_t)yy * p.os) + x0;
-      HIPDEC_GLOBAL Pix* g = (HIPDEC_GLOBAL Pix*)((HIPDEC_GLOBAL uint8_t*)p.o1 + (size_t)yy * p.os) + x0;
-      HIPDEC_GLOBAL Pix* b = (HIPDEC_GLOBAL Pix*)((HIPDEC_GLOBAL uint8_t*)p.o2 + (size_t)yy * p.os) + x0;
-      if (npx == 4 && sizeof(Pix) == 1 && ((p.os | (uintptr_t)p.o0 | (uintptr_t)p.o1 | (uintptr_t)p.o2) & 3) == 0) {
-        *(HIPDEC_GLOBAL uint32_t*)r = R[0] | (R[1] << 8) | (R[2] << 16) | ((uint32_t)R[3] << 24);
-        *(HIPDEC_GLOBAL uint32_t*)g = G[0] | (G[1] << 8) | (G[2] << 16) | ((uint32_t)G[3] << 24);
-        *(HIPDEC_GLOBAL uint32_t*)b = B[0] | (B[1] << 8) | (B[2] << 16) | ((uint32_t)B[3] << 24);
-      } else if (npx == 4 && sizeof(Pix) == 2 && ((p.os | (uintptr_t)p.o0 | (uintptr_t)p.o1 | (uintptr_t)p.o2) & 7) == 0) {
-        *(HIPDEC_GLOBAL uint2*)r = make_uint2(R[0] | (R[1] << 16), R[2] | (R[3] << 16));
-        *(HIPDEC_GLOBAL uint2*)g = make_uint2(G[0] | (G[1] << 16), G[2] | (G[3] << 16));
-        *(HIPDEC_GLOBAL uint2*)b = make_uint2(B[0] | (B[1] << 16), B[2] | (B[3] << 16));
+    uint32_t A[4] = {255u, 255u, 255u, 255u};
+    if (LAYOUT == LO_RGBA32 && p.a) {
+      HIPDEC_GLOBAL const uint8_t* arow = (HIPDEC_GLOBAL const uint8_t*)p.a + (size_t)yy * p.as + x0;
+      if (npx == 4 && (((uintptr_t)arow) & 3) == 0) {
+        const uint32_t v = *(HIPDEC_GLOBAL const uint32_t*)arow;
+        A[0] = v & 255u; A[1] = (v >> 8) & 255u; A[2] = (v >> 16) & 255u; A[3] = v >> 24;
       } else {
-        for (int i = 0; i < npx; i++) { r[i] = (Pix)R[i]; g[i] = (Pix)G[i]; b[i] = (Pix)B[i]; }
-      }
-    } else if (LAYOUT == LO_RGB24) {
-      HIPDEC_GLOBAL uint8_t* o = (HIPDEC_GLOBAL uint8_t*)p.o0 + (size_t)yy * p.os + (size_t)x0 * 3;
-      if (npx == 4 && ((p.os | (uintptr_t)p.o0) & 3) == 0) {
-        U3 v;
-        v.a = R[0] | (G[0] << 8) | (B[0] << 16) | ((uint32_t)R[1] << 24);
-        v.b = G[1] | (B[1] << 8) | (R[2] << 16) | ((uint32_t)G[2] << 24);
-        v.c = B[2] | (R[3] << 8) | (G[3] << 16) | ((uint32_t)B[3] << 24);
-        *(HIPDEC_GLOBAL U3*)o = v;
-      } else {
-        for (int i = 0; i < npx; i++) { o[3 * i] = (uint8_t)R[i]; o[3 * i + 1] = (uint8_t)G[i]; o[3 * i + 2] = (uint8_t)B[i]; }
-      }
-    } else if (LAYOUT == LO_RGBA32) {
-      HIPDEC_GLOBAL uint8_t* o = (HIPDEC_GLOBAL uint8_t*)p.o0 + (size_t)yy * p.os + (size_t)x0 * 4;
-      uint32_t A[4] = {255u, 255u, 255u, 255u};
-      if (p.a) {
-        HIPDEC_GLOBAL const uint8_t* arow = (HIPDEC_GLOBAL const uint8_t*)p.a + (size_t)yy * p.as + x0;
-        if (npx == 4 && (((uintptr_t)arow) & 3) == 0) {
-          const uint32_t v = *(HIPDEC_GLOBAL const uint32_t*)arow;
-          A[0] = v & 255u; A[1] = (v >> 8) & 255u; A[2] = (v >> 16) & 255u; A[3] = v >> 24;
-        } else {
-          for (int i = 0; i < npx; i++) A[i] = arow[i];
-        }
-      }
-      if (npx == 4 && ((p.os | (uintptr_t)p.o0) & 15) == 0) {
-        uint4 v;
-        v.x = R[0] | (G[0] << 8) | (B[0] << 16) | (A[0] << 24);
-        v.y = R[1] | (G[1] << 8) | (B[1] << 16) | (A[1] << 24);
-        v.z = R[2] | (G[2] << 8) | (B[2] << 16) | (A[2] << 24);
-        v.w = R[3] | (G[3] << 8) | (B[3] << 16) | (A[3] << 24);
-        *(HIPDEC_GLOBAL uint4*)o = v;
-      } else {
-        for (int i = 0; i < npx; i++) { o[4 * i] = (uint8_t)R[i]; o[4 * i + 1] = (uint8_t)G[i]; o[4 * i + 2] = (uint8_t)B[i]; o[4 * i + 3] = (uint8_t)A[i]; }
-      }
-    } else {  // RRGGBB BE / LE, yuv2rgb.cc:717-723
-      HIPDEC_GLOBAL uint8_t* o = (HIPDEC_GLOBAL uint8_t*)p.o0 + (size_t)yy * p.os + (size_t)x0 * 6;
-      const bool le = LAYOUT == LO_RRGGBB_LE;
-      uint16_t s[12];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        int r = R[i], g = G[i], b = B[i];
-        if (!le) { r = ((r & 255) << 8) | (r >> 8); g = ((g & 255) << 8) | (g >> 8); b = ((b & 255) << 8) | (b >> 8); }
-        s[3 * i] = (uint16_t)r; s[3 * i + 1] = (uint16_t)g; s[3 * i + 2] = (uint16_t)b;
-      }
-      if (npx == 4 && ((p.os | (uintptr_t)p.o0) & 3) == 0) {
-        U3 v0, v1;
-        v0.a = s[0] | ((uint32_t)s[1] << 16); v0.b = s[2] | ((uint32_t)s[3] << 16); v0.c = s[4] | ((uint32_t)s[5] << 16);
-        v1.a = s[6] | ((uint32_t)s[7] << 16); v1.b = s[8] | ((uint32_t)s[9] << 16); v1.c = s[10] | ((uint32_t)s[11] << 16);
-        ((HIPDEC_GLOBAL U3*)o)[0] = v0; ((HIPDEC_GLOBAL U3*)o)[1] = v1;
-      } else {
-        for (int i = 0; i < npx * 3; i++) { o[2 * i] = (uint8_t)(s[i] & 255); o[2 * i + 1] = (uint8_t)(s[i] >> 8); }
+        for (int i = 0; i < npx; i++) A[i] = arow[i];
       }
     }
+    store_rgb4<Pix, LAYOUT>(p, x0, yy, npx, R, G, B, A);
   }
 }
 
@@ -152,6 +160,239 @@ __global__ __launch_bounds__(256) void k_ycbcr_to_rgb_batch(const ColorParams* _
 {
   const ColorParams p = ps[blockIdx.z];   // wave-uniform: scalar loads into SGPRs
   rgb_block<Pix, LAYOUT>(p);
+}
+
+// ---- scaled output (thumbnails): nearest neighbour = HeifPixelImage::scale_nearest_neighbor (libheif/image/pixelimage.cc:1783-1972) bit for bit, box =
+// the area average defined in include/heif_hipdec.h (not in the reference; integer-exact).  Two forms of each: a plane scaler (Pix in, Pix out) and a
+// kernel fused with the colour conversion above (planes in, scaled interleaved RGB out: no full-size or scaled intermediate goes through HBM).
+//
+// Box, the streaming one.  Bytes per input luma pixel of 8-bit 4:2:0: 1.5 read, 3 / (scale factor)^2 written.  A workgroup of 256 threads owns `tile`
+// output pixels of one output row; their boxes tile a span of at most kBoxSpan input columns (the host chooses `tile` that way) and rows [y0, y1).  Every
+// thread walks those rows over ITS four columns - one aligned 32-bit load per row for 8-bit samples, 64-bit for 16-bit ones, a wave reads 256 / 512
+// contiguous bytes of a row - and keeps four column sums in registers, for the three planes at once so that their loads are in flight together; the column
+// sums go to LDS, and after one barrier the thread that owns an output pixel adds the columns of its box, divides ONCE (S + n / 2) / n and hands the three
+// averages to the 4-pixel store path.  No division per input sample, no edge case inside the row loop (the cut group at a row's end takes the byte loop
+// as a whole), every input sample comes from HBM once (the 4-column group in front of the tile's first box is the neighbour tile's last: L2).
+// A box wider than kBoxSpan columns (a 4K plane to 1 x 1 is legal) takes the chunk loop more than once.
+constexpr int kBoxSpan = 1024;
+template <typename Pix> struct BoxAcc { typedef uint32_t T; };        // 8-bit samples: 2^24 rows fit
+template <> struct BoxAcc<uint16_t> { typedef uint64_t T; };          // 16-bit samples: any legal number of rows
+
+struct ScaledParams {
+  ColorParams c;     // planes, destination and arithmetic as the full-size kernels get them (c.w / c.h: the SOURCE luma size)
+  int ow, oh;        // output size
+  int sH, sV;        // subsampling shifts of the source chroma planes (box: c.shiftH / c.shiftV describe the 4:4:4 image the arithmetic was planned for)
+  int tile;          // box: output pixels per workgroup
+};
+
+__device__ __forceinline__ void box_range(int o, int pn, int qn, int& a, int& b)
+{
+  a = (int)((uint64_t)o * (uint64_t)pn / (uint64_t)qn);
+  b = (int)((uint64_t)(o + 1) * (uint64_t)pn / (uint64_t)qn);
+  if (b <= a) b = a + 1;
+}
+
+// sums of rows [y0, y1) over the four columns xs .. xs + 3 of a plane (columns at or behind xend: nothing)
+template <typename Pix, typename Acc>
+__device__ __forceinline__ void box_columns(const uint8_t* plane, size_t stride, int pw, int xs, int xend, int y0, int y1, Acc (&a)[4])
+{
+  a[0] = a[1] = a[2] = a[3] = 0;
+  if (xs >= xend) return;
+  HIPDEC_GLOBAL const uint8_t* row = (HIPDEC_GLOBAL const uint8_t*)plane + (size_t)y0 * stride + (size_t)xs * sizeof(Pix);
+  if (xs + 4 <= pw && ((((uintptr_t)plane + (size_t)xs * sizeof(Pix)) | stride) & (4 * sizeof(Pix) - 1)) == 0) {
+#pragma unroll 4
+    for (int y = y0; y < y1; y++, row += stride) {
+      if (sizeof(Pix) == 1) {
+        const uint32_t v = *(HIPDEC_GLOBAL const uint32_t*)row;
+        a[0] += v & 255u; a[1] += (v >> 8) & 255u; a[2] += (v >> 16) & 255u; a[3] += v >> 24;
+      } else {
+        const uint2 v = *(HIPDEC_GLOBAL const uint2*)row;
+        a[0] += v.x & 0xffffu; a[1] += v.x >> 16; a[2] += v.y & 0xffffu; a[3] += v.y >> 16;
+      }
+    }
+  } else {
+    const int n = min(4, pw - xs);
+    for (int y = y0; y < y1; y++, row += stride)
+      for (int k = 0; k < n; k++) a[k] += ((HIPDEC_GLOBAL const Pix*)row)[k];
+  }
+}
+
+struct BoxPlane { const uint8_t* p; size_t stride; int pw, ph; };
+
+// Box averages of NP planes for output pixel (oxA + threadIdx.x, oy) of a qw x qh result; all 256 threads of the workgroup call it (barriers inside),
+// `val` is meaningful where threadIdx.x < nox.  live: planes [0, live) are worked on (wave-uniform).
+template <typename Pix, int NP>
+__device__ __forceinline__ void box_tile(const BoxPlane (&pl)[NP], int live, int qw, int qh, int oxA, int nox, int oy, typename BoxAcc<Pix>::T (*colsum)[kBoxSpan],
+                                         uint32_t (&val)[NP])
+{
+  typedef typename BoxAcc<Pix>::T Acc;
+  const int tid = threadIdx.x;
+  const bool owner = tid < nox;
+  int x0[NP], x1[NP], y0[NP], y1[NP], base[NP], xb[NP];
+  uint64_t S[NP];
+  int chunks = 0;
+#pragma unroll
+  for (int k = 0; k < NP; k++) {
+    S[k] = 0; x0[k] = x1[k] = y0[k] = y1[k] = base[k] = xb[k] = 0;
+    if (k >= live) continue;
+    int xa, t;
+    box_range(oxA, pl[k].pw, qw, xa, t);                    // the tile's span of input columns [xa, xb): wave-uniform
+    box_range(oxA + nox - 1, pl[k].pw, qw, t, xb[k]);
+    box_range(oy, pl[k].ph, qh, y0[k], y1[k]);
+    box_range(owner ? oxA + tid : oxA, pl[k].pw, qw, x0[k], x1[k]);
+    base[k] = xa & ~3;
+    chunks = max(chunks, (xb[k] - base[k] + kBoxSpan - 1) / kBoxSpan);
+  }
+  for (int j = 0; j < chunks; j++) {
+    Acc a[NP][4];
+#pragma unroll
+    for (int k = 0; k < NP; k++) {
+      if (k < live) box_columns<Pix, Acc>(pl[k].p, pl[k].stride, pl[k].pw, base[k] + j * kBoxSpan + tid * 4, xb[k], y0[k], y1[k], a[k]);
+    }
+    if (j) __syncthreads();                                // the owners have finished with the previous chunk's sums
+#pragma unroll
+    for (int k = 0; k < NP; k++) {
+      if (k < live) { colsum[k][tid * 4] = a[k][0]; colsum[k][tid * 4 + 1] = a[k][1]; colsum[k][tid * 4 + 2] = a[k][2]; colsum[k][tid * 4 + 3] = a[k][3]; }
+    }
+    __syncthreads();
+    if (owner) {
+#pragma unroll
+      for (int k = 0; k < NP; k++) {
+        if (k >= live) continue;
+        const int cs = base[k] + j * kBoxSpan;
+        const int lo = max(x0[k], cs) - cs, hi = min(x1[k], cs + kBoxSpan) - cs;
+        for (int x = lo; x < hi; x++) S[k] += colsum[k][x];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NP; k++) {
+    const uint64_t n = (uint64_t)(x1[k] - x0[k]) * (uint64_t)(y1[k] - y0[k]);
+    val[k] = (k < live && owner) ? (uint32_t)((S[k] + n / 2) / n) : 0u;
+  }
+}
+
+// the per-pixel arithmetic of rgb_block for one group of four
+template <typename Pix, int LAYOUT>
+__device__ __forceinline__ void convert4(const ColorParams& p, const int (&Y)[4], const int (&CB)[4], const int (&CR)[4], int (&R)[4], int (&G)[4], int (&B)[4])
+{
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    if (sizeof(Pix) == 2 && (LAYOUT == LO_RGB24 || LAYOUT == LO_RGBA32)) {
+      convert_px(p, Y[i] >> p.in_shift, CB[i] >> p.in_shift, CR[i] >> p.in_shift, R[i], G[i], B[i]);
+      R[i] >>= p.out_shift; G[i] >>= p.out_shift; B[i] >>= p.out_shift;
+    } else convert_px(p, Y[i], CB[i], CR[i], R[i], G[i], B[i]);
+  }
+}
+
+template <typename Pix, int LAYOUT>
+__device__ __forceinline__ void box_rgb_block(const ScaledParams& sp)
+{
+  __shared__ typename BoxAcc<Pix>::T colsum[3][kBoxSpan];
+  __shared__ uint32_t avg[3][256];
+  const ColorParams& p = sp.c;
+  const int tid = threadIdx.x;
+  const int oxA = blockIdx.x * sp.tile;
+  if (oxA >= sp.ow) return;                               // (the whole workgroup)
+  const int nox = min(sp.tile, sp.ow - oxA);
+  const bool mono = p.arith == AR_MONO;
+  const int cw = (p.w + (1 << sp.sH) - 1) >> sp.sH, ch = (p.h + (1 << sp.sV) - 1) >> sp.sV;
+  const BoxPlane pl[3] = {{p.y, p.ys, p.w, p.h}, {p.cb, p.cbs, cw, ch}, {p.cr, p.crs, cw, ch}};
+  for (int oy = blockIdx.y; oy < sp.oh; oy += gridDim.y) {
+    uint32_t v[3];
+    box_tile<Pix, 3>(pl, mono ? 1 : 3, sp.ow, sp.oh, oxA, nox, oy, colsum, v);
+    avg[0][tid] = v[0]; avg[1][tid] = v[1]; avg[2][tid] = v[2];
+    __syncthreads();
+    if (tid * 4 < nox) {
+      const int npx = min(4, nox - tid * 4);
+      int Y[4], CB[4], CR[4], R[4], G[4], B[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) { Y[i] = (int)avg[0][(tid * 4 + i) & 255]; CB[i] = (int)avg[1][(tid * 4 + i) & 255]; CR[i] = (int)avg[2][(tid * 4 + i) & 255]; }
+      convert4<Pix, LAYOUT>(p, Y, CB, CR, R, G, B);
+      const uint32_t A[4] = {255u, 255u, 255u, 255u};
+      store_rgb4<Pix, LAYOUT>(p, oxA + tid * 4, oy, npx, R, G, B, A);
+    }
+    __syncthreads();                                      // avg and colsum are written again by the next row
+  }
+}
+
+// nearest neighbour: out(x, y) = full(x * W / ow, y * H / oh) where `full` is what rgb_block writes - only the sampled pixels are read
+template <typename Pix, int LAYOUT>
+__device__ __forceinline__ void nearest_rgb_block(const ScaledParams& sp)
+{
+  const ColorParams& p = sp.c;
+  const int ox0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (ox0 >= sp.ow) return;
+  const int npx = min(4, sp.ow - ox0);
+  const bool mono = p.arith == AR_MONO;
+  for (int oy = blockIdx.y * blockDim.y + threadIdx.y; oy < sp.oh; oy += gridDim.y * blockDim.y) {
+    const int iy = (int)((uint64_t)oy * (uint64_t)p.h / (uint64_t)sp.oh);
+    HIPDEC_GLOBAL const Pix* yrow = (HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.y + (size_t)iy * p.ys);
+    HIPDEC_GLOBAL const Pix* cbrow = (HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.cb + (size_t)(iy >> sp.sV) * p.cbs);
+    HIPDEC_GLOBAL const Pix* crrow = (HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.cr + (size_t)(iy >> sp.sV) * p.crs);
+    int Y[4], CB[4], CR[4], R[4], G[4], B[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int ix = (int)((uint64_t)min(ox0 + i, sp.ow - 1) * (uint64_t)p.w / (uint64_t)sp.ow);
+      Y[i] = yrow[ix];
+      CB[i] = mono ? 0 : cbrow[ix >> sp.sH];
+      CR[i] = mono ? 0 : crrow[ix >> sp.sH];
+    }
+    convert4<Pix, LAYOUT>(p, Y, CB, CR, R, G, B);
+    const uint32_t A[4] = {255u, 255u, 255u, 255u};
+    store_rgb4<Pix, LAYOUT>(p, ox0, oy, npx, R, G, B, A);
+  }
+}
+
+template <typename Pix, int LAYOUT>
+__global__ __launch_bounds__(256) void k_scale_rgb_box(ScaledParams sp) { box_rgb_block<Pix, LAYOUT>(sp); }
+template <typename Pix, int LAYOUT>
+__global__ __launch_bounds__(256) void k_scale_rgb_nearest(ScaledParams sp) { nearest_rgb_block<Pix, LAYOUT>(sp); }
+// all items of a batch in ONE launch, as k_ycbcr_to_rgb_batch: blockIdx.z selects the parameter block
+template <typename Pix, int LAYOUT>
+__global__ __launch_bounds__(256) void k_scale_rgb_box_batch(const ScaledParams* __restrict__ ps)
+{
+  const ScaledParams sp = ps[blockIdx.z];
+  box_rgb_block<Pix, LAYOUT>(sp);
+}
+template <typename Pix, int LAYOUT>
+__global__ __launch_bounds__(256) void k_scale_rgb_nearest_batch(const ScaledParams* __restrict__ ps)
+{
+  const ScaledParams sp = ps[blockIdx.z];
+  nearest_rgb_block<Pix, LAYOUT>(sp);
+}
+
+// the plane scalers: blockIdx.z selects the plane (all planes of an image, or of all items of a batch, are ONE launch)
+template <typename Pix>
+__global__ __launch_bounds__(256) void k_scale_plane_nearest(const hipdec::PlaneScaleParams* __restrict__ ps)
+{
+  const hipdec::PlaneScaleParams p = ps[blockIdx.z];
+  const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (x0 >= p.qw) return;
+  for (int y = blockIdx.y * blockDim.y + threadIdx.y; y < p.qh; y += gridDim.y * blockDim.y) {
+    // pixelimage.cc:1936-1943: the IMAGE's sizes, also for the chroma planes (the index stays inside the plane: x < (ow + 1) / 2 gives ix < (W + 1) / 2)
+    const int iy = min((int)((uint64_t)y * (uint64_t)p.ih / (uint64_t)p.oh), p.ph - 1);
+    HIPDEC_GLOBAL const Pix* src = (HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.in + (size_t)iy * p.is);
+    HIPDEC_GLOBAL Pix* dst = (HIPDEC_GLOBAL Pix*)((HIPDEC_GLOBAL uint8_t*)p.out + (size_t)y * p.os);
+    for (int i = 0; i < 4 && x0 + i < p.qw; i++) dst[x0 + i] = src[min((int)((uint64_t)(x0 + i) * (uint64_t)p.iw / (uint64_t)p.ow), p.pw - 1)];
+  }
+}
+
+template <typename Pix>
+__global__ __launch_bounds__(256) void k_scale_plane_box(const hipdec::PlaneScaleParams* __restrict__ ps)
+{
+  __shared__ typename BoxAcc<Pix>::T colsum[1][kBoxSpan];
+  const hipdec::PlaneScaleParams p = ps[blockIdx.z];
+  const int oxA = blockIdx.x * p.tile;
+  if (oxA >= p.qw) return;
+  const int nox = min(p.tile, p.qw - oxA);
+  const BoxPlane pl[1] = {{p.in, p.is, p.pw, p.ph}};
+  for (int oy = blockIdx.y; oy < p.qh; oy += gridDim.y) {
+    uint32_t v[1];
+    box_tile<Pix, 1>(pl, 1, p.qw, p.qh, oxA, nox, oy, colsum, v);
+    if ((int)threadIdx.x < nox) ((HIPDEC_GLOBAL Pix*)((HIPDEC_GLOBAL uint8_t*)p.out + (size_t)oy * p.os))[oxA + threadIdx.x] = (Pix)v[0];
+    __syncthreads();                                      // colsum is written again by the next row
+  }
 }
 
 // a13: one thread per 4 output samples of one row
@@ -452,9 +693,62 @@ struct Captured { ColorParams p; int variant; };
 thread_local std::vector<Captured> t_captured;
 thread_local bool t_capture = false;
 
+// Scaled output: a request set on this thread (hipdec::color_scale_request) turns the NEXT launch of an interleaved layout into the fused scale + colour
+// kernel - run at once, or recorded in capture mode (hipdec_batch_to_rgb_scaled_all).  The launch that takes the request clears it, and the caller checks
+// that it was taken (hipdec::color_scale_pending), so an entry point that does not come through launch_rgb is refused instead of writing a full-size picture.
+struct ScaleReq { bool on = false; int ow = 0, oh = 0, filter = 0, sH = 0, sV = 0; };
+thread_local ScaleReq t_scale;
+struct CapturedScaled { ScaledParams p; int variant; int filter; };
+thread_local std::vector<CapturedScaled> t_captured_scaled;
+
+int box_tile_of(int pw, int qw)
+{
+  long long t = (long long)(kBoxSpan - 4) * qw / pw;   // span of t boxes <= t * pw / qw + 1 columns, + 3 in front of it for the aligned start
+  if (t > 256) t = 256;
+  if (t < 1) t = 1;                                     // a box wider than the span: the kernel's chunk loop
+  if (t >= 4) t &= ~3ll;                                // whole 4-pixel store groups
+  return (int)t;
+}
+
+template <typename Pix, int LAYOUT>
+void launch_scaled_grid(const ScaledParams* one, const ScaledParams* dev, int n, int filter, int max_ow, int max_oh, int max_tiles, hipStream_t s)
+{
+  if (filter == HIPDEC_SCALE_BOX) {
+    dim3 block(256), grid(max_tiles, max_oh < 65535 ? max_oh : 65535, n);
+    if (one) hipLaunchKernelGGL((k_scale_rgb_box<Pix, LAYOUT>), grid, block, 0, s, *one);
+    else hipLaunchKernelGGL((k_scale_rgb_box_batch<Pix, LAYOUT>), grid, block, 0, s, dev);
+  } else {
+    const int gy = (max_oh + 3) / 4;
+    dim3 block(64, 4), grid(((max_ow + 3) / 4 + 63) / 64, gy < 16384 ? gy : 16384, n);
+    if (one) hipLaunchKernelGGL((k_scale_rgb_nearest<Pix, LAYOUT>), grid, block, 0, s, *one);
+    else hipLaunchKernelGGL((k_scale_rgb_nearest_batch<Pix, LAYOUT>), grid, block, 0, s, dev);
+  }
+}
+
+template <typename Pix, int LAYOUT>
+int launch_rgb_scaled(const ColorParams& p, hipStream_t s)
+{
+  if constexpr (LAYOUT == LO_PLANAR) return hipdec::set_error(HIPDEC_ERR_UNSUPPORTED, "scaled colour stage: interleaved outputs only");
+  else {
+  if (p.a) return hipdec::set_error(HIPDEC_ERR_UNSUPPORTED, "scaled colour stage: no alpha plane");
+  ScaledParams sp;
+  memset(&sp, 0, sizeof(sp));
+  sp.c = p; sp.ow = t_scale.ow; sp.oh = t_scale.oh; sp.sH = t_scale.sH; sp.sV = t_scale.sV;
+  sp.tile = box_tile_of(p.w, sp.ow);
+  const int filter = t_scale.filter;
+  t_scale.on = false;   // taken
+  if (t_capture) { t_captured_scaled.push_back(CapturedScaled{sp, (int)sizeof(Pix) * 16 + LAYOUT, filter}); return 0; }
+  launch_scaled_grid<Pix, LAYOUT>(&sp, nullptr, 1, filter, sp.ow, sp.oh, (sp.ow + sp.tile - 1) / sp.tile, s);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hipdec::set_error(HIPDEC_ERR_DEVICE, "scaled colour kernel launch: %s", hipGetErrorString(e));
+  return 0;
+  }
+}
+
 template <typename Pix, int LAYOUT>
 int launch_rgb(const ColorParams& p, hipStream_t s)
 {
+  if (t_scale.on) return launch_rgb_scaled<Pix, LAYOUT>(p, s);
   if (t_capture) { t_captured.push_back(Captured{p, (int)sizeof(Pix) * 16 + LAYOUT}); return 0; }
   dim3 block(64, 4);
   dim3 grid(((p.w + 3) / 4 + 63) / 64, ((p.h + 1) / 2 + 3) / 4);
@@ -510,16 +804,22 @@ void launch_rgb_batch(const ColorParams* dev, int n, int max_w, int max_h, hipSt
   X(16 + LO_RGBA32, uint8_t, LO_RGBA32) X(32 + LO_RRGGBB_BE, uint16_t, LO_RRGGBB_BE) X(32 + LO_RRGGBB_LE, uint16_t, LO_RRGGBB_LE)                     \
   X(32 + LO_RGB24, uint16_t, LO_RGB24) X(32 + LO_RGBA32, uint16_t, LO_RGBA32)
 
+#define HIPDEC_RGB_SCALED_VARIANTS(X)                                                                              \
+  X(16 + LO_RGB24, uint8_t, LO_RGB24) X(16 + LO_RGBA32, uint8_t, LO_RGBA32) X(32 + LO_RRGGBB_BE, uint16_t, LO_RRGGBB_BE) \
+  X(32 + LO_RRGGBB_LE, uint16_t, LO_RRGGBB_LE) X(32 + LO_RGB24, uint16_t, LO_RGB24) X(32 + LO_RGBA32, uint16_t, LO_RGBA32)
+
 namespace hipdec {
 
 void color_capture_begin()
 {
+  t_captured_scaled.clear();
   t_captured.clear();
   t_capture = true;
 }
 
 void color_capture_abort()
 {
+  t_captured_scaled.clear();
   t_captured.clear();
   t_capture = false;
 }
@@ -599,6 +899,80 @@ int color_capture_launch(ColorBatchState& st, hipStream_t s)
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "colour batch launch: %s", hipGetErrorString(e));
+  return 0;
+}
+
+void color_scale_request(int out_width, int out_height, int filter, int sH, int sV)
+{
+  t_scale.on = true; t_scale.ow = out_width; t_scale.oh = out_height; t_scale.filter = filter; t_scale.sH = sH; t_scale.sV = sV;
+}
+void color_scale_clear() { t_scale.on = false; }
+bool color_scale_pending() { return t_scale.on; }
+
+// hipdec_batch_to_rgb_scaled_all: the scaled blocks recorded since color_capture_begin() as one launch
+int color_capture_launch_scaled(ColorBatchState& st, int filter, hipStream_t s)
+{
+  t_capture = false;
+  std::vector<CapturedScaled> caps;
+  caps.swap(t_captured_scaled);
+  if (caps.empty()) return 0;
+  int max_ow = 0, max_oh = 0, max_tiles = 0;
+  for (const auto& c : caps) {
+    if (c.variant != caps[0].variant || c.filter != filter) return set_error(HIPDEC_ERR_UNSUPPORTED, "scaled colour batch: the items select different kernel variants");
+    max_ow = c.p.ow > max_ow ? c.p.ow : max_ow; max_oh = c.p.oh > max_oh ? c.p.oh : max_oh;
+    const int tiles = (c.p.ow + c.p.tile - 1) / c.p.tile;
+    max_tiles = tiles > max_tiles ? tiles : max_tiles;
+  }
+  const size_t bytes = caps.size() * sizeof(ScaledParams);
+  std::vector<uint8_t> host(bytes);
+  for (size_t i = 0; i < caps.size(); i++) memcpy(host.data() + i * sizeof(ScaledParams), &caps[i].p, sizeof(ScaledParams));
+  if (st.dev_bytes < bytes) {
+    if (st.dev) arena_release(st.dev, st.dev_bytes);
+    st.dev = nullptr; st.dev_bytes = 0; st.host.clear();
+    HIPDEC_CHECK_HIP(arena_acquire(&st.dev, bytes, &st.dev_bytes));
+  }
+  if (st.host != host) {   // steady state (same planes, sizes and outputs): nothing to upload
+    st.prev.swap(st.host);
+    st.host.swap(host);
+    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), bytes, hipMemcpyHostToDevice, s));
+  }
+  const ScaledParams* dev = (const ScaledParams*)st.dev;
+  switch (caps[0].variant) {
+#define X(id, Pix, LO) case id: launch_scaled_grid<Pix, LO>(nullptr, dev, (int)caps.size(), filter, max_ow, max_oh, max_tiles, s); break;
+    HIPDEC_RGB_SCALED_VARIANTS(X)
+#undef X
+    default: return set_error(HIPDEC_ERR_UNSUPPORTED, "scaled colour batch: unknown kernel variant");
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "scaled colour batch launch: %s", hipGetErrorString(e));
+  return 0;
+}
+
+int scale_planes_launch(PlaneScaleParams* jobs, int n, int bytes_per_sample, int filter, void* dev_params, hipStream_t s)
+{
+  if (n <= 0) return 0;
+  int max_qw = 0, max_qh = 0, max_tiles = 0;
+  for (int i = 0; i < n; i++) {
+    PlaneScaleParams& j = jobs[i];
+    j.tile = box_tile_of(j.pw, j.qw);
+    max_qw = j.qw > max_qw ? j.qw : max_qw; max_qh = j.qh > max_qh ? j.qh : max_qh;
+    const int tiles = (j.qw + j.tile - 1) / j.tile;
+    max_tiles = tiles > max_tiles ? tiles : max_tiles;
+  }
+  HIPDEC_CHECK_HIP(hipMemcpyAsync(dev_params, jobs, (size_t)n * sizeof(PlaneScaleParams), hipMemcpyHostToDevice, s));
+  const PlaneScaleParams* dev = (const PlaneScaleParams*)dev_params;
+  if (filter == HIPDEC_SCALE_BOX) {
+    dim3 block(256), grid(max_tiles, max_qh < 65535 ? max_qh : 65535, n);
+    if (bytes_per_sample == 1) hipLaunchKernelGGL(k_scale_plane_box<uint8_t>, grid, block, 0, s, dev);
+    else hipLaunchKernelGGL(k_scale_plane_box<uint16_t>, grid, block, 0, s, dev);
+  } else {
+    const int gy = (max_qh + 3) / 4;
+    dim3 block(64, 4), grid(((max_qw + 3) / 4 + 63) / 64, gy < 16384 ? gy : 16384, n);
+    if (bytes_per_sample == 1) hipLaunchKernelGGL(k_scale_plane_nearest<uint8_t>, grid, block, 0, s, dev);
+    else hipLaunchKernelGGL(k_scale_plane_nearest<uint16_t>, grid, block, 0, s, dev);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "plane scaler launch: %s", hipGetErrorString(e));
   return 0;
 }
 
@@ -820,6 +1194,29 @@ int hipdec_color_swap_endianness(const void* in, size_t is, int w, int h, int co
   hipLaunchKernelGGL(k_swap16, grid, block, 0, s, (const uint8_t*)in, is, row_bytes, h, (uint8_t*)out, os);
   HIPDEC_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+/* one plane through the plane scaler (HIPDEC_SCALE_NEAREST: HeifPixelImage::scale_nearest_neighbor's per-plane loop, libheif/image/pixelimage.cc:1936-1967;
+ * HIPDEC_SCALE_BOX: the area average of heif_hipdec.h); runs on `stream` and waits for it (the parameter block is this call's) */
+int hipdec_plane_scale(const void* in, size_t in_stride, int in_w, int in_h, int bytes_per_sample, int image_w, int image_h, int image_out_w, int image_out_h,
+                       int out_w, int out_h, int filter, void* out, size_t out_stride, void* stream)
+{
+  if (int rc = ensure_init()) return rc;
+  if (!in || !out || in_w <= 0 || in_h <= 0 || out_w <= 0 || out_h <= 0 || image_w <= 0 || image_h <= 0 || image_out_w <= 0 || image_out_h <= 0 ||
+      (bytes_per_sample != 1 && bytes_per_sample != 2))
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "plane_scale: bad arguments");
+  if (filter != HIPDEC_SCALE_NEAREST && filter != HIPDEC_SCALE_BOX) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "plane_scale: unknown filter %d", filter);
+  if (in_stride < (size_t)in_w * bytes_per_sample || out_stride < (size_t)out_w * bytes_per_sample)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "plane_scale: a stride is smaller than its rows");
+  hipStream_t s = stream ? (hipStream_t)stream : default_stream();
+  PlaneScaleParams j{(const uint8_t*)in, in_stride, in_w, in_h, (uint8_t*)out, out_stride, out_w, out_h, image_w, image_h, image_out_w, image_out_h, 0};
+  void* dev = nullptr; size_t cap = 0;
+  HIPDEC_CHECK_HIP(arena_acquire(&dev, sizeof(j), &cap));
+  int rc = scale_planes_launch(&j, 1, bytes_per_sample, filter, dev, s);
+  hipError_t e = hipStreamSynchronize(s);   // (the parameter block and its pageable source are this call's)
+  arena_release(dev, cap);
+  if (!rc && e != hipSuccess) rc = set_error(HIPDEC_ERR_DEVICE, "plane_scale: %s", hipGetErrorString(e));
+  return rc;
 }
 
 int hipdec_color_pq_to_linear(const void* in, size_t is, int w, int h, int components, int bits, int big_endian, void* out, size_t os, void* stream)

@@ -59,6 +59,8 @@ struct hipdec_batch : BatchLayout {
   bool retired = false;         // its arena went to another batch (hipdec_batch_create_recycling): only status / timing / free remain
   uint32_t wave_share = 1;      // the CABAC work pool of this batch takes 1 / wave_share of the wave budget (launch sets of the decoder path overlap in pairs)
   ColorBatchState color;        // parameter blocks of hipdec_batch_to_rgb_all
+  ColorBatchState color_scaled; // ... and of hipdec_batch_to_rgb_scaled_all (its own, so that a host alternating the two uploads nothing in the steady state)
+  uint64_t max_pixels = 0;      // the limit given at creation (0: none): scaled outputs are held against it as well
   // decoder path (plugin): the output planes of every item staged in pinned host memory by ONE set of asynchronous copies behind the
   // kernels, so that N decoder instances sharing the batch do not queue N x 3 pageable device-to-host copies (stage_planes_to_host)
   struct HostItem { void* p = nullptr; size_t off[3] = {0, 0, 0}; const uint8_t* rgb = nullptr; };   // p points into one of host_chunks; rgb: tight RGB24 rows (resident RGB)
@@ -117,6 +119,7 @@ struct hipdec_batch : BatchLayout {
     for (auto& c : rgb_chunks) pinned_release(c.first, c.second);
     if (rgb_dev) { arena_release(rgb_dev, rgb_capacity); rgb_note_unused((int)rgb_off.size() - rgb_consumed.load()); }
     color_batch_state_free(color);
+    color_batch_state_free(color_scaled);
     if (arena) arena_release(arena, arena_capacity);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : chain_events) if (e) (void)hipEventDestroy(e);
@@ -140,6 +143,7 @@ int build_batch(hipdec_batch& b, int n, const void* const* data, const size_t* s
 {
   std::string err;
   b.device = active_device();
+  b.max_pixels = max_pixels;
   int rc = chains ? layout_batch_plan_chains(b, chains->n_tracks, chains->first, chains->count, data, sizes, max_pixels, err, chains->seqs, chains->bad_track)
                   : layout_batch_plan(b, n, data, sizes, max_pixels, err, seqs);
   if (rc != HIPDEC_OK) return set_error(rc, "%s", err.c_str());
@@ -642,22 +646,46 @@ int hipdec_copy2d_d2d(void* dst_dev, size_t dst_stride, const void* src_dev, siz
   return 0;
 }
 
-int hipdec_batch_to_rgb(hipdec_batch* b, int i, int out_chroma, void* out_dev, size_t out_stride, void* stream)
+}  // extern "C"
+
+namespace {
+
+// hipdec_batch_to_rgb, and - with a scale request - hipdec_batch_to_rgb_scaled: the same argument checks and planner rules; the request makes the colour
+// entry points end in the fused scale + colour kernel (color.hip).  Box presents the planes as the 4:4:4 image they are scaled to.
+struct ScaleRequest { int ow, oh, filter; };
+int copy_rows_to_host(void* dst, size_t dst_stride, const void* dsrc, size_t src_stride, size_t row_bytes, int rows, hipStream_t s);   // decoder_color_boundary.inc
+int batch_to_rgb_impl(hipdec_batch* b, int i, int out_chroma, void* out_dev, size_t out_stride, void* stream, const ScaleRequest* rq)
 {
   if (!b || i < 0 || i >= (int)b->pics.size() || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb: bad arguments");
   DeviceScope scope(b->device);
   if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb: the batch's arena was handed to another batch");
   const PicParams& P = b->params[i];
+  int cf = P.chroma_format_idc;   // the chroma format the planner rules below see
   const hipdec_image_info& I = b->pics[i].info;
+  struct ScaleScope { bool on; ~ScaleScope() { if (on) color_scale_clear(); } } scale_scope{rq != nullptr};
+  // a request serves exactly ONE launch and the entry point that takes it clears it: one that did not (it launched a full-size kernel) is an error here
+  auto taken = [&](int rc) -> int {
+    if (!rc && rq && color_scale_pending()) return set_error(HIPDEC_ERR_UNSUPPORTED, "to_rgb_scaled: the colour entry point did not take the scale request");
+    return rc;
+  };
+  if (rq) {
+    if (rq->ow < 1 || rq->oh < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb_scaled: output size %d x %d", rq->ow, rq->oh);
+    if (rq->filter != HIPDEC_SCALE_NEAREST && rq->filter != HIPDEC_SCALE_BOX) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb_scaled: unknown filter %d", rq->filter);
+    if (b->max_pixels && (uint64_t)rq->ow * (uint64_t)rq->oh > b->max_pixels)
+      return set_error(HIPDEC_ERR_LIMIT, "to_rgb_scaled: output of %d x %d pixels exceeds max_image_size_pixels", rq->ow, rq->oh);
+    color_scale_request(rq->ow, rq->oh, rq->filter, P.chroma_format_idc == 1 || P.chroma_format_idc == 2 ? 1 : 0, P.chroma_format_idc == 1 ? 1 : 0);
+    if (rq->filter == HIPDEC_SCALE_BOX && cf) cf = 3;   // (box: the 4:4:4 image the planes are scaled to)
+  }
   {
     const size_t bpp = out_chroma == 10 ? 3 : (out_chroma == 11 ? 4 : (out_chroma == 12 || out_chroma == 14 ? 6 : 0));
-    if (bpp && out_stride < (size_t)P.out_width * bpp)
-      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb: out_stride %zu is smaller than a row of %zu bytes", out_stride, (size_t)P.out_width * bpp);
+    const size_t row_px = rq ? (size_t)rq->ow : (size_t)P.out_width;
+    if (bpp && out_stride < row_px * bpp)
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb: out_stride %zu is smaller than a row of %zu bytes", out_stride, row_px * bpp);
   }
-  if (!P.chroma_format_idc) {   // Op_mono_to_RGB24_32: 8-bit only, as in the reference
+  if (!cf) {   // Op_mono_to_RGB24_32: 8-bit only, as in the reference
     if (b->wide || (out_chroma != 10 && out_chroma != 11)) return set_error(HIPDEC_ERR_UNSUPPORTED, "to_rgb: monochrome input goes to 8-bit RGB / RGBA only");
     void* ms = stream ? (void*)follow_stream(b, stream) : (void*)b->last_stream;
-    const int rc = hipdec_color_mono_to_rgb24(b->arena + P.off_out[0], P.out_stride[0], nullptr, 0, P.out_width, P.out_height, out_dev, out_stride, out_chroma == 11, ms);
+    const int rc = taken(hipdec_color_mono_to_rgb24(b->arena + P.off_out[0], P.out_stride[0], nullptr, 0, P.out_width, P.out_height, out_dev, out_stride, out_chroma == 11, ms));
     b->mark_done(ms ? (hipStream_t)ms : default_stream());
     return rc;
   }
@@ -672,30 +700,100 @@ int hipdec_batch_to_rgb(hipdec_batch* b, int i, int out_chroma, void* out_dev, s
   if ((out_chroma == 10 || out_chroma == 11) && b->wide) {
     // > 8-bit planes to 8-bit RGB(A): one of the two chains of the planner (nearest-neighbour upsampling is this entry point's), fused into one pass
     const int m = I.matrix_coeffs == 2 ? 6 : I.matrix_coeffs;
-    const int sdr_first = P.chroma_format_idc == 1 && I.full_range_flag && m != 0 && m != 8;
-    return hipdec_color_hdr_to_rgb24(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height, I.bit_depth_luma,
-                                     P.chroma_format_idc, &nclx, out_dev, out_stride, out_chroma == 11, sdr_first, s);
+    const int sdr_first = cf == 1 && I.full_range_flag && m != 0 && m != 8;
+    return taken(hipdec_color_hdr_to_rgb24(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height, I.bit_depth_luma,
+                                     cf, &nclx, out_dev, out_stride, out_chroma == 11, sdr_first, s));
   }
   if (out_chroma == 10 || out_chroma == 11) {
     // planner rule: integer op only for full range and a matrix it accepts
     const int m = I.matrix_coeffs == 2 ? 6 : I.matrix_coeffs;
-    if (P.chroma_format_idc == 1 && I.full_range_flag && m != 0 && m != 8)
-      return hipdec_color_420_to_rgb24(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height, &nclx, out_dev,
-                                       out_stride, out_chroma == 11, s);
+    if (cf == 1 && I.full_range_flag && m != 0 && m != 8)
+      return taken(hipdec_color_420_to_rgb24(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height, &nclx, out_dev,
+                                       out_stride, out_chroma == 11, s));
     // 4:4:4 planes take Op_YCbCr_to_RGB<uint8_t> + Op_RGB_to_RGB24_32 whatever the range (the only chain the planner has for them)
-    return hipdec_color_ycbcr_to_rgb24_float(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height,
-                                             P.chroma_format_idc, &nclx, out_dev, out_stride, out_chroma == 11, s);
+    return taken(hipdec_color_ycbcr_to_rgb24_float(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height,
+                                             cf, &nclx, out_dev, out_stride, out_chroma == 11, s));
   }
   if (out_chroma == 12 || out_chroma == 14) {
     if (!b->wide) return set_error(HIPDEC_ERR_UNSUPPORTED, "to_rgb: RRGGBB output needs >8-bit planes");
     const int m = I.matrix_coeffs == 2 ? 6 : I.matrix_coeffs;
-    if (P.chroma_format_idc != 1 || m == 0 || m == 8)     // planner rule: the 4:2:0 op does not take these; Op_YCbCr_to_RGB<uint16_t> + the interleave does
-      return hipdec_color_ycbcr_to_rrggbb_float(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height, I.bit_depth_luma,
-                                                P.chroma_format_idc, &nclx, out_dev, out_stride, out_chroma == 14, s);
-    return hipdec_color_420_to_rrggbb(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height, I.bit_depth_luma,
-                                      &nclx, out_dev, out_stride, out_chroma == 14, s);
+    if (cf != 1 || m == 0 || m == 8)     // planner rule: the 4:2:0 op does not take these; Op_YCbCr_to_RGB<uint16_t> + the interleave does
+      return taken(hipdec_color_ycbcr_to_rrggbb_float(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height, I.bit_depth_luma,
+                                                cf, &nclx, out_dev, out_stride, out_chroma == 14, s));
+    return taken(hipdec_color_420_to_rrggbb(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height, I.bit_depth_luma,
+                                      &nclx, out_dev, out_stride, out_chroma == 14, s));
   }
   return set_error(HIPDEC_ERR_UNSUPPORTED, "to_rgb: unsupported output chroma %d", out_chroma);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hipdec_batch_to_rgb(hipdec_batch* b, int i, int out_chroma, void* out_dev, size_t out_stride, void* stream)
+{
+  return batch_to_rgb_impl(b, i, out_chroma, out_dev, out_stride, stream, nullptr);
+}
+
+int hipdec_batch_to_rgb_scaled(hipdec_batch* b, int i, int out_chroma, int out_width, int out_height, int filter, void* out_dev, size_t out_stride, void* stream)
+{
+  const ScaleRequest rq{out_width, out_height, filter};
+  return batch_to_rgb_impl(b, i, out_chroma, out_dev, out_stride, stream, &rq);
+}
+
+int hipdec_batch_to_rgb_scaled_all(hipdec_batch* b, int out_chroma, const int* out_widths, const int* out_heights, int filter, void* const* outs_dev,
+                                   const size_t* out_strides, void* stream)
+{
+  if (!b || !out_widths || !out_heights || !outs_dev || !out_strides) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb_scaled_all: bad arguments");
+  DeviceScope scope(b->device);
+  if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb_scaled_all: the batch's arena was handed to another batch");
+  hipStream_t s = follow_stream(b, stream);
+  color_capture_begin();
+  for (int i = 0; i < (int)b->pics.size(); i++) {
+    const ScaleRequest rq{out_widths[i], out_heights[i], filter};
+    if (int rc = batch_to_rgb_impl(b, i, out_chroma, outs_dev[i], out_strides[i], (void*)s, &rq)) { color_capture_abort(); return rc; }
+  }
+  const size_t slot = b->runs ? (b->runs - 1) % (b->ev.size() / kEv) : 0;
+  hipEvent_t* ev = b->ev.data() + kEv * slot;
+  HIPDEC_CHECK_HIP(hipEventRecord(ev[6], s));
+  int rc = color_capture_launch_scaled(b->color_scaled, filter, s);
+  HIPDEC_CHECK_HIP(hipEventRecord(ev[7], s));
+  if (!rc && b->runs) b->colour_timed[slot] = 1;
+  b->mark_done(s);
+  return rc;
+}
+
+// plane c of item i through the plane scaler into a host buffer: what hipdec_image_scale hands out for that plane
+int hipdec_batch_read_plane_scaled(hipdec_batch* b, int i, int c, int out_width, int out_height, int filter, void* dst, size_t dst_stride)
+{
+  if (!b || i < 0 || i >= (int)b->pics.size() || c < 0 || c > 2 || !dst) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "read_plane_scaled: bad arguments");
+  DeviceScope scope(b->device);
+  if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "read_plane_scaled: the batch's arena was handed to another batch");
+  if (out_width < 1 || out_height < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "read_plane_scaled: output size %d x %d", out_width, out_height);
+  if (filter != HIPDEC_SCALE_NEAREST && filter != HIPDEC_SCALE_BOX) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "read_plane_scaled: unknown filter %d", filter);
+  if (b->max_pixels && (uint64_t)out_width * (uint64_t)out_height > b->max_pixels)
+    return set_error(HIPDEC_ERR_LIMIT, "read_plane_scaled: output of %d x %d pixels exceeds max_image_size_pixels", out_width, out_height);
+  const PicParams& P = b->params[i];
+  if (c > 0 && !P.chroma_format_idc) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "read_plane_scaled: monochrome image has no chroma planes");
+  const size_t es = b->wide ? 2 : 1;
+  const int sx = c && P.chroma_format_idc != 3 ? 2 : 1, sy = c && P.chroma_format_idc == 1 ? 2 : 1;
+  const int qw = (out_width + sx - 1) / sx, qh = (out_height + sy - 1) / sy;
+  if (dst_stride < (size_t)qw * es) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "read_plane_scaled: dst_stride %zu is smaller than a row of %zu bytes", dst_stride, (size_t)qw * es);
+  return guarded("read_plane_scaled", [&]() -> int {
+    hipStream_t s = follow_stream(b, nullptr);
+    const size_t st = ((size_t)qw * es + 255) & ~(size_t)255;
+    void* d = nullptr; size_t cap = 0;
+    HIPDEC_CHECK_HIP(arena_acquire(&d, st * (size_t)qh + 256, &cap));
+    struct Release { hipStream_t s; void* d; size_t cap; ~Release() { (void)hipStreamSynchronize(s); arena_release(d, cap); } } rel{s, d, cap};
+    uint8_t* rows = (uint8_t*)d + 256;   // (the parameter block in front of the rows)
+    PlaneScaleParams j{b->arena + P.off_out[c], P.out_stride[c], c ? P.out_cwidth : P.out_width, c ? P.out_cheight : P.out_height, rows, st, qw, qh,
+                       P.out_width, P.out_height, out_width, out_height, 0};
+    static_assert(sizeof(PlaneScaleParams) <= 256, "parameter block");
+    int rc = scale_planes_launch(&j, 1, (int)es, filter, d, s);
+    b->mark_done(s);
+    if (rc) return rc;
+    return copy_rows_to_host(dst, dst_stride, rows, st, (size_t)qw * es, qh, s);
+  });
 }
 
 int hipdec_batch_to_rgb_all(hipdec_batch* b, int out_chroma, void* const* outs_dev, const size_t* out_strides, void* stream)

@@ -31,7 +31,7 @@ std::mutex g_res_mu;
 //  run after the HIP runtime and this library's pools are gone; hipdec_shutdown() / the plugin's deinit empty it in good time)
 std::unordered_map<const void*, ResidentPlane>& g_resident = *new std::unordered_map<const void*, ResidentPlane>();   // by host plane address
 uint64_t g_res_tick = 0;
-std::atomic<uint64_t> g_cb_conversions{0}, g_cb_resident{0}, g_cb_launches{0}, g_xf_transforms{0}, g_grid_canvases{0};
+std::atomic<uint64_t> g_cb_conversions{0}, g_cb_resident{0}, g_cb_launches{0}, g_xf_transforms{0}, g_grid_canvases{0}, g_img_scales{0};
 
 // Content identity of a host plane: EVERY byte of every row (64-bit lanes, four independent multiply-rotate chains, ~10 GB/s on one
 // host core).  libheif edits decoded planes in place between the plugin's hand-over and the colour conversion (mirror_inplace,
@@ -677,6 +677,93 @@ int hipdec_image_transform(const hipdec_color_image* in, int op, const int* args
     return 0;
   });
 }
+
+// heif_image_scale_image() (libheif/api/libheif/heif_image.cc:240 -> HeifPixelImage::scale_nearest_neighbor, image/pixelimage.cc:1783-1972) over the planes
+// of an image, on the device: all planes as ONE launch of the plane scaler (color.hip).  HIPDEC_SCALE_NEAREST is the reference's arithmetic (every plane
+// indexed with the IMAGE's sizes, chroma planes at the subsampled size of the output image), HIPDEC_SCALE_BOX the area average of heif_hipdec.h (every
+// plane with its own sizes).  Same plane conventions as hipdec_image_transform.
+int hipdec_image_scale(const hipdec_color_image* in, int out_width, int out_height, int filter, hipdec_color_image* out)
+{
+  if (!in || !out || in->width <= 0 || in->height <= 0 || !in->plane[0] || in->bit_depth < 8 || in->bit_depth > 16)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "image_scale: bad arguments");
+  if (out_width < 1 || out_height < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "image_scale: output size %d x %d", out_width, out_height);
+  if (filter != HIPDEC_SCALE_NEAREST && filter != HIPDEC_SCALE_BOX) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "image_scale: unknown filter %d", filter);
+  if (int rc = ensure_init()) return rc;
+  return guarded("image_scale", [&]() -> int {
+    const int w = in->width, h = in->height;
+    const bool has_chroma = in->plane[1] && in->plane[2];
+    const int chroma = has_chroma ? in->chroma : 0;
+    if (has_chroma && (chroma < 1 || chroma > 3)) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "image_scale: chroma must be 1 (4:2:0), 2 (4:2:2) or 3 (4:4:4)");
+    const size_t es = in->bit_depth > 8 ? 2 : 1;
+    const int sx = (chroma == 1 || chroma == 2) ? 2 : 1, sy = chroma == 1 ? 2 : 1;
+    hipStream_t s = stream_acquire_priority();
+    struct Release { hipStream_t s; std::vector<std::pair<void*, size_t>> bufs;
+                     ~Release() { (void)hipStreamSynchronize(s); for (auto& b : bufs) arena_release(b.first, b.second); stream_release(s); } } rel{s, {}};
+    auto scratch = [&](size_t bytes, uint8_t** p) -> int {
+      void* d = nullptr; size_t cap = 0;
+      HIPDEC_CHECK_HIP(arena_acquire(&d, bytes ? bytes : 256, &cap));
+      rel.bufs.emplace_back(d, cap); *p = (uint8_t*)d;
+      return 0;
+    };
+    std::shared_ptr<void> keep[4];
+    struct Result { int c, w, h; const uint8_t* dev; size_t dev_stride; std::shared_ptr<void> owner; };
+    std::vector<Result> results;
+    PlaneScaleParams jobs[4];
+    int job_plane[4], n_jobs = 0;
+    for (int c = 0; c < 4; c++) {
+      if (!in->plane[c]) continue;
+      if ((c == 1 || c == 2) && !has_chroma) continue;
+      if (!out->plane[c]) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "image_scale: no destination for plane %d", c);
+      const bool sub = c == 1 || c == 2;
+      const int pw = sub ? (w + sx - 1) / sx : w, ph = sub ? (h + sy - 1) / sy : h;
+      const int qw = sub ? (out_width + sx - 1) / sx : out_width, qh = sub ? (out_height + sy - 1) / sy : out_height;   // get_subsampled_size, pixelimage.cc:1832-1843
+      if (in->stride[c] < (size_t)pw * es) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "image_scale: stride %zu of plane %d is smaller than its rows", in->stride[c], c);
+      if (out->stride[c] < (size_t)qw * es) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "image_scale: destination stride of plane %d too small", c);
+      const uint8_t* dp = nullptr; size_t ds = 0;
+      if (in->on_device) { dp = (const uint8_t*)in->plane[c]; ds = in->stride[c]; }
+      else if (resident_find(in->plane[c], in->stride[c], pw, ph, in->bit_depth, &dp, &ds, keep[c])) g_cb_resident++;
+      else {
+        uint8_t* d = nullptr;
+        const size_t st = ((size_t)pw * es + 255) & ~(size_t)255;
+        if (int rc = scratch(st * ph, &d)) return rc;
+        HIPDEC_CHECK_HIP(hipMemcpy2DAsync(d, st, in->plane[c], in->stride[c], (size_t)pw * es, ph, hipMemcpyHostToDevice, s));
+        dp = d; ds = st;
+      }
+      uint8_t* dout = (uint8_t*)out->plane[c];
+      size_t dout_stride = out->stride[c];
+      if (!out->on_device) {
+        dout_stride = ((size_t)qw * es + 255) & ~(size_t)255;
+        if (g_track_planes.load(std::memory_order_relaxed)) {
+          // the result stays on the device behind its host copy: the colour conversion of the scaled image reads it there
+          void* d = nullptr; size_t cap = 0;
+          HIPDEC_CHECK_HIP(arena_acquire(&d, dout_stride * qh ? dout_stride * qh : 256, &cap));
+          int dev_index = 0;
+          (void)hipGetDevice(&dev_index);
+          std::shared_ptr<void> owner(d, [cap, dev_index](void* q) { DeviceScope scope(dev_index); arena_release(q, cap); });
+          dout = (uint8_t*)d;
+          results.push_back(Result{c, qw, qh, dout, dout_stride, std::move(owner)});
+        } else if (int rc = scratch(dout_stride * qh, &dout)) return rc;
+      }
+      jobs[n_jobs] = PlaneScaleParams{dp, ds, pw, ph, dout, dout_stride, qw, qh, w, h, out_width, out_height, 0};
+      job_plane[n_jobs++] = c;
+    }
+    uint8_t* dev_params = nullptr;
+    if (int rc = scratch(sizeof(jobs), &dev_params)) return rc;
+    if (int rc = scale_planes_launch(jobs, n_jobs, (int)es, filter, dev_params, s)) return rc;
+    if (!out->on_device)
+      for (int k = 0; k < n_jobs; k++) {
+        const int c = job_plane[k];
+        if (int rc = copy_rows_to_host((void*)out->plane[c], out->stride[c], jobs[k].out, jobs[k].os, (size_t)jobs[k].qw * es, jobs[k].qh, s)) return rc;
+      }
+    HIPDEC_CHECK_HIP(hipStreamSynchronize(s));
+    for (auto& r : results) resident_note_buffer(out->plane[r.c], out->stride[r.c], r.w, r.h, in->bit_depth, r.dev, r.dev_stride, std::move(r.owner));
+    out->width = out_width; out->height = out_height; out->chroma = in->chroma; out->bit_depth = in->bit_depth;
+    g_img_scales++;
+    return 0;
+  });
+}
+
+void hipdec_image_scale_stats(uint64_t* images) { if (images) *images = g_img_scales.load(); }
 
 }  // extern "C"
 

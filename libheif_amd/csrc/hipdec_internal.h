@@ -72,6 +72,24 @@ int color_capture_take(ColorBatchState& st, hipStream_t s, const void** dev, int
 int color_variant_rgb24_u8();
 void color_batch_state_free(ColorBatchState& st);
 
+// Scaled output (color.hip).  A scale request set on this thread makes the NEXT hipdec_color_* entry point that ends in an interleaved layout run (or,
+// in capture mode, record) the fused scale + colour kernel instead of the full-size one: argument checks, planner rules and coefficients stay theirs.
+// The launch clears the request; color_scale_pending() afterwards means the entry point did not take it (the caller refuses).
+// sH / sV: subsampling shifts of the chroma planes that are handed in (the box filter presents them to the entry points as 4:4:4).
+void color_scale_request(int out_width, int out_height, int filter, int sH, int sV);
+void color_scale_clear();
+bool color_scale_pending();
+int color_capture_launch_scaled(ColorBatchState& st, int filter, hipStream_t s);   // the recorded scaled blocks of this thread as ONE launch
+// one plane through the plane scaler; (pw, ph) -> (qw, qh) are the PLANE's sizes, (iw, ih) -> (ow, oh) the image's (what the nearest-neighbour index uses)
+struct PlaneScaleParams {
+  const uint8_t* in; size_t is; int pw, ph;
+  uint8_t* out; size_t os; int qw, qh;
+  int iw, ih, ow, oh;
+  int tile;   // box: output samples per workgroup (filled in by scale_planes_launch)
+};
+// n planes as one launch; dev_params: room for n blocks in device memory, `jobs` must stay alive until `s` has passed the upload
+int scale_planes_launch(PlaneScaleParams* jobs, int n, int bytes_per_sample, int filter, void* dev_params, hipStream_t s);
+
 // No C++ exception may cross the C ABI (the caller is libheif, or cgo / JNI / ctypes): every entry point that parses untrusted
 // input or allocates runs its body through guarded().
 template <class F> int guarded(const char* what, F&& body)

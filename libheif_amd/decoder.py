@@ -37,6 +37,9 @@ def _bind(lib):
     lib.hipdec_batch_to_rgb.argtypes = [vp, ci, ci, vp, sz, vp]
     lib.hipdec_batch_to_rgb_all.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(sz), vp]
     lib.hipdec_batch_run_rgb.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(sz), vp]
+    lib.hipdec_batch_to_rgb_scaled.argtypes = [vp, ci, ci, ci, ci, ci, vp, sz, vp]
+    lib.hipdec_batch_to_rgb_scaled_all.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(vp), C.POINTER(sz), vp]
+    lib.hipdec_batch_read_plane_scaled.argtypes = [vp, ci, ci, ci, ci, ci, vp, sz]
     lib.hipdec_batch_last_timing_us.argtypes = [vp, C.POINTER(C.c_float)]
     lib.hipdec_batch_item_packed_bytes.restype = sz
     lib.hipdec_batch_item_packed_bytes.argtypes = [vp, ci]
@@ -87,6 +90,20 @@ def pipeline_stats():
     a, b = C.c_uint64(), C.c_uint64()
     lib.hipdec_decoder_pipeline_stats(C.byref(a), C.byref(b))
     return a.value, b.value
+
+
+SCALE_NEAREST, SCALE_BOX = 0, 1   # hipdec_scale_filter
+
+
+def fit_within(width, height, size):
+    """The thumbnail size examples/heif_thumbnailer.cc:172-186 computes: the image as it is when both sides fit into `size`, else the longer
+    side becomes `size` and the other one follows with integer division (which may give 0: the thumbnailer refuses that, and so does
+    every scaled entry point here)."""
+    if width <= size and height <= size:
+        return width, height
+    if width > height:
+        return size, height * size // width
+    return width * size // height, size
 
 
 class DecodedImage:
@@ -256,6 +273,51 @@ class Batch:
         """asynchronous: decode + colour stage into the pre-allocated buffers as ONE call (for 8-bit 4:2:0 -> RGB24 the colour conversion is
         fused into the SAO kernel's store path)"""
         check(self._lib.hipdec_batch_run_rgb(self._h, self._rgb_chroma, self._rgb_ptrs, self._rgb_strides, stream))
+
+    def to_rgb_scaled(self, i, width, height, filter=SCALE_BOX, out_chroma=10):
+        """item i as interleaved rows of width x height pixels straight from its decoded planes (one fused scale + colour kernel)"""
+        bpp = {10: 3, 11: 4, 12: 6, 14: 6}[out_chroma]
+        buf = DeviceBuffer(max(1, width) * max(1, height) * bpp)
+        check(self._lib.hipdec_batch_to_rgb_scaled(self._h, i, out_chroma, width, height, filter, buf.ptr, width * bpp, None))
+        check(self._lib.hipdec_stream_synchronize(None))
+        return buf.to_numpy((height, width * bpp), np.uint8)
+
+    def alloc_rgb_scaled(self, sizes, out_chroma=10):
+        """pre-allocates one scaled output buffer per item for to_rgb_scaled_all(); sizes: (width, height) per item, or one pair for all"""
+        if len(sizes) == 2 and not hasattr(sizes[0], "__len__"):
+            sizes = [tuple(sizes)] * self.n
+        assert len(sizes) == self.n
+        bpp = {10: 3, 11: 4, 12: 6, 14: 6}[out_chroma]
+        self._srgb = [(DeviceBuffer(w * h * bpp), w * bpp, h) for w, h in sizes]
+        self._srgb_chroma = out_chroma
+        self._srgb_w = (C.c_int * self.n)(*[w for w, _ in sizes])
+        self._srgb_h = (C.c_int * self.n)(*[h for _, h in sizes])
+        self._srgb_ptrs = (C.c_void_p * self.n)(*[buf.ptr for buf, _, _ in self._srgb])
+        self._srgb_strides = (C.c_size_t * self.n)(*[stride for _, stride, _ in self._srgb])
+
+    def to_rgb_scaled_all(self, filter=SCALE_BOX, stream=None):
+        """asynchronous: every item scaled to its pre-allocated size, ONE launch"""
+        check(self._lib.hipdec_batch_to_rgb_scaled_all(self._h, self._srgb_chroma, self._srgb_w, self._srgb_h, filter, self._srgb_ptrs,
+                                                       self._srgb_strides, stream))
+
+    def rgb_scaled(self, i):
+        buf, stride, h = self._srgb[i]
+        check(self._lib.hipdec_stream_synchronize(None))
+        return buf.to_numpy((h, stride), np.uint8)
+
+    def planes_scaled(self, i, width, height, filter=SCALE_BOX):
+        """the planes of item i scaled as hipdec_image_scale does it (chroma planes at the subsampled size of the width x height image)"""
+        d = self.info(i)
+        dt = np.uint16 if d["bit_depth_luma"] > 8 else np.uint8
+        cf = d["chroma_format_idc"]
+        out = []
+        for c in range(3 if cf else 1):
+            w = width if c == 0 or cf == 3 else (width + 1) // 2
+            h = height if c == 0 or cf != 1 else (height + 1) // 2
+            a = np.empty((max(h, 0), max(w, 0)), dt)
+            check(self._lib.hipdec_batch_read_plane_scaled(self._h, i, c, width, height, filter, a.ctypes.data, w * a.itemsize))
+            out.append(a)
+        return out
 
     def rgb(self, i):
         buf, stride, h = self._rgb[i]
