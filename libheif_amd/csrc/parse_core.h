@@ -37,6 +37,11 @@
 #if defined(HIPDEC_HOST_EMU)
 #include <string.h>
 #define PC_DEV static inline
+// path counters of the CPU tests (read by tests/emu/parse_emu.cc: emu_path_counts): 0 / 1 / 2 = coeff_abs_level_remaining decoded by one division, by
+// two, bin by bin; 3 = ... bin by bin because the window holds emulation-prevention candidates (or ends); 4 = a level outside 16 bits refused.
+// Defined here (one object per library, C++17 inline variable): the header needs nothing from the harness that includes it
+inline uint64_t hipdec_emu_path_counts[8] = {};
+#define PC_COUNT(k) (hipdec_emu_path_counts[k]++)
 struct VReg { uint32_t v[64]; };
 #define PC_VEC_BEGIN for (int lane = 0; lane < 64; lane++) { (void)lane;
 #define PC_VEC_END }
@@ -60,6 +65,7 @@ PC_DEV uint32_t pc_mul24(uint32_t a, uint32_t b) { return a * b; }
 // value of the lane below (lane 0: its own); only valid inside PC_VEC_BEGIN .. PC_VEC_END
 #define PC_FROM_LANE_BELOW(r) ((r).v[lane ? lane - 1 : 0])
 #else
+#define PC_COUNT(k) do { } while (0)
 #include <hip/hip_runtime.h>
 #define PC_DEV __device__ __forceinline__
 typedef uint32_t VReg;
@@ -607,6 +613,7 @@ PC_DEV UReg decode_remaining_v(PS& s, UReg rice)
         if (took) { vl += byte << bn2; s.pos = p + 1u; }
         s.value = vl - pc_mul24(q >> (8u - len), scaled);
         s.bits_needed = took ? bn2 - 8u : bn2;
+        PC_COUNT(0);
         return val;
       }
       // codes of 9 .. 16 bins (escape codes of large levels: the first coefficients of a busy sub-block, before cRiceParam has grown): the next 8
@@ -637,12 +644,15 @@ PC_DEV UReg decode_remaining_v(PS& s, UReg rice)
             s.pos = p + (took2 ? 2u : 1u);
             s.value = vl - pc_mul24(q2 >> (8u - m), scaled);
             s.bits_needed = took2 ? bn3 - 8u : bn3;
+            PC_COUNT(1);
             return val;
           }
         }
       }
     }
   }
+  PC_COUNT(2);
+  if (!(s.pos < s.fast_limit)) PC_COUNT(3);
   return pc_vec((uint32_t)decode_remaining(s, (int)pc_uni(rice)));
 }
 // scan of sub-blocks: lg = log2 of the sub-block grid width (0..3)
@@ -824,7 +834,7 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
   {
     VReg vbad;
     PC_VEC_BEGIN PC_L(vbad) = PC_L(vovf) > 32767u ? 1u : 0u; PC_VEC_END
-    if (pc_ballot(vbad)) s.err = DEV_ERR_SYNTAX;
+    if (pc_ballot(vbad)) { s.err = DEV_ERR_SYNTAX; PC_COUNT(4); }
   }
   return ts;
 }

@@ -2,7 +2,7 @@
 //
 // Stands in for libde265's scaling / transform stages behind de265_decode() (reference call site
 // libheif/plugins/decoder_libde265.cc:402).  ITU-T H.265 8.6.2-8.6.4: scaling with flat lists,
-// transform skip, cu_transquant_bypass, DST-VII 4x4 for intra luma, DCT 4..32, 16-bit intermediate clip.
+// transform skip, cu_transquant_bypass, DST-VII 4x4 for intra luma, DCT 4..32, 16-bit intermediate clip; the residual is stored saturated to 16 bits.
 //
 // MI355X mapping: residuals do not depend on prediction, so they are taken off the intra-prediction
 // dependency chain entirely: this kernel runs over ALL transform blocks of the batch in parallel (one
@@ -120,6 +120,19 @@ inline int dot2(uint32_t a, uint32_t b, int acc)
 }
 #endif
 
+// Two residual samples as the int16 pair the kernel hands on, SATURATED: 8.6.4.2 does not bound the second-stage output to 16 bits (a first-stage row
+// at 32767 gives 32767 * 1862 >> 10 = 59 582 in a 32x32 block of a 10-bit picture, up to 238 336 at 12 bits), and every consumer computes
+// Clip1(pred + res) with pred <= 4095: a residual beyond +-32767 decides the clip either way, its low 16 bits would not.  One v_cvt_pk_i16_i32.
+#ifndef HIPDEC_HOST_EMU
+__device__ __forceinline__ uint32_t pack16(int lo, int hi) { return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(lo, hi)); }
+#else
+inline uint32_t pack16(int lo, int hi)
+{
+  lo = lo < -32768 ? -32768 : (lo > 32767 ? 32767 : lo); hi = hi < -32768 ? -32768 : (hi > 32767 ? 32767 : hi);
+  return ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16);
+}
+#endif
+
 // one transform block, by one wave: coef (global, n*n int16, raster) -> residual in place
 // SL: the block's ScalingFactor table m[y * n + x] (read from the picture's 2 KB table in HBM: cache-resident, and only
 // streams with scaling lists pay for it - no LDS is set aside) replaces the flat factor 16 (8.6.4.2)
@@ -204,10 +217,10 @@ __device__ __forceinline__ void residual_block(ResLds& L, int wave, int lane, in
 #pragma unroll
       for (int k = 0; k < 4; k++) sum[k] = dot2(((const uint32_t*)(et + (i0 + k) * n))[j], t, sum[k]);
     }
-    int16_t r[4];
+    int r[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++) r[k] = (int16_t)((sum[k] + (1 << (bd_shift2 - 1))) >> bd_shift2);
-    *(uint2*)&coef[idx] = make_uint2((uint16_t)r[0] | ((uint32_t)(uint16_t)r[1] << 16), (uint16_t)r[2] | ((uint32_t)(uint16_t)r[3] << 16));
+    for (int k = 0; k < 4; k++) r[k] = (sum[k] + (1 << (bd_shift2 - 1))) >> bd_shift2;
+    *(uint2*)&coef[idx] = make_uint2(pack16(r[0], r[1]), pack16(r[2], r[3]));
   }
   lds_sync();
 }
@@ -336,7 +349,6 @@ __device__ __forceinline__ void row_store(int16_t* p, const RowRaw<N>& r)
   }
 }
 template <int N> __device__ __forceinline__ int row_get(const RowRaw<N>& r, int k) { return (int)(int16_t)(r.w[k >> 1] >> ((k & 1) * 16)); }
-__device__ __forceinline__ uint32_t pack16(int lo, int hi) { return ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16); }
 
 // All blocks of one size (N = 1 << LG) of the CTB: pass q takes the blocks q * BPP .. of `list`, lane = block * N + row; a wave takes the passes
 // first, first + 4, ...  The NEXT pass's rows are requested before the current pass is worked on.

@@ -282,6 +282,73 @@ static void sdh_fix(int32_t* lev, int log2n, int scanIdx)
 }
 
 /* ------------------------------------------------------------------------------------------ */
+/* value torture (hevc_testenc_params::level_torture_*): levels no honest quantiser produces   */
+/* ------------------------------------------------------------------------------------------ */
+static int remaining_code_len(int v, int rice)   /* bins of coeff_abs_level_remaining = v with cRiceParam = rice (9.3.3.11) */
+{
+  if (v < (4 << rice)) return (v >> rice) + 1 + rice;
+  int p3 = 0;
+  while ((v >> rice) >= ((1 << (p3 + 1)) + 2)) p3++;
+  return 2 * p3 + 4 + rice;
+}
+static void torture_levels(Enc* e, int32_t* lev, int log2n, int scanIdx, int trType)
+{
+  const int n = 1 << log2n;
+  int kind = e->prm.level_torture_kind;
+  if (kind == 0) kind = 1 + (int)(rnd(e) % 3);
+  if (kind == 1) {
+    const int y0 = (int)(rnd(e) % (unsigned)n), mirror = (int)(rnd(e) & 1), deep = (int)(rnd(e) & 1);
+    for (int j = 0; j < n; j++) {
+      int c = trType ? g_dst[j][y0] : g_dct[j * (32 / n)][y0];
+      int neg = (c < 0) ^ mirror;
+      for (int x = 0; x < n; x++) lev[j * n + x] = neg ? (deep ? -32768 : -32767) : 32767;
+    }
+  } else if (kind == 2) {
+    const int shape = (int)(rnd(e) % 3);
+    if (shape < 2) {
+      memset(lev, 0, sizeof(int32_t) * n * n);
+      int v = (int)(rnd(e) & 0xffff) - 32768;
+      lev[shape == 0 ? 0 : n * n - 1] = v ? v : 32767;
+    } else {
+      static const int dens[3] = {100, 50, 8};
+      const int pct = dens[rnd(e) % 3];
+      for (int i = 0; i < n * n; i++) lev[i] = rnd_pct(e, pct) ? (int)(rnd(e) & 0xffff) - 32768 : 0;
+      if (!lev[0] && !lev[n * n - 1]) lev[rnd(e) % (unsigned)(n * n)] = (rnd(e) & 1) ? 32767 : -32768;
+    }
+  } else if (kind == 3) {
+    static int bound[5][4];   /* per cRiceParam: largest value of an 8-bin code, smallest of a 9-bin code, largest of a 16-bin code, smallest of a 17-bin code */
+    if (!bound[0][0])
+      for (int r = 0; r < 5; r++) {
+        int v = 0;
+        while (remaining_code_len(v + 1, r) <= 8) v++;
+        bound[r][0] = v; bound[r][1] = v + 1;
+        while (remaining_code_len(v + 1, r) <= 16) v++;
+        bound[r][2] = v; bound[r][3] = v + 1;
+      }
+    const uint8_t* scanPos = g_scan[2][scanIdx];
+    const int sbw = n >> 2;
+    memset(lev, 0, sizeof(int32_t) * n * n);
+    int done = 0;
+    for (int sb = 0; sb < sbw * sbw; sb++) {
+      if (done && !rnd_pct(e, 60)) continue;
+      done = 1;
+      const int xS = sb % sbw, yS = sb / sbw;
+      /* all 16 positions are significant and large, so position 15 - k is coded with cRiceParam Min(k, 4) and baseLevel 3 (k = 0: the
+         greater2 flag), 2 (k < 8) or 1 */
+      for (int k = 0; k < 16; k++) {
+        const int rice = k < 4 ? k : 4, base = k == 0 ? 3 : (k < 8 ? 2 : 1), t = (int)(rnd(e) % 5), neg = (int)(rnd(e) & 1);
+        int a = t < 4 ? base + bound[rice][t] : (neg ? 32768 : 32767);
+        lev[((yS << 2) + (scanPos[15 - k] >> 4)) * n + (xS << 2) + (scanPos[15 - k] & 15)] = neg ? -a : a;
+      }
+    }
+  } else {
+    memset(lev, 0, sizeof(int32_t) * n * n);
+    const int pos = (int)(rnd(e) % (unsigned)(n * n)), neg = (int)(rnd(e) & 1);
+    lev[pos] = kind == 4 ? 32768 : (kind == 5 ? (neg ? -32769 : 32769) : (neg ? -32768 : 32767));
+  }
+}
+
+/* ------------------------------------------------------------------------------------------ */
 /* residual_coding writer (mirror of the decoder's residual_coding)                            */
 /* ------------------------------------------------------------------------------------------ */
 static void emit_last_prefix(Enc* e, int base, int ctxOffset, int ctxShift, int cMax, int p)
@@ -477,7 +544,7 @@ static int analyse_tb(Enc* e, int x0c, int y0c, int log2n, int cIdx, int mode, i
     for (int x = 0; x < n; x++)
       res[y * n + x] = (int)e->src[cIdx][(y0c + y) * stride + x0c + x] - (int)d->rec[cIdx][(y0c + y) * stride + x0c + x];
   int ts = 0;
-  if (p->transform_skip_enabled_flag && !d->cu_transquant_bypass_flag && log2n == 2) ts = rnd_pct(e, 25);
+  if (p->transform_skip_enabled_flag && !d->cu_transquant_bypass_flag && log2n == 2) ts = e->prm.transform_skip == 2 ? 1 : rnd_pct(e, 25);   /* 2: every 4x4 block */
   int qP;
   if (cIdx == 0) qP = d->cur_qp_y + 6 * (s->bit_depth_luma - 8);
   else {
@@ -488,15 +555,15 @@ static int analyse_tb(Enc* e, int x0c, int y0c, int log2n, int cIdx, int mode, i
   }
   forward_quant(e, lev, res, n, qP, bit_depth, cIdx == 0 && n == 4 && !d->cu_pred_inter, ts, d->cu_transquant_bypass_flag);
   if (e->prm.zero_residual_pct && rnd_pct(e, e->prm.zero_residual_pct)) memset(lev, 0, sizeof(int32_t) * n * n);
+  int scanIdx = 0;
+  if (log2n == 2 || (log2n == 3 && (cIdx == 0 || s->chroma_format_idc == 3))) {
+    if (mode >= 6 && mode <= 14) scanIdx = 2; else if (mode >= 22 && mode <= 30) scanIdx = 1;
+  }
+  if (e->prm.level_torture_pct && rnd_pct(e, e->prm.level_torture_pct))
+    torture_levels(e, lev, log2n, scanIdx, cIdx == 0 && n == 4 && !d->cu_pred_inter);
   int cbf = 0;
   for (int i = 0; i < n * n; i++) if (lev[i]) { cbf = 1; break; }
-  if (cbf && p->sign_data_hiding_enabled_flag && !d->cu_transquant_bypass_flag) {
-    int scanIdx = 0;
-    if (log2n == 2 || (log2n == 3 && (cIdx == 0 || s->chroma_format_idc == 3))) {
-      if (mode >= 6 && mode <= 14) scanIdx = 2; else if (mode >= 22 && mode <= 30) scanIdx = 1;
-    }
-    sdh_fix(lev, log2n, scanIdx);
-  }
+  if (cbf && p->sign_data_hiding_enabled_flag && !d->cu_transquant_bypass_flag) sdh_fix(lev, log2n, scanIdx);
   *ts_out = ts;
   if (cbf) e->cu_any_cbf = 1;
   reconstruct_tb(d, x0c, y0c, log2n, cIdx, mode, cbf, lev, ts);
@@ -944,6 +1011,14 @@ static void enc_coding_quadtree(Enc* e, int x0, int y0, int log2CbSize, int cqtD
     int q = d->qPY_PRED + want;
     if (q < 1 || q > 50) want = 0;
     e->qg_delta = rnd_pct(e, 60) ? want : 0;
+    if (e->prm.qp_delta_wrap_pct && rnd_pct(e, e->prm.qp_delta_wrap_pct)) {
+      /* aim at any QpY of -QpBdOffsetY .. 51 with the one CuQpDeltaVal of the legal range (7.4.9.14) that gets there: far targets wrap in (8-283) */
+      const int off = 6 * (s->bit_depth_luma - 8), period = 52 + off;
+      int delta = (int)(rnd(e) % (unsigned)period) - off - d->qPY_PRED;
+      if (delta > 25 + off / 2) delta -= period;
+      if (delta < -(26 + off / 2)) delta += period;
+      e->qg_delta = delta;
+    }
   }
   if (split) {
     int x1 = x0 + (1 << (log2CbSize - 1)), y1 = y0 + (1 << (log2CbSize - 1));
@@ -1103,7 +1178,7 @@ static void enc_parameter_sets(Enc* e, Bytes* pstream)
   p->sign_data_hiding_enabled_flag = prm->sign_data_hiding;
   p->init_qp_minus26 = 0;
   p->constrained_intra_pred_flag = prm->constrained_intra_pred ? 1 : 0;
-  p->transform_skip_enabled_flag = prm->transform_skip;
+  p->transform_skip_enabled_flag = prm->transform_skip ? 1 : 0;
   p->cu_qp_delta_enabled_flag = prm->cu_qp_delta;
   p->diff_cu_qp_delta_depth = prm->cu_qp_delta ? Min(prm->diff_cu_qp_delta_depth, s->log2_ctb - s->log2_min_cb) : 0;
   p->pps_cb_qp_offset = prm->cb_qp_offset; p->pps_cr_qp_offset = prm->cr_qp_offset;

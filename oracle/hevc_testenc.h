@@ -17,6 +17,7 @@ typedef struct hevc_testenc_params {
   int sao, deblock_disable, beta_offset_div2, tc_offset_div2;
   int sign_data_hiding, cu_qp_delta, diff_cu_qp_delta_depth, transform_skip;
   int lossless_pct;             /* >0 enables transquant bypass; % of CUs coded lossless           */
+                                /* transform_skip: 1 = a quarter of the 4x4 blocks at random, 2 = every 4x4 block */
   int pcm_pct, pcm_loop_filter_disabled;
   int strong_intra_smoothing, scaling_list;
   int cb_qp_offset, cr_qp_offset;
@@ -51,6 +52,18 @@ typedef struct hevc_testenc_params {
                                    at the CRA picture drops the RASL pictures (8.3.3) and decodes everything else identically */
   int hidden_poc;               /* > 0: output_flag_present_flag = 1 and the picture with this PicOrderCnt carries pic_output_flag = 0: it is decoded and may be
                                    referenced but never output (C.5.2.2); every other picture carries pic_output_flag = 1 */
+  /* ---- value torture (all 0 by default: the streams are then byte-identical to those written without these knobs) ---- */
+  int level_torture_pct;        /* % of the coded transform blocks (intra and inter, luma and chroma) whose quantised levels are REPLACED before sign data
+                                   hiding and the residual writer; the encoder reconstructs from what it wrote, fidelity to the source does not matter */
+  int level_torture_kind;       /* 0: one of 1 .. 3 per block.  1 "aligned": lev[j][x] = +-32767 * sign(E[j][y0]) for a random row y0 of the transform matrix
+                                   (a whole first-stage row saturates, the second stage is maximal; mirrored, and with -32768 on the negative side).
+                                   2 "uniform": random levels over -32768 .. 32767: one at DC, one at the last scan position, or dense.
+                                   3 "ladder": every position of a sub-block coded, |level| on the code-length boundaries of coeff_abs_level_remaining
+                                   (9.3.3.11) for the cRiceParam the position is coded with: largest 8-bin code, smallest 9-bin, largest 16-bin, smallest
+                                   17-bin code, 32767 / -32768.  4: NOT a conforming stream: a lone level of +32768; 5: a lone level of magnitude 32769;
+                                   6: the conforming neighbour of 4 / 5: a lone level of +32767 or -32768 */
+  int qp_delta_wrap_pct;        /* % of the quantisation groups whose cu_qp_delta_abs aims at a random QpY of the whole range -QpBdOffsetY .. 51: the
+                                   sum of (8-283) leaves that range and wraps (without this knob QpY stays inside 1 .. 50 and never does) */
 } hevc_testenc_params;
 
 /* planes: tightly packed uint16 samples at display size (chroma (w+1)/2 x (h+1)/2).

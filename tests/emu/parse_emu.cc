@@ -205,6 +205,9 @@ void launch_parse_general(const ParseArgs& a, bool, hipStream_t s) { launch_pars
 
 extern "C" {
 
+// path counters of parse_core.h since the last call (see PC_COUNT there); reading resets them
+void emu_path_counts(uint64_t* out) { for (int k = 0; k < 8; k++) { out[k] = hipdec_emu_path_counts[k]; hipdec_emu_path_counts[k] = 0; } }
+
 // runs every substream in index order (a WPP predecessor always has a smaller index); returns the device status word
 int emu_run_parse(EmuBatch* b)
 {
