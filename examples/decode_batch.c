@@ -7,6 +7,8 @@
  *   ./decode_batch item0.hevc item1.hevc ...          (files as written by tools/streamgen.py, or dumped from a HEIC's hvcC + item data)
  *   ./decode_batch --thumb 256 item0.hevc ...         ends in ONE launch that turns every item into an RGB24 preview that fits into 256 x 256
  *                                                     (the size rule of libheif's examples/heif_thumbnailer.cc:172-186, area-averaged on the device)
+ *   ./decode_batch --tensor 224 item0.hevc ...        ends in ONE launch that writes a float16 N x 3 x 224 x 224 tensor: the centred square of every item,
+ *                                                     area-averaged, (V / 255 - mean) / std with the usual ImageNet constants
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -37,7 +39,13 @@ int main(int argc, char** argv)
     if (thumb < 1) argc = 0;                                       /* no or a bad N: usage */
     else { argv += 2; argc -= 2; }
   }
-  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N] item.hevc [item.hevc ...]\n", prog); return 2; }
+  int tensor = 0;
+  if (!thumb && argc >= 2 && !strcmp(argv[1], "--tensor")) {
+    tensor = argc >= 3 ? atoi(argv[2]) : 0;
+    if (tensor < 1) argc = 0;
+    else { argv += 2; argc -= 2; }
+  }
+  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N | --tensor N] item.hevc [item.hevc ...]\n", prog); return 2; }
   const int n = argc - 1;
   const void** data = (const void**)calloc((size_t)n, sizeof(void*));
   size_t* sizes = (size_t*)calloc((size_t)n, sizeof(size_t));
@@ -106,6 +114,32 @@ int main(int argc, char** argv)
       hipdec_free(outs[i]);
     }
     free(ws); free(hs); free(outs); free(strides);
+  }
+  if (tensor) {                                                    /* the loader's batch tensor as one launch: crop, scale, normalise, float16 NCHW */
+    static const float mean[3] = {0.485f, 0.456f, 0.406f}, std[3] = {0.229f, 0.224f, 0.225f};
+    hipdec_tensor_desc d;
+    memset(&d, 0, sizeof d);
+    d.width = d.height = tensor; d.dtype = HIPDEC_TENSOR_F16; d.layout = HIPDEC_TENSOR_NCHW; d.filter = HIPDEC_SCALE_BOX;
+    for (int c = 0; c < 3; c++) { d.scale[c] = 1.0f / (255.0f * std[c]); d.bias[c] = -mean[c] / std[c]; }
+    hipdec_tensor_entry* e = (hipdec_tensor_entry*)calloc((size_t)n, sizeof(hipdec_tensor_entry));
+    for (int i = 0; i < n; i++) {
+      hipdec_image_info info;
+      hipdec_batch_info(prev, i, &info);
+      const int side = info.width < info.height ? info.width : info.height;
+      e[i].item = i; e[i].left = (info.width - side) / 2; e[i].top = (info.height - side) / 2; e[i].width = e[i].height = side;
+    }
+    const size_t bytes = hipdec_tensor_bytes(&d, n);
+    void* t = bytes ? hipdec_malloc(bytes) : NULL;
+    uint16_t* host = (uint16_t*)malloc(bytes ? bytes : 1);
+    if (!t || !host || hipdec_batch_to_tensor(prev, &d, e, n, t, bytes, NULL) || hipdec_batch_status(prev) || hipdec_memcpy_d2h(host, t, bytes)) {
+      fprintf(stderr, "%s\n", hipdec_last_error());
+      return 1;
+    }
+    unsigned long long sum = 0;
+    for (size_t k = 0; k < bytes / 2; k++) sum += host[k];
+    printf("tensor %dx3x%dx%d float16, sum of the bit patterns %llu\n", n, tensor, tensor, sum);
+    free(host); free(e);
+    hipdec_free(t);
   }
   hipdec_batch_free(prev);
   hipdec_shutdown();

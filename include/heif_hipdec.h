@@ -460,6 +460,56 @@ HIPDEC_API int hipdec_batch_to_rgb_scaled_all(hipdec_batch* b, int out_chroma, c
 /* plane c of item i as hipdec_image_scale would hand it out for an image of out_width x out_height (c > 0: the subsampled size of that), into a host buffer */
 HIPDEC_API int hipdec_batch_read_plane_scaled(hipdec_batch* b, int i, int c, int out_width, int out_height, int filter, void* dst_host, size_t dst_stride);
 
+/* ---- tensor output on the device: cropped, scaled, normalised batches ---------------------------------------------------------------------------
+ * What a training-data loader builds from decoded pictures: a crop window per sample, an optional horizontal flip, one common output size, float values
+ * already multiplied and shifted, one dense tensor.  ONE fused kernel from the decoded planes: no full-size RGB, no scaled intermediate in HBM.
+ *
+ * Output: n_entries samples of three channels R, G, B (a monochrome source gives R = G = B).  Entry e starts at element e * 3 * height * width; NCHW places
+ * element (c, y, x) at (c * height + y) * width + x, NHWC at (y * width + x) * 3 + c; there is no padding.
+ * Entries: `item` selects the batch item (the image form ignores it); [left, left + width) x [top, top + height) is a window in luma samples of the
+ * cropped picture, at any offset and parity; all zeros after `item` mean the whole picture; flip != 0 mirrors the result horizontally (output column x
+ * holds what column width - 1 - x would hold).  Several entries may name one item; up-scaling is allowed.
+ * Integer stage, rw x rh the window and ow x oh the output:
+ *  HIPDEC_SCALE_NEAREST  V(x, y) = full(left + x * rw / ow, top + y * rh / oh), `full` the picture hipdec_batch_to_rgb writes (64-bit products, integer
+ *                        division).  For the whole picture: hipdec_batch_to_rgb_scaled NEAREST.
+ *  HIPDEC_SCALE_BOX      the box definition above applied to each plane CROPPED to the window, with that plane's own cropped size: luma columns
+ *                        [left, left + rw), chroma columns [left >> sH, ((left + rw - 1) >> sH) + 1), the same in y with sV; then the colour conversion
+ *                        of hipdec_color_convert on the three averaged planes as a 4:4:4 image.  For the whole picture: hipdec_batch_to_rgb_scaled BOX.
+ *  The component value V is the out_chroma 10 value (8 bits; sources above 8 bits go through to-SDR) for 8-bit sources and for HIPDEC_TENSOR_U8 from any
+ *  source; float dtypes from sources above 8 bits get the native-depth value out_chroma 14 would store (0 .. 2^bits - 1: fold 1 / 1023 into `scale`).
+ * Float stage: (float)V * scale[c] + bias[c] in fp32 - a multiply, then an add, each rounded once - and for F16 / BF16 the IEEE round-to-nearest-even
+ * conversion of that value, subnormals included.  HIPDEC_TENSOR_U8 stores V and ignores scale / bias. */
+typedef enum hipdec_tensor_dtype { HIPDEC_TENSOR_U8 = 0, HIPDEC_TENSOR_F32 = 1, HIPDEC_TENSOR_F16 = 2, HIPDEC_TENSOR_BF16 = 3 } hipdec_tensor_dtype;
+typedef enum hipdec_tensor_layout { HIPDEC_TENSOR_NCHW = 0, HIPDEC_TENSOR_NHWC = 1 } hipdec_tensor_layout;
+typedef struct hipdec_tensor_desc {
+  int width, height;       /* of every sample */
+  int dtype, layout;       /* hipdec_tensor_dtype, hipdec_tensor_layout */
+  int filter;              /* hipdec_scale_filter */
+  int reserved;            /* 0 */
+  float scale[3], bias[3]; /* per channel R, G, B */
+} hipdec_tensor_desc;
+typedef struct hipdec_tensor_entry { int item, left, top, width, height, flip; } hipdec_tensor_entry;
+/* bytes of a tensor of n_entries samples (0 for a description that would be refused) */
+HIPDEC_API size_t hipdec_tensor_bytes(const hipdec_tensor_desc* desc, int n_entries);
+/* All entries as ONE launch (65535 entries per launch), asynchronous on `stream`; the device time lands in slot [5] of hipdec_batch_slot_kernel_timing_us.
+ * entries NULL: n_entries must be the item count, entry i = the whole of item i.  A window that leaves the picture, a non-positive size, an unknown dtype,
+ * layout or filter, non-finite scale / bias with a float dtype, out_bytes below hipdec_tensor_bytes: HIPDEC_ERR_INVALID_ARGUMENT; width * height above the
+ * batch's max_image_size_pixels: HIPDEC_ERR_LIMIT.  Sources of all entries are 8-bit, or all wider. */
+HIPDEC_API int hipdec_batch_to_tensor(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, int n_entries, void* out_dev,
+                                      size_t out_bytes, void* stream);
+/* The single-image form over any hipdec_color_image (host or device planes; host planes the decoder handed over are found device-resident), with the planner
+ * rules of hipdec_color_convert (nclx, range, matrix; nearest-neighbour chroma).  plane[3] is ignored; entries NULL: n_entries must be 1, the whole image.
+ * `out` is a host buffer, or a device buffer with out_on_device.  Synchronises. */
+HIPDEC_API int hipdec_image_to_tensor(const hipdec_color_image* in, const hipdec_nclx* nclx, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries,
+                                      int n_entries, void* out, size_t out_bytes, int out_on_device);
+/* counters since load: tensors written by the two calls above, and their entries */
+HIPDEC_API void hipdec_tensor_stats(uint64_t* tensors, uint64_t* entries);
+/* Debug inspection: plane `plane` (0 .. 2) of entry `entry` as the kernel of the batch's LAST hipdec_batch_to_tensor received it - the device pointer and
+ * stride of the PLANE and the window of it that is scaled.  A window is carried as an offset and never moves the pointer, so the box kernel's aligned
+ * 32- / 64-bit row loads start at a 4-sample boundary of the plane whatever the window's parity. */
+HIPDEC_API int hipdec_batch_tensor_block(hipdec_batch* b, int entry, int plane, const void** plane_dev, size_t* plane_stride, int* x, int* y, int* width,
+                                         int* height);
+
 /* counters since load: images through hipdec_image_transform, grid canvases handed out by hipdec_grid_read_plane_tracked (hipdec_image_scale counts in
  * hipdec_image_scale_stats) */
 HIPDEC_API void hipdec_image_ops_stats(uint64_t* transforms, uint64_t* grid_canvases);

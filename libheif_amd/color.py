@@ -122,6 +122,32 @@ def image_scale(planes, bpp, chroma, width, height, filter=SCALE_BOX, alpha=None
     return res
 
 
+def image_to_tensor(planes, bpp, chroma, nclx, size, entries=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None,
+                    filter=SCALE_BOX):
+    """Batch.to_tensor for one image that is not a batch item (hipdec_image_to_tensor): planes [Y] or [Y, Cb, Cr] NumPy arrays of `bpp` bits, chroma
+    0 / CHROMA_420 / CHROMA_422 / CHROMA_444, nclx (primaries, transfer, matrix, full_range) or None.  entries: (left, top, width, height[, flip])
+    windows, or None for the whole image.  Returns the tensor as a NumPy array (bfloat16 as uint16 bits).  dtype, layout, mean / std / scale / bias
+    as Batch.to_tensor states them (max_value = 2^bpp - 1 for float dtypes from more than 8 bits, else 255)."""
+    from . import decoder as dec
+    lib = dec._bind(load_library())
+    dt = np.uint16 if bpp > 8 else np.uint8
+    src = [np.ascontiguousarray(p, dtype=dt) for p in planes]
+    h, w = src[0].shape
+    img = ColorImage()
+    img.width, img.height, img.chroma, img.bit_depth, img.on_device = w, h, chroma, bpp, 0
+    for c, a in enumerate(src):
+        img.plane[c], img.stride[c] = a.ctypes.data, a.strides[0]
+    max_value = (1 << bpp) - 1 if (dtype != "uint8" and bpp > 8) else 255
+    sc, bi = dec.tensor_scale_bias(mean, std, scale, bias, max_value)
+    desc = dec.tensor_desc(size, dtype, layout, filter, sc, bi)
+    n = 1 if entries is None else len(entries)
+    arr = None if entries is None else dec.tensor_entries([(0,) + tuple(e) for e in entries])
+    out = np.empty(dec.tensor_shape(n, size, layout), dec._TENSOR_NUMPY[dtype])
+    ns = _nclx_struct(nclx)
+    check(lib.hipdec_image_to_tensor(C.byref(img), C.byref(ns) if nclx is not None else None, C.byref(desc), arr, n, out.ctypes.data, out.nbytes, 0))
+    return out
+
+
 class DevicePlanes:
     """Decoded Y/Cb/Cr planes resident in HBM (tight strides)."""
 

@@ -185,6 +185,16 @@ struct ScaledParams {
   int tile;          // box: output pixels per workgroup
 };
 
+// a value every lane of the wave holds alike, moved to a scalar register (a 64-bit division runs on the vector unit even for uniform operands)
+__device__ __forceinline__ int wave_uniform(int v)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(HIPDEC_HOST_EMU)
+  return __builtin_amdgcn_readfirstlane(v);
+#else
+  return v;
+#endif
+}
+
 __device__ __forceinline__ void box_range(int o, int pn, int qn, int& a, int& b)
 {
   a = (int)((uint64_t)o * (uint64_t)pn / (uint64_t)qn);
@@ -217,11 +227,13 @@ __device__ __forceinline__ void box_columns(const uint8_t* plane, size_t stride,
   }
 }
 
-struct BoxPlane { const uint8_t* p; size_t stride; int pw, ph; };
+// pw x ph: the samples that are scaled - the whole plane, or a window of it at (wx, wy) (tensor output); fw: the plane's full width, which bounds the
+// row loads.  The pointer is the PLANE's in either case: a window is carried as an offset so that the span still starts at a 4-sample boundary of the plane.
+struct BoxPlane { const uint8_t* p; size_t stride; int pw, ph, fw, wx, wy; };
 
 // Box averages of NP planes for output pixel (oxA + threadIdx.x, oy) of a qw x qh result; all 256 threads of the workgroup call it (barriers inside),
-// `val` is meaningful where threadIdx.x < nox.  live: planes [0, live) are worked on (wave-uniform).
-template <typename Pix, int NP>
+// `val` is meaningful where threadIdx.x < nox.  live: planes [0, live) are worked on (wave-uniform).  WINDOW: the planes' wx / wy are applied.
+template <typename Pix, int NP, bool WINDOW = false>
 __device__ __forceinline__ void box_tile(const BoxPlane (&pl)[NP], int live, int qw, int qh, int oxA, int nox, int oy, typename BoxAcc<Pix>::T (*colsum)[kBoxSpan],
                                          uint32_t (&val)[NP])
 {
@@ -240,6 +252,10 @@ __device__ __forceinline__ void box_tile(const BoxPlane (&pl)[NP], int live, int
     box_range(oxA + nox - 1, pl[k].pw, qw, t, xb[k]);
     box_range(oy, pl[k].ph, qh, y0[k], y1[k]);
     box_range(owner ? oxA + tid : oxA, pl[k].pw, qw, x0[k], x1[k]);
+    if (WINDOW) {   // columns and rows of the PLANE from here on; the wave-uniform ones in scalar registers (3 planes x 4 of them: the window form's budget)
+      xa = wave_uniform(xa) + pl[k].wx; xb[k] = wave_uniform(xb[k]) + pl[k].wx; x0[k] += pl[k].wx; x1[k] += pl[k].wx;
+      y0[k] = wave_uniform(y0[k]) + pl[k].wy; y1[k] = wave_uniform(y1[k]) + pl[k].wy;
+    }
     base[k] = xa & ~3;
     chunks = max(chunks, (xb[k] - base[k] + kBoxSpan - 1) / kBoxSpan);
   }
@@ -247,7 +263,7 @@ __device__ __forceinline__ void box_tile(const BoxPlane (&pl)[NP], int live, int
     Acc a[NP][4];
 #pragma unroll
     for (int k = 0; k < NP; k++) {
-      if (k < live) box_columns<Pix, Acc>(pl[k].p, pl[k].stride, pl[k].pw, base[k] + j * kBoxSpan + tid * 4, xb[k], y0[k], y1[k], a[k]);
+      if (k < live) box_columns<Pix, Acc>(pl[k].p, pl[k].stride, pl[k].fw, base[k] + j * kBoxSpan + tid * 4, xb[k], y0[k], y1[k], a[k]);
     }
     if (j) __syncthreads();                                // the owners have finished with the previous chunk's sums
 #pragma unroll
@@ -297,7 +313,7 @@ __device__ __forceinline__ void box_rgb_block(const ScaledParams& sp)
   const int nox = min(sp.tile, sp.ow - oxA);
   const bool mono = p.arith == AR_MONO;
   const int cw = (p.w + (1 << sp.sH) - 1) >> sp.sH, ch = (p.h + (1 << sp.sV) - 1) >> sp.sV;
-  const BoxPlane pl[3] = {{p.y, p.ys, p.w, p.h}, {p.cb, p.cbs, cw, ch}, {p.cr, p.crs, cw, ch}};
+  const BoxPlane pl[3] = {{p.y, p.ys, p.w, p.h, p.w, 0, 0}, {p.cb, p.cbs, cw, ch, cw, 0, 0}, {p.cr, p.crs, cw, ch, cw, 0, 0}};
   for (int oy = blockIdx.y; oy < sp.oh; oy += gridDim.y) {
     uint32_t v[3];
     box_tile<Pix, 3>(pl, mono ? 1 : 3, sp.ow, sp.oh, oxA, nox, oy, colsum, v);
@@ -362,6 +378,208 @@ __global__ __launch_bounds__(256) void k_scale_rgb_nearest_batch(const ScaledPar
   nearest_rgb_block<Pix, LAYOUT>(sp);
 }
 
+// ---- tensor output: a window of the picture, scaled to one common size, as float16 / bfloat16 / float32 / uint8 in a dense N x 3 x H x W or N x H x W x 3
+// tensor (include/heif_hipdec.h).  The integer stage is the scaled kernels' - box_tile over the window, convert4 - and the store path is new: the component
+// value V becomes (float)V * scale[c] + bias[c] (a multiply and an add, each rounded once: -ffp-contract=off), narrowed with round-to-nearest-even, and a lane
+// writes its four pixels as one 16 / 8 / 4-byte store per channel plane (NCHW) or as one run of 12 elements (NHWC).  A horizontal flip is a store index.
+// Traffic is the box kernel's: 1.5 bytes read per luma pixel of the window (8-bit 4:2:0), 3 * sizeof(element) written per OUTPUT pixel.
+enum TensorDtype { TD_U8 = 0, TD_F32 = 1, TD_F16 = 2, TD_BF16 = 3 };
+
+struct TensorParams {
+  ColorParams c;            // planes and arithmetic (c.w / c.h: the source luma size; c.o0: the entry's first element)
+  int ow, oh;               // output size
+  int sH, sV;               // subsampling shifts of the source chroma planes
+  int tile;                 // box: output pixels per workgroup
+  int left, top, rw, rh;    // the window, in luma samples
+  int flip, nhwc;
+  float scale[3], bias[3];
+};
+
+// IEEE round-to-nearest-even narrowing in integer arithmetic (subnormals included): the host build's conversions, and the statement the device's
+// v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32 are held to bit for bit (tests/test_tensor_gpu.py compares bit patterns)
+__host__ __device__ __attribute__((unused)) inline uint32_t f32_to_f16_rne(uint32_t x)
+{
+  const uint32_t sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
+  if (a >= 0x7f800000u) return sign | 0x7c00u | (a > 0x7f800000u ? 0x200u : 0u);
+  if (a >= 0x47800000u) return sign | 0x7c00u;                     // 2^16 and above
+  const uint32_t e = a >> 23;
+  if (e < 113) {                                                     // below 2^-14: a multiple of 2^-24
+    if (e < 102) return sign;                                        // below 2^-25
+    const uint32_t m = (a & 0x7fffffu) | 0x800000u, sh = 126 - e, half = 1u << (sh - 1), rem = m & ((1u << sh) - 1u);
+    uint32_t r = m >> sh;
+    if (rem > half || (rem == half && (r & 1u))) r++;
+    return sign | r;
+  }
+  uint32_t r = ((e - 112) << 10) | ((a & 0x7fffffu) >> 13);
+  const uint32_t rem = a & 0x1fffu;
+  if (rem > 0x1000u || (rem == 0x1000u && (r & 1u))) r++;           // (a carry runs into the exponent, up to infinity)
+  return sign | r;
+}
+__host__ __device__ __attribute__((unused)) inline uint32_t f32_to_bf16_rne(uint32_t x)
+{
+  if ((x & 0x7fffffffu) > 0x7f800000u) return (x >> 16) | 0x40u;
+  return (x + 0x7fffu + ((x >> 16) & 1u)) >> 16;
+}
+
+template <int DT> struct TensorElem { typedef uint16_t T; };
+template <> struct TensorElem<TD_U8> { typedef uint8_t T; };
+template <> struct TensorElem<TD_F32> { typedef uint32_t T; };
+
+// the element (its bit pattern) of component value v
+template <int DT>
+__device__ __forceinline__ uint32_t tensor_elem(int v, float scale, float bias)
+{
+  if (DT == TD_U8) return (uint32_t)v;
+  const float f = (float)v * scale + bias;
+  if (DT == TD_F32) return __builtin_bit_cast(uint32_t, f);
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(HIPDEC_HOST_EMU)
+  if (DT == TD_F16) return __builtin_bit_cast(uint16_t, (_Float16)f);
+  return __builtin_bit_cast(uint16_t, (__bf16)f);
+#else
+  return DT == TD_F16 ? f32_to_f16_rne(__builtin_bit_cast(uint32_t, f)) : f32_to_bf16_rne(__builtin_bit_cast(uint32_t, f));
+#endif
+}
+
+// four elements as the 4 * sizeof(element) bytes they occupy in memory
+template <int DT> struct TensorQuad;
+template <> struct TensorQuad<TD_U8> {
+  typedef uint32_t V;
+  static __device__ __forceinline__ V pack(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return a | (b << 8) | (c << 16) | (d << 24); }
+};
+template <> struct TensorQuad<TD_F16> {
+  typedef uint2 V;
+  static __device__ __forceinline__ V pack(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return make_uint2(a | (b << 16), c | (d << 16)); }
+};
+template <> struct TensorQuad<TD_BF16> : TensorQuad<TD_F16> {};
+template <> struct TensorQuad<TD_F32> {
+  typedef uint4 V;
+  static __device__ __forceinline__ V pack(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { uint4 v; v.x = a; v.y = b; v.z = c; v.w = d; return v; }
+};
+
+// The store path of a 4-pixel group of output row oy starting at pixel x0 (npx of them inside the row).  Flip: pixel x goes to column ow - 1 - x, so a
+// whole group lands, reversed, on the four columns from ow - 4 - x0.  Vector stores where the group is whole and its destination aligned to them
+// (always, for output widths that are multiples of 4), element stores otherwise.
+template <int DT>
+__device__ __forceinline__ void store_tensor4(const TensorParams& tp, int x0, int oy, int npx, const int (&R)[4], const int (&G)[4], const int (&B)[4])
+{
+  typedef typename TensorElem<DT>::T E;
+  typedef TensorQuad<DT> Q;
+  typedef typename Q::V V;
+  uint32_t v[3][4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    v[0][i] = tensor_elem<DT>(tp.flip ? R[3 - i] : R[i], tp.scale[0], tp.bias[0]);
+    v[1][i] = tensor_elem<DT>(tp.flip ? G[3 - i] : G[i], tp.scale[1], tp.bias[1]);
+    v[2][i] = tensor_elem<DT>(tp.flip ? B[3 - i] : B[i], tp.scale[2], tp.bias[2]);
+  }
+  const size_t ow = (size_t)tp.ow, oh = (size_t)tp.oh;
+  const size_t xs = tp.flip ? ow - (size_t)npx - (size_t)x0 : (size_t)x0;   // the group's first column in memory
+  HIPDEC_GLOBAL E* o = (HIPDEC_GLOBAL E*)tp.c.o0;
+  if (tp.nhwc) {
+    HIPDEC_GLOBAL E* d = o + ((size_t)oy * ow + xs) * 3;
+    if (npx == 4 && (((uintptr_t)d) & (4 * sizeof(E) - 1)) == 0) {   // 12 elements in a row: R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
+      ((HIPDEC_GLOBAL V*)d)[0] = Q::pack(v[0][0], v[1][0], v[2][0], v[0][1]);
+      ((HIPDEC_GLOBAL V*)d)[1] = Q::pack(v[1][1], v[2][1], v[0][2], v[1][2]);
+      ((HIPDEC_GLOBAL V*)d)[2] = Q::pack(v[2][2], v[0][3], v[1][3], v[2][3]);
+      return;
+    }
+  } else {
+    HIPDEC_GLOBAL E* r = o + ((size_t)oy) * ow + xs;
+    HIPDEC_GLOBAL E* g = r + oh * ow;
+    HIPDEC_GLOBAL E* b = g + oh * ow;
+    if (npx == 4 && ((((uintptr_t)r) | ((uintptr_t)g) | ((uintptr_t)b)) & (4 * sizeof(E) - 1)) == 0) {
+      *(HIPDEC_GLOBAL V*)r = Q::pack(v[0][0], v[0][1], v[0][2], v[0][3]);
+      *(HIPDEC_GLOBAL V*)g = Q::pack(v[1][0], v[1][1], v[1][2], v[1][3]);
+      *(HIPDEC_GLOBAL V*)b = Q::pack(v[2][0], v[2][1], v[2][2], v[2][3]);
+      return;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    if (i >= npx) break;
+    const int k = tp.flip ? 3 - i : i;                               // where pixel x0 + i sits in v
+    const size_t col = tp.flip ? ow - 1 - (size_t)(x0 + i) : (size_t)(x0 + i);
+    if (tp.nhwc) {
+      HIPDEC_GLOBAL E* d = o + ((size_t)oy * ow + col) * 3;
+      d[0] = (E)v[0][k]; d[1] = (E)v[1][k]; d[2] = (E)v[2][k];
+    } else {
+      HIPDEC_GLOBAL E* d = o + (size_t)oy * ow + col;
+      d[0] = (E)v[0][k]; d[oh * ow] = (E)v[1][k]; d[2 * oh * ow] = (E)v[2][k];
+    }
+  }
+}
+
+// > 8-bit planes: the to-SDR shifts of the parameter block apply where the entry point set them (TD_U8) and are zero for the native-depth value of the
+// float dtypes, so one statement of the arithmetic serves both
+template <typename Pix>
+__device__ __forceinline__ void tensor_convert4(const ColorParams& p, const int (&Y)[4], const int (&CB)[4], const int (&CR)[4], int (&R)[4], int (&G)[4], int (&B)[4])
+{
+  convert4<Pix, LO_RGB24>(p, Y, CB, CR, R, G, B);
+}
+
+// all entries of a tensor in ONE launch: blockIdx.z selects the entry's parameter block
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) void k_tensor_box(const TensorParams* __restrict__ ps)
+{
+  __shared__ typename BoxAcc<Pix>::T colsum[3][kBoxSpan];
+  __shared__ uint32_t avg[3][256];
+  const TensorParams tp = ps[blockIdx.z];   // wave-uniform: scalar loads into SGPRs
+  const ColorParams& p = tp.c;
+  const int tid = threadIdx.x;
+  const int oxA = blockIdx.x * tp.tile;
+  if (oxA >= tp.ow) return;                               // (the whole workgroup)
+  const int nox = min(tp.tile, tp.ow - oxA);
+  const bool mono = p.arith == AR_MONO;
+  // each plane cropped to the window: luma columns [left, left + rw), chroma columns [left >> sH, ((left + rw - 1) >> sH) + 1), the same in y
+  const int cl = tp.left >> tp.sH, ct = tp.top >> tp.sV;
+  const int cw = ((tp.left + tp.rw - 1) >> tp.sH) - cl + 1, ch = ((tp.top + tp.rh - 1) >> tp.sV) - ct + 1;
+  const int fcw = (p.w + (1 << tp.sH) - 1) >> tp.sH;
+  const BoxPlane pl[3] = {{p.y, p.ys, tp.rw, tp.rh, p.w, tp.left, tp.top}, {p.cb, p.cbs, cw, ch, fcw, cl, ct}, {p.cr, p.crs, cw, ch, fcw, cl, ct}};
+  for (int oy = blockIdx.y; oy < tp.oh; oy += gridDim.y) {
+    uint32_t v[3];
+    box_tile<Pix, 3, true>(pl, mono ? 1 : 3, tp.ow, tp.oh, oxA, nox, oy, colsum, v);
+    avg[0][tid] = v[0]; avg[1][tid] = v[1]; avg[2][tid] = v[2];
+    __syncthreads();
+    if (tid * 4 < nox) {
+      const int npx = min(4, nox - tid * 4);
+      int Y[4], CB[4], CR[4], R[4], G[4], B[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) { Y[i] = (int)avg[0][(tid * 4 + i) & 255]; CB[i] = (int)avg[1][(tid * 4 + i) & 255]; CR[i] = (int)avg[2][(tid * 4 + i) & 255]; }
+      tensor_convert4<Pix>(p, Y, CB, CR, R, G, B);
+      store_tensor4<DT>(tp, oxA + tid * 4, oy, npx, R, G, B);
+    }
+    __syncthreads();                                      // avg and colsum are written again by the next row
+  }
+}
+
+// nearest neighbour: V(x, y) = full(left + x * rw / ow, top + y * rh / oh), `full` what rgb_block writes - only the sampled pixels are read
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) void k_tensor_nearest(const TensorParams* __restrict__ ps)
+{
+  const TensorParams tp = ps[blockIdx.z];
+  const ColorParams& p = tp.c;
+  const int ox0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (ox0 >= tp.ow) return;
+  const int npx = min(4, tp.ow - ox0);
+  const bool mono = p.arith == AR_MONO;
+  for (int oy = blockIdx.y * blockDim.y + threadIdx.y; oy < tp.oh; oy += gridDim.y * blockDim.y) {
+    const int iy = tp.top + (int)((uint64_t)oy * (uint64_t)tp.rh / (uint64_t)tp.oh);
+    HIPDEC_GLOBAL const Pix* yrow = (HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.y + (size_t)iy * p.ys);
+    HIPDEC_GLOBAL const Pix* cbrow = (HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.cb + (size_t)(iy >> tp.sV) * p.cbs);
+    HIPDEC_GLOBAL const Pix* crrow = (HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.cr + (size_t)(iy >> tp.sV) * p.crs);
+    int Y[4], CB[4], CR[4], R[4], G[4], B[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int ix = tp.left + (int)((uint64_t)min(ox0 + i, tp.ow - 1) * (uint64_t)tp.rw / (uint64_t)tp.ow);
+      Y[i] = yrow[ix];
+      CB[i] = mono ? 0 : cbrow[ix >> tp.sH];
+      CR[i] = mono ? 0 : crrow[ix >> tp.sH];
+    }
+    tensor_convert4<Pix>(p, Y, CB, CR, R, G, B);
+    store_tensor4<DT>(tp, ox0, oy, npx, R, G, B);
+  }
+}
+
 // the plane scalers: blockIdx.z selects the plane (all planes of an image, or of all items of a batch, are ONE launch)
 template <typename Pix>
 __global__ __launch_bounds__(256) void k_scale_plane_nearest(const hipdec::PlaneScaleParams* __restrict__ ps)
@@ -386,7 +604,7 @@ __global__ __launch_bounds__(256) void k_scale_plane_box(const hipdec::PlaneScal
   const int oxA = blockIdx.x * p.tile;
   if (oxA >= p.qw) return;
   const int nox = min(p.tile, p.qw - oxA);
-  const BoxPlane pl[1] = {{p.in, p.is, p.pw, p.ph}};
+  const BoxPlane pl[1] = {{p.in, p.is, p.pw, p.ph, p.pw, 0, 0}};
   for (int oy = blockIdx.y; oy < p.qh; oy += gridDim.y) {
     uint32_t v[1];
     box_tile<Pix, 1>(pl, 1, p.qw, p.qh, oxA, nox, oy, colsum, v);
@@ -701,6 +919,13 @@ thread_local ScaleReq t_scale;
 struct CapturedScaled { ScaledParams p; int variant; int filter; };
 thread_local std::vector<CapturedScaled> t_captured_scaled;
 
+// Tensor output: a request set on this thread (hipdec::color_tensor_request) makes the NEXT launch of an interleaved layout RECORD a tensor block instead;
+// the recorded blocks go out as one launch (hipdec::color_tensor_launch).  Taken and checked like a scale request.
+struct TensorReq { bool on = false; hipdec::TensorRequest r; };
+thread_local TensorReq t_tensor;
+struct CapturedTensor { TensorParams p; int wide; };
+thread_local std::vector<CapturedTensor> t_captured_tensor;
+
 int box_tile_of(int pw, int qw)
 {
   long long t = (long long)(kBoxSpan - 4) * qw / pw;   // span of t boxes <= t * pw / qw + 1 columns, + 3 in front of it for the aligned start
@@ -745,9 +970,30 @@ int launch_rgb_scaled(const ColorParams& p, hipStream_t s)
   }
 }
 
+// the entry points a tensor request reaches end in RGB24 (the 8-bit value, to-SDR shifts included) or little-endian RRGGBB (the native-depth value)
+template <typename Pix, int LAYOUT>
+int record_tensor(const ColorParams& p)
+{
+  if constexpr (LAYOUT != LO_RGB24 && LAYOUT != LO_RRGGBB_LE) return hipdec::set_error(HIPDEC_ERR_UNSUPPORTED, "tensor output: not a colour entry point it takes");
+  else {
+  if (p.a) return hipdec::set_error(HIPDEC_ERR_UNSUPPORTED, "tensor output: no alpha plane");
+  const hipdec::TensorRequest& r = t_tensor.r;
+  TensorParams tp;
+  memset(&tp, 0, sizeof(tp));
+  tp.c = p; tp.ow = r.ow; tp.oh = r.oh; tp.sH = r.sH; tp.sV = r.sV;
+  tp.left = r.left; tp.top = r.top; tp.rw = r.rw; tp.rh = r.rh; tp.flip = r.flip ? 1 : 0; tp.nhwc = r.nhwc ? 1 : 0;
+  for (int c = 0; c < 3; c++) { tp.scale[c] = r.scale[c]; tp.bias[c] = r.bias[c]; }
+  tp.tile = box_tile_of(r.rw, r.ow);
+  t_tensor.on = false;   // taken
+  t_captured_tensor.push_back(CapturedTensor{tp, sizeof(Pix) == 2});
+  return 0;
+  }
+}
+
 template <typename Pix, int LAYOUT>
 int launch_rgb(const ColorParams& p, hipStream_t s)
 {
+  if (t_tensor.on) return record_tensor<Pix, LAYOUT>(p);
   if (t_scale.on) return launch_rgb_scaled<Pix, LAYOUT>(p, s);
   if (t_capture) { t_captured.push_back(Captured{p, (int)sizeof(Pix) * 16 + LAYOUT}); return 0; }
   dim3 block(64, 4);
@@ -945,6 +1191,84 @@ int color_capture_launch_scaled(ColorBatchState& st, int filter, hipStream_t s)
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "scaled colour batch launch: %s", hipGetErrorString(e));
+  return 0;
+}
+
+void color_tensor_request(const TensorRequest& r) { t_tensor.on = true; t_tensor.r = r; }
+void color_tensor_clear() { t_tensor.on = false; }
+bool color_tensor_pending() { return t_tensor.on; }
+void color_tensor_begin() { t_captured_tensor.clear(); }
+void color_tensor_abort() { t_captured_tensor.clear(); t_tensor.on = false; }
+
+namespace {
+template <typename Pix, int DT>
+void launch_tensor_grid(const TensorParams* dev, int n, int filter, int ow, int oh, int tiles, hipStream_t s)
+{
+  if (filter == HIPDEC_SCALE_BOX) {
+    dim3 block(256), grid(tiles, oh < 65535 ? oh : 65535, n);
+    hipLaunchKernelGGL((k_tensor_box<Pix, DT>), grid, block, 0, s, dev);
+  } else {
+    const int gy = (oh + 3) / 4;
+    dim3 block(64, 4), grid(((ow + 3) / 4 + 63) / 64, gy < 16384 ? gy : 16384, n);
+    hipLaunchKernelGGL((k_tensor_nearest<Pix, DT>), grid, block, 0, s, dev);
+  }
+}
+}  // namespace
+
+// the tensor blocks recorded on this thread since color_tensor_begin() as ONE launch (a grid's z extent is 65535: more entries take as few launches as that allows)
+int color_tensor_launch(ColorBatchState& st, int filter, int dtype, hipStream_t s)
+{
+  std::vector<CapturedTensor> caps;
+  caps.swap(t_captured_tensor);
+  if (caps.empty()) return 0;
+  int max_tiles = 0;
+  for (const auto& c : caps) {
+    if (c.wide != caps[0].wide) return set_error(HIPDEC_ERR_UNSUPPORTED, "tensor output: the entries mix 8-bit and wider sources");
+    const int tiles = (c.p.ow + c.p.tile - 1) / c.p.tile;
+    max_tiles = tiles > max_tiles ? tiles : max_tiles;
+  }
+  const size_t bytes = caps.size() * sizeof(TensorParams);
+  std::vector<uint8_t> host(bytes);
+  for (size_t i = 0; i < caps.size(); i++) memcpy(host.data() + i * sizeof(TensorParams), &caps[i].p, sizeof(TensorParams));
+  if (st.dev_bytes < bytes) {
+    if (st.dev) arena_release(st.dev, st.dev_bytes);
+    st.dev = nullptr; st.dev_bytes = 0; st.host.clear();
+    HIPDEC_CHECK_HIP(arena_acquire(&st.dev, bytes, &st.dev_bytes));
+  }
+  if (st.host != host) {   // steady state (same windows, same output): nothing to upload
+    st.prev.swap(st.host);
+    st.host.swap(host);
+    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), bytes, hipMemcpyHostToDevice, s));
+  }
+  const int ow = caps[0].p.ow, oh = caps[0].p.oh;
+  for (size_t first = 0; first < caps.size(); first += 65535) {
+    const TensorParams* dev = (const TensorParams*)st.dev + first;
+    const int n = (int)(caps.size() - first < 65535 ? caps.size() - first : 65535);
+    switch (caps[0].wide * 4 + dtype) {
+#define X(DT) case DT: launch_tensor_grid<uint8_t, DT>(dev, n, filter, ow, oh, max_tiles, s); break; \
+              case 4 + DT: launch_tensor_grid<uint16_t, DT>(dev, n, filter, ow, oh, max_tiles, s); break;
+      X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
+#undef X
+      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor output: unknown dtype %d", dtype);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "tensor kernel launch: %s", hipGetErrorString(e));
+  }
+  return 0;
+}
+
+// debug inspection of the blocks last handed to the tensor kernels: plane `plane` of entry `entry` as the kernel receives it - the pointer and stride of the
+// PLANE, and the window of it that is scaled
+int color_tensor_inspect(const ColorBatchState& st, int entry, int plane, const void** plane_dev, size_t* stride, int* x, int* y, int* w, int* h)
+{
+  if (entry < 0 || plane < 0 || plane > 2 || (size_t)(entry + 1) * sizeof(TensorParams) > st.host.size()) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_block: no such block");
+  TensorParams tp;
+  memcpy(&tp, st.host.data() + (size_t)entry * sizeof(TensorParams), sizeof(tp));
+  const int sH = plane ? tp.sH : 0, sV = plane ? tp.sV : 0;
+  *plane_dev = plane == 0 ? tp.c.y : (plane == 1 ? tp.c.cb : tp.c.cr);
+  *stride = plane == 0 ? tp.c.ys : (plane == 1 ? tp.c.cbs : tp.c.crs);
+  *x = tp.left >> sH; *y = tp.top >> sV;
+  *w = ((tp.left + tp.rw - 1) >> sH) - *x + 1; *h = ((tp.top + tp.rh - 1) >> sV) - *y + 1;
   return 0;
 }
 

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <deque>
 #include <unordered_map>
@@ -60,6 +61,7 @@ struct hipdec_batch : BatchLayout {
   uint32_t wave_share = 1;      // the CABAC work pool of this batch takes 1 / wave_share of the wave budget (launch sets of the decoder path overlap in pairs)
   ColorBatchState color;        // parameter blocks of hipdec_batch_to_rgb_all
   ColorBatchState color_scaled; // ... and of hipdec_batch_to_rgb_scaled_all (its own, so that a host alternating the two uploads nothing in the steady state)
+  ColorBatchState color_tensor; // ... and of hipdec_batch_to_tensor
   uint64_t max_pixels = 0;      // the limit given at creation (0: none): scaled outputs are held against it as well
   // decoder path (plugin): the output planes of every item staged in pinned host memory by ONE set of asynchronous copies behind the
   // kernels, so that N decoder instances sharing the batch do not queue N x 3 pageable device-to-host copies (stage_planes_to_host)
@@ -120,6 +122,7 @@ struct hipdec_batch : BatchLayout {
     if (rgb_dev) { arena_release(rgb_dev, rgb_capacity); rgb_note_unused((int)rgb_off.size() - rgb_consumed.load()); }
     color_batch_state_free(color);
     color_batch_state_free(color_scaled);
+    color_batch_state_free(color_tensor);
     if (arena) arena_release(arena, arena_capacity);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : chain_events) if (e) (void)hipEventDestroy(e);
@@ -726,9 +729,141 @@ int batch_to_rgb_impl(hipdec_batch* b, int i, int out_chroma, void* out_dev, siz
   return set_error(HIPDEC_ERR_UNSUPPORTED, "to_rgb: unsupported output chroma %d", out_chroma);
 }
 
+// ---- tensor output (include/heif_hipdec.h): what hipdec_batch_to_tensor and hipdec_image_to_tensor (decoder_color_boundary.inc) share
+std::atomic<uint64_t> g_tensor_calls{0}, g_tensor_entries{0};
+
+size_t tensor_elem_bytes(int dtype) { return dtype == HIPDEC_TENSOR_U8 ? 1 : (dtype == HIPDEC_TENSOR_F32 ? 4 : 2); }
+
+// the description's own refusals; *bytes: the size of the tensor
+int tensor_check_desc(const char* who, const hipdec_tensor_desc* d, int n_entries, size_t* bytes)
+{
+  if (!d || n_entries < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  if (d->width < 1 || d->height < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: output size %d x %d", who, d->width, d->height);
+  if (d->dtype < HIPDEC_TENSOR_U8 || d->dtype > HIPDEC_TENSOR_BF16) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown dtype %d", who, d->dtype);
+  if (d->layout != HIPDEC_TENSOR_NCHW && d->layout != HIPDEC_TENSOR_NHWC) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown layout %d", who, d->layout);
+  if (d->filter != HIPDEC_SCALE_NEAREST && d->filter != HIPDEC_SCALE_BOX) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown filter %d", who, d->filter);
+  if (d->dtype != HIPDEC_TENSOR_U8)
+    for (int c = 0; c < 3; c++)
+      if (!std::isfinite(d->scale[c]) || !std::isfinite(d->bias[c])) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: scale / bias of channel %d is not finite", who, c);
+  const uint64_t per = 3ull * (uint64_t)d->width * (uint64_t)d->height * tensor_elem_bytes(d->dtype);   // (evaluated before the check below, which keeps it far from 2^64)
+  if ((uint64_t)d->width * (uint64_t)d->height > (1ull << 40) || per > (~0ull) / (uint64_t)n_entries) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: tensor too large", who);
+  *bytes = (size_t)(per * (uint64_t)n_entries);
+  return 0;
+}
+
+// the window of an entry inside a w x h picture (all zeros: the whole picture)
+int tensor_window(const char* who, const hipdec_tensor_entry* e, int idx, int w, int h, int* left, int* top, int* rw, int* rh)
+{
+  *left = 0; *top = 0; *rw = w; *rh = h;
+  if (!e || (!e->left && !e->top && !e->width && !e->height)) return 0;
+  if (e->width < 1 || e->height < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: window size %d x %d", who, idx, e->width, e->height);
+  if (e->left < 0 || e->top < 0 || (int64_t)e->left + e->width > w || (int64_t)e->top + e->height > h)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: window %d x %d at (%d, %d) leaves the picture of %d x %d", who, idx, e->width, e->height, e->left, e->top, w, h);
+  *left = e->left; *top = e->top; *rw = e->width; *rh = e->height;
+  return 0;
+}
+
+// One entry: sets the tensor request and goes through the colour entry point the planner rules of hipdec_batch_to_rgb / hipdec_color_convert select for
+// these planes (cf: their chroma format, 0 monochrome) - out_chroma 10 for 8-bit sources and the U8 dtype, 14 (the native-depth value) otherwise; box
+// presents the planes as the 4:4:4 image they are scaled to.  The entry point records the block (color.hip); elem0: the entry's first element.
+int tensor_record_entry(const char* who, const uint8_t* y, size_t ys, const uint8_t* cb, size_t cbs, const uint8_t* cr, size_t crs, int w, int h, int bits, int cf,
+                        const hipdec_nclx* nclx, const hipdec_nclx* nclx_after_sdr, const hipdec_tensor_desc* d, int left, int top, int rw, int rh, int flip, void* elem0)
+{
+  TensorRequest rq;
+  memset(&rq, 0, sizeof(rq));
+  rq.ow = d->width; rq.oh = d->height; rq.sH = cf == 1 || cf == 2 ? 1 : 0; rq.sV = cf == 1 ? 1 : 0;
+  rq.left = left; rq.top = top; rq.rw = rw; rq.rh = rh; rq.flip = flip; rq.nhwc = d->layout == HIPDEC_TENSOR_NHWC;
+  for (int c = 0; c < 3; c++) { rq.scale[c] = d->scale[c]; rq.bias[c] = d->bias[c]; }
+  struct Scope { ~Scope() { color_tensor_clear(); } } scope;
+  color_tensor_request(rq);
+  const bool wide = bits > 8;
+  int rc;
+  if (!cf) {   // Op_mono_to_RGB24_32: 8-bit only, as hipdec_batch_to_rgb
+    if (wide) return set_error(HIPDEC_ERR_UNSUPPORTED, "%s: monochrome input goes to 8-bit RGB only", who);
+    rc = hipdec_color_mono_to_rgb24(y, ys, nullptr, 0, w, h, elem0, 0, 0, nullptr);
+  } else {
+    if (d->filter == HIPDEC_SCALE_BOX) cf = 3;
+    const int matrix = nclx && nclx->has_nclx ? (nclx->matrix_coefficients == 2 ? 6 : nclx->matrix_coefficients) : 6;
+    const int full = nclx && nclx->has_nclx ? nclx->full_range_flag : 1;
+    const bool int_op = cf == 1 && full && matrix != 0 && matrix != 8;
+    if (!wide) {
+      rc = int_op ? hipdec_color_420_to_rgb24(y, ys, cb, cbs, cr, crs, w, h, nclx, elem0, 0, 0, nullptr)
+                  : hipdec_color_ycbcr_to_rgb24_float(y, ys, cb, cbs, cr, crs, w, h, cf, nclx, elem0, 0, 0, nullptr);
+    } else if (d->dtype == HIPDEC_TENSOR_U8) {
+      rc = hipdec_color_hdr_to_rgb24(y, ys, cb, cbs, cr, crs, w, h, bits, cf, int_op ? nclx_after_sdr : nclx, elem0, 0, 0, int_op, nullptr);
+    } else {
+      rc = (cf != 1 || matrix == 0 || matrix == 8) ? hipdec_color_ycbcr_to_rrggbb_float(y, ys, cb, cbs, cr, crs, w, h, bits, cf, nclx, elem0, 0, 1, nullptr)
+                                                   : hipdec_color_420_to_rrggbb(y, ys, cb, cbs, cr, crs, w, h, bits, nclx, elem0, 0, 1, nullptr);
+    }
+  }
+  if (!rc && color_tensor_pending()) return set_error(HIPDEC_ERR_UNSUPPORTED, "%s: the colour entry point did not take the tensor request", who);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t hipdec_tensor_bytes(const hipdec_tensor_desc* desc, int n_entries)
+{
+  size_t bytes = 0;
+  return tensor_check_desc("tensor_bytes", desc, n_entries, &bytes) ? 0 : bytes;
+}
+
+void hipdec_tensor_stats(uint64_t* tensors, uint64_t* entries)
+{
+  if (tensors) *tensors = g_tensor_calls.load();
+  if (entries) *entries = g_tensor_entries.load();
+}
+
+int hipdec_batch_to_tensor(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, int n_entries, void* out_dev, size_t out_bytes,
+                           void* stream)
+{
+  if (!b || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: bad arguments");
+  size_t bytes = 0;
+  if (int rc = tensor_check_desc("to_tensor", desc, n_entries, &bytes)) return rc;
+  if (!entries && n_entries != (int)b->pics.size())
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: %d entries without an entry list, the batch has %d items", n_entries, (int)b->pics.size());
+  if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
+  DeviceScope scope(b->device);
+  if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: the batch's arena was handed to another batch");
+  if (b->max_pixels && (uint64_t)desc->width * (uint64_t)desc->height > b->max_pixels)
+    return set_error(HIPDEC_ERR_LIMIT, "to_tensor: output of %d x %d pixels exceeds max_image_size_pixels", desc->width, desc->height);
+  return guarded("to_tensor", [&]() -> int {
+    hipStream_t s = follow_stream(b, stream);
+    const size_t entry_bytes = bytes / (size_t)n_entries;
+    color_tensor_begin();
+    for (int e = 0; e < n_entries; e++) {
+      const int i = entries ? entries[e].item : e;
+      if (i < 0 || i >= (int)b->pics.size()) { color_tensor_abort(); return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: entry %d names item %d of %d", e, i, (int)b->pics.size()); }
+      const PicParams& P = b->params[i];
+      const hipdec_image_info& I = b->pics[i].info;
+      int left, top, rw, rh;
+      int rc = tensor_window("to_tensor", entries ? entries + e : nullptr, e, P.out_width, P.out_height, &left, &top, &rw, &rh);
+      // the decoder reports the VUI colour description exactly as the libde265 plugin would attach it (hipdec_batch_to_rgb hands it on as it is)
+      hipdec_nclx nclx{1, I.colour_primaries, I.transfer_characteristics, I.matrix_coeffs, I.full_range_flag};
+      if (!rc) rc = tensor_record_entry("to_tensor", b->arena + P.off_out[0], P.out_stride[0], b->arena + P.off_out[1], P.out_stride[1], b->arena + P.off_out[2], P.out_stride[2],
+                                        P.out_width, P.out_height, b->wide ? I.bit_depth_luma : 8, P.chroma_format_idc, &nclx, &nclx, desc, left, top, rw, rh,
+                                        entries ? entries[e].flip : 0, (uint8_t*)out_dev + (size_t)e * entry_bytes);
+      if (rc) { color_tensor_abort(); return rc; }
+    }
+    const size_t slot = b->runs ? (b->runs - 1) % (b->ev.size() / kEv) : 0;
+    hipEvent_t* ev = b->ev.data() + kEv * slot;
+    HIPDEC_CHECK_HIP(hipEventRecord(ev[6], s));
+    int rc = color_tensor_launch(b->color_tensor, desc->filter, desc->dtype, s);
+    HIPDEC_CHECK_HIP(hipEventRecord(ev[7], s));
+    if (!rc && b->runs) b->colour_timed[slot] = 1;
+    b->mark_done(s);
+    if (!rc) { g_tensor_calls++; g_tensor_entries += (uint64_t)n_entries; }
+    return rc;
+  });
+}
+
+int hipdec_batch_tensor_block(hipdec_batch* b, int entry, int plane, const void** plane_dev, size_t* plane_stride, int* x, int* y, int* width, int* height)
+{
+  if (!b || !plane_dev || !plane_stride || !x || !y || !width || !height) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_block: bad arguments");
+  return color_tensor_inspect(b->color_tensor, entry, plane, plane_dev, plane_stride, x, y, width, height);
+}
 
 int hipdec_batch_to_rgb(hipdec_batch* b, int i, int out_chroma, void* out_dev, size_t out_stride, void* stream)
 {

@@ -765,5 +765,81 @@ int hipdec_image_scale(const hipdec_color_image* in, int out_width, int out_heig
 
 void hipdec_image_scale_stats(uint64_t* images) { if (images) *images = g_img_scales.load(); }
 
+// hipdec_batch_to_tensor's single-image form: the planes of any image (found device-resident like hipdec_image_scale's, uploaded otherwise), the planner
+// rules of hipdec_color_convert with nearest-neighbour chroma, all entries as ONE launch of the tensor kernel (color.hip).  plane[3] is ignored.
+int hipdec_image_to_tensor(const hipdec_color_image* in, const hipdec_nclx* nclx, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, int n_entries,
+                           void* out, size_t out_bytes, int out_on_device)
+{
+  if (!in || !out || in->width <= 0 || in->height <= 0 || !in->plane[0] || in->bit_depth < 8 || in->bit_depth > 14 || in->chroma < 0 || in->chroma > 3 ||
+      (in->chroma != 0 && (!in->plane[1] || !in->plane[2])))
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "image_to_tensor: bad arguments");
+  size_t bytes = 0;
+  if (int rc = tensor_check_desc("image_to_tensor", desc, n_entries, &bytes)) return rc;
+  if (!entries && n_entries != 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "image_to_tensor: %d entries without an entry list (an image is one item)", n_entries);
+  if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "image_to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
+  const int w = in->width, h = in->height, chroma = in->chroma;
+  const size_t es = in->bit_depth > 8 ? 2 : 1;
+  const int cw = chroma == 3 ? w : (w + 1) / 2, ch = chroma == 1 ? (h + 1) / 2 : h;
+  for (int c = 0; c < (chroma ? 3 : 1); c++)
+    if (in->stride[c] < (size_t)(c ? cw : w) * es) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "image_to_tensor: stride %zu of plane %d is smaller than its rows", in->stride[c], c);
+  {
+    int left, top, rw, rh;
+    for (int e = 0; entries && e < n_entries; e++)
+      if (int rc = tensor_window("image_to_tensor", entries + e, e, w, h, &left, &top, &rw, &rh)) return rc;
+  }
+  if (int rc = ensure_init()) return rc;
+  return guarded("image_to_tensor", [&]() -> int {
+    hipStream_t s = stream_acquire_priority();
+    ColorBatchState blocks;
+    struct Release { hipStream_t s; ColorBatchState& blocks; std::vector<std::pair<void*, size_t>> bufs;
+                     ~Release() { (void)hipStreamSynchronize(s); color_batch_state_free(blocks); for (auto& b : bufs) arena_release(b.first, b.second); stream_release(s); } } rel{s, blocks, {}};
+    auto scratch = [&](size_t n, uint8_t** p) -> int {
+      void* d = nullptr; size_t cap = 0;
+      HIPDEC_CHECK_HIP(arena_acquire(&d, n ? n : 256, &cap));
+      rel.bufs.emplace_back(d, cap); *p = (uint8_t*)d;
+      return 0;
+    };
+    const uint8_t* dp[3] = {nullptr, nullptr, nullptr};
+    size_t ds[3] = {0, 0, 0};
+    std::shared_ptr<void> keep[3];
+    for (int c = 0; c < (chroma ? 3 : 1); c++) {
+      const int pw = c ? cw : w, ph = c ? ch : h;
+      if (in->on_device) { dp[c] = (const uint8_t*)in->plane[c]; ds[c] = in->stride[c]; continue; }
+      if (resident_find(in->plane[c], in->stride[c], pw, ph, in->bit_depth, &dp[c], &ds[c], keep[c])) { g_cb_resident++; continue; }
+      uint8_t* d = nullptr;
+      const size_t st = ((size_t)pw * es + 255) & ~(size_t)255;
+      if (int rc = scratch(st * ph, &d)) return rc;
+      HIPDEC_CHECK_HIP(hipMemcpy2DAsync(d, st, in->plane[c], in->stride[c], (size_t)pw * es, ph, hipMemcpyHostToDevice, s));
+      dp[c] = d; ds[c] = st;
+    }
+    if (!chroma) { dp[1] = dp[2] = dp[0]; ds[1] = ds[2] = ds[0]; }   // (never read)
+    uint8_t* dout = (uint8_t*)out;
+    if (!out_on_device) { if (int rc = scratch(bytes, &dout)) return rc; }
+    // an op behind Op_to_sdr_planes reads the profile the pipeline attached to the intermediate image (see hipdec_color_convert)
+    hipdec_nclx later{1, 1, 13, 6, 1};
+    if (nclx && nclx->has_nclx) {
+      later = *nclx;
+      if (later.colour_primaries == 2) later.colour_primaries = 1;
+      if (later.transfer_characteristics == 2) later.transfer_characteristics = 13;
+      if (later.matrix_coefficients == 2) later.matrix_coefficients = 6;
+    }
+    const size_t entry_bytes = bytes / (size_t)n_entries;
+    color_tensor_begin();
+    for (int e = 0; e < n_entries; e++) {
+      int left, top, rw, rh;
+      int rc = tensor_window("image_to_tensor", entries ? entries + e : nullptr, e, w, h, &left, &top, &rw, &rh);
+      if (!rc) rc = tensor_record_entry("image_to_tensor", dp[0], ds[0], dp[1], ds[1], dp[2], ds[2], w, h, in->bit_depth, chroma, nclx, &later, desc, left, top, rw, rh,
+                                        entries ? entries[e].flip : 0, dout + (size_t)e * entry_bytes);
+      if (rc) { color_tensor_abort(); return rc; }
+    }
+    if (int rc = color_tensor_launch(blocks, desc->filter, desc->dtype, s)) return rc;
+    g_cb_launches++;
+    if (!out_on_device) { if (int rc = copy_rows_to_host(out, bytes, dout, bytes, bytes, 1, s)) return rc; }
+    else HIPDEC_CHECK_HIP(hipStreamSynchronize(s));
+    g_tensor_calls++; g_tensor_entries += (uint64_t)n_entries;
+    return 0;
+  });
+}
+
 }  // extern "C"
 

@@ -90,6 +90,18 @@ struct PlaneScaleParams {
 // n planes as one launch; dev_params: room for n blocks in device memory, `jobs` must stay alive until `s` has passed the upload
 int scale_planes_launch(PlaneScaleParams* jobs, int n, int bytes_per_sample, int filter, void* dev_params, hipStream_t s);
 
+// Tensor output (color.hip).  As a scale request: the NEXT hipdec_color_* entry point that ends in interleaved RGB24 (8-bit value) or little-endian RRGGBB
+// (native-depth value) records a tensor block instead of launching - its `out` is the entry's first element - and color_tensor_launch() sends the recorded
+// blocks out as ONE launch.  The window is in luma samples of the planes handed in; sH / sV are their chroma shifts (box presents them as 4:4:4).
+struct TensorRequest { int ow, oh, sH, sV, left, top, rw, rh, flip, nhwc; float scale[3], bias[3]; };
+void color_tensor_request(const TensorRequest& r);
+void color_tensor_clear();
+bool color_tensor_pending();
+void color_tensor_begin();
+void color_tensor_abort();
+int color_tensor_launch(ColorBatchState& st, int filter, int dtype, hipStream_t s);
+int color_tensor_inspect(const ColorBatchState& st, int entry, int plane, const void** plane_dev, size_t* stride, int* x, int* y, int* w, int* h);
+
 // No C++ exception may cross the C ABI (the caller is libheif, or cgo / JNI / ctypes): every entry point that parses untrusted
 // input or allocates runs its body through guarded().
 template <class F> int guarded(const char* what, F&& body)

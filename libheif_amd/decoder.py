@@ -40,6 +40,13 @@ def _bind(lib):
     lib.hipdec_batch_to_rgb_scaled.argtypes = [vp, ci, ci, ci, ci, ci, vp, sz, vp]
     lib.hipdec_batch_to_rgb_scaled_all.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(vp), C.POINTER(sz), vp]
     lib.hipdec_batch_read_plane_scaled.argtypes = [vp, ci, ci, ci, ci, ci, vp, sz]
+    lib.hipdec_tensor_bytes.restype = sz
+    lib.hipdec_tensor_bytes.argtypes = [C.POINTER(TensorDesc), ci]
+    lib.hipdec_batch_to_tensor.argtypes = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), ci, vp, sz, vp]
+    lib.hipdec_image_to_tensor.argtypes = [vp, vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), ci, vp, sz, ci]
+    lib.hipdec_tensor_stats.restype = None
+    lib.hipdec_tensor_stats.argtypes = [C.POINTER(C.c_uint64)] * 2
+    lib.hipdec_batch_tensor_block.argtypes = [vp, ci, ci, C.POINTER(vp), C.POINTER(sz)] + [C.POINTER(ci)] * 4
     lib.hipdec_batch_last_timing_us.argtypes = [vp, C.POINTER(C.c_float)]
     lib.hipdec_batch_item_packed_bytes.restype = sz
     lib.hipdec_batch_item_packed_bytes.argtypes = [vp, ci]
@@ -52,6 +59,118 @@ def _bind(lib):
     lib.hipdec_batch_read_maps.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, sz]
     lib._dec_bound = True
     return lib
+
+
+class TensorDesc(C.Structure):
+    """hipdec_tensor_desc"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("filter", C.c_int), ("reserved", C.c_int),
+                ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+class TensorEntry(C.Structure):
+    """hipdec_tensor_entry"""
+    _fields_ = [("item", C.c_int), ("left", C.c_int), ("top", C.c_int), ("width", C.c_int), ("height", C.c_int), ("flip", C.c_int)]
+
+
+TENSOR_DTYPES = {"uint8": 0, "float32": 1, "float16": 2, "bfloat16": 3}       # hipdec_tensor_dtype
+TENSOR_LAYOUTS = {"NCHW": 0, "NHWC": 1}                                       # hipdec_tensor_layout
+_TENSOR_NUMPY = {"uint8": np.uint8, "float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}   # (NumPy has no bfloat16: its bits)
+
+
+def tensor_scale_bias(mean=None, std=None, scale=None, bias=None, max_value=255):
+    """The per-channel (scale, bias) of a tensor description, float32 arrays of three.  Either scale / bias as they are (a number or three; defaults
+    1 and 0: the raw component values), or the usual 0..1 convention of mean / std, (V / max_value - mean) / std, folded in float32 arithmetic as
+        scale[c] = float32(1) / (float32(max_value) * float32(std[c]))        bias[c] = -float32(mean[c]) / float32(std[c])
+    (mean defaults to 0, std to 1).  max_value is the largest component value V: 255, or 2^bits - 1 for float dtypes from sources above 8 bits."""
+    three = lambda v, d: np.broadcast_to(np.asarray(d if v is None else v, np.float32), (3,)).copy()
+    if mean is not None or std is not None:
+        if scale is not None or bias is not None:
+            raise ValueError("give mean / std or scale / bias, not both")
+        m, sd = three(mean, 0.0), three(std, 1.0)
+        return np.float32(1) / (np.float32(max_value) * sd), -m / sd
+    return three(scale, 1.0), three(bias, 0.0)
+
+
+def tensor_desc(size, dtype="float16", layout="NCHW", filter=1, scale=None, bias=None):
+    """hipdec_tensor_desc for size = (width, height)"""
+    if dtype not in TENSOR_DTYPES:
+        raise ValueError("dtype must be one of %s" % sorted(TENSOR_DTYPES))
+    if layout not in TENSOR_LAYOUTS:
+        raise ValueError("layout must be NCHW or NHWC")
+    d = TensorDesc()
+    d.width, d.height, d.dtype, d.layout, d.filter = int(size[0]), int(size[1]), TENSOR_DTYPES[dtype], TENSOR_LAYOUTS[layout], int(filter)
+    sc, bi = tensor_scale_bias(scale=scale, bias=bias)
+    for c in range(3):
+        d.scale[c], d.bias[c] = float(sc[c]), float(bi[c])
+    return d
+
+
+def tensor_entries(entries):
+    """a ctypes array of hipdec_tensor_entry from (item, left, top, width, height[, flip]) tuples or TensorEntry objects"""
+    arr = (TensorEntry * len(entries))()
+    for k, e in enumerate(entries):
+        if isinstance(e, TensorEntry):
+            arr[k] = e
+        else:
+            e = tuple(int(v) for v in e)
+            arr[k] = TensorEntry(*(e + (0,) * (6 - len(e))))
+    return arr
+
+
+def tensor_shape(n, size, layout):
+    return (n, 3, size[1], size[0]) if layout == "NCHW" else (n, size[1], size[0], 3)
+
+
+def center_crop_entry(item, width, height, crop_width, crop_height=None, flip=False):
+    """the window of crop_width x crop_height (default: square) in the middle of a width x height picture, as an entry tuple; the offsets round down"""
+    cw = int(crop_width)
+    ch = cw if crop_height is None else int(crop_height)
+    if cw < 1 or ch < 1 or cw > width or ch > height:
+        raise ValueError("a crop of %d x %d does not fit a picture of %d x %d" % (cw, ch, width, height))
+    return (int(item), (width - cw) // 2, (height - ch) // 2, cw, ch, int(bool(flip)))
+
+
+def random_resized_crop_entries(rng, sizes, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip_probability=0.5, items=None, attempts=10):
+    """One random-resized-crop window per picture, as entry tuples: `sizes` are the pictures' (width, height), `items` the batch items they name
+    (default 0, 1, ...).  The usual recipe in plain host arithmetic, deterministic for a seeded numpy.random.Generator: up to `attempts` draws of an area
+    fraction uniform in `scale` and an aspect ratio log-uniform in `ratio`, w = round(sqrt(area * r)), h = round(sqrt(area / r)), taken when it fits, at an
+    offset uniform over the positions that fit; failing that, the largest centred window whose aspect ratio is clamped into `ratio`.  Then one draw for the
+    flip.  Every picture consumes the generator in this order, whether a draw fits or not."""
+    out = []
+    for k, (w, h) in enumerate(sizes):
+        item = k if items is None else int(items[k])
+        area = float(w) * float(h)
+        win = None
+        for _ in range(attempts):
+            a = area * rng.uniform(scale[0], scale[1])
+            r = float(np.exp(rng.uniform(np.log(ratio[0]), np.log(ratio[1]))))
+            cw, ch = int(round(np.sqrt(a * r))), int(round(np.sqrt(a / r)))
+            if win is None and 0 < cw <= w and 0 < ch <= h:
+                left, top = int(rng.integers(0, w - cw + 1)), int(rng.integers(0, h - ch + 1))
+                win = (left, top, cw, ch)
+        if win is None:
+            r = min(max(w / h, ratio[0]), ratio[1])
+            cw, ch = (w, max(1, min(h, int(round(w / r))))) if w / h <= r else (max(1, min(w, int(round(h * r)))), h)
+            win = ((w - cw) // 2, (h - ch) // 2, cw, ch)
+        out.append((item,) + win + (int(rng.random() < flip_probability),))
+    return out
+
+
+def tensor_stats():
+    """(tensors written by Batch.to_tensor / color.image_to_tensor, their entries) since the library was loaded"""
+    lib = _bind(load_library())
+    a, b = C.c_uint64(), C.c_uint64()
+    lib.hipdec_tensor_stats(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def _torch_gpu():
+    """torch when it is importable and sees a GPU, else None"""
+    try:
+        import torch
+    except Exception:
+        return None
+    return torch if torch.cuda.is_available() else None
 
 
 def _info_dict(info):
@@ -299,6 +418,78 @@ class Batch:
         """asynchronous: every item scaled to its pre-allocated size, ONE launch"""
         check(self._lib.hipdec_batch_to_rgb_scaled_all(self._h, self._srgb_chroma, self._srgb_w, self._srgb_h, filter, self._srgb_ptrs,
                                                        self._srgb_strides, stream))
+
+    def to_tensor(self, size, entries=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, filter=SCALE_BOX, out=None,
+                  stream=None):
+        """asynchronous: crop windows of the decoded pictures, scaled to size = (width, height), optionally flipped, as ONE dense tensor of shape
+        (N, 3, height, width) ("NCHW") or (N, height, width, 3) ("NHWC") written by one fused kernel (hipdec_batch_to_tensor).
+
+        entries: (item, left, top, width, height[, flip]) tuples - the window in luma samples, all zeros after `item` for the whole picture, several
+        entries may name one item (center_crop_entry, random_resized_crop_entries) - or None: every item whole, in order.
+        dtype: "float16" | "bfloat16" | "float32" | "uint8".  Element = float32(V) * scale[c] + bias[c] (uint8: V itself), V the 8-bit component value,
+        or for float dtypes from sources above 8 bits the native-depth one.  scale / bias: a number or three per channel; or mean / std in the usual
+        0..1 convention, folded in float32 exactly as tensor_scale_bias() states:
+            scale[c] = float32(1) / (float32(max_value) * float32(std[c])),  bias[c] = -float32(mean[c]) / float32(std[c]),
+        max_value = 255, or 2^bits - 1 of item 0 for float dtypes from sources above 8 bits.
+        out: a DeviceBuffer of at least the tensor's bytes (returned as it is; tensor_to_host() reads it back as a NumPy array), or a contiguous
+        CUDA / HIP torch.Tensor of the tensor's shape and dtype (its data_ptr() is written; the stream defaults to torch's current stream - when that
+        is torch's legacy default stream the call waits on the host instead), or None: a torch tensor where torch sees a GPU, a DeviceBuffer elsewhere."""
+        n = self.n if entries is None else len(entries)
+        d0 = self.info(0)
+        max_value = (1 << d0["bit_depth_luma"]) - 1 if (dtype != "uint8" and d0["bit_depth_luma"] > 8) else 255
+        sc, bi = tensor_scale_bias(mean, std, scale, bias, max_value)
+        desc = tensor_desc(size, dtype, layout, filter, sc, bi)
+        shape = tensor_shape(n, size, layout)
+        nbytes = int(np.prod(shape)) * np.dtype(_TENSOR_NUMPY[dtype]).itemsize
+        arr = None if entries is None else tensor_entries(entries)
+        host_wait = False
+        if out is None:
+            torch = _torch_gpu()
+            out = torch.empty(shape, dtype=getattr(torch, dtype), device="cuda") if torch is not None else DeviceBuffer(max(nbytes, 1))
+        if isinstance(out, DeviceBuffer):
+            ptr, room = out.ptr, out.nbytes
+        else:
+            import torch
+            if not isinstance(out, torch.Tensor) or not out.is_cuda:
+                raise TypeError("out must be a DeviceBuffer or a CUDA / HIP torch.Tensor")
+            if tuple(out.shape) != shape:
+                raise ValueError("out has shape %s, the tensor has %s" % (tuple(out.shape), shape))
+            if out.dtype != getattr(torch, dtype):
+                raise ValueError("out has dtype %s, the tensor has %s" % (out.dtype, dtype))
+            if not out.is_contiguous():
+                raise ValueError("out must be contiguous")
+            ptr, room = out.data_ptr(), nbytes
+            if stream is None:
+                ts = torch.cuda.current_stream(out.device)
+                stream = ts.cuda_stream or None
+                if stream is None:
+                    # torch's legacy default stream has no handle the C ABI could name (NULL selects the library's own stream): order the two
+                    # on the host - what torch has queued for `out` first, and the tensor is complete when this call returns
+                    ts.synchronize()
+                    host_wait = True
+        check(self._lib.hipdec_batch_to_tensor(self._h, C.byref(desc), arr, n, ptr, room, stream))
+        if host_wait:
+            check(self._lib.hipdec_stream_synchronize(None))
+        self._tensor = (out, shape, _TENSOR_NUMPY[dtype], stream)
+        return out
+
+    def tensor_to_host(self):
+        """the last to_tensor() result as a NumPy array of the tensor's shape (bfloat16 as uint16 bit patterns); waits for its stream"""
+        out, shape, dt, stream = self._tensor
+        check(self._lib.hipdec_stream_synchronize(stream))
+        if isinstance(out, DeviceBuffer):
+            return out.to_numpy(shape, dt)
+        import torch
+        t = out.view(torch.int16) if dt == np.uint16 else out
+        a = t.cpu().numpy()
+        return a.view(np.uint16) if dt == np.uint16 else a
+
+    def tensor_block(self, entry, plane):
+        """debug inspection (hipdec_batch_tensor_block): (device pointer, stride, x, y, width, height) of a plane of an entry of the last to_tensor()"""
+        p, st = C.c_void_p(), C.c_size_t()
+        x, y, w, h = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(self._lib.hipdec_batch_tensor_block(self._h, entry, plane, C.byref(p), C.byref(st), C.byref(x), C.byref(y), C.byref(w), C.byref(h)))
+        return p.value, st.value, x.value, y.value, w.value, h.value
 
     def rgb_scaled(self, i):
         buf, stride, h = self._srgb[i]
