@@ -280,7 +280,7 @@ PC_DEV uint32_t read_byte(PS& s)
     if (s.pos >= s.end) { s.pos++; if (s.pos > s.end + 8) s.err = DEV_ERR_BITSTREAM_END; return 0; }
     b = fetch_byte(s, s.pos++);
     if (s.fast_limit) break;                                                   // a fresh window without candidates
-    if (s.zeros >= 2 && b == 3 && s.pos < s.end) { s.zeros = 0; continue; }  // emulation_prevention_three_byte
+    if (s.zeros >= 2 && b == 3) { s.zeros = 0; continue; }  // emulation_prevention_three_byte (7.3.1.1: also as the last byte, behind cabac_zero_words)
     s.zeros = b == 0 ? s.zeros + 1 : 0;
     break;
   }
@@ -301,6 +301,15 @@ PC_DEV UReg read_byte_v(PS& s)
 PC_DEV void cabac_start(PS& s, uint32_t start, uint32_t end)
 {
   s.pos = start; s.end = end; s.zeros = 0; s.win_base = 0xfffff000u; s.fast_limit = 0;
+  s.range = pc_vec(510u << 7); s.bits_needed = pc_vec((uint32_t)-8);
+  const uint32_t b0 = read_byte(s), b1 = read_byte(s);
+  s.value = pc_vec((b0 << 8) | b1);
+}
+// 9.3.2.5 behind a terminating bin of 1 and what follows it up to a byte boundary (pcm_flag: the PCM samples): the engine starts again at the byte
+// behind the last one read - the terminating bin's last bit is the final 1 of the encoder's flush, the bits up to the boundary are alignment zeros -
+// and the byte reader keeps its window and zero run
+PC_DEV void cabac_restart(PS& s)
+{
   s.range = pc_vec(510u << 7); s.bits_needed = pc_vec((uint32_t)-8);
   const uint32_t b0 = read_byte(s), b1 = read_byte(s);
   s.value = pc_vec((b0 << 8) | b1);
@@ -919,11 +928,7 @@ PC_DEV void pcm_coding_unit(PS& s, int zb, int log2cb, int16_t* coef_y, int16_t*
     }
     flush_coef(s, c == 0 ? coef_y + zb * 16 : (c == 1 ? coef_cb : coef_cr) + zb * (cfi == 3 ? 16 : (cfi == 2 ? 8 : 4)) + t * n2, n2);
   }
-  s.range = pc_vec(510u << 7); s.bits_needed = pc_vec((uint32_t)-8);
-  {
-    const uint32_t b0 = read_byte(s), b1 = read_byte(s);
-    s.value = pc_vec((b0 << 8) | b1);
-  }
+  cabac_restart(s);
   fill_tu_maps(s, zb, n_units, (uint32_t)(UF_PCM | (s.cu_tq_bypass ? UF_BYPASS : 0)), 1u, (uint32_t)((log2cb << 4) | log2cb));
   map_fill(s.m_ipmc, zb, n_units, 1u);
   map_fill(s.m_qp, zb, n_units, (uint32_t)(uint8_t)(int8_t)s.cur_qp_y);

@@ -178,11 +178,12 @@ def test_parser_pool_scheduler_emulation(cfg, yield_ctbs, monkeypatch):
 
 
 def _unescape_like_the_spec(buf):
-    """7.4.2: 00 00 03 -> 00 00 inside a NAL unit; a trailing 03 (no byte behind it) is data"""
+    """7.3.1.1 / 7.4.2: 00 00 03 -> 00 00 inside a NAL unit.  A trailing 03 (no byte behind it) is an emulation prevention byte too: the syntax
+    tests i + 2 < NumBytesInNalUnit with i at the first zero, and 7.4.2 appends exactly this byte behind cabac_zero_words (tests/cabac_ref.py)"""
     out, zeros, i = bytearray(), 0, 0
     while i < len(buf):
         b = buf[i]
-        if zeros >= 2 and b == 3 and i + 1 < len(buf):
+        if zeros >= 2 and b == 3:
             zeros = 0; i += 1
             continue
         out.append(b)
