@@ -113,6 +113,9 @@ PC_DEV uint32_t pc_mul24(uint32_t a, uint32_t b) { return __umul24(a, b); }     
 #ifndef HIPDEC_PARSE_LDS_CTX
 #define HIPDEC_PARSE_LDS_CTX 0          // 1: context variables and the rangeTabLps / transIdxLps tables live in LDS (the throughput kernel, see "LDS-resident contexts" below)
 #endif
+#ifndef HIPDEC_PARSE_LDS_MAPS
+#define HIPDEC_PARSE_LDS_MAPS HIPDEC_PARSE_LDS_CTX   // 1: the CTB's five unit maps live in LDS as well (see "LDS-resident unit maps" below)
+#endif
 #ifndef HIPDEC_PARSE_INTER
 #define HIPDEC_PARSE_INTER 0            // 1: the build that also parses P slices (sequence tracks; parse_kernel_inter.hip, the CPU emulation)
 #endif
@@ -136,7 +139,25 @@ struct Lds {
   uint32_t tnext[64];                 // entry p': the variable after an LPS - (p'_next << 2), bit 16 set where the LPS flips valMps (pStateIdx 0)
   uint32_t vctx[16];                  // sig_coeff_flag run: byte address (inside this struct) of the context variable of each scan position
 #endif
+#if HIPDEC_PARSE_LDS_MAPS
+  // LDS-resident unit maps: the CTB's five byte maps (size, flags, intra mode, chroma mode | inter bits, QP), 256 B each, one byte per 4x4 unit
+  // in z-scan order - dword l of a map is what lane l of its register held.  A single-unit fill is one byte store at a wave-uniform address
+  // instead of v_readlane + scalar insert + v_writelane, a get is a broadcast byte read, and five VGPRs are free for the whole CTB body.
+  // Appended BEHIND the fields that the hand-scheduled statements address by byte offset; 3776 + 1280 = 5056 B of the 5120 B a workgroup may
+  // use at 32 one-wave workgroups per CU.
+  uint32_t umap[5 * 64];
+#endif
 };
+#if HIPDEC_PARSE_LDS_MAPS
+struct UMap { int base; };             // a unit map is a byte range of Lds::umap ...
+typedef UMap MapRef;
+#define PC_MAP_SYNC() PC_LDS_SYNC()    /* marks where a get follows a fill of the same bytes (the accesses are plain loads / stores that the compiler orders itself) */
+#define PC_MAP_DW(s, m) ((s).L->umap[((m).base >> 2) + lane])   /* this lane's four units of map m; only inside PC_VEC_BEGIN .. PC_VEC_END */
+#else
+typedef VReg& MapRef;                  // ... or a 64-lane register, four units per lane
+#define PC_MAP_DW(s, m) PC_L(m)
+#define PC_MAP_SYNC() do { } while (0)
+#endif
 #if HIPDEC_PARSE_LDS_CTX
 struct CtxGroup { int base; };         // a context group is an index range of Lds::ctx
 typedef CtxGroup CtxRef;
@@ -166,7 +187,11 @@ struct PS {
   VReg t_lps, t_next;
 #endif
   VReg win, win_next;
+#if HIPDEC_PARSE_LDS_MAPS
+  static constexpr UMap m_size{0}, m_flags{256}, m_ipm{512}, m_ipmc{768}, m_qp{1024};
+#else
   VReg m_size, m_flags, m_ipm, m_ipmc, m_qp;  // 4 units per lane, z-scan order
+#endif
   VReg p_left;                                  // left neighbour CTB: lane y = size byte | intra mode byte << 8 of its rightmost unit in unit row y
   VReg up;                                      // hand-off record of the CTB above: lanes 0..8 SaoParams dwords, lanes 9..12 the
                                                 //   size bytes of its bottom unit row (4 units per lane)
@@ -211,21 +236,43 @@ PC_DEV uint32_t compact1by1(uint32_t v)
 // cost the scalar-bound 4:2:0 parser 1.5 % (measured), so batches that hold such pictures run the general build (parse_kernel_general.hip) instead
 PC_DEV bool pc_is444(const PS& s) { return HIPDEC_PARSE_CHROMA_GENERAL && s.chroma_format_idc == 3; }
 PC_DEV bool pc_is422(const PS& s) { return HIPDEC_PARSE_CHROMA_GENERAL && s.chroma_format_idc == 2; }
-PC_DEV uint32_t map_get(const VReg& m, int z) { return (pc_rdlane(m, z >> 2) >> ((z & 3) * 8)) & 255u; }
+#if HIPDEC_PARSE_LDS_MAPS
+// (a wave's LDS operations execute in order; PC_LDS_SYNC() stands where a get follows a fill of the same bytes)
+PC_DEV uint32_t map_get(PS& s, MapRef m, int z)
+{
+  uint32_t v = 0;
+  PC_VEC_BEGIN v = ((const uint8_t*)s.L->umap)[m.base + z]; PC_VEC_END   // wave-uniform address: a broadcast read
+  return pc_uni(v);
+}
+// two gets of one decision (left and up neighbour): both reads are issued before the one wait
+PC_DEV void map_get2(PS& s, MapRef m, int z0, int z1, uint32_t& v0, uint32_t& v1)
+{
+  uint32_t a = 0, b = 0;
+  PC_VEC_BEGIN a = ((const uint8_t*)s.L->umap)[m.base + z0]; b = ((const uint8_t*)s.L->umap)[m.base + z1]; PC_VEC_END
+  v0 = pc_uni(a); v1 = pc_uni(b);
+}
+#else
+PC_DEV uint32_t map_get(PS&, MapRef m, int z) { return (pc_rdlane(m, z >> 2) >> ((z & 3) * 8)) & 255u; }
+PC_DEV void map_get2(PS& s, MapRef m, int z0, int z1, uint32_t& v0, uint32_t& v1) { v0 = map_get(s, m, z0); v1 = map_get(s, m, z1); }
+#endif
 // fills units [zb, zb + n) with byte b; n is 1 or a multiple of 4 with zb aligned to it
-PC_DEV void map_fill(VReg& m, int zb, int n, uint32_t b)
+PC_DEV void map_fill(PS& s, MapRef m, int zb, int n, uint32_t b)
 {
   if (n >= 4) {
     const int l0 = zb >> 2, nl = n >> 2;
     const uint32_t w = b * 0x01010101u;
     PC_VEC_BEGIN
-      if ((uint32_t)(lane - l0) < (uint32_t)nl) PC_L(m) = w;
+      if ((uint32_t)(lane - l0) < (uint32_t)nl) PC_MAP_DW(s, m) = w;
     PC_VEC_END
   } else {
+#if HIPDEC_PARSE_LDS_MAPS
+    PC_VEC_BEGIN ((uint8_t*)s.L->umap)[m.base + zb] = (uint8_t)b; PC_VEC_END   // every lane stores the same byte to the same address
+#else
     const int sh = (zb & 3) * 8;
     uint32_t w = pc_rdlane(m, zb >> 2);
     w = (w & ~(255u << sh)) | (b << sh);
     pc_wrlane(m, zb >> 2, w);
+#endif
   }
 }
 
@@ -534,13 +581,13 @@ PC_DEV void load_tables(PS& s)
 // log2 CB size of the unit left of / above unit (ux, uy) of the current CTB, or 0 if unavailable
 PC_DEV int left_cb_log2(PS& s, int ux, int uy)
 {
-  if (ux > 0) return (int)(map_get(s.m_size, (int)interleave4((uint32_t)ux - 1, (uint32_t)uy)) >> 4);
+  if (ux > 0) return (int)(map_get(s, s.m_size, (int)interleave4((uint32_t)ux - 1, (uint32_t)uy)) >> 4);
   if (s.ctb_avail & AV_LEFT) return (int)((pc_rdlane(s.p_left, uy) & 255u) >> 4);
   return 0;
 }
 PC_DEV int up_cb_log2(PS& s, int ux, int uy)
 {
-  if (uy > 0) return (int)(map_get(s.m_size, (int)interleave4((uint32_t)ux, (uint32_t)uy - 1)) >> 4);
+  if (uy > 0) return (int)(map_get(s, s.m_size, (int)interleave4((uint32_t)ux, (uint32_t)uy - 1)) >> 4);
   if (s.ctb_avail & AV_UP) return (int)(((pc_rdlane(s.up, 9 + (ux >> 2)) >> ((ux & 3) * 8)) & 255u) >> 4);
   return 0;
 }
@@ -549,8 +596,12 @@ PC_DEV void derive_qp_pred(PS& s, int ux, int uy)
 {
   const int prev = s.last_qp_y;
   int a = prev, b = prev;
-  if (ux > 0) a = (int8_t)map_get(s.m_qp, (int)interleave4((uint32_t)ux - 1, (uint32_t)uy));
-  if (uy > 0) b = (int8_t)map_get(s.m_qp, (int)interleave4((uint32_t)ux, (uint32_t)uy - 1));
+  if (ux > 0 && uy > 0) {
+    uint32_t va, vb;
+    map_get2(s, s.m_qp, (int)interleave4((uint32_t)ux - 1, (uint32_t)uy), (int)interleave4((uint32_t)ux, (uint32_t)uy - 1), va, vb);
+    a = (int8_t)va; b = (int8_t)vb;
+  } else if (ux > 0) a = (int8_t)map_get(s, s.m_qp, (int)interleave4((uint32_t)ux - 1, (uint32_t)uy));
+  else if (uy > 0) b = (int8_t)map_get(s, s.m_qp, (int)interleave4((uint32_t)ux, (uint32_t)uy - 1));
   s.qpy_pred = (a + b + 1) >> 1;
 }
 PC_DEV void set_qp_y(PS& s)
@@ -890,15 +941,15 @@ PC_DEV void fill_tu_maps(PS& s, int zu, int tu_units, uint32_t fl, uint32_t ipm,
           if ((i & 0xAAAAAAAAu) == 0) f |= he;         // y == 0
           wf |= f << (8 * k);
         }
-        PC_L(s.m_flags) = wf;
-        PC_L(s.m_size) = szb * 0x01010101u;
-        PC_L(s.m_ipm) = ipm * 0x01010101u;
+        PC_MAP_DW(s, s.m_flags) = wf;
+        PC_MAP_DW(s, s.m_size) = szb * 0x01010101u;
+        PC_MAP_DW(s, s.m_ipm) = ipm * 0x01010101u;
       }
     PC_VEC_END
   } else {
-    map_fill(s.m_flags, zu, 1, fl | ve | he);
-    map_fill(s.m_size, zu, 1, szb);
-    map_fill(s.m_ipm, zu, 1, ipm);
+    map_fill(s, s.m_flags, zu, 1, fl | ve | he);
+    map_fill(s, s.m_size, zu, 1, szb);
+    map_fill(s, s.m_ipm, zu, 1, ipm);
   }
 }
 
@@ -930,8 +981,9 @@ PC_DEV void pcm_coding_unit(PS& s, int zb, int log2cb, int16_t* coef_y, int16_t*
   }
   cabac_restart(s);
   fill_tu_maps(s, zb, n_units, (uint32_t)(UF_PCM | (s.cu_tq_bypass ? UF_BYPASS : 0)), 1u, (uint32_t)((log2cb << 4) | log2cb));
-  map_fill(s.m_ipmc, zb, n_units, 1u);
-  map_fill(s.m_qp, zb, n_units, (uint32_t)(uint8_t)(int8_t)s.cur_qp_y);
+  map_fill(s, s.m_ipmc, zb, n_units, 1u);
+  map_fill(s, s.m_qp, zb, n_units, (uint32_t)(uint8_t)(int8_t)s.cur_qp_y);
+  PC_MAP_SYNC();   // later coding units (and the publish block) read what this one filled
   s.last_qp_y = s.cur_qp_y;
 }
 
@@ -1034,10 +1086,10 @@ PC_DEV void inter_coding_unit(PS& s, int zb, int log2cb, int cu_skip, int16_t* c
   const int n_units = 1 << (2 * (log2cb - 2)), nw = 1 << (log2cb - 2);   // units in the CU, units per CU side
   set_qp_y(s);
   const uint32_t bypass = s.cu_tq_bypass ? UF_BYPASS : 0u;
-  map_fill(s.m_size, zb, n_units, (uint32_t)(log2cb << 4));
-  map_fill(s.m_flags, zb, n_units, bypass);
-  map_fill(s.m_ipm, zb, n_units, 1u);                                     // a neighbour that is not intra coded counts as INTRA_DC (8.4.2)
-  map_fill(s.m_ipmc, zb, n_units, 1u | UM_INTER | (cu_skip ? UM_SKIP : 0u));
+  map_fill(s, s.m_size, zb, n_units, (uint32_t)(log2cb << 4));
+  map_fill(s, s.m_flags, zb, n_units, bypass);
+  map_fill(s, s.m_ipm, zb, n_units, 1u);                                     // a neighbour that is not intra coded counts as INTRA_DC (8.4.2)
+  map_fill(s, s.m_ipmc, zb, n_units, 1u | UM_INTER | (cu_skip ? UM_SKIP : 0u));
   int part_mode = PM_2Nx2N;
   if (!cu_skip) {
     part_mode = parse_part_mode_inter(s, log2cb);
@@ -1147,16 +1199,18 @@ PC_DEV void inter_coding_unit(PS& s, int zb, int log2cb, int cu_skip, int16_t* c
       if (c422 && do_chroma) {
         // 4:2:2: the lower chroma blocks' cbf and transform-skip bits go to unit index ^ 1, as in the intra tree
         const int z2 = zu ^ 1;
-        const uint32_t f2 = (map_get(s.m_flags, z2) & ~(uint32_t)(UF_CBF_CB | UF_CBF_CR)) | (cbf_cb2 ? UF_CBF_CB : 0u) | (cbf_cr2 ? UF_CBF_CR : 0u);
-        const uint32_t m2 = (map_get(s.m_ipm, z2) & 63u) | (((ts_bits >> 3) & 1u) ? 64u : 0u) | (((ts_bits >> 4) & 1u) ? 128u : 0u);
-        map_fill(s.m_flags, z2, 1, f2);
-        map_fill(s.m_ipm, z2, 1, m2);
+        PC_MAP_SYNC();
+        const uint32_t f2 = (map_get(s, s.m_flags, z2) & ~(uint32_t)(UF_CBF_CB | UF_CBF_CR)) | (cbf_cb2 ? UF_CBF_CB : 0u) | (cbf_cr2 ? UF_CBF_CR : 0u);
+        const uint32_t m2 = (map_get(s, s.m_ipm, z2) & 63u) | (((ts_bits >> 3) & 1u) ? 64u : 0u) | (((ts_bits >> 4) & 1u) ? 128u : 0u);
+        map_fill(s, s.m_flags, z2, 1, f2);
+        map_fill(s, s.m_ipm, z2, 1, m2);
       }
       qn += tu_units;
     }
   }
   // prediction block edges inside the coding unit (only those on the 8x8 luma grid get filtered; the deblocking kernel checks that)
   if (s.deblock && (vx >= 0 || hy >= 0)) {
+    PC_MAP_SYNC();
     PC_VEC_BEGIN
       uint32_t add = 0;
 #pragma unroll
@@ -1168,11 +1222,12 @@ PC_DEV void inter_coding_unit(PS& s, int zb, int log2cb, int cu_skip, int16_t* c
           if (uy == hy) add |= (uint32_t)UF_HEDGE << (8 * k);
         }
       }
-      PC_L(s.m_flags) |= add;
+      PC_MAP_DW(s, s.m_flags) |= add;
     PC_VEC_END
   }
   set_qp_y(s);
-  map_fill(s.m_qp, zb, n_units, (uint32_t)(uint8_t)(int8_t)s.cur_qp_y);
+  map_fill(s, s.m_qp, zb, n_units, (uint32_t)(uint8_t)(int8_t)s.cur_qp_y);
+  PC_MAP_SYNC();   // later coding units (and the publish block) read what this one filled
   s.last_qp_y = s.cur_qp_y;
 }
 #endif   // HIPDEC_PARSE_INTER
@@ -1187,9 +1242,9 @@ PC_DEV void coding_unit(PS& s, int zb /*unit z-index of the CU inside the CTB*/,
 #if HIPDEC_PARSE_INTER
   if (s.is_p) {   // cu_skip_flag (context: the left / above neighbours' flags, 9.3.4.2.2), pred_mode_flag
     int inc = 0;
-    if (ux0 > 0) inc += (int)(map_get(s.m_ipmc, (int)interleave4((uint32_t)ux0 - 1, (uint32_t)uy0)) >> 7);
+    if (ux0 > 0) inc += (int)(map_get(s, s.m_ipmc, (int)interleave4((uint32_t)ux0 - 1, (uint32_t)uy0)) >> 7);
     else if (s.ctb_avail & AV_LEFT) inc += (int)((pc_rdlane(s.p_left, uy0) >> 23) & 1u);
-    if (uy0 > 0) inc += (int)(map_get(s.m_ipmc, (int)interleave4((uint32_t)ux0, (uint32_t)uy0 - 1)) >> 7);
+    if (uy0 > 0) inc += (int)(map_get(s, s.m_ipmc, (int)interleave4((uint32_t)ux0, (uint32_t)uy0 - 1)) >> 7);
     else if (s.ctb_avail & AV_UP) inc += (int)((pc_rdlane(s.up, 13) >> ux0) & 1u);
     const int cu_skip = decode_bin(s, s.ctxC, C_SKIP_FLAG + inc);
     int inter = 1;
@@ -1205,9 +1260,9 @@ PC_DEV void coding_unit(PS& s, int zb /*unit z-index of the CU inside the CTB*/,
   }
   set_qp_y(s);
   // CU-level map fill (contiguous in z-order)
-  map_fill(s.m_size, zb, n_units, (uint32_t)(log2cb << 4));
-  map_fill(s.m_flags, zb, n_units, (uint32_t)(s.cu_tq_bypass ? UF_BYPASS : 0));
-  map_fill(s.m_ipm, zb, n_units, 1u);
+  map_fill(s, s.m_size, zb, n_units, (uint32_t)(log2cb << 4));
+  map_fill(s, s.m_flags, zb, n_units, (uint32_t)(s.cu_tq_bypass ? UF_BYPASS : 0));
+  map_fill(s, s.m_ipm, zb, n_units, 1u);
   // intra prediction modes 7.3.8.5 / 8.4.2
   const int n_part = part_nxn ? 4 : 1;
   const int pu_units = n_units / n_part;                    // units per PU (contiguous quadrant)
@@ -1220,9 +1275,15 @@ PC_DEV void coding_unit(PS& s, int zb /*unit z-index of the CU inside the CTB*/,
     else rem = decode_bypass_bits(s, 5);
     const int ux = ux0 + (k & 1) * pu_w, uy = uy0 + (k >> 1) * pu_w;
     int cand_a = 1, cand_b = 1;
-    if (ux > 0) cand_a = (int)(map_get(s.m_ipm, (int)interleave4((uint32_t)ux - 1, (uint32_t)uy)) & 63u);
-    else if (s.ctb_avail & AV_LEFT) cand_a = (int)((pc_rdlane(s.p_left, uy) >> 8) & 63u);
-    if (uy > 0) cand_b = (int)(map_get(s.m_ipm, (int)interleave4((uint32_t)ux, (uint32_t)uy - 1)) & 63u);  // above CTB row: INTRA_DC (8.4.2)
+    if (ux > 0 && uy > 0) {
+      uint32_t va, vb;
+      map_get2(s, s.m_ipm, (int)interleave4((uint32_t)ux - 1, (uint32_t)uy), (int)interleave4((uint32_t)ux, (uint32_t)uy - 1), va, vb);
+      cand_a = (int)(va & 63u); cand_b = (int)(vb & 63u);
+    } else {
+      if (ux > 0) cand_a = (int)(map_get(s, s.m_ipm, (int)interleave4((uint32_t)ux - 1, (uint32_t)uy)) & 63u);
+      else if (s.ctb_avail & AV_LEFT) cand_a = (int)((pc_rdlane(s.p_left, uy) >> 8) & 63u);
+      if (uy > 0) cand_b = (int)(map_get(s, s.m_ipm, (int)interleave4((uint32_t)ux, (uint32_t)uy - 1)) & 63u);  // above CTB row: INTRA_DC (8.4.2)
+    }
     int c0, c1, c2;
     if (cand_a == cand_b) {
       if (cand_a < 2) { c0 = 0; c1 = 1; c2 = 26; }
@@ -1243,7 +1304,8 @@ PC_DEV void coding_unit(PS& s, int zb /*unit z-index of the CU inside the CTB*/,
       if (mode >= c1) mode++;
       if (mode >= c2) mode++;
     }
-    map_fill(s.m_ipm, zb + k * pu_units, pu_units, (uint32_t)mode);
+    map_fill(s, s.m_ipm, zb + k * pu_units, pu_units, (uint32_t)mode);
+    PC_MAP_SYNC();   // the next partition's candidates and the transform tree's luma_mode read these bytes
   }
   // intra_chroma_pred_mode: one per coding unit, or one per partition of an NxN coding unit when ChromaArrayType is 3 (7.3.8.5)
   const int c444 = pc_is444(s);
@@ -1253,13 +1315,13 @@ PC_DEV void coding_unit(PS& s, int zb /*unit z-index of the CU inside the CTB*/,
     for (int k = 0; k < n_cp; k++) {
       int icpm = 4;
       if (decode_bin(s, s.ctxA, A_INTRA_CHROMA)) icpm = decode_bypass_bits(s, 2);
-      const int lm = (int)(map_get(s.m_ipm, zb + k * cp_units) & 63u);
+      const int lm = (int)(map_get(s, s.m_ipm, zb + k * cp_units) & 63u);
       if (icpm == 4) chroma_mode = lm;
       else { const int m = icpm == 0 ? 0 : icpm == 1 ? 26 : icpm == 2 ? 10 : 1; chroma_mode = (m == lm) ? 34 : m; }
       if (pc_is422(s)) chroma_mode = (int)c_map422[chroma_mode];   // 8.4.3, Table 8-3: the 4:2:2 sampling grid is not square
-      map_fill(s.m_ipmc, zb + k * cp_units, cp_units, (uint32_t)chroma_mode);
+      map_fill(s, s.m_ipmc, zb + k * cp_units, cp_units, (uint32_t)chroma_mode);
     }
-  } else map_fill(s.m_ipmc, zb, n_units, 1u);
+  } else map_fill(s, s.m_ipmc, zb, n_units, 1u);
 
   // ---- transform tree ----
   const int max_trafo_depth = s.max_th_depth_intra + part_nxn;
@@ -1303,9 +1365,9 @@ PC_DEV void coding_unit(PS& s, int zb /*unit z-index of the CU inside the CTB*/,
     const int cbf_cb = (int)((cbf_cb_bits >> depth) & 1u), cbf_cr = (int)((cbf_cr_bits >> depth) & 1u);
     const int cbf_cb2 = (int)((cbf_cb_bits >> (8 + depth)) & 1u), cbf_cr2 = (int)((cbf_cr_bits >> (8 + depth)) & 1u);   // 4:2:2 only
     if ((cbf_luma | cbf_cb | cbf_cr | cbf_cb2 | cbf_cr2) && (s.tools & TOOL_CUQPD) && !s.is_cu_qp_delta_coded) parse_cu_qp_delta(s);
-    const int luma_mode = (int)(map_get(s.m_ipm, zu) & 63u);
+    const int luma_mode = (int)(map_get(s, s.m_ipm, zu) & 63u);
     int do_chroma = 0, zc = zu, tc = t - 1;
-    if (c444) { do_chroma = 1; tc = t; chroma_mode = (int)map_get(s.m_ipmc, zu); }   // chroma blocks coincide with the luma blocks
+    if (c444) { do_chroma = 1; tc = t; chroma_mode = (int)map_get(s, s.m_ipmc, zu); }   // chroma blocks coincide with the luma blocks
     else if (s.chroma_format_idc) {
       if (t > 2) do_chroma = 1;
       else if ((q & 3) == 3) { do_chroma = 1; zc = zb + (q & ~3); tc = 2; }
@@ -1344,15 +1406,17 @@ PC_DEV void coding_unit(PS& s, int zb /*unit z-index of the CU inside the CTB*/,
       // 4:2:2: the flags of the LOWER chroma blocks live in the unit next to the one that carries the upper blocks' (index ^ 1: the 2nd unit of a
       // block of 8x8 and up, the 3rd of a quad of 4x4 luma blocks): its cbf_cb / cbf_cr bits and the transform-skip bits of its mode byte
       const int z2 = zu ^ 1;
-      const uint32_t f2 = (map_get(s.m_flags, z2) & ~(uint32_t)(UF_CBF_CB | UF_CBF_CR)) | (cbf_cb2 ? UF_CBF_CB : 0u) | (cbf_cr2 ? UF_CBF_CR : 0u);
-      const uint32_t m2 = (map_get(s.m_ipm, z2) & 63u) | (((ts_bits >> 3) & 1u) ? 64u : 0u) | (((ts_bits >> 4) & 1u) ? 128u : 0u);
-      map_fill(s.m_flags, z2, 1, f2);
-      map_fill(s.m_ipm, z2, 1, m2);
+      PC_MAP_SYNC();
+      const uint32_t f2 = (map_get(s, s.m_flags, z2) & ~(uint32_t)(UF_CBF_CB | UF_CBF_CR)) | (cbf_cb2 ? UF_CBF_CB : 0u) | (cbf_cr2 ? UF_CBF_CR : 0u);
+      const uint32_t m2 = (map_get(s, s.m_ipm, z2) & 63u) | (((ts_bits >> 3) & 1u) ? 64u : 0u) | (((ts_bits >> 4) & 1u) ? 128u : 0u);
+      map_fill(s, s.m_flags, z2, 1, f2);
+      map_fill(s, s.m_ipm, z2, 1, m2);
     }
     q += tu_units;
   }
   set_qp_y(s);
-  map_fill(s.m_qp, zb, n_units, (uint32_t)(uint8_t)(int8_t)s.cur_qp_y);
+  map_fill(s, s.m_qp, zb, n_units, (uint32_t)(uint8_t)(int8_t)s.cur_qp_y);
+  PC_MAP_SYNC();   // later coding units (and the publish block) read what this one filled
   s.last_qp_y = s.cur_qp_y;
 }
 
@@ -1680,7 +1744,7 @@ PC_DEV int parse_substream(const ParseArgs& A, uint32_t sub_idx, int same_wave_d
 
   load_tables(s);
   PC_VEC_BEGIN
-    PC_L(s.m_size) = 0; PC_L(s.m_flags) = 0; PC_L(s.m_ipm) = 0; PC_L(s.m_ipmc) = 0; PC_L(s.m_qp) = 0;
+    PC_MAP_DW(s, s.m_size) = 0; PC_MAP_DW(s, s.m_flags) = 0; PC_MAP_DW(s, s.m_ipm) = 0; PC_MAP_DW(s, s.m_ipmc) = 0; PC_MAP_DW(s, s.m_qp) = 0;
     PC_L(s.p_left) = 0; PC_L(s.up) = 0; PC_L(s.sao) = 0; PC_L(s.sao_left) = 0;
 #if HIPDEC_PARSE_LDS_CTX
     for (int g = 0; g < 3; g++) s.L->ctx[g * 64 + lane] = 0;
@@ -1690,6 +1754,7 @@ PC_DEV int parse_substream(const ParseArgs& A, uint32_t sub_idx, int same_wave_d
 #endif
     PC_L(s.win) = 0; PC_L(s.win_next) = 0;
   PC_VEC_END
+  PC_MAP_SYNC();   // (LDS maps outlive the task that ran on this wave before: units this activation never parses are published as zero)
   uint32_t k0 = 0;
   uint32_t* saved = A.saved + (size_t)sub_idx * SAVE_DWORDS;
   if (pool) k0 = pc_load_wt_uni(A.resume_k + sub_idx);
@@ -1785,7 +1850,12 @@ PC_DEV int parse_substream(const ParseArgs& A, uint32_t sub_idx, int same_wave_d
         if (x0 + size <= s.width && y0 + size <= s.height && lg > s.log2_min_cb) {
           const int depth = s.log2_ctb - lg;
           int inc = 0;
-          const int l = left_cb_log2(s, ux, uy), u = up_cb_log2(s, ux, uy);
+          int l, u;
+          if (ux > 0 && uy > 0) {   // both neighbours inside this CTB: one wait for the two reads
+            uint32_t vl, vu;
+            map_get2(s, s.m_size, (int)interleave4((uint32_t)ux - 1, (uint32_t)uy), (int)interleave4((uint32_t)ux, (uint32_t)uy - 1), vl, vu);
+            l = (int)(vl >> 4); u = (int)(vu >> 4);
+          } else { l = left_cb_log2(s, ux, uy); u = up_cb_log2(s, ux, uy); }
           if (l && s.log2_ctb - l > depth) inc++;
           if (u && s.log2_ctb - u > depth) inc++;
           split = decode_bin(s, s.ctxA, A_SPLIT_CU + inc);
@@ -1828,11 +1898,11 @@ PC_DEV int parse_substream(const ParseArgs& A, uint32_t sub_idx, int same_wave_d
       uint8_t* const g_qp = arena + uload64(&P->off_u_qp);
       PC_VEC_BEGIN
         if (lane < nl) {
-          ((uint32_t*)(g_size + base))[lane] = PC_L(s.m_size);
-          ((uint32_t*)(g_flags + base))[lane] = PC_L(s.m_flags);
-          ((uint32_t*)(g_ipm + base))[lane] = PC_L(s.m_ipm);
-          ((uint32_t*)(g_ipmc + base))[lane] = PC_L(s.m_ipmc);
-          ((uint32_t*)(g_qp + base))[lane] = PC_L(s.m_qp);
+          ((uint32_t*)(g_size + base))[lane] = PC_MAP_DW(s, s.m_size);
+          ((uint32_t*)(g_flags + base))[lane] = PC_MAP_DW(s, s.m_flags);
+          ((uint32_t*)(g_ipm + base))[lane] = PC_MAP_DW(s, s.m_ipm);
+          ((uint32_t*)(g_ipmc + base))[lane] = PC_MAP_DW(s, s.m_ipmc);
+          ((uint32_t*)(g_qp + base))[lane] = PC_MAP_DW(s, s.m_qp);
         }
         if (lane < 9) sao_dst[lane] = PC_L(s.sao);
         // this CTB becomes the left neighbour of the next one
@@ -1842,8 +1912,16 @@ PC_DEV int parse_substream(const ParseArgs& A, uint32_t sub_idx, int same_wave_d
         VReg col;
         PC_VEC_BEGIN
           const uint32_t z = interleave4((uint32_t)uw - 1u, (uint32_t)lane & 15u);
+#if HIPDEC_PARSE_LDS_MAPS
+          const uint8_t* const um = (const uint8_t*)s.L->umap;
+          const uint32_t sz = um[s.m_size.base + z], im = um[s.m_ipm.base + z];
+#else
           const uint32_t sz = (PC_GATHER(s.m_size, z >> 2) >> ((z & 3u) * 8u)) & 255u, im = (PC_GATHER(s.m_ipm, z >> 2) >> ((z & 3u) * 8u)) & 255u;
-#if HIPDEC_PARSE_INTER
+#endif
+#if HIPDEC_PARSE_INTER && HIPDEC_PARSE_LDS_MAPS
+          const uint32_t ic = um[s.m_ipmc.base + z];   // bit 7: the unit is skipped (cu_skip_flag's context)
+          PC_L(col) = (lane < uw) ? (sz | (im << 8) | (ic << 16)) : 0u;
+#elif HIPDEC_PARSE_INTER
           const uint32_t ic = (PC_GATHER(s.m_ipmc, z >> 2) >> ((z & 3u) * 8u)) & 255u;   // bit 7: the unit is skipped (cu_skip_flag's context)
           PC_L(col) = (lane < uw) ? (sz | (im << 8) | (ic << 16)) : 0u;
 #else
@@ -1856,18 +1934,38 @@ PC_DEV int parse_substream(const ParseArgs& A, uint32_t sub_idx, int same_wave_d
       {
         VReg rec;
         PC_VEC_BEGIN PC_L(rec) = PC_L(s.sao); PC_VEC_END
+#if HIPDEC_PARSE_LDS_MAPS
+        PC_VEC_BEGIN   // lane 9 + j: the size bytes of bottom-row units 4j .. 4j + 3, one byte read each
+          const int j = lane - 9;
+          if ((uint32_t)j < (uint32_t)((uw + 3) / 4)) {
+            uint32_t w = 0;
+            for (int b = 0; b < 4; b++)
+              if (4 * j + b < uw) w |= (uint32_t)((const uint8_t*)s.L->umap)[s.m_size.base + interleave4((uint32_t)(4 * j + b), (uint32_t)uw - 1)] << (8 * b);
+            PC_L(rec) = w;
+          }
+        PC_VEC_END
+#if HIPDEC_PARSE_INTER
+        {   // lane 13: cu_skip_flag of the bottom unit row, one bit per unit column
+          VReg skv;
+          PC_VEC_BEGIN PC_L(skv) = lane < uw ? (uint32_t)(((const uint8_t*)s.L->umap)[s.m_ipmc.base + interleave4((uint32_t)lane & 15u, (uint32_t)uw - 1)] >> 7) : 0u; PC_VEC_END
+          const uint32_t sk = (uint32_t)pc_ballot(skv);
+          PC_VEC_BEGIN if (lane == 13) PC_L(rec) = sk; PC_VEC_END
+        }
+#endif
+#else
         for (int j = 0; j < (uw + 3) / 4; j++) {
           uint32_t w = 0;
-          for (int b = 0; b < 4 && 4 * j + b < uw; b++) w |= map_get(s.m_size, (int)interleave4((uint32_t)(4 * j + b), (uint32_t)uw - 1)) << (8 * b);
+          for (int b = 0; b < 4 && 4 * j + b < uw; b++) w |= map_get(s, s.m_size, (int)interleave4((uint32_t)(4 * j + b), (uint32_t)uw - 1)) << (8 * b);
           pc_wrlane(rec, 9 + j, w);
         }
 #if HIPDEC_PARSE_INTER
         {   // lane 13: cu_skip_flag of the bottom unit row, one bit per unit column
           uint32_t sk = 0;
-          for (int j = 0; j < uw; j++) sk |= (map_get(s.m_ipmc, (int)interleave4((uint32_t)j, (uint32_t)uw - 1)) >> 7) << j;
+          for (int j = 0; j < uw; j++) sk |= (map_get(s, s.m_ipmc, (int)interleave4((uint32_t)j, (uint32_t)uw - 1)) >> 7) << j;
           pc_wrlane(rec, 13, sk);
         }
 #endif
+#endif   // HIPDEC_PARSE_LDS_MAPS
         uint32_t* dst = (uint32_t*)(arena + uload64(&P->off_handoff)) + (size_t)ctb_rs * HANDOFF_DWORDS;
         PC_VEC_BEGIN
           if (lane < (HIPDEC_PARSE_INTER ? 14 : 13)) pc_store_wt(dst + lane, PC_L(rec));

@@ -8,7 +8,7 @@ what=${1:-parse}
 mkdir -p $B; cd $B; rm -f *.gcda *.gcov
 if [ ! -f libparse_emu_cov.so ] || [ -n "$(find $C $E -newer libparse_emu_cov.so -name '*.h' -o -newer libparse_emu_cov.so -name '*.hip' -o -newer libparse_emu_cov.so -name '*.cc' | head -1)" ]; then
   rm -f *.gcno
-  g++ -O1 --coverage -std=c++17 -fPIC -Wno-unknown-pragmas -fno-strict-aliasing -DHIPDEC_HOST_EMU=1 -DHIPDEC_PARSE_INTER=0 -I$E/shim -I$E -I$ROOT/include -I$C -shared \
+  g++ -O1 --coverage -std=c++17 -fPIC -Wno-unknown-pragmas -fno-strict-aliasing -DHIPDEC_HOST_EMU=1 -DHIPDEC_PARSE_INTER=0 -DHIPDEC_PARSE_LDS_CTX=1 -I$E/shim -I$E -I$ROOT/include -I$C -shared \
     -o libparse_emu_cov.so $E/parse_emu.cc $E/pipeline_emu.cc $E/color_emu.cc -x c++ $C/hevc_headers.hip $C/batch_layout.hip $C/transform.hip \
     $C/residual_kernel.hip $C/recon_kernel.hip $C/filter_kernels.hip $C/color.hip $C/inter_kernels.hip -lpthread 2>&1 | grep -E "error" || true
 fi
@@ -30,7 +30,7 @@ if "$what" != "parse": print("pipeline status", L.emu_run_pipeline(h, 15))
 PY
 python runcov.py
 case $what in
-  parse) gcov -o . libparse_emu_cov.so-parse_emu.gcda > /dev/null 2>&1; python $ROOT/tools/dyn_profile.py $C/parse_kernel.hip k_parse_occ8 parse_core.h $B/parse_core.h.gcov 2073600;;
+  parse) gcov -o . libparse_emu_cov.so-parse_emu.gcda > /dev/null 2>&1; python $ROOT/tools/dyn_profile.py $C/parse_kernel_tp.hip k_parse_occ8 parse_core.h $B/parse_core.h.gcov 2073600;;
   recon) gcov -o . libparse_emu_cov.so-recon_kernel.gcda > /dev/null 2>&1; python $ROOT/tools/dyn_profile.py $C/recon_kernel.hip k_recon8 recon_kernel.hip $B/recon_kernel.hip.gcov 2073600;;
   residual) gcov -o . libparse_emu_cov.so-residual_kernel.gcda > /dev/null 2>&1; python $ROOT/tools/dyn_profile.py $C/residual_kernel.hip k_residual residual_kernel.hip $B/residual_kernel.hip.gcov 2073600;;
 esac
