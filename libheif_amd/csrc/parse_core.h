@@ -42,6 +42,9 @@
 // Defined here (one object per library, C++17 inline variable): the header needs nothing from the harness that includes it
 inline uint64_t hipdec_emu_path_counts[8] = {};
 #define PC_COUNT(k) (hipdec_emu_path_counts[k]++)
+// ... and of residual_coding's branches (tests/test_parse_residual_glue.py reads the array by name): see the PC_GLUE() sites
+inline uint64_t hipdec_emu_glue_counts[32] = {};
+#define PC_GLUE(k) (hipdec_emu_glue_counts[k]++)
 struct VReg { uint32_t v[64]; };
 #define PC_VEC_BEGIN for (int lane = 0; lane < 64; lane++) { (void)lane;
 #define PC_VEC_END }
@@ -66,6 +69,7 @@ PC_DEV uint32_t pc_mul24(uint32_t a, uint32_t b) { return a * b; }
 #define PC_FROM_LANE_BELOW(r) ((r).v[lane ? lane - 1 : 0])
 #else
 #define PC_COUNT(k) do { } while (0)
+#define PC_GLUE(k) do { } while (0)
 #include <hip/hip_runtime.h>
 #define PC_DEV __device__ __forceinline__
 typedef uint32_t VReg;
@@ -115,6 +119,9 @@ PC_DEV uint32_t pc_mul24(uint32_t a, uint32_t b) { return __umul24(a, b); }     
 #endif
 #ifndef HIPDEC_PARSE_LDS_MAPS
 #define HIPDEC_PARSE_LDS_MAPS HIPDEC_PARSE_LDS_CTX   // 1: the CTB's five unit maps live in LDS as well (see "LDS-resident unit maps" below)
+#endif
+#ifndef HIPDEC_PARSE_LEAN_GLUE
+#define HIPDEC_PARSE_LEAN_GLUE HIPDEC_PARSE_LDS_CTX   // 1: residual_coding's glue between the bins in its shorter form (see "lean glue" in residual_coding)
 #endif
 #ifndef HIPDEC_PARSE_INTER
 #define HIPDEC_PARSE_INTER 0            // 1: the build that also parses P slices (sequence tracks; parse_kernel_inter.hip, the CPU emulation)
@@ -756,8 +763,14 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
   {
     const int xs_t = last_x >> 2, ys_t = last_y >> 2;
     const uint32_t r_t = (uint32_t)((last_x & 3) | ((last_y & 3) << 2));
+#if HIPDEC_PARSE_LEAN_GLUE
+    // lean glue: the horizontal scan IS the raster order and the vertical one its transpose (parse_tables.h asserts both), so only the diagonal
+    // scan needs its table - one 64-bit constant instead of a run-time choice among three
+    last_pos = scan_idx == 0 ? (int)((uint32_t)(PC_INV_DIAG4 >> (r_t * 4u)) & 15u) : (scan_idx == 1 ? (int)r_t : (int)(((r_t & 3u) << 2) | (r_t >> 2)));
+#else
     const uint64_t inv4 = scan_idx == 0 ? PC_INV_DIAG4 : (scan_idx == 1 ? PC_INV_HORZ4 : PC_INV_VERT4);
     last_pos = (int)((uint32_t)(inv4 >> (r_t * 4u)) & 15u);
+#endif
     if (lg == 0) last_sb = 0;
     else if (lg == 1) last_sb = scan_idx == 1 ? (xs_t | (ys_t << 1)) : ((xs_t << 1) | ys_t);   // see scan_sb
     else if (lg == 2) last_sb = (int)((uint32_t)(PC_INV_DIAG4 >> ((uint32_t)(xs_t | (ys_t << 2)) * 4u)) & 15u);
@@ -765,19 +778,62 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
   }
   uint64_t csbf = 0;  // coded_sub_block_flag bitmap, bit (ys*8 + xs)
   const int sbw = 1 << lg;
+  (void)sbw;
+  // (CPU tests only) 0 transform_skip_flag set; 1 .. 4 luma 4x4 .. 32x32; 5 / 6 chroma 4x4 / 8x8; 7 .. 9 the scans of 4x4 blocks, 10 .. 12 of 8x8
+  // blocks; 13 / 14 the last position in the first / the last sub-block of a block of several; 16 / 17 coded_sub_block_flag decoded as 0 / 1, 18 / 19
+  // with the right / lower neighbour coded, 20 with neither; 21 a hidden sign, 22 none although the distance asks for one; 23 a block of a
+  // cu_transquant_bypass unit; 24 cu_qp_delta parsed; 26 a block with a level of 32767 and up that passes the range check; 27 / 28 4:2:2 / 4:4:4
+  if (ts) PC_GLUE(0);
+  PC_GLUE(c_idx ? 3 + log2n : log2n - 1);
+  if (log2n <= 3) PC_GLUE((log2n == 2 ? 7 : 10) + scan_idx);
+  if (lg > 0 && last_sb == 0) PC_GLUE(13);
+  if (lg > 0 && last_sb == (1 << (2 * lg)) - 1) PC_GLUE(14);
+  if (s.cu_tq_bypass) PC_GLUE(23);
+  if (pc_is422(s)) PC_GLUE(27);
+  if (pc_is444(s)) PC_GLUE(28);
+#if HIPDEC_PARSE_LEAN_GLUE
+  // lean glue (the throughput build): what the sub-block loop below derives per sub-block in the plain form is derived once per block here, or
+  // from ONE number per sub-block - its position ys * 8 + xs in the coded_sub_block_flag bitmap
+  int g1_zero = 0;   // the previous sub-block with greater1 flags left greater1Ctx at 0 (9.3.4.2.6: its successor's ctxSet is one up)
+  const int sdh = (s.tools & TOOL_SDH) != 0 && !s.cu_tq_bypass;
+  const int sig_dc = (c_idx == 0 && log2n > 2) ? 3 : 0;   // luma blocks above 4x4: the DC sub-block's contexts lie 3 below the others'
+  const int sig_base = log2n == 2 ? (c_idx ? 27 : 0) : (c_idx == 0 ? 3 + (log2n == 3 ? (scan_idx == 0 ? 9 : 15) : 21) : 27 + (log2n == 3 ? 9 : 12));
+#else
   int g1_carry = 1, first_sb_with_g1 = 1;
   const int sdh = (s.tools & TOOL_SDH) != 0;
+#endif
   VReg vovf;   // per lane: the largest |level| - (level < 0) it has stored for this block
   PC_VEC_BEGIN PC_L(vovf) = 0u; PC_VEC_END
   for (int i = last_sb; i >= 0; i--) {
+    int infer_dc = 0, coded;
+#if HIPDEC_PARSE_LEAN_GLUE
+    int pos;   // ys * 8 + xs (see scan_sb)
+    if (lg == 3) pos = (int)((pc_rdlane(s.t_next, i) >> 8) & 63u);
+    else if (lg == 2) { const uint32_t v = (uint32_t)(PC_DIAG4 >> (i * 4)) & 15u; pos = (int)((v & 3u) | ((v & 12u) << 1)); }
+    else if (lg == 1) pos = scan_idx == 1 ? ((i & 1) | ((i & 2) << 2)) : ((i >> 1) | ((i & 1) << 3));
+    else pos = 0;
+    // the flags of the right (bit 1) and lower (bit 8) neighbours with one 64-bit shift: rows and columns outside the block are never set, the
+    // row below row 7 is shifted out, and only column 7's right neighbour would be the next row's column 0
+    const uint32_t nb = (uint32_t)(csbf >> pos) & ((pos & 7) == 7 ? 0x100u : 0x102u);
+    if (i < last_sb && i > 0) {
+      coded = decode_bin(s, s.ctxA, A_CODED_SUB_BLOCK + (nb ? 1 : 0) + (c_idx ? 2 : 0));
+      infer_dc = 1;
+      PC_GLUE(coded ? 17 : 16); if (nb & 2u) PC_GLUE(18); if (nb & 0x100u) PC_GLUE(19); if (!nb) PC_GLUE(20);
+    } else coded = 1;
+    if (!coded) continue;
+    csbf |= 1ull << pos;
+    const uint32_t pat = log2n == 2 ? 0u : (nb == 0u ? PC_SIGPAT0 : (nb == 2u ? PC_SIGPAT1 : (nb == 0x100u ? PC_SIGPAT2 : PC_SIGPAT3)));
+    const int sig_off = sig_base - (pos ? 0 : sig_dc);
+    const int xs = pos, ys = 0;   // (only their union is looked at below)
+#else
     int xs, ys;
     scan_sb(s, lg, scan_idx, i, xs, ys);
-    int infer_dc = 0, coded;
     const int right = (xs < sbw - 1) ? (int)((csbf >> (ys * 8 + xs + 1)) & 1) : 0;
     const int below = (ys < sbw - 1) ? (int)((csbf >> ((ys + 1) * 8 + xs)) & 1) : 0;
     if (i < last_sb && i > 0) {
       coded = decode_bin(s, s.ctxA, A_CODED_SUB_BLOCK + ((right | below) ? 1 : 0) + (c_idx ? 2 : 0));
       infer_dc = 1;
+      PC_GLUE(coded ? 17 : 16); if (right) PC_GLUE(18); if (below) PC_GLUE(19); if (!(right | below)) PC_GLUE(20);
     } else coded = 1;
     if (!coded) continue;
     csbf |= 1ull << (ys * 8 + xs);
@@ -791,6 +847,7 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
       if (c_idx == 0) sig_off = ((xs | ys) ? 3 : 0) + ((log2n == 3) ? (scan_idx == 0 ? 9 : 15) : 21);
       else sig_off = 27 + ((log2n == 3) ? 9 : 12);
     }
+#endif
     // sig_coeff_flag contexts of the 16 scan positions, one per lane (vector), then the serial bin loop
     VReg vctx;
     {
@@ -819,14 +876,22 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
     }
     if (!sig) continue;
     // greater1 / greater2 flags
+#if HIPDEC_PARSE_LEAN_GLUE
+    const int ctx_set = ((i == 0 || c_idx > 0) ? 0 : 2) + g1_zero;
+#else
     int ctx_set = (i == 0 || c_idx > 0) ? 0 : 2;
     if (!first_sb_with_g1 && g1_carry == 0) ctx_set++;
     first_sb_with_g1 = 0;
+#endif
     const int last_sig_pos = 31 - pc_clz(sig), first_sig_pos = pc_ffs(sig) - 1;
     const int n_sig = pc_popc(sig), n_g1 = n_sig < 8 ? n_sig : 8;
     int g1_ctx = 1;
     const uint32_t gbits = decode_g1_run(s, C_GREATER1 + ctx_set * 4 + (c_idx ? 16 : 0), n_g1, g1_ctx);
+#if HIPDEC_PARSE_LEAN_GLUE
+    g1_zero = g1_ctx == 0;
+#else
     g1_carry = g1_ctx;
+#endif
     // the run's flags back at their scan positions: the r-th significant position from the top carries flag r (r < 8)
     uint32_t g1, g1_coded;
     {
@@ -841,14 +906,28 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
       g1_coded = (uint32_t)pc_ballot(vcoded);
       g1 = (uint32_t)pc_ballot(vg1);
     }
+#if HIPDEC_PARSE_LEAN_GLUE
+    const int sign_hidden = sdh && (last_sig_pos - first_sig_pos > 3);   // (sdh is already off in a cu_transquant_bypass unit)
+#else
     const int sign_hidden = s.cu_tq_bypass ? 0 : (sdh && (last_sig_pos - first_sig_pos > 3));
+#endif
+    if (sign_hidden) PC_GLUE(21); else if (last_sig_pos - first_sig_pos > 3) PC_GLUE(22);
     const uint32_t first_g1_bit = g1 ? 1u << (31 - pc_clz(g1)) : 0u;   // the first flag that was 1 (descending scan order)
     uint32_t g2 = 0;
     if (first_g1_bit && decode_bin(s, s.ctxB, B_GREATER2 + ctx_set + (c_idx ? 4 : 0))) g2 = first_g1_bit;
     // coeff_sign_flag: all of the sub-block's sign bins in one multi-bit bypass read (MSB = highest scan position)
+#if HIPDEC_PARSE_LEAN_GLUE
+    const uint32_t sig_signed = sig & ~((uint32_t)sign_hidden << first_sig_pos);
+#else
     const uint32_t sig_signed = sign_hidden ? sig & ~(1u << first_sig_pos) : sig;
+#endif
     const int n_signs = pc_popc(sig_signed);
     const uint32_t sign_bits = (uint32_t)decode_bypass_bits(s, n_signs);
+#if HIPDEC_PARSE_LEAN_GLUE
+    // the sign bins left-aligned (1 <= n_signs <= 16: a hidden sign needs two significant positions): the bin of the position with `rank` signs
+    // before it is then bit 31 - rank, and a position without a sign bin (the hidden one: rank == n_signs) reads a zero
+    const uint32_t sign_top = sign_bits << (32 - n_signs);
+#endif
     // coeff_abs_level_remaining for the positions whose base level hit its cap (9.3.3.11 order: descending k)
     const uint32_t need_rem = (g1_coded & g1 & ~(first_g1_bit & ~g2)) | (sig & ~g1_coded);
     VReg vrem, vbase;   // vbase: baseLevel of scan position k (1 + greater1 + greater2) on lane k, computed once for the sub-block
@@ -872,11 +951,19 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
       const uint32_t on = lane < 16 ? (sig >> k) & 1u : 0u;
       const uint32_t a = on ? 1u + ((g1 >> k) & 1u) + ((g2 >> k) & 1u) + PC_L(vrem) : 0u;
       const int rank = pc_popc(sig_signed >> (k + 1));       // sign bins decoded before this position's
+#if HIPDEC_PARSE_LEAN_GLUE
+      const uint32_t sgn = (sign_top << rank) >> 31;   // (positions that are not significant, and lanes 16 .. 63, hold a = 0: their sign is never looked at)
+#else
       const uint32_t sgn = (lane < 16 && ((sig_signed >> k) & 1u)) ? (sign_bits >> (n_signs - 1 - rank)) & 1u : 0u;
+#endif
       PC_L(vabs) = a; PC_L(vneg) = sgn; PC_L(vodd) = a & 1u;
     PC_VEC_END
     const uint32_t flip_first = sign_hidden ? (uint32_t)(pc_popc((uint32_t)pc_ballot(vodd)) & 1) : 0u;   // 9.3.4.? sign data hiding: parity of sumAbsLevel
+#if HIPDEC_PARSE_LEAN_GLUE
+    const int sb_base = ((pos >> 3) << (log2n + 2)) + ((pos & 7) << 2);
+#else
     const int sb_base = (ys << 2) * n + (xs << 2);
+#endif
     PC_VEC_BEGIN
       const int k = lane & 15;
       const uint32_t a = PC_L(vabs);
@@ -895,6 +982,9 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
     VReg vbad;
     PC_VEC_BEGIN PC_L(vbad) = PC_L(vovf) > 32767u ? 1u : 0u; PC_VEC_END
     if (pc_ballot(vbad)) { s.err = DEV_ERR_SYNTAX; PC_COUNT(4); }
+#if defined(HIPDEC_HOST_EMU)
+    else { VReg vbig; PC_VEC_BEGIN PC_L(vbig) = PC_L(vovf) >= 32767u ? 1u : 0u; PC_VEC_END if (pc_ballot(vbig)) PC_GLUE(26); }
+#endif
   }
   return ts;
 }
@@ -914,6 +1004,7 @@ PC_DEV void parse_cu_qp_delta(PS& s)
   }
   const int sign = v ? decode_bypass(s) : 0;
   s.is_cu_qp_delta_coded = 1;
+  PC_GLUE(24);
   s.cu_qp_delta_val = sign ? -v : v;
   const int off = 6 * (s.bit_depth_luma - 8);
   if (s.cu_qp_delta_val < -(26 + off / 2) || s.cu_qp_delta_val > 25 + off / 2) s.err = DEV_ERR_SYNTAX;
@@ -1398,10 +1489,18 @@ PC_DEV void coding_unit(PS& s, int zb /*unit z-index of the CU inside the CTB*/,
     }
     const int ts_y = (int)(ts_bits & 1u), ts_cb = (int)((ts_bits >> 1) & 1u), ts_cr = (int)((ts_bits >> 2) & 1u);
     // TU-level map fill: size, cbf, transform-skip, deblocking edges (8.7.2.2 / 8.7.2.3)
+#if HIPDEC_PARSE_LEAN_GLUE
+    // lean glue: coded_bits and ts_bits already hold the flags at (a shift of) their places in the flag and mode bytes
+    static_assert(UF_CBF_LUMA == 1 && UF_CBF_CB == 2 && UF_CBF_CR == 4 && UF_TS_LUMA == 128, "unit flag bits");
+    (void)ts_y; (void)ts_cb; (void)ts_cr;
+    fill_tu_maps(s, zu, tu_units, (coded_bits & 7u) | (uint32_t)(s.cu_tq_bypass ? UF_BYPASS : 0) | ((ts_bits & 1u) << 7),
+                 (uint32_t)luma_mode | ((ts_bits & 6u) << 5), (uint32_t)((log2cb << 4) | t));
+#else
     fill_tu_maps(s, zu, tu_units,
                  (uint32_t)((cbf_luma ? UF_CBF_LUMA : 0) | ((do_chroma && cbf_cb) ? UF_CBF_CB : 0) | ((do_chroma && cbf_cr) ? UF_CBF_CR : 0) |
                             (s.cu_tq_bypass ? UF_BYPASS : 0) | (ts_y ? UF_TS_LUMA : 0)),
                  (uint32_t)(luma_mode | (ts_cb ? 64 : 0) | (ts_cr ? 128 : 0)), (uint32_t)((log2cb << 4) | t));
+#endif
     if (c422 && do_chroma) {
       // 4:2:2: the flags of the LOWER chroma blocks live in the unit next to the one that carries the upper blocks' (index ^ 1: the 2nd unit of a
       // block of 8x8 and up, the 3rd of a quad of 4x4 luma blocks): its cbf_cb / cbf_cr bits and the transform-skip bits of its mode byte

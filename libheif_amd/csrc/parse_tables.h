@@ -100,6 +100,13 @@ constexpr uint64_t pc_invert_scan4(uint64_t scan)
 }
 constexpr uint64_t PC_INV_DIAG4 = pc_invert_scan4(PC_DIAG4), PC_INV_HORZ4 = pc_invert_scan4(PC_HORZ4), PC_INV_VERT4 = pc_invert_scan4(PC_VERT4);
 static_assert(PC_INV_HORZ4 == PC_HORZ4 && ((PC_INV_DIAG4 >> (4 * 4)) & 15u) == 1u && ((PC_INV_VERT4 >> (4 * 1)) & 15u) == 4u, "inverse scans");
+// the vertical scan is the transpose of the raster order: position ((x << 2) | y) holds raster index (x | (y << 2)), and so does its inverse
+constexpr bool pc_vert4_is_transpose()
+{
+  for (unsigned r = 0; r < 16; r++) if (((PC_INV_VERT4 >> (r * 4)) & 15u) != (((r & 3u) << 2) | (r >> 2))) return false;
+  return true;
+}
+static_assert(pc_vert4_is_transpose(), "inverse vertical scan");
 // sig_coeff_flag ctxIdxMap for 4x4 blocks (9.3.4.2.5), nibble r = ctxIdxMap[raster index r]
 #define PC_CTXIDXMAP4 0x8877886654325410ULL
 // sigCtx of 9.3.4.2.5 for larger blocks before the size / component offsets, two bits per raster

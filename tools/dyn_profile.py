@@ -1,14 +1,15 @@
 """Estimated DYNAMIC instruction profile of a kernel by source line: static ISA count per line (hipcc -S -g) x execution
 count per line from a gcov run of the host emulation (tests/emu built with --coverage).  Lines inside the emulated-lane
 loops of parse_core.h (PC_VEC_BEGIN..PC_VEC_END) run 64x per wave step on the host and are scaled back.  Dev tool.
-usage: dyn_profile.py <kernel.hip> <kernel-symbol-substring> <source-with-gcov> <file.gcov> [pixels]"""
+usage: dyn_profile.py <kernel.hip> <kernel-symbol-substring> <source-with-gcov> <file.gcov> [pixels]
+env: SALU=1 / VS=1 / SPILL=1 add the top lines of that class, BY_ELEMENT=1 the parser's table by syntax element, TOPN=<lines>"""
 import collections, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 kern, sym, srcname, gcovf = sys.argv[1:5]
 px = float(sys.argv[5]) if len(sys.argv) > 5 else None
 out = "/tmp/isa_%s.s" % os.path.basename(kern)
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-g", "-std=c++17", "-ffp-contract=off", "-I%s/include" % ROOT,
-                       "-I%s/libheif_amd/csrc" % ROOT, "-S", "--cuda-device-only", "-o", out, kern], stderr=subprocess.DEVNULL)
+                       "-I%s/libheif_amd/csrc" % ROOT, "-S", "--cuda-device-only", "-o", out, kern] + os.environ.get("EXTRA", "").split(), stderr=subprocess.DEVNULL)
 lines = open(out).read().split("\n")
 start = [i for i, l in enumerate(lines) if re.match(r"^_Z\S*%s\S*:" % re.escape(sym), l)][0]
 files = {}
@@ -118,6 +119,72 @@ if os.environ.get("SALU"):
     print("-- SALU by function:", {f: round(d / (px or 1), 2) for f, d in sbyf.most_common(12)})
     print("-- top SALU lines")
     for d, ln, c, k in srows[:int(os.environ.get("TOPN", "45"))]: print("%5.2f/px line %4d static %5.1f x %9.0f  %s" % (d / (px or 1), ln, c, k, text[ln].strip()[:100]))
+if os.environ.get("BY_ELEMENT"):
+    # the parser's estimate by SYNTAX ELEMENT (profiles/parse_residual_glue.txt): a group starts at the first line of its function that matches the
+    # anchor and runs to the next anchor or the function's end; a function without anchors is one group.  Occurrences: executions of the anchor line.
+    # SGPR spill reloads / stores (v_readlane / v_writelane with a constant lane) are taken out of their groups and shown as a class of their own.
+    ANCHORS = [("residual_coding", r"^PC_DEV int residual_coding", "transform_skip, last_x / last_y prefix and suffix"),
+               ("residual_coding", r"int scan_idx = 0;", "last-position lookup"),
+               ("residual_coding", r"uint64_t csbf = 0;", "sub-block loop control and csbf"),
+               ("residual_coding", r"per-sub-block sig_coeff_flag context selection|const uint32_t pat = log2n == 2", "sig-context setup"),
+               ("residual_coding", r"^#else", "sub-block loop control and csbf"),
+               ("residual_coding", r"sig_coeff_flag contexts of the 16 scan positions", "sig-context setup"),
+               ("residual_coding", r"// greater1 / greater2 flags", "greater1 / greater2 glue"),
+               ("residual_coding", r"// coeff_sign_flag:", "sign and remaining glue"),
+               ("residual_coding", r"// levels, signs \(incl", "level assembly and store"),
+               ("residual_coding", r"VReg vbad;", "overflow check"),
+               ("coding_unit", r"^PC_DEV void coding_unit", "coding_unit"),
+               ("coding_unit", r"// ---- transform tree ----", "transform-tree glue (cbf, split, destination, map arguments)")]
+    FUNCS = {"scan_sb": "sub-block loop control and csbf", "flush_coef": "level assembly and store",
+             "fill_tu_maps": "transform-tree glue (cbf, split, destination, map arguments)", "parse_cu_qp_delta": "coding_unit", "derive_qp_pred": "coding_unit",
+             "set_qp_y": "coding_unit", "left_cb_log2": "coding_unit", "up_cb_log2": "coding_unit",
+             "read_byte_v": "byte reading", "read_byte": "byte reading", "refill_byte": "byte reading", "load_window": "byte reading", "fetch_byte": "byte reading",
+             "map_fill": "unit-map access (map_fill, map_get, interleave4)", "map_get": "unit-map access (map_fill, map_get, interleave4)",
+             "map_get2": "unit-map access (map_fill, map_get, interleave4)", "interleave4": "unit-map access (map_fill, map_get, interleave4)",
+             "compact1by1": "unit-map access (map_fill, map_get, interleave4)",
+             "decode_remaining_v": "decode helpers (bypass, remaining: not glue)", "decode_remaining": "decode helpers (bypass, remaining: not glue)",
+             "decode_bypass_multi": "decode helpers (bypass, remaining: not glue)", "decode_bypass_bits": "decode helpers (bypass, remaining: not glue)",
+             "decode_bypass": "decode helpers (bypass, remaining: not glue)", "parse_substream": "CTB loop, quadtree, SAO, publish", "parse_sao": "CTB loop, quadtree, SAO, publish"}
+    group_at = {}; occ_line = {}; curg = None; lastf = None
+    for ln in sorted(text):
+        f = func_at.get(ln, "?")
+        if f != lastf: curg = FUNCS.get(f, "everything else"); lastf = f
+        for af, rx, g in ANCHORS:
+            if af == f and re.search(rx, text[ln]):
+                # the #else anchor only counts inside the sub-block loop's two forms of the head
+                if rx == r"^#else" and curg != "sig-context setup": continue
+                curg = g
+                if g not in occ_line: occ_line[g] = ln
+        group_at[ln] = curg
+    def occurrences(g):
+        ln = occ_line.get(g)
+        if ln is None: return 0
+        for k in range(ln, ln + 12):
+            if k in dyn and dyn[k] > 0 and group_at.get(k) == g: return dyn[k] / 64.0 if k in invec else dyn[k]
+        return 0
+    gt = collections.defaultdict(collections.Counter)
+    for (key, cls), cc in static_cls.items():
+        if not (key[0].endswith(srcname) and key[1]): continue
+        ln = key[1]; k = max(1, copies.get(func_at.get(ln, "?"), 1))
+        gt[group_at.get(ln, "everything else")][cls] += cc / k * count(ln)
+    print("-- by syntax element: instructions per pixel without SGPR spill traffic | per occurrence | scalar-file-touching (SALU + branch + Vs) | pure VALU | other (nop / waitcnt / memory)")
+    order = []
+    for _, _, g in ANCHORS:
+        if g not in order: order.append(g)
+    for g in FUNCS.values():
+        if g not in order: order.append(g)
+    order.append("everything else")
+    sp_r = sp_s = 0.0; tsum = 0.0
+    for g in order:
+        c = gt.get(g)
+        if not c: continue
+        spill = c["spill_reload"] + c["spill_store"]; sp_r += c["spill_reload"]; sp_s += c["spill_store"]
+        scal = c["S"] + c["B"] + c["Vs"] - spill; pure = c["Vp"]; other = c["N"] + c["M"]
+        tot_g = scal + pure + other; tsum += tot_g
+        o = occurrences(g)
+        print("%-62s %6.2f  %8s  %6.2f  %6.2f  %6.2f" % (g, tot_g / (px or 1), ("%.1f" % (tot_g / o)) if o else "-", scal / (px or 1), pure / (px or 1), other / (px or 1)))
+    print("%-62s %6.2f  (reloads %.2f, stores %.2f)" % ("SGPR spill reloads and stores", (sp_r + sp_s) / (px or 1), sp_r / (px or 1), sp_s / (px or 1)))
+    print("%-62s %6.2f" % ("sum", (tsum + sp_r + sp_s) / (px or 1)))
 rows.sort(reverse=True)
 print("estimated dynamic wave-instructions: %.3g%s" % (tot, (" = %.1f per pixel" % (tot / px)) if px else ""))
 byf = collections.Counter()

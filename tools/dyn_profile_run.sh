@@ -1,14 +1,15 @@
 #!/bin/bash
 # Estimated dynamic instruction profile of a kernel on the CPU (no GPU needed): builds the host emulation with --coverage under build/cov, runs
 # one 1080p still of the bench's content through it, gcov's the kernel source and weights the static ISA of <kernel> with the line counts
-# (tools/dyn_profile.py).  usage: dyn_profile_run.sh [parse|recon|residual] ;  env: SALU=1 (scalar instructions only), TOPN=<lines>
+# (tools/dyn_profile.py).  usage: dyn_profile_run.sh [parse|recon|residual] ;  env: SALU=1 (scalar instructions only), TOPN=<lines>,
+# BY_ELEMENT=1 (the parser's table by syntax element), EXTRA="-D..." (flags for both compilers, e.g. -DHIPDEC_PARSE_LEAN_GLUE=0; remove build/cov first)
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd); C=$ROOT/libheif_amd/csrc; E=$ROOT/tests/emu; B=$ROOT/build/cov
 what=${1:-parse}
 mkdir -p $B; cd $B; rm -f *.gcda *.gcov
 if [ ! -f libparse_emu_cov.so ] || [ -n "$(find $C $E -newer libparse_emu_cov.so -name '*.h' -o -newer libparse_emu_cov.so -name '*.hip' -o -newer libparse_emu_cov.so -name '*.cc' | head -1)" ]; then
   rm -f *.gcno
-  g++ -O1 --coverage -std=c++17 -fPIC -Wno-unknown-pragmas -fno-strict-aliasing -DHIPDEC_HOST_EMU=1 -DHIPDEC_PARSE_INTER=0 -DHIPDEC_PARSE_LDS_CTX=1 -I$E/shim -I$E -I$ROOT/include -I$C -shared \
+  g++ -O1 --coverage -std=c++17 -fPIC -Wno-unknown-pragmas -fno-strict-aliasing -DHIPDEC_HOST_EMU=1 -DHIPDEC_PARSE_INTER=0 -DHIPDEC_PARSE_LDS_CTX=1 $EXTRA -I$E/shim -I$E -I$ROOT/include -I$C -shared \
     -o libparse_emu_cov.so $E/parse_emu.cc $E/pipeline_emu.cc $E/color_emu.cc -x c++ $C/hevc_headers.hip $C/batch_layout.hip $C/transform.hip \
     $C/residual_kernel.hip $C/recon_kernel.hip $C/filter_kernels.hip $C/color.hip $C/inter_kernels.hip -lpthread 2>&1 | grep -E "error" || true
 fi
