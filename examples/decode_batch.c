@@ -9,11 +9,14 @@
  *                                                     (the size rule of libheif's examples/heif_thumbnailer.cc:172-186, area-averaged on the device)
  *   ./decode_batch --tensor 224 item0.hevc ...        ends in ONE launch that writes a float16 N x 3 x 224 x 224 tensor: the centred square of every item,
  *                                                     area-averaged, (V / 255 - mean) / std with the usual ImageNet constants
+ *   ./decode_batch --album 16 6x8 tile0.hevc ...      the items are TILES: 16 grid photos of 6 x 8 tiles (tile t of photo k is item (k * 48 + t) mod n; the
+ *                                                     output is the whole tiled area) composed by ONE launch set and ONE paste launch; prints Mpixel/s
  */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 #include "heif_hipdec.h"
 
 static void* slurp(const char* path, size_t* size)
@@ -30,9 +33,55 @@ static void* slurp(const char* path, size_t* size)
   return p;
 }
 
+/* K grid photos of rows x cols tiles as one album: create, then run + status three times (the first loads code objects), the last one timed */
+static int run_album(int k_photos, int rows, int cols, int n, const void** data, const size_t* sizes)
+{
+  hipdec_image_info tile;
+  if (hipdec_probe(data[0], sizes[0], 0, &tile)) { fprintf(stderr, "%s\n", hipdec_last_error()); return 1; }
+  const int per = rows * cols, n_tiles = k_photos * per;
+  hipdec_album_photo* photos = (hipdec_album_photo*)calloc((size_t)k_photos, sizeof(hipdec_album_photo));
+  const void** tiles = (const void**)calloc((size_t)n_tiles, sizeof(void*));
+  size_t* tile_sizes = (size_t*)calloc((size_t)n_tiles, sizeof(size_t));
+  for (int t = 0; t < n_tiles; t++) { tiles[t] = data[t % n]; tile_sizes[t] = sizes[t % n]; }
+  for (int k = 0; k < k_photos; k++) {
+    photos[k].rows = rows; photos[k].cols = cols; photos[k].first_tile = k * per;
+    photos[k].out_width = cols * tile.width; photos[k].out_height = rows * tile.height;
+  }
+  hipdec_album* a = NULL;
+  if (hipdec_album_create(&a, k_photos, photos, tiles, tile_sizes, n_tiles, 0)) { fprintf(stderr, "%s\n", hipdec_last_error()); return 1; }
+  double ms = 0;
+  for (int step = 0; step < 3; step++) {
+    struct timespec t0, t1;
+    timespec_get(&t0, TIME_UTC);
+    if (hipdec_album_run(a, NULL) || hipdec_album_status(a)) { fprintf(stderr, "%s\n", hipdec_last_error()); return 1; }
+    timespec_get(&t1, TIME_UTC);
+    ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) / 1e6;
+  }
+  const double mpix = (double)k_photos * photos[0].out_width * photos[0].out_height / 1e6;
+  const size_t es = tile.bit_depth_luma > 8 ? 2 : 1, row = (size_t)photos[0].out_width * es;
+  uint8_t* y = (uint8_t*)malloc(row * (size_t)photos[0].out_height);
+  if (!y || hipdec_album_read_plane(a, k_photos - 1, 0, y, row)) { fprintf(stderr, "%s\n", hipdec_last_error()); return 1; }
+  unsigned long long sum = 0;
+  for (size_t i = 0; i < row * (size_t)photos[0].out_height; i++) sum += y[i];
+  uint64_t albums = 0, n_photos = 0, pastes = 0;
+  hipdec_album_stats(&albums, &n_photos, &pastes);
+  printf("album: %d photos of %d x %d tiles, %dx%d each: %.2f ms, %.0f Mpixel/s of composed photos; %llu paste launches for %llu runs; luma byte sum of the last photo %llu\n",
+         k_photos, rows, cols, photos[0].out_width, photos[0].out_height, ms, mpix / ms * 1e3, (unsigned long long)pastes, 3ull, sum);
+  free(y); free(photos); free(tiles); free(tile_sizes);
+  hipdec_album_free(a);
+  hipdec_shutdown();
+  return 0;
+}
+
 int main(int argc, char** argv)
 {
   const char* prog = argv[0];
+  int album = 0, album_rows = 0, album_cols = 0;
+  if (argc >= 2 && !strcmp(argv[1], "--album")) {
+    album = argc >= 4 ? atoi(argv[2]) : 0;
+    if (album < 1 || sscanf(argv[3], "%dx%d", &album_rows, &album_cols) != 2 || album_rows < 1 || album_cols < 1 || album_rows > 256 || album_cols > 256) argc = 0;
+    else { argv += 3; argc -= 3; }
+  }
   int thumb = 0;
   if (argc >= 2 && !strcmp(argv[1], "--thumb")) {
     thumb = argc >= 3 ? atoi(argv[2]) : 0;
@@ -45,7 +94,7 @@ int main(int argc, char** argv)
     if (tensor < 1) argc = 0;
     else { argv += 2; argc -= 2; }
   }
-  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N | --tensor N] item.hevc [item.hevc ...]\n", prog); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
   const int n = argc - 1;
   const void** data = (const void**)calloc((size_t)n, sizeof(void*));
   size_t* sizes = (size_t*)calloc((size_t)n, sizeof(size_t));
@@ -57,6 +106,7 @@ int main(int argc, char** argv)
     if (rc) { fprintf(stderr, "%s: %s\n", argv[1 + i], hipdec_last_error()); return 1; }
   }
   hipdec_set_arena_cache_bytes((size_t)64 << 30);                  /* keep two large arenas parked instead of hipFree()ing them */
+  if (album) return run_album(album, album_rows, album_cols, n, data, sizes);
   hipdec_batch* prev = NULL;
   for (int step = 0; step < 3; step++) {                           /* the same items three times: a stand-in for a stream of batches */
     hipdec_batch* b = NULL;

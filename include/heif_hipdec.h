@@ -510,6 +510,45 @@ HIPDEC_API void hipdec_tensor_stats(uint64_t* tensors, uint64_t* entries);
 HIPDEC_API int hipdec_batch_tensor_block(hipdec_batch* b, int entry, int plane, const void** plane_dev, size_t* plane_stride, int* x, int* y, int* width,
                                          int* height);
 
+/* ---- albums of grid photos: K photos, ONE launch set, ONE fused paste ---------------------------------------------------------------------------------
+ * hipdec_grid_* composes one photo per object, so a host with an album pays one launch set per photo, each bound by a single tile's CABAC critical path.
+ * An album takes the tiles of all its photos into ONE hipdec_batch (the album owns it), so their substreams fill the CABAC pool together, and pastes
+ * every tile plane of every photo into its canvas - HeifPixelImage::copy_image_to (libheif/image/pixelimage.cc:1115-1172), clipped to the photo's output
+ * size - with ONE kernel launch over a job table.  The canvases stay in HBM until hipdec_album_free and feed the colour, scaled and tensor stages of the
+ * batch forms, one launch each.
+ *  photos[p]: a grid of rows x cols tiles (1 .. 256 each way) with output out_width x out_height; its tiles are tile_data[first_tile .. first_tile +
+ *  rows * cols - 1] in 'dimg' order (push_data framing).  Tile ranges lie inside n_tiles and do not overlap; reserved is 0.  Photos may differ in grid
+ *  geometry, tile size and output size; the album has one chroma format and one bit depth.  Per photo the rules of hipdec_grid_create hold: tiles of
+ *  one size, the output fits the tiled area, no subsampled tiles with odd dimensions.  max_image_size_pixels bounds every tile and every photo's output.
+ *  Whatever the arguments alone decide is refused before the library touches a device; what the tiles' headers decide, before anything is allocated.
+ * Out of scope: sharding an album over several devices (hipdec_grid_* remains the multi-GPU form), alpha and auxiliary images, the libheif integration
+ * hook, decoding straight into the canvas. */
+typedef struct hipdec_album hipdec_album;
+typedef struct hipdec_album_photo { int rows, cols, out_width, out_height, first_tile, reserved; } hipdec_album_photo;
+HIPDEC_API int hipdec_album_create(hipdec_album** out, int n_photos, const hipdec_album_photo* photos, const void* const* tile_data,
+                                   const size_t* tile_sizes, int n_tiles, uint64_t max_image_size_pixels);
+HIPDEC_API void hipdec_album_free(hipdec_album* a);
+HIPDEC_API int hipdec_album_count(const hipdec_album* a);           /* photos (a NULL album is an error, as for every call here) */
+/* info of the composed photo, as hipdec_grid_info (output size, coded size = tiled area, VUI colour description of the photo's tile 0) */
+HIPDEC_API int hipdec_album_info(const hipdec_album* a, int photo, hipdec_image_info* info);
+/* asynchronous: the batch's launch set over all tiles, then ONE paste launch (more than 65535 tile planes take as few launches as the grid size allows) */
+HIPDEC_API int hipdec_album_run(hipdec_album* a, void* stream);
+HIPDEC_API int hipdec_album_status(hipdec_album* a);                /* as hipdec_batch_status: waits for the album's work; device errors */
+/* plane c of photo's canvas in HBM (rows of the output size, 256-byte-aligned stride; the bytes between a row's end and its stride are unspecified) */
+HIPDEC_API int hipdec_album_canvas_plane(hipdec_album* a, int photo, int c, const void** dptr, size_t* stride);
+HIPDEC_API int hipdec_album_read_plane(hipdec_album* a, int photo, int c, void* dst_host, size_t dst_stride);
+/* hipdec_batch_to_rgb_all / _to_rgb_scaled_all / _to_tensor over pictures whose planes are the canvases: the same colour entry points, planner rules
+ * (nearest-neighbour chroma), refusals and window rules, one launch per call; outs_dev[p] / out_widths[p] / entry.item name photo p. */
+HIPDEC_API int hipdec_album_to_rgb_all(hipdec_album* a, int out_chroma, void* const* outs_dev, const size_t* out_strides, void* stream);
+HIPDEC_API int hipdec_album_to_rgb_scaled_all(hipdec_album* a, int out_chroma, const int* out_widths, const int* out_heights, int filter,
+                                              void* const* outs_dev, const size_t* out_strides, void* stream);
+HIPDEC_API int hipdec_album_to_tensor(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, int n_entries,
+                                      void* out_dev, size_t out_bytes, void* stream);
+/* counters since load: albums created, their photos, paste launches (exactly one per hipdec_album_run) */
+HIPDEC_API void hipdec_album_stats(uint64_t* albums, uint64_t* photos, uint64_t* paste_launches);
+/* measurement aid: device time of the paste of the last hipdec_album_run in microseconds (HIP events around its launch); waits for it */
+HIPDEC_API int hipdec_album_paste_timing_us(hipdec_album* a, float* us);
+
 /* counters since load: images through hipdec_image_transform, grid canvases handed out by hipdec_grid_read_plane_tracked (hipdec_image_scale counts in
  * hipdec_image_scale_stats) */
 HIPDEC_API void hipdec_image_ops_stats(uint64_t* transforms, uint64_t* grid_canvases);

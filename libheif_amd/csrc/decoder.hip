@@ -18,6 +18,7 @@
 #include <cmath>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <unordered_map>
 #include <cstdlib>
 #include <cstring>
@@ -141,8 +142,9 @@ namespace {
 // chains: the n items are consecutive samples of sequence tracks (BatchLayout::chain; items [first[t], first[t] + count[t]) belong to track t whose
 // state is *seqs[t]): the batch may come out EMPTY (every sample was a RASL picture 8.3.3 drops) - then nothing is allocated
 struct ChainPlan { int n_tracks; const int* first; const int* count; const SeqContext* const* seqs; int* bad_track; };
+// after_plan: the caller's own rules over the parsed items (hipdec_album_create: the grid geometry of every photo), applied before anything is allocated
 int build_batch(hipdec_batch& b, int n, const void* const* data, const size_t* sizes, uint64_t max_pixels, hipdec_batch* recycle = nullptr,
-                const SeqContext* const* seqs = nullptr, const ChainPlan* chains = nullptr)
+                const SeqContext* const* seqs = nullptr, const ChainPlan* chains = nullptr, const std::function<int(const hipdec_batch&)>* after_plan = nullptr)
 {
   std::string err;
   b.device = active_device();
@@ -150,6 +152,7 @@ int build_batch(hipdec_batch& b, int n, const void* const* data, const size_t* s
   int rc = chains ? layout_batch_plan_chains(b, chains->n_tracks, chains->first, chains->count, data, sizes, max_pixels, err, chains->seqs, chains->bad_track)
                   : layout_batch_plan(b, n, data, sizes, max_pixels, err, seqs);
   if (rc != HIPDEC_OK) return set_error(rc, "%s", err.c_str());
+  if (after_plan) if (int vrc = (*after_plan)(b)) return vrc;
   if (b.pics.empty()) return 0;
   HIPDEC_CHECK_HIP(hipEventCreateWithFlags(&b.done, hipEventDisableTiming));
   b.host_status = status_slot_acquire();
@@ -657,14 +660,21 @@ namespace {
 // entry points end in the fused scale + colour kernel (color.hip).  Box presents the planes as the 4:4:4 image they are scaled to.
 struct ScaleRequest { int ow, oh, filter; };
 int copy_rows_to_host(void* dst, size_t dst_stride, const void* dsrc, size_t src_stride, size_t row_bytes, int rows, hipStream_t s);   // decoder_color_boundary.inc
-int batch_to_rgb_impl(hipdec_batch* b, int i, int out_chroma, void* out_dev, size_t out_stride, void* stream, const ScaleRequest* rq)
+// The planes one picture hands to the colour entry points: a decoded item of a batch (hipdec_batch_to_rgb*), or the composed canvas of a photo of an
+// album (hipdec_album_to_rgb*, decoder_album.inc).  info: the VUI colour description and the bit depth.
+struct RgbSource {
+  const uint8_t* plane[3]; size_t stride[3];
+  int width, height, chroma_format_idc;
+  bool wide;
+  const hipdec_image_info* info;
+  uint64_t max_pixels;
+};
+// resolve_stream(): called once, when the argument checks have passed, for the stream the launch goes on
+template <class ResolveStream>
+int source_to_rgb(const RgbSource& S, int out_chroma, void* out_dev, size_t out_stride, const ScaleRequest* rq, ResolveStream&& resolve_stream)
 {
-  if (!b || i < 0 || i >= (int)b->pics.size() || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb: bad arguments");
-  DeviceScope scope(b->device);
-  if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb: the batch's arena was handed to another batch");
-  const PicParams& P = b->params[i];
-  int cf = P.chroma_format_idc;   // the chroma format the planner rules below see
-  const hipdec_image_info& I = b->pics[i].info;
+  int cf = S.chroma_format_idc;   // the chroma format the planner rules below see
+  const hipdec_image_info& I = *S.info;
   struct ScaleScope { bool on; ~ScaleScope() { if (on) color_scale_clear(); } } scale_scope{rq != nullptr};
   // a request serves exactly ONE launch and the entry point that takes it clears it: one that did not (it launched a full-size kernel) is an error here
   auto taken = [&](int rc) -> int {
@@ -674,59 +684,72 @@ int batch_to_rgb_impl(hipdec_batch* b, int i, int out_chroma, void* out_dev, siz
   if (rq) {
     if (rq->ow < 1 || rq->oh < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb_scaled: output size %d x %d", rq->ow, rq->oh);
     if (rq->filter != HIPDEC_SCALE_NEAREST && rq->filter != HIPDEC_SCALE_BOX) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb_scaled: unknown filter %d", rq->filter);
-    if (b->max_pixels && (uint64_t)rq->ow * (uint64_t)rq->oh > b->max_pixels)
+    if (S.max_pixels && (uint64_t)rq->ow * (uint64_t)rq->oh > S.max_pixels)
       return set_error(HIPDEC_ERR_LIMIT, "to_rgb_scaled: output of %d x %d pixels exceeds max_image_size_pixels", rq->ow, rq->oh);
-    color_scale_request(rq->ow, rq->oh, rq->filter, P.chroma_format_idc == 1 || P.chroma_format_idc == 2 ? 1 : 0, P.chroma_format_idc == 1 ? 1 : 0);
+    color_scale_request(rq->ow, rq->oh, rq->filter, S.chroma_format_idc == 1 || S.chroma_format_idc == 2 ? 1 : 0, S.chroma_format_idc == 1 ? 1 : 0);
     if (rq->filter == HIPDEC_SCALE_BOX && cf) cf = 3;   // (box: the 4:4:4 image the planes are scaled to)
   }
   {
     const size_t bpp = out_chroma == 10 ? 3 : (out_chroma == 11 ? 4 : (out_chroma == 12 || out_chroma == 14 ? 6 : 0));
-    const size_t row_px = rq ? (size_t)rq->ow : (size_t)P.out_width;
+    const size_t row_px = rq ? (size_t)rq->ow : (size_t)S.width;
     if (bpp && out_stride < row_px * bpp)
       return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb: out_stride %zu is smaller than a row of %zu bytes", out_stride, row_px * bpp);
   }
   if (!cf) {   // Op_mono_to_RGB24_32: 8-bit only, as in the reference
-    if (b->wide || (out_chroma != 10 && out_chroma != 11)) return set_error(HIPDEC_ERR_UNSUPPORTED, "to_rgb: monochrome input goes to 8-bit RGB / RGBA only");
-    void* ms = stream ? (void*)follow_stream(b, stream) : (void*)b->last_stream;
-    const int rc = taken(hipdec_color_mono_to_rgb24(b->arena + P.off_out[0], P.out_stride[0], nullptr, 0, P.out_width, P.out_height, out_dev, out_stride, out_chroma == 11, ms));
-    b->mark_done(ms ? (hipStream_t)ms : default_stream());
-    return rc;
+    if (S.wide || (out_chroma != 10 && out_chroma != 11)) return set_error(HIPDEC_ERR_UNSUPPORTED, "to_rgb: monochrome input goes to 8-bit RGB / RGBA only");
+    void* ms = resolve_stream();
+    return taken(hipdec_color_mono_to_rgb24(S.plane[0], S.stride[0], nullptr, 0, S.width, S.height, out_dev, out_stride, out_chroma == 11, ms));
   }
   // the decoder reports the VUI colour description exactly as the libde265 plugin would attach it
   hipdec_nclx nclx{1, I.colour_primaries, I.transfer_characteristics, I.matrix_coeffs, I.full_range_flag};
-  const uint8_t* y = b->arena + P.off_out[0]; const uint8_t* cb = b->arena + P.off_out[1]; const uint8_t* cr = b->arena + P.off_out[2];
-  void* s = stream ? (void*)follow_stream(b, stream) : (void*)b->last_stream;
-  struct MarkDone {   // whatever is enqueued below belongs to this batch (hipdec_batch_status / free wait for it)
-    hipdec_batch* b; hipStream_t s;
-    ~MarkDone() { b->mark_done(s ? s : default_stream()); }
-  } mark{b, (hipStream_t)s};
-  if ((out_chroma == 10 || out_chroma == 11) && b->wide) {
+  const uint8_t* y = S.plane[0]; const uint8_t* cb = S.plane[1]; const uint8_t* cr = S.plane[2];
+  void* s = resolve_stream();
+  if ((out_chroma == 10 || out_chroma == 11) && S.wide) {
     // > 8-bit planes to 8-bit RGB(A): one of the two chains of the planner (nearest-neighbour upsampling is this entry point's), fused into one pass
     const int m = I.matrix_coeffs == 2 ? 6 : I.matrix_coeffs;
     const int sdr_first = cf == 1 && I.full_range_flag && m != 0 && m != 8;
-    return taken(hipdec_color_hdr_to_rgb24(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height, I.bit_depth_luma,
+    return taken(hipdec_color_hdr_to_rgb24(y, S.stride[0], cb, S.stride[1], cr, S.stride[2], S.width, S.height, I.bit_depth_luma,
                                      cf, &nclx, out_dev, out_stride, out_chroma == 11, sdr_first, s));
   }
   if (out_chroma == 10 || out_chroma == 11) {
     // planner rule: integer op only for full range and a matrix it accepts
     const int m = I.matrix_coeffs == 2 ? 6 : I.matrix_coeffs;
     if (cf == 1 && I.full_range_flag && m != 0 && m != 8)
-      return taken(hipdec_color_420_to_rgb24(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height, &nclx, out_dev,
+      return taken(hipdec_color_420_to_rgb24(y, S.stride[0], cb, S.stride[1], cr, S.stride[2], S.width, S.height, &nclx, out_dev,
                                        out_stride, out_chroma == 11, s));
     // 4:4:4 planes take Op_YCbCr_to_RGB<uint8_t> + Op_RGB_to_RGB24_32 whatever the range (the only chain the planner has for them)
-    return taken(hipdec_color_ycbcr_to_rgb24_float(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height,
+    return taken(hipdec_color_ycbcr_to_rgb24_float(y, S.stride[0], cb, S.stride[1], cr, S.stride[2], S.width, S.height,
                                              cf, &nclx, out_dev, out_stride, out_chroma == 11, s));
   }
   if (out_chroma == 12 || out_chroma == 14) {
-    if (!b->wide) return set_error(HIPDEC_ERR_UNSUPPORTED, "to_rgb: RRGGBB output needs >8-bit planes");
+    if (!S.wide) return set_error(HIPDEC_ERR_UNSUPPORTED, "to_rgb: RRGGBB output needs >8-bit planes");
     const int m = I.matrix_coeffs == 2 ? 6 : I.matrix_coeffs;
     if (cf != 1 || m == 0 || m == 8)     // planner rule: the 4:2:0 op does not take these; Op_YCbCr_to_RGB<uint16_t> + the interleave does
-      return taken(hipdec_color_ycbcr_to_rrggbb_float(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height, I.bit_depth_luma,
+      return taken(hipdec_color_ycbcr_to_rrggbb_float(y, S.stride[0], cb, S.stride[1], cr, S.stride[2], S.width, S.height, I.bit_depth_luma,
                                                 cf, &nclx, out_dev, out_stride, out_chroma == 14, s));
-    return taken(hipdec_color_420_to_rrggbb(y, P.out_stride[0], cb, P.out_stride[1], cr, P.out_stride[2], P.out_width, P.out_height, I.bit_depth_luma,
+    return taken(hipdec_color_420_to_rrggbb(y, S.stride[0], cb, S.stride[1], cr, S.stride[2], S.width, S.height, I.bit_depth_luma,
                                       &nclx, out_dev, out_stride, out_chroma == 14, s));
   }
   return set_error(HIPDEC_ERR_UNSUPPORTED, "to_rgb: unsupported output chroma %d", out_chroma);
+}
+
+int batch_to_rgb_impl(hipdec_batch* b, int i, int out_chroma, void* out_dev, size_t out_stride, void* stream, const ScaleRequest* rq)
+{
+  if (!b || i < 0 || i >= (int)b->pics.size() || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb: bad arguments");
+  DeviceScope scope(b->device);
+  if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb: the batch's arena was handed to another batch");
+  const PicParams& P = b->params[i];
+  const RgbSource S{{b->arena + P.off_out[0], b->arena + P.off_out[1], b->arena + P.off_out[2]}, {P.out_stride[0], P.out_stride[1], P.out_stride[2]},
+                    P.out_width, P.out_height, P.chroma_format_idc, b->wide, &b->pics[i].info, b->max_pixels};
+  struct MarkDone {   // whatever is enqueued from the point the stream is resolved belongs to this batch (hipdec_batch_status / free wait for it)
+    hipdec_batch* b; bool armed; hipStream_t s;
+    ~MarkDone() { if (armed) b->mark_done(s ? s : default_stream()); }
+  } mark{b, false, nullptr};
+  return source_to_rgb(S, out_chroma, out_dev, out_stride, rq, [&]() -> void* {
+    void* s = stream ? (void*)follow_stream(b, stream) : (void*)b->last_stream;
+    mark.armed = true; mark.s = (hipStream_t)s;
+    return s;
+  });
 }
 
 // ---- tensor output (include/heif_hipdec.h): what hipdec_batch_to_tensor and hipdec_image_to_tensor (decoder_color_boundary.inc) share
@@ -1101,3 +1124,4 @@ int hipdec_probe(const void* data, size_t size, uint64_t max_image_size_pixels, 
 #include "decoder_chains.inc"          // look-ahead chains of sequence tracks, DPB / output order
 #include "decoder_color_boundary.inc"  // resident planes, colour planner, hipdec_color_convert, image transforms
 #include "decoder_grid.inc"            // grid photos over the node's GPUs
+#include "decoder_album.inc"           // albums of grid photos: one launch set, one fused paste

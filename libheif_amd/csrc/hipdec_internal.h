@@ -102,6 +102,15 @@ void color_tensor_abort();
 int color_tensor_launch(ColorBatchState& st, int filter, int dtype, hipStream_t s);
 int color_tensor_inspect(const ColorBatchState& st, int entry, int plane, const void** plane_dev, size_t* stride, int* x, int* y, int* w, int* h);
 
+// The paste of an album of grid photos (transform.hip k_album_paste): one job per (tile, plane), already clipped to the photo's output size by the host
+// (a job clipped to nothing is not emitted); the job table lives in device memory and all jobs go out as ONE launch.
+struct PasteJob {
+  const uint8_t* src; uint64_t src_stride;
+  uint8_t* dst; uint64_t dst_stride;
+  uint32_t width_bytes, rows;
+};
+int album_paste_launch(const PasteJob* jobs_dev, int n_jobs, uint32_t max_rows, hipStream_t s);
+
 // No C++ exception may cross the C ABI (the caller is libheif, or cgo / JNI / ctypes): every entry point that parses untrusted
 // input or allocates runs its body through guarded().
 template <class F> int guarded(const char* what, F&& body)

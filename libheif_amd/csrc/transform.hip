@@ -11,9 +11,14 @@
 //     samples per lane.
 // All are HBM-bound: algorithmic bytes = one read + one write of the plane.  The chroma rules of the reference (odd sizes of a subsampled
 // image would first be converted to 4:4:4) are applied by hipdec_image_transform (decoder.hip), which owns the plane bookkeeping.
+//
+// k_album_paste: HeifPixelImage::copy_image_to (libheif/image/pixelimage.cc:1115-1172) for all tiles of all photos of an album (hipdec_album_*,
+// decoder_album.inc) as one launch over a job table - a byte mover, so one kernel serves every sample size and chroma format.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include "heif_hipdec.h"
 #include "hipdec_internal.h"
+#include "color_device.h"   // HIPDEC_GLOBAL
 
 namespace hipdec {
 namespace {
@@ -50,6 +55,36 @@ __global__ __launch_bounds__(256) void k_remap(const T* __restrict__ src, size_t
   for (int i = 0; i < n; i++) out[i] = v[i];
 }
 
+// One job per (tile, plane): blockIdx.y selects it, blockIdx.x strides over groups of rows.  A row is spread over a power of two of lanes (16 .. 256,
+// enough for its 16-byte units), so a workgroup moves 16 .. 1 rows per pass.  Per row: the head bytes up to the destination's 16-byte boundary, one byte
+// per lane; the body as 16-byte stores to aligned addresses, consecutive lanes on consecutive units (a wave writes 1 KiB of whole 64-byte segments);
+// the tail bytes, one per lane.  The source keeps whatever phase x0 * bytes_per_sample gives it against the destination: its 16 bytes are loaded
+// through memcpy (the unaligned vector load of the target - global_load_dwordx4 - not a type-punned access).  No LDS, no scratch.
+__global__ __launch_bounds__(256) void k_album_paste(const PasteJob* __restrict__ jobs)
+{
+  const PasteJob j = jobs[blockIdx.y];
+  const uint32_t wb = j.width_bytes;
+  const uint32_t units = (wb + 15u) >> 4;
+  const uint32_t lg = units <= 16u ? 4u : (units > 128u ? 8u : (uint32_t)(32 - __clz((int)(units - 1u))));
+  const uint32_t lpr = 1u << lg, rpp = 256u >> lg;   // lanes per row, rows per pass
+  const uint32_t lane = (uint32_t)threadIdx.x & (lpr - 1u);
+  for (uint32_t row = (uint32_t)blockIdx.x * rpp + ((uint32_t)threadIdx.x >> lg); row < j.rows; row += (uint32_t)gridDim.x * rpp) {
+    const HIPDEC_GLOBAL uint8_t* s = (const HIPDEC_GLOBAL uint8_t*)j.src + (size_t)row * j.src_stride;   // (typed as global memory: no FLAT accesses)
+    HIPDEC_GLOBAL uint8_t* d = (HIPDEC_GLOBAL uint8_t*)j.dst + (size_t)row * j.dst_stride;
+    uint32_t head = (uint32_t)(0u - (uint32_t)(uintptr_t)d) & 15u;
+    if (head > wb) head = wb;
+    const uint32_t body = (wb - head) >> 4, tail = (wb - head) & 15u;
+    if (lane < head) d[lane] = s[lane];
+    s += head; d += head;
+    for (uint32_t u = lane; u < body; u += lpr) {
+      uint4 v;
+      __builtin_memcpy(&v, s + (size_t)u * 16u, 16);
+      *(HIPDEC_GLOBAL uint4*)(d + (size_t)u * 16u) = v;
+    }
+    if (lane < tail) d[(size_t)body * 16u + lane] = s[(size_t)body * 16u + lane];
+  }
+}
+
 template <typename T>
 int rotate_plane(const void* in, size_t is, int w, int h, int angle, void* out, size_t os, hipStream_t s)
 {
@@ -77,6 +112,19 @@ bool bad_plane(const void* in, const void* out, int w, int h, int bps, size_t is
 }
 
 }  // namespace
+
+// all jobs as one launch (a grid's y extent is 65535: more jobs - beyond 21845 tiles - take as few launches as that allows)
+int album_paste_launch(const PasteJob* jobs_dev, int n_jobs, uint32_t max_rows, hipStream_t s)
+{
+  const unsigned gx = std::min(32u, std::max(1u, (max_rows + 15u) / 16u));
+  for (int first = 0; first < n_jobs; first += 65535) {
+    const int n = std::min(65535, n_jobs - first);
+    hipLaunchKernelGGL(k_album_paste, dim3(gx, (unsigned)n), dim3(256), 0, s, jobs_dev + first);
+    HIPDEC_CHECK_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
 }  // namespace hipdec
 
 using namespace hipdec;

@@ -57,8 +57,28 @@ def _bind(lib):
     lib.hipdec_batch_slot_kernel_timing_us.argtypes = [vp, ci, C.POINTER(C.c_float)]
     lib.hipdec_batch_read_tap.argtypes = [vp, ci, ci, ci, vp, sz]
     lib.hipdec_batch_read_maps.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, sz]
+    lib.hipdec_album_create.argtypes = [C.POINTER(vp), ci, C.POINTER(AlbumPhoto), C.POINTER(C.c_char_p), C.POINTER(sz), ci, C.c_uint64]
+    lib.hipdec_album_free.argtypes = [vp]
+    lib.hipdec_album_free.restype = None
+    lib.hipdec_album_count.argtypes = [vp]
+    lib.hipdec_album_info.argtypes = [vp, ci, C.POINTER(ImageInfo)]
+    lib.hipdec_album_run.argtypes = [vp, vp]
+    lib.hipdec_album_status.argtypes = [vp]
+    lib.hipdec_album_canvas_plane.argtypes = [vp, ci, ci, C.POINTER(vp), C.POINTER(sz)]
+    lib.hipdec_album_read_plane.argtypes = [vp, ci, ci, vp, sz]
+    lib.hipdec_album_to_rgb_all.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(sz), vp]
+    lib.hipdec_album_to_rgb_scaled_all.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(vp), C.POINTER(sz), vp]
+    lib.hipdec_album_to_tensor.argtypes = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), ci, vp, sz, vp]
+    lib.hipdec_album_stats.restype = None
+    lib.hipdec_album_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
+    lib.hipdec_album_paste_timing_us.argtypes = [vp, C.POINTER(C.c_float)]
     lib._dec_bound = True
     return lib
+
+
+class AlbumPhoto(C.Structure):
+    """hipdec_album_photo"""
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("out_width", C.c_int), ("out_height", C.c_int), ("first_tile", C.c_int), ("reserved", C.c_int)]
 
 
 class TensorDesc(C.Structure):
@@ -223,6 +243,48 @@ def fit_within(width, height, size):
     if width > height:
         return size, height * size // width
     return width * size // height, size
+
+
+def _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream):
+    """Batch.to_tensor / Album.to_tensor: the description, the output buffer (DeviceBuffer or torch.Tensor) and the stream, then `call`"""
+    n = self.n if entries is None else len(entries)
+    d0 = self.info(0)
+    max_value = (1 << d0["bit_depth_luma"]) - 1 if (dtype != "uint8" and d0["bit_depth_luma"] > 8) else 255
+    sc, bi = tensor_scale_bias(mean, std, scale, bias, max_value)
+    desc = tensor_desc(size, dtype, layout, filter, sc, bi)
+    shape = tensor_shape(n, size, layout)
+    nbytes = int(np.prod(shape)) * np.dtype(_TENSOR_NUMPY[dtype]).itemsize
+    arr = None if entries is None else tensor_entries(entries)
+    host_wait = False
+    if out is None:
+        torch = _torch_gpu()
+        out = torch.empty(shape, dtype=getattr(torch, dtype), device="cuda") if torch is not None else DeviceBuffer(max(nbytes, 1))
+    if isinstance(out, DeviceBuffer):
+        ptr, room = out.ptr, out.nbytes
+    else:
+        import torch
+        if not isinstance(out, torch.Tensor) or not out.is_cuda:
+            raise TypeError("out must be a DeviceBuffer or a CUDA / HIP torch.Tensor")
+        if tuple(out.shape) != shape:
+            raise ValueError("out has shape %s, the tensor has %s" % (tuple(out.shape), shape))
+        if out.dtype != getattr(torch, dtype):
+            raise ValueError("out has dtype %s, the tensor has %s" % (out.dtype, dtype))
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+        ptr, room = out.data_ptr(), nbytes
+        if stream is None:
+            ts = torch.cuda.current_stream(out.device)
+            stream = ts.cuda_stream or None
+            if stream is None:
+                # torch's legacy default stream has no handle the C ABI could name (NULL selects the library's own stream): order the two
+                # on the host - what torch has queued for `out` first, and the tensor is complete when this call returns
+                ts.synchronize()
+                host_wait = True
+    check(call(self._h, C.byref(desc), arr, n, ptr, room, stream))
+    if host_wait:
+        check(self._lib.hipdec_stream_synchronize(None))
+    self._tensor = (out, shape, _TENSOR_NUMPY[dtype], stream)
+    return out
 
 
 class DecodedImage:
@@ -434,44 +496,7 @@ class Batch:
         out: a DeviceBuffer of at least the tensor's bytes (returned as it is; tensor_to_host() reads it back as a NumPy array), or a contiguous
         CUDA / HIP torch.Tensor of the tensor's shape and dtype (its data_ptr() is written; the stream defaults to torch's current stream - when that
         is torch's legacy default stream the call waits on the host instead), or None: a torch tensor where torch sees a GPU, a DeviceBuffer elsewhere."""
-        n = self.n if entries is None else len(entries)
-        d0 = self.info(0)
-        max_value = (1 << d0["bit_depth_luma"]) - 1 if (dtype != "uint8" and d0["bit_depth_luma"] > 8) else 255
-        sc, bi = tensor_scale_bias(mean, std, scale, bias, max_value)
-        desc = tensor_desc(size, dtype, layout, filter, sc, bi)
-        shape = tensor_shape(n, size, layout)
-        nbytes = int(np.prod(shape)) * np.dtype(_TENSOR_NUMPY[dtype]).itemsize
-        arr = None if entries is None else tensor_entries(entries)
-        host_wait = False
-        if out is None:
-            torch = _torch_gpu()
-            out = torch.empty(shape, dtype=getattr(torch, dtype), device="cuda") if torch is not None else DeviceBuffer(max(nbytes, 1))
-        if isinstance(out, DeviceBuffer):
-            ptr, room = out.ptr, out.nbytes
-        else:
-            import torch
-            if not isinstance(out, torch.Tensor) or not out.is_cuda:
-                raise TypeError("out must be a DeviceBuffer or a CUDA / HIP torch.Tensor")
-            if tuple(out.shape) != shape:
-                raise ValueError("out has shape %s, the tensor has %s" % (tuple(out.shape), shape))
-            if out.dtype != getattr(torch, dtype):
-                raise ValueError("out has dtype %s, the tensor has %s" % (out.dtype, dtype))
-            if not out.is_contiguous():
-                raise ValueError("out must be contiguous")
-            ptr, room = out.data_ptr(), nbytes
-            if stream is None:
-                ts = torch.cuda.current_stream(out.device)
-                stream = ts.cuda_stream or None
-                if stream is None:
-                    # torch's legacy default stream has no handle the C ABI could name (NULL selects the library's own stream): order the two
-                    # on the host - what torch has queued for `out` first, and the tensor is complete when this call returns
-                    ts.synchronize()
-                    host_wait = True
-        check(self._lib.hipdec_batch_to_tensor(self._h, C.byref(desc), arr, n, ptr, room, stream))
-        if host_wait:
-            check(self._lib.hipdec_stream_synchronize(None))
-        self._tensor = (out, shape, _TENSOR_NUMPY[dtype], stream)
-        return out
+        return _to_tensor(self, self._lib.hipdec_batch_to_tensor, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
 
     def tensor_to_host(self):
         """the last to_tensor() result as a NumPy array of the tensor's shape (bfloat16 as uint16 bit patterns); waits for its stream"""
@@ -543,6 +568,131 @@ class Batch:
     def free(self):
         if self._h:
             self._lib.hipdec_batch_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def album_stats():
+    """(albums created, their photos, paste launches - one per Album.run) since the library was loaded"""
+    lib = _bind(load_library())
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    lib.hipdec_album_stats(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+class Album:
+    """Many grid photos composed by one set of launches (hipdec_album_*): the tiles of all photos decode as ONE batch and ONE paste kernel puts every
+    tile plane into its photo's canvas; the canvases feed the colour, scaled and tensor stages of Batch, one launch each."""
+
+    def __init__(self, photos, max_image_size_pixels=0):
+        """photos: (tile_streams, rows, cols, out_w, out_h) per photo, the tiles in grid ('dimg') order"""
+        self._lib = _bind(load_library())
+        self._keep = []
+        desc = (AlbumPhoto * max(len(photos), 1))()
+        for p, (tiles, rows, cols, out_w, out_h) in enumerate(photos):
+            desc[p] = AlbumPhoto(int(rows), int(cols), int(out_w), int(out_h), len(self._keep), 0)
+            self._keep += [bytes(t) for t in tiles]
+        n = len(self._keep)
+        arr = (C.c_char_p * max(n, 1))(*self._keep)
+        sizes = (C.c_size_t * max(n, 1))(*[len(t) for t in self._keep])
+        self._h = C.c_void_p()
+        check(self._lib.hipdec_album_create(C.byref(self._h), len(photos), desc, arr, sizes, n, int(max_image_size_pixels)))
+        self.n = len(photos)
+
+    def info(self, p):
+        info = ImageInfo()
+        check(self._lib.hipdec_album_info(self._h, p, C.byref(info)))
+        return _info_dict(info)
+
+    def run(self, stream=None):
+        """asynchronous: the launch set of all tiles + ONE paste launch"""
+        check(self._lib.hipdec_album_run(self._h, stream))
+
+    def status(self):
+        check(self._lib.hipdec_album_status(self._h))
+
+    def planes(self, p):
+        """the composed planes of photo p (host arrays of the output size)"""
+        d = self.info(p)
+        dt = np.uint16 if d["bit_depth_luma"] > 8 else np.uint8
+        out = []
+        for c in range(3 if d["chroma_format_idc"] else 1):
+            w, h = (d["width"], d["height"]) if c == 0 else (d["chroma_width"], d["chroma_height"])
+            a = np.empty((h, w), dt)
+            check(self._lib.hipdec_album_read_plane(self._h, p, c, a.ctypes.data, w * a.itemsize))
+            out.append(a)
+        return out
+
+    def canvas_plane(self, p, c):
+        """(device pointer, stride) of plane c of photo p's canvas"""
+        ptr, st = C.c_void_p(), C.c_size_t()
+        check(self._lib.hipdec_album_canvas_plane(self._h, p, c, C.byref(ptr), C.byref(st)))
+        return ptr.value, st.value
+
+    def alloc_rgb(self, out_chroma=10):
+        """pre-allocates one interleaved output buffer per photo for to_rgb_all()"""
+        bpp = {10: 3, 11: 4, 12: 6, 14: 6}[out_chroma]
+        self._rgb = []
+        for p in range(self.n):
+            d = self.info(p)
+            self._rgb.append((DeviceBuffer(d["width"] * d["height"] * bpp), d["width"] * bpp, d["height"]))
+        self._rgb_chroma = out_chroma
+        self._rgb_ptrs = (C.c_void_p * self.n)(*[buf.ptr for buf, _, _ in self._rgb])
+        self._rgb_strides = (C.c_size_t * self.n)(*[stride for _, stride, _ in self._rgb])
+
+    def to_rgb_all(self, stream=None):
+        """asynchronous: fused colour stage over every photo's canvas into the pre-allocated buffers, ONE launch"""
+        check(self._lib.hipdec_album_to_rgb_all(self._h, self._rgb_chroma, self._rgb_ptrs, self._rgb_strides, stream))
+
+    def rgb(self, p):
+        buf, stride, h = self._rgb[p]
+        check(self._lib.hipdec_stream_synchronize(None))
+        return buf.to_numpy((h, stride), np.uint8)
+
+    def alloc_rgb_scaled(self, sizes, out_chroma=10):
+        """pre-allocates one scaled output buffer per photo for to_rgb_scaled_all(); sizes: (width, height) per photo, or one pair for all"""
+        if len(sizes) == 2 and not hasattr(sizes[0], "__len__"):
+            sizes = [tuple(sizes)] * self.n
+        assert len(sizes) == self.n
+        bpp = {10: 3, 11: 4, 12: 6, 14: 6}[out_chroma]
+        self._srgb = [(DeviceBuffer(w * h * bpp), w * bpp, h) for w, h in sizes]
+        self._srgb_chroma = out_chroma
+        self._srgb_w = (C.c_int * self.n)(*[w for w, _ in sizes])
+        self._srgb_h = (C.c_int * self.n)(*[h for _, h in sizes])
+        self._srgb_ptrs = (C.c_void_p * self.n)(*[buf.ptr for buf, _, _ in self._srgb])
+        self._srgb_strides = (C.c_size_t * self.n)(*[stride for _, stride, _ in self._srgb])
+
+    def to_rgb_scaled_all(self, filter=SCALE_BOX, stream=None):
+        """asynchronous: every photo scaled to its pre-allocated size, ONE launch"""
+        check(self._lib.hipdec_album_to_rgb_scaled_all(self._h, self._srgb_chroma, self._srgb_w, self._srgb_h, filter, self._srgb_ptrs,
+                                                       self._srgb_strides, stream))
+
+    def rgb_scaled(self, p):
+        buf, stride, h = self._srgb[p]
+        check(self._lib.hipdec_stream_synchronize(None))
+        return buf.to_numpy((h, stride), np.uint8)
+
+    def to_tensor(self, size, entries=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, filter=SCALE_BOX, out=None,
+                  stream=None):
+        """Batch.to_tensor over the composed photos: an entry's item names a photo, its window lies in the photo's output size"""
+        return _to_tensor(self, self._lib.hipdec_album_to_tensor, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
+
+    tensor_to_host = Batch.tensor_to_host
+
+    def paste_timing_us(self):
+        """device time of the paste launch of the last run(), microseconds"""
+        t = C.c_float()
+        check(self._lib.hipdec_album_paste_timing_us(self._h, C.byref(t)))
+        return t.value
+
+    def free(self):
+        if self._h:
+            self._lib.hipdec_album_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
