@@ -7,6 +7,8 @@
  *   ./decode_batch item0.hevc item1.hevc ...          (files as written by tools/streamgen.py, or dumped from a HEIC's hvcC + item data)
  *   ./decode_batch --thumb 256 item0.hevc ...         ends in ONE launch that turns every item into an RGB24 preview that fits into 256 x 256
  *                                                     (the size rule of libheif's examples/heif_thumbnailer.cc:172-186, area-averaged on the device)
+ *   ./decode_batch --thumb 256 --orient 1 item0.hevc  the previews as they are DISPLAYED for orientation code 0 .. 7 (hipdec_orientation: what the host folded the
+ *                                                     items' 'irot' / 'imir' into with hipdec_orientation_compose), still ONE launch: the rotation is in its store
  *   ./decode_batch --tensor 224 item0.hevc ...        ends in ONE launch that writes a float16 N x 3 x 224 x 224 tensor: the centred square of every item,
  *                                                     area-averaged, (V / 255 - mean) / std with the usual ImageNet constants
  *   ./decode_batch --album 16 6x8 tile0.hevc ...      the items are TILES: 16 grid photos of 6 x 8 tiles (tile t of photo k is item (k * 48 + t) mod n; the
@@ -88,13 +90,19 @@ int main(int argc, char** argv)
     if (thumb < 1) argc = 0;                                       /* no or a bad N: usage */
     else { argv += 2; argc -= 2; }
   }
+  int orient = -1;                                                 /* -1: the unoriented call */
+  if (thumb && argc >= 2 && !strcmp(argv[1], "--orient")) {
+    orient = argc >= 3 ? atoi(argv[2]) : -1;
+    if (orient < 0 || orient > 7 || (argv[2][0] < '0' || argv[2][0] > '7') || argv[2][1]) argc = 0;
+    else { argv += 2; argc -= 2; }
+  }
   int tensor = 0;
   if (!thumb && argc >= 2 && !strcmp(argv[1], "--tensor")) {
     tensor = argc >= 3 ? atoi(argv[2]) : 0;
     if (tensor < 1) argc = 0;
     else { argv += 2; argc -= 2; }
   }
-  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
   const int n = argc - 1;
   const void** data = (const void**)calloc((size_t)n, sizeof(void*));
   size_t* sizes = (size_t*)calloc((size_t)n, sizeof(size_t));
@@ -134,22 +142,28 @@ int main(int argc, char** argv)
   if (thumb) {                                                     /* previews of all items as one launch: no full-size RGB exists anywhere, and of the colour stage only the previews cross to the host */
     int* ws = (int*)calloc((size_t)n, sizeof(int));
     int* hs = (int*)calloc((size_t)n, sizeof(int));
+    int* codes = (int*)calloc((size_t)n, sizeof(int));
     void** outs = (void**)calloc((size_t)n, sizeof(void*));
     size_t* strides = (size_t*)calloc((size_t)n, sizeof(size_t));
     for (int i = 0; i < n; i++) {
       hipdec_image_info info;
       hipdec_batch_info(prev, i, &info);
-      ws[i] = info.width; hs[i] = info.height;
-      if (info.width > thumb || info.height > thumb) {             /* heif_thumbnailer.cc:172-186 */
-        if (info.width > info.height) { hs[i] = (int)((long long)info.height * thumb / info.width); ws[i] = thumb; }
-        else { ws[i] = (int)((long long)info.width * thumb / info.height); hs[i] = thumb; }
+      const int dw = orient > 0 && (orient & 1) ? info.height : info.width;   /* the size rule sees the DISPLAYED picture: a quarter turn swaps the sides */
+      const int dh = orient > 0 && (orient & 1) ? info.width : info.height;
+      ws[i] = dw; hs[i] = dh;
+      codes[i] = orient > 0 ? orient : 0;
+      if (dw > thumb || dh > thumb) {                              /* heif_thumbnailer.cc:172-186 */
+        if (dw > dh) { hs[i] = (int)((long long)dh * thumb / dw); ws[i] = thumb; }
+        else { ws[i] = (int)((long long)dw * thumb / dh); hs[i] = thumb; }
       }
       if (ws[i] < 1 || hs[i] < 1) { fprintf(stderr, "%s: zero thumbnail output size\n", argv[1 + i]); return 1; }
       strides[i] = (size_t)ws[i] * 3;
       outs[i] = hipdec_malloc(strides[i] * (size_t)hs[i]);
       if (!outs[i]) { fprintf(stderr, "%s\n", hipdec_last_error()); return 1; }
     }
-    if (hipdec_batch_to_rgb_scaled_all(prev, 10, ws, hs, HIPDEC_SCALE_BOX, (void* const*)outs, strides, NULL) || hipdec_batch_status(prev)) {
+    const int rc = orient < 0 ? hipdec_batch_to_rgb_scaled_all(prev, 10, ws, hs, HIPDEC_SCALE_BOX, (void* const*)outs, strides, NULL)
+                              : hipdec_batch_to_rgb_scaled_oriented_all(prev, 10, codes, ws, hs, HIPDEC_SCALE_BOX, (void* const*)outs, strides, NULL);
+    if (rc || hipdec_batch_status(prev)) {
       fprintf(stderr, "%s\n", hipdec_last_error());
       return 1;
     }
@@ -163,7 +177,7 @@ int main(int argc, char** argv)
       free(rgb);
       hipdec_free(outs[i]);
     }
-    free(ws); free(hs); free(outs); free(strides);
+    free(ws); free(hs); free(codes); free(outs); free(strides);
   }
   if (tensor) {                                                    /* the loader's batch tensor as one launch: crop, scale, normalise, float16 NCHW */
     static const float mean[3] = {0.485f, 0.456f, 0.406f}, std[3] = {0.229f, 0.224f, 0.225f};

@@ -549,6 +549,50 @@ HIPDEC_API void hipdec_album_stats(uint64_t* albums, uint64_t* photos, uint64_t*
 /* measurement aid: device time of the paste of the last hipdec_album_run in microseconds (HIP events around its launch); waits for it */
 HIPDEC_API int hipdec_album_paste_timing_us(hipdec_album* a, float* us);
 
+/* ---- oriented output: 'irot' / 'imir' folded into the scaled RGB and tensor kernels ----------------------------------------------------------------------
+ * Every phone HEIC carries an orientation.  hipdec_image_transform applies it plane by plane at full size before the colour stage; these calls apply it in
+ * the store of the ONE fused launch that scales, converts and normalises, so a portrait thumbnail or training sample costs no second pass.
+ *
+ * hipdec_orientation: code = r + 4 * m.  The displayed picture is the stored picture rotated COUNTER-CLOCKWISE by r quarter turns, then mirrored
+ * horizontally if m is set.  A quarter turn is HeifPixelImage::rotate_ccw(90): out(X, Y) = in(x = w - 1 - Y, y = X), the output is h x w; the horizontal
+ * mirror is out(X, Y) = in(W - 1 - X, Y).  (NumPy, on an (H, W, ...) array: np.rot90(a, r), then np.fliplr if m.)
+ * The host folds an item's 'ipma'-ordered 'irot' / 'imir' list into one code with hipdec_orientation_compose; reading the properties is the caller's. */
+typedef enum hipdec_orientation {
+  HIPDEC_ORIENT_0 = 0, HIPDEC_ORIENT_CCW90 = 1, HIPDEC_ORIENT_180 = 2, HIPDEC_ORIENT_CCW270 = 3,
+  HIPDEC_ORIENT_MIRROR = 4, HIPDEC_ORIENT_CCW90_MIRROR = 5, HIPDEC_ORIENT_180_MIRROR = 6, HIPDEC_ORIENT_CCW270_MIRROR = 7
+} hipdec_orientation;
+/* Host only (no device is touched).  The code of "apply `op` to the displayed picture of `orientation`": op HIPDEC_XF_ROTATE_CCW with arg 90 / 180 / 270,
+ * or HIPDEC_XF_MIRROR with arg 0 (vertical) / 1 (horizontal).  Anything else: -1, and hipdec_last_error says why. */
+HIPDEC_API int hipdec_orientation_compose(int orientation, int op, int arg);
+/* Host only.  The code of EXIF orientation 1 .. 8; anything else: -1. */
+HIPDEC_API int hipdec_orientation_from_exif(int exif);
+/* THE DEFINITION OF THE RESULT.  Output sizes are sizes of the DISPLAYED picture (desc->width x height, out_widths[i] x out_heights[i]), ow x oh below.
+ *  - For an even r, the pre-orientation result P is what the unoriented call (hipdec_batch_to_tensor, hipdec_batch_to_rgb_scaled_all, and the album forms)
+ *    writes for the same item, window, filter and size ow x oh; for an odd r, what it writes for size oh x ow (width oh, height ow).
+ *  - The oriented result is orient(code, P), applied to PIXELS.  The integer stage, the float stage and the to-SDR rules are untouched.
+ *  - Tensor entry windows stay in luma samples of the STORED picture, exactly as in the unoriented call.
+ *  - An entry's flip mirrors the displayed result: fliplr^flip(orient(code, P)) (= the code hipdec_orientation_compose(code, HIPDEC_XF_MIRROR, 1)).
+ * This agrees with libheif's own order - transform the planes, then convert with nearest-neighbour chroma - for 4:4:4 and 4:0:0 pictures, and for subsampled
+ * pictures of even size.  For odd sizes of subsampled pictures the reference converts to 4:4:4 before it transforms; there the definition above is what holds.
+ *
+ * Tensor forms: as hipdec_batch_to_tensor / hipdec_album_to_tensor, with orientations[e] the code of entry e (NULL: all 0).
+ * RGB forms: out_chroma 10 (interleaved RGB24) only, from 8-bit or wider sources (wider ones through to-SDR, as in the scaled call); any other out_chroma is
+ * HIPDEC_ERR_UNSUPPORTED.  orientations[i] is the code of item / photo i (NULL: all 0); rows of picture i are out_strides[i] bytes apart and the bytes between
+ * a row's end and the stride are not written.  Full-size oriented RGB is HIPDEC_SCALE_NEAREST at the displayed full size (the identity index map).
+ * Everything the unoriented call refuses is refused with the same status; a code outside 0 .. 7 is HIPDEC_ERR_INVALID_ARGUMENT and names the entry; an
+ * out_stride below 3 * out_width is refused; whatever the arguments alone decide is refused before a device is touched.  ONE launch per call (65535 entries per
+ * launch), entries of different orientation share it; the device time lands in slot [5] of hipdec_batch_slot_kernel_timing_us like the sibling calls'. */
+HIPDEC_API int hipdec_batch_to_tensor_oriented(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                               int n_entries, void* out_dev, size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_album_to_tensor_oriented(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                               int n_entries, void* out_dev, size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_batch_to_rgb_scaled_oriented_all(hipdec_batch* b, int out_chroma, const int* orientations, const int* out_widths, const int* out_heights,
+                                                       int filter, void* const* outs_dev, const size_t* out_strides, void* stream);
+HIPDEC_API int hipdec_album_to_rgb_scaled_oriented_all(hipdec_album* a, int out_chroma, const int* orientations, const int* out_widths, const int* out_heights,
+                                                       int filter, void* const* outs_dev, const size_t* out_strides, void* stream);
+/* counters since load: launches of the oriented kernels, the entries they wrote, and how many of those had a quarter turn (odd r) */
+HIPDEC_API void hipdec_oriented_stats(uint64_t* launches, uint64_t* entries, uint64_t* quarter_turn_entries);
+
 /* counters since load: images through hipdec_image_transform, grid canvases handed out by hipdec_grid_read_plane_tracked (hipdec_image_scale counts in
  * hipdec_image_scale_stats) */
 HIPDEC_API void hipdec_image_ops_stats(uint64_t* transforms, uint64_t* grid_canvases);

@@ -20,6 +20,7 @@
 #include <cmath>
 #include <cstring>
 #include <vector>
+#include <atomic>
 
 namespace {
 
@@ -580,6 +581,243 @@ __global__ __launch_bounds__(256) void k_tensor_nearest(const TensorParams* __re
   }
 }
 
+// ---- oriented output: the tensor kernels with the picture's orientation (irot / imir, include/heif_hipdec.h hipdec_orientation) folded into the store.
+// The integer stage runs on the PRE-orientation picture P of t.ow x t.oh pixels exactly as the tensor kernels run it; pixel (x, y) of P is stored at
+// displayed position (X, Y).  With code = r + 4 * m:
+//   r even:  X = fx ? W - 1 - x : x,  Y = fy ? H - 1 - y : y      (W x H = t.ow x t.oh, displayed W x H)
+//   r odd:   X = fx ? H - 1 - y : y,  Y = fy ? W - 1 - x : x      (displayed H x W: a row of P becomes a column)
+//   fx = bit 1 of r XOR m, fy = bit 1 of r XOR bit 0 of r.
+// An entry's flip is folded into the code by the host, the code is wave-uniform, and entries of all eight codes share a launch.
+struct OrientedParams {
+  TensorParams t;     // t.ow x t.oh: the size of P; t.flip is 0; t.c.o0: the entry's first element
+  int code;           // hipdec_orientation, 0 .. 7
+  int rb;             // box: rows of P a workgroup takes at a time - the kernel's RB for a quarter turn, fewer (more workgroups) where rows stay rows
+  uint64_t pitch;     // elements from one DISPLAYED row to the next (dense for tensors, out_stride for RGB24)
+};
+
+// store_tensor4's shape with a row pitch: a 4-pixel group of displayed row `row` (of dh rows of dw pixels) whose pixels are columns x0 .. x0 + npx - 1 before
+// the reversal `rev` (column x goes to dw - 1 - x).  Vector stores where the group is whole and its destination aligned, element stores otherwise.
+template <int DT>
+__device__ __forceinline__ void store_oriented4(const OrientedParams& op, int dw_, int dh_, int rev, int x0, int row, int npx, const int (&R)[4], const int (&G)[4],
+                                                const int (&B)[4])
+{
+  typedef typename TensorElem<DT>::T E;
+  typedef TensorQuad<DT> Q;
+  typedef typename Q::V V;
+  const TensorParams& tp = op.t;
+  uint32_t v[3][4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    v[0][i] = tensor_elem<DT>(rev ? R[3 - i] : R[i], tp.scale[0], tp.bias[0]);
+    v[1][i] = tensor_elem<DT>(rev ? G[3 - i] : G[i], tp.scale[1], tp.bias[1]);
+    v[2][i] = tensor_elem<DT>(rev ? B[3 - i] : B[i], tp.scale[2], tp.bias[2]);
+  }
+  const size_t dw = (size_t)dw_, pitch = (size_t)op.pitch, plane = (size_t)dh_ * pitch;
+  const size_t xs = rev ? dw - (size_t)npx - (size_t)x0 : (size_t)x0;   // the group's first column in memory
+  HIPDEC_GLOBAL E* o = (HIPDEC_GLOBAL E*)tp.c.o0 + (size_t)row * pitch;
+  if (tp.nhwc) {
+    HIPDEC_GLOBAL E* d = o + xs * 3;
+    if (npx == 4 && (((uintptr_t)d) & (4 * sizeof(E) - 1)) == 0) {
+      ((HIPDEC_GLOBAL V*)d)[0] = Q::pack(v[0][0], v[1][0], v[2][0], v[0][1]);
+      ((HIPDEC_GLOBAL V*)d)[1] = Q::pack(v[1][1], v[2][1], v[0][2], v[1][2]);
+      ((HIPDEC_GLOBAL V*)d)[2] = Q::pack(v[2][2], v[0][3], v[1][3], v[2][3]);
+      return;
+    }
+  } else {
+    HIPDEC_GLOBAL E* r = o + xs;
+    HIPDEC_GLOBAL E* g = r + plane;
+    HIPDEC_GLOBAL E* b = g + plane;
+    if (npx == 4 && ((((uintptr_t)r) | ((uintptr_t)g) | ((uintptr_t)b)) & (4 * sizeof(E) - 1)) == 0) {
+      *(HIPDEC_GLOBAL V*)r = Q::pack(v[0][0], v[0][1], v[0][2], v[0][3]);
+      *(HIPDEC_GLOBAL V*)g = Q::pack(v[1][0], v[1][1], v[1][2], v[1][3]);
+      *(HIPDEC_GLOBAL V*)b = Q::pack(v[2][0], v[2][1], v[2][2], v[2][3]);
+      return;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    if (i >= npx) break;
+    const int k = rev ? 3 - i : i;                                   // where pixel x0 + i sits in v
+    const size_t col = rev ? dw - 1 - (size_t)(x0 + i) : (size_t)(x0 + i);
+    if (tp.nhwc) {
+      HIPDEC_GLOBAL E* d = o + col * 3;
+      d[0] = (E)v[0][k]; d[1] = (E)v[1][k]; d[2] = (E)v[2][k];
+    } else {
+      HIPDEC_GLOBAL E* d = o + col;
+      d[0] = (E)v[0][k]; d[plane] = (E)v[1][k]; d[2 * plane] = (E)v[2][k];
+    }
+  }
+}
+
+// The quarter-turn store of the box kernel.  The box stage has to walk SOURCE rows (box_columns lives on aligned row loads), but a row of P is a COLUMN of
+// the displayed picture: stored as it is computed, every element would open a 64-byte segment of its own.  So a workgroup takes RB consecutive rows of P for
+// its tile of at most TC columns, stages the converted integer components in LDS (one row of the stage per row of P, one 32-bit word per pixel where the
+// component values are 8 bits wide - 8-bit sources, and the U8 dtype of any source - and 64 bits for native-depth values), and then writes along DISPLAYED
+// rows: column x of the tile is displayed row Y and receives ONE contiguous run of RB pixels - RB elements per channel plane (NCHW), 3 * RB elements
+// (NHWC / RGB24) - with consecutive lanes on consecutive elements.  The float stage runs at that store.
+//   RB:  64 where the narrowest element is one byte (a run of 64 bytes per channel plane, 192 interleaved), 32 for native-depth values, whose narrowest
+//        element is two bytes (64 / 192 bytes again).  An output lower than RB, or the last block of one, gets the shorter run it has.
+//   TC:  96 columns for 8-bit samples, 64 for 16-bit ones (whose column sums are 64-bit).  The host caps the box tile at TC.  (TC = 128 was measured first:
+//        48 KB of LDS left three workgroups per CU where k_tensor_box has four, and the kernel ran 30 - 58 % behind it.)
+//   LDS: stage rows are padded by one element, so lanes on consecutive stage ROWS of one column - what the write-out reads - are TC + 1 words apart: an odd
+//        number of 32-bit banks (twice an odd number for the 64-bit stage, read as b64 over 64 banks), conflict-free over a 32-lane group.  The staging
+//        write is lane = column: consecutive words.
+//        8-bit:            colsum 3 * 1024 * 4 + stage 64 * 97 * 4  = 12288 + 24832 = 37120 bytes: FOUR workgroups per CU, the step its 120 VGPRs allow
+//        16-bit, U8:       colsum 3 * 1024 * 8 + stage 64 * 65 * 4  = 24576 + 16640 = 41216 bytes
+//        16-bit, floats:   colsum 24576 + stage 32 * 65 * 8         = 41216 bytes
+//        16-bit: below 160 KiB / 3 = 54613, three workgroups per CU, the step of its 168 VGPRs.
+// Row-preserving codes go through the same stage - one box loop, one set of registers: with k_tensor_box's avg path beside the stage the kernel took 130 - 138
+// VGPRs (8-bit) and 178 - 186 (16-bit), past the 128 / 168 steps - and leave it with k_tensor_box's store shape: 4-pixel groups of row oy or H - 1 - oy,
+// columns forward or reversed, vector stores where aligned (store_oriented4).
+template <typename Pix, int DT> struct OrientedTile {
+  static constexpr bool kNarrow = sizeof(Pix) == 1 || DT == TD_U8;
+  static constexpr int TC = sizeof(Pix) == 1 ? 96 : 64;
+  static constexpr int RB = kNarrow ? 64 : 32;
+};
+template <bool NARROW> struct OrientedStage {
+  typedef uint32_t S;
+  static __device__ __forceinline__ S pack(int r, int g, int b) { return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16); }
+  static __device__ __forceinline__ int get(S s, uint32_t ch) { return (int)((s >> (8u * ch)) & 255u); }
+};
+template <> struct OrientedStage<false> {
+  typedef uint2 S;
+  static __device__ __forceinline__ S pack(int r, int g, int b) { return make_uint2((uint32_t)r | ((uint32_t)g << 16), (uint32_t)b); }
+  static __device__ __forceinline__ int get(S s, uint32_t ch) { return (int)(ch == 0 ? (s.x & 0xffffu) : (ch == 1 ? (s.x >> 16) : s.y)); }
+};
+
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) void k_oriented_box(const OrientedParams* __restrict__ ps)
+{
+  typedef OrientedTile<Pix, DT> T;
+  typedef OrientedStage<T::kNarrow> St;
+  typedef typename TensorElem<DT>::T E;
+  constexpr int RB = T::RB, TC = T::TC;
+  __shared__ typename BoxAcc<Pix>::T colsum[3][kBoxSpan];
+  __shared__ typename St::S stage[RB][TC + 1];
+  const OrientedParams op = ps[blockIdx.z];   // wave-uniform: scalar loads into SGPRs
+  const TensorParams& tp = op.t;
+  const ColorParams& p = tp.c;
+  const int tid = threadIdx.x;
+  const int oxA = blockIdx.x * tp.tile;
+  if (oxA >= tp.ow) return;                               // (the whole workgroup)
+  const int nox = min(tp.tile, tp.ow - oxA);              // <= TC: the host caps the tile
+  const bool mono = p.arith == AR_MONO;
+  const int quarter = op.code & 1, fx = ((op.code >> 1) ^ (op.code >> 2)) & 1, fy = ((op.code >> 1) ^ op.code) & 1;
+  const int cl = tp.left >> tp.sH, ct = tp.top >> tp.sV;
+  const int cw = ((tp.left + tp.rw - 1) >> tp.sH) - cl + 1, ch = ((tp.top + tp.rh - 1) >> tp.sV) - ct + 1;
+  const int fcw = (p.w + (1 << tp.sH) - 1) >> tp.sH;
+  const BoxPlane pl[3] = {{p.y, p.ys, tp.rw, tp.rh, p.w, tp.left, tp.top}, {p.cb, p.cbs, cw, ch, fcw, cl, ct}, {p.cr, p.crs, cw, ch, fcw, cl, ct}};
+  const int rb = max(1, min(op.rb, RB));                  // (the stage has RB rows whatever the block says)
+  for (int yb = blockIdx.y * rb; yb < tp.oh; yb += gridDim.y * rb) {
+    const int nrows = min(rb, tp.oh - yb);
+    for (int r = 0; r < nrows; r++) {
+      uint32_t v[3];
+      box_tile<Pix, 3, true>(pl, mono ? 1 : 3, tp.ow, tp.oh, oxA, nox, yb + r, colsum, v);
+      if (tid < nox) {                                    // the owner of column oxA + tid converts its own pixel (four copies of it: one statement of the arithmetic)
+        const int Y[4] = {(int)v[0], (int)v[0], (int)v[0], (int)v[0]}, CB[4] = {(int)v[1], (int)v[1], (int)v[1], (int)v[1]}, CR[4] = {(int)v[2], (int)v[2], (int)v[2], (int)v[2]};
+        int R[4], G[4], B[4];
+        tensor_convert4<Pix>(p, Y, CB, CR, R, G, B);
+        stage[r][tid] = St::pack(R[0], G[0], B[0]);
+      }
+      __syncthreads();                                    // colsum is written again by the next row; after the last one the stage is complete
+    }
+    if (!quarter) {   // k_tensor_box's store shape: 4-pixel groups of row oy or H - 1 - oy, columns forward or reversed, vector stores where aligned
+      const uint32_t ng = ((uint32_t)nox + 3u) >> 2, total = ng * (uint32_t)nrows;
+      for (uint32_t idx = (uint32_t)tid; idx < total; idx += 256u) {
+        const uint32_t r = idx / ng, g = idx - r * ng;
+        int R[4], G[4], B[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {                     // (past the tile's last pixel: inside the padded stage row, not stored)
+          const typename St::S s = stage[r][g * 4u + (uint32_t)i];
+          R[i] = St::get(s, 0); G[i] = St::get(s, 1); B[i] = St::get(s, 2);
+        }
+        const int oy = yb + (int)r;
+        store_oriented4<DT>(op, tp.ow, tp.oh, fx, oxA + (int)g * 4, fy ? tp.oh - 1 - oy : oy, min(4, nox - (int)g * 4), R, G, B);
+      }
+      __syncthreads();                                    // the stage is written again by the next block of rows
+      continue;
+    }
+    // rows yb .. yb + nrows - 1 of P are displayed columns Xrun .. Xrun + nrows - 1 (in reverse order where fx), column x of P is displayed row Y
+    const uint32_t n = (uint32_t)nrows;
+    const size_t pitch = (size_t)op.pitch, xrun = (size_t)(fx ? tp.oh - yb - nrows : yb);
+    HIPDEC_GLOBAL E* o = (HIPDEC_GLOBAL E*)p.o0;
+    if (tp.nhwc) {
+      const uint32_t per = 3u * n, total = per * (uint32_t)nox;
+      for (uint32_t idx = (uint32_t)tid; idx < total; idx += 256u) {
+        const uint32_t c = idx / per, e = idx - c * per, j = e / 3u, k = e - 3u * j;
+        const int x = oxA + (int)c;
+        const size_t Yd = (size_t)(fy ? tp.ow - 1 - x : x);
+        const int val = St::get(stage[fx ? n - 1u - j : j][c], k);
+        o[Yd * pitch + xrun * 3 + e] = (E)tensor_elem<DT>(val, k == 0 ? tp.scale[0] : (k == 1 ? tp.scale[1] : tp.scale[2]), k == 0 ? tp.bias[0] : (k == 1 ? tp.bias[1] : tp.bias[2]));
+      }
+    } else {
+      const uint32_t total = n * (uint32_t)nox;
+      const size_t plane = (size_t)tp.ow * pitch;          // the displayed picture has t.ow rows
+      for (uint32_t idx = (uint32_t)tid; idx < total; idx += 256u) {
+        const uint32_t c = idx / n, j = idx - c * n;
+        const int x = oxA + (int)c;
+        const size_t Yd = (size_t)(fy ? tp.ow - 1 - x : x);
+        const typename St::S s = stage[fx ? n - 1u - j : j][c];
+        HIPDEC_GLOBAL E* d = o + Yd * pitch + xrun + j;
+        d[0] = (E)tensor_elem<DT>(St::get(s, 0), tp.scale[0], tp.bias[0]);
+        d[plane] = (E)tensor_elem<DT>(St::get(s, 1), tp.scale[1], tp.bias[1]);
+        d[2 * plane] = (E)tensor_elem<DT>(St::get(s, 2), tp.scale[2], tp.bias[2]);
+      }
+    }
+    __syncthreads();                                      // the stage is written again by the next block of rows
+  }
+}
+
+// Nearest neighbour runs in OUTPUT space for all eight codes: a lane owns four pixels of a DISPLAYED row, maps each back to its pixel (x, y) of P and from
+// there to the source sample k_tensor_nearest reads, and stores them with store_tensor4's shape.  The stores are as coalesced as the unoriented kernel's; the
+// reads of a quarter turn walk down source columns, which a down-scaling nearest kernel - it reads one sample in (scale factor)^2 - does sparsely either way.
+// No LDS.
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) void k_oriented_nearest(const OrientedParams* __restrict__ ps)
+{
+  const OrientedParams op = ps[blockIdx.z];
+  const TensorParams& tp = op.t;
+  const ColorParams& p = tp.c;
+  const int quarter = op.code & 1, fx = ((op.code >> 1) ^ (op.code >> 2)) & 1, fy = ((op.code >> 1) ^ op.code) & 1;
+  const int dw = quarter ? tp.oh : tp.ow, dh = quarter ? tp.ow : tp.oh;   // the displayed size
+  const int X0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (X0 >= dw) return;
+  const int npx = min(4, dw - X0);
+  const bool mono = p.arith == AR_MONO;
+  const int ra = quarter ? tp.rh : tp.rw, rc = quarter ? tp.rw : tp.rh;   // the window's extent along a displayed row, and across the rows
+  for (int Yd = blockIdx.y * blockDim.y + threadIdx.y; Yd < dh; Yd += gridDim.y * blockDim.y) {
+    const int c = fy ? dh - 1 - Yd : Yd;
+    const int sc = (int)((uint64_t)c * (uint64_t)rc / (uint64_t)dh);
+    int Y[4], CB[4], CR[4], R[4], G[4], B[4];
+    if (!quarter) {   // rows stay rows: k_tensor_nearest's row pointers, one source row per lane
+      const int iy = tp.top + sc;
+      HIPDEC_GLOBAL const Pix* yrow = (HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.y + (size_t)iy * p.ys);
+      HIPDEC_GLOBAL const Pix* cbrow = (HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.cb + (size_t)(iy >> tp.sV) * p.cbs);
+      HIPDEC_GLOBAL const Pix* crrow = (HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.cr + (size_t)(iy >> tp.sV) * p.crs);
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int X = min(X0 + i, dw - 1), a = fx ? dw - 1 - X : X;
+        const int ix = tp.left + (int)((uint64_t)a * (uint64_t)ra / (uint64_t)dw);
+        Y[i] = yrow[ix];
+        CB[i] = mono ? 0 : cbrow[ix >> tp.sH];
+        CR[i] = mono ? 0 : crrow[ix >> tp.sH];
+      }
+    } else {
+      const int ix = tp.left + sc;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int X = min(X0 + i, dw - 1), a = fx ? dw - 1 - X : X;
+        const int iy = tp.top + (int)((uint64_t)a * (uint64_t)ra / (uint64_t)dw);
+        Y[i] = *(HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.y + (size_t)iy * p.ys + (size_t)ix * sizeof(Pix));
+        CB[i] = mono ? 0 : *(HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.cb + (size_t)(iy >> tp.sV) * p.cbs + (size_t)(ix >> tp.sH) * sizeof(Pix));
+        CR[i] = mono ? 0 : *(HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.cr + (size_t)(iy >> tp.sV) * p.crs + (size_t)(ix >> tp.sH) * sizeof(Pix));
+      }
+    }
+    tensor_convert4<Pix>(p, Y, CB, CR, R, G, B);
+    store_oriented4<DT>(op, dw, dh, 0, X0, Yd, npx, R, G, B);
+  }
+}
+
 // the plane scalers: blockIdx.z selects the plane (all planes of an image, or of all items of a batch, are ONE launch)
 template <typename Pix>
 __global__ __launch_bounds__(256) void k_scale_plane_nearest(const hipdec::PlaneScaleParams* __restrict__ ps)
@@ -923,7 +1161,7 @@ thread_local std::vector<CapturedScaled> t_captured_scaled;
 // the recorded blocks go out as one launch (hipdec::color_tensor_launch).  Taken and checked like a scale request.
 struct TensorReq { bool on = false; hipdec::TensorRequest r; };
 thread_local TensorReq t_tensor;
-struct CapturedTensor { TensorParams p; int wide; };
+struct CapturedTensor { TensorParams p; int wide; int oriented, code; uint64_t pitch; };   // oriented: for the k_oriented_* kernels, with a code and a row pitch
 thread_local std::vector<CapturedTensor> t_captured_tensor;
 
 int box_tile_of(int pw, int qw)
@@ -984,8 +1222,13 @@ int record_tensor(const ColorParams& p)
   tp.left = r.left; tp.top = r.top; tp.rw = r.rw; tp.rh = r.rh; tp.flip = r.flip ? 1 : 0; tp.nhwc = r.nhwc ? 1 : 0;
   for (int c = 0; c < 3; c++) { tp.scale[c] = r.scale[c]; tp.bias[c] = r.bias[c]; }
   tp.tile = box_tile_of(r.rw, r.ow);
+  if (r.oriented) {   // (r.ow x r.oh: the pre-orientation size; the quarter-turn stage holds kOrientedTile columns)
+    const int cap = sizeof(Pix) == 1 ? OrientedTile<uint8_t, TD_U8>::TC : OrientedTile<uint16_t, TD_U8>::TC;
+    tp.tile = tp.tile < cap ? tp.tile : cap;
+    tp.flip = 0;      // folded into the code
+  }
   t_tensor.on = false;   // taken
-  t_captured_tensor.push_back(CapturedTensor{tp, sizeof(Pix) == 2});
+  t_captured_tensor.push_back(CapturedTensor{tp, sizeof(Pix) == 2, r.oriented ? 1 : 0, r.code, (uint64_t)r.pitch});
   return 0;
   }
 }
@@ -1213,6 +1456,75 @@ void launch_tensor_grid(const TensorParams* dev, int n, int filter, int ow, int 
     hipLaunchKernelGGL((k_tensor_nearest<Pix, DT>), grid, block, 0, s, dev);
   }
 }
+
+std::atomic<uint64_t> g_oriented_launches{0}, g_oriented_entries{0}, g_oriented_quarter{0};
+
+// ow x oh: the largest DISPLAYED size among the entries (nearest); gy_box / tiles: the most row blocks and column tiles an entry has (box)
+template <typename Pix, int DT>
+void launch_oriented_grid(const OrientedParams* dev, int n, int filter, int ow, int oh, int gy_box, int tiles, hipStream_t s)
+{
+  if (filter == HIPDEC_SCALE_BOX) {
+    dim3 block(256), grid(tiles, gy_box < 65535 ? gy_box : 65535, n);
+    hipLaunchKernelGGL((k_oriented_box<Pix, DT>), grid, block, 0, s, dev);
+  } else {
+    const int gy = (oh + 3) / 4;
+    dim3 block(64, 4), grid(((ow + 3) / 4 + 63) / 64, gy < 16384 ? gy : 16384, n);
+    hipLaunchKernelGGL((k_oriented_nearest<Pix, DT>), grid, block, 0, s, dev);
+  }
+}
+
+// the oriented form of color_tensor_launch: entries of all codes and (RGB form) sizes share the launch, so the grid covers the largest of each extent
+int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int filter, int dtype, hipStream_t s)
+{
+  int max_tiles = 0, max_dw = 0, max_dh = 0, max_blocks = 0;
+  uint64_t quarter = 0;
+  // rows of P per workgroup: the kernel's RB where a row of P becomes a column (the length of a contiguous run), 16 where rows stay rows (more workgroups)
+  const int RB = !caps[0].wide || dtype == TD_U8 ? OrientedTile<uint8_t, TD_U8>::RB : OrientedTile<uint16_t, TD_F32>::RB;
+  auto block_rows = [&](const CapturedTensor& c) { return c.code & 1 ? RB : 16; };
+  for (const auto& c : caps) {
+    if (c.wide != caps[0].wide) return set_error(HIPDEC_ERR_UNSUPPORTED, "oriented output: the entries mix 8-bit and wider sources");
+    const int tiles = (c.p.ow + c.p.tile - 1) / c.p.tile;
+    const int dw = c.code & 1 ? c.p.oh : c.p.ow, dh = c.code & 1 ? c.p.ow : c.p.oh;
+    max_tiles = tiles > max_tiles ? tiles : max_tiles;
+    const int blocks = (c.p.oh + block_rows(c) - 1) / block_rows(c);
+    max_dw = dw > max_dw ? dw : max_dw; max_dh = dh > max_dh ? dh : max_dh; max_blocks = blocks > max_blocks ? blocks : max_blocks;
+    quarter += (uint64_t)(c.code & 1);
+  }
+  const size_t bytes = caps.size() * sizeof(OrientedParams);
+  std::vector<uint8_t> host(bytes);
+  for (size_t i = 0; i < caps.size(); i++) {
+    OrientedParams op;
+    memset(&op, 0, sizeof(op));
+    op.t = caps[i].p; op.code = caps[i].code; op.rb = block_rows(caps[i]); op.pitch = caps[i].pitch;
+    memcpy(host.data() + i * sizeof(OrientedParams), &op, sizeof(op));
+  }
+  if (st.dev_bytes < bytes) {
+    if (st.dev) arena_release(st.dev, st.dev_bytes);
+    st.dev = nullptr; st.dev_bytes = 0; st.host.clear();
+    HIPDEC_CHECK_HIP(arena_acquire(&st.dev, bytes, &st.dev_bytes));
+  }
+  if (st.host != host) {   // steady state (same windows, codes and output): nothing to upload
+    st.prev.swap(st.host);
+    st.host.swap(host);
+    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), bytes, hipMemcpyHostToDevice, s));
+  }
+  for (size_t first = 0; first < caps.size(); first += 65535) {
+    const OrientedParams* dev = (const OrientedParams*)st.dev + first;
+    const int n = (int)(caps.size() - first < 65535 ? caps.size() - first : 65535);
+    switch (caps[0].wide * 4 + dtype) {
+#define X(DT) case DT: launch_oriented_grid<uint8_t, DT>(dev, n, filter, max_dw, max_dh, max_blocks, max_tiles, s); break; \
+              case 4 + DT: launch_oriented_grid<uint16_t, DT>(dev, n, filter, max_dw, max_dh, max_blocks, max_tiles, s); break;
+      X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
+#undef X
+      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "oriented output: unknown dtype %d", dtype);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "oriented kernel launch: %s", hipGetErrorString(e));
+    g_oriented_launches++;
+  }
+  g_oriented_entries += (uint64_t)caps.size(); g_oriented_quarter += quarter;
+  return 0;
+}
 }  // namespace
 
 // the tensor blocks recorded on this thread since color_tensor_begin() as ONE launch (a grid's z extent is 65535: more entries take as few launches as that allows)
@@ -1221,6 +1533,7 @@ int color_tensor_launch(ColorBatchState& st, int filter, int dtype, hipStream_t 
   std::vector<CapturedTensor> caps;
   caps.swap(t_captured_tensor);
   if (caps.empty()) return 0;
+  if (caps[0].oriented) return oriented_launch(caps, st, filter, dtype, s);   // (a call's entries are all oriented, or none is)
   int max_tiles = 0;
   for (const auto& c : caps) {
     if (c.wide != caps[0].wide) return set_error(HIPDEC_ERR_UNSUPPORTED, "tensor output: the entries mix 8-bit and wider sources");
@@ -1311,6 +1624,13 @@ void color_batch_state_free(ColorBatchState& st)
 using namespace hipdec;
 
 extern "C" {
+
+void hipdec_oriented_stats(uint64_t* launches, uint64_t* entries, uint64_t* quarter_turn_entries)
+{
+  if (launches) *launches = g_oriented_launches.load();
+  if (entries) *entries = g_oriented_entries.load();
+  if (quarter_turn_entries) *quarter_turn_entries = g_oriented_quarter.load();
+}
 
 void hipdec_color_coefficients(const hipdec_nclx* nclx, float out[4]) { if (out) coefficients(nclx, out); }   // (nclx NULL: the reference's defaults)
 

@@ -63,6 +63,7 @@ struct hipdec_batch : BatchLayout {
   ColorBatchState color;        // parameter blocks of hipdec_batch_to_rgb_all
   ColorBatchState color_scaled; // ... and of hipdec_batch_to_rgb_scaled_all (its own, so that a host alternating the two uploads nothing in the steady state)
   ColorBatchState color_tensor; // ... and of hipdec_batch_to_tensor
+  ColorBatchState color_oriented; // ... and of the oriented forms (hipdec_batch_to_tensor_oriented, hipdec_batch_to_rgb_scaled_oriented_all)
   uint64_t max_pixels = 0;      // the limit given at creation (0: none): scaled outputs are held against it as well
   // decoder path (plugin): the output planes of every item staged in pinned host memory by ONE set of asynchronous copies behind the
   // kernels, so that N decoder instances sharing the batch do not queue N x 3 pageable device-to-host copies (stage_planes_to_host)
@@ -124,6 +125,7 @@ struct hipdec_batch : BatchLayout {
     color_batch_state_free(color);
     color_batch_state_free(color_scaled);
     color_batch_state_free(color_tensor);
+    color_batch_state_free(color_oriented);
     if (arena) arena_release(arena, arena_capacity);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : chain_events) if (e) (void)hipEventDestroy(e);
@@ -752,6 +754,25 @@ int batch_to_rgb_impl(hipdec_batch* b, int i, int out_chroma, void* out_dev, siz
   });
 }
 
+// ---- orientation codes (include/heif_hipdec.h hipdec_orientation): code = r + 4 * m is "rotate counter-clockwise by r quarter turns, then mirror horizontally
+// if m" - M^m R^r in the dihedral group of the square, where R M = M R^-1.  A further rotation R^k in front gives M^m R^(r + k) (m clear) or M^m R^(r - k)
+// (m set); a horizontal mirror toggles m; the vertical mirror is M R^2 and so toggles m after adding a half turn.  -1: not an operation.
+int orientation_compose(int o, int op, int arg)
+{
+  if (o < 0 || o > 7) return -1;
+  const int r = o & 3, m = o >> 2;
+  if (op == HIPDEC_XF_ROTATE_CCW) {
+    if (arg != 90 && arg != 180 && arg != 270) return -1;
+    const int k = arg / 90;
+    return ((m ? r - k + 4 : r + k) & 3) + 4 * m;
+  }
+  if (op == HIPDEC_XF_MIRROR) {
+    if (arg == 1) return r + 4 * (m ^ 1);
+    if (arg == 0) return ((m ? r - 2 + 4 : r + 2) & 3) + 4 * (m ^ 1);
+  }
+  return -1;
+}
+
 // ---- tensor output (include/heif_hipdec.h): what hipdec_batch_to_tensor and hipdec_image_to_tensor (decoder_color_boundary.inc) share
 std::atomic<uint64_t> g_tensor_calls{0}, g_tensor_entries{0};
 
@@ -790,11 +811,20 @@ int tensor_window(const char* who, const hipdec_tensor_entry* e, int idx, int w,
 // these planes (cf: their chroma format, 0 monochrome) - out_chroma 10 for 8-bit sources and the U8 dtype, 14 (the native-depth value) otherwise; box
 // presents the planes as the 4:4:4 image they are scaled to.  The entry point records the block (color.hip); elem0: the entry's first element.
 int tensor_record_entry(const char* who, const uint8_t* y, size_t ys, const uint8_t* cb, size_t cbs, const uint8_t* cr, size_t crs, int w, int h, int bits, int cf,
-                        const hipdec_nclx* nclx, const hipdec_nclx* nclx_after_sdr, const hipdec_tensor_desc* d, int left, int top, int rw, int rh, int flip, void* elem0)
+                        const hipdec_nclx* nclx, const hipdec_nclx* nclx_after_sdr, const hipdec_tensor_desc* d, int left, int top, int rw, int rh, int flip, void* elem0,
+                        int orientation = -1, size_t pitch = 0)
 {
   TensorRequest rq;
   memset(&rq, 0, sizeof(rq));
-  rq.ow = d->width; rq.oh = d->height; rq.sH = cf == 1 || cf == 2 ? 1 : 0; rq.sV = cf == 1 ? 1 : 0;
+  rq.ow = d->width; rq.oh = d->height;
+  if (orientation >= 0) {   // oriented output: d->width x height is the DISPLAYED size, the kernels work on the pre-orientation picture; the flip becomes part of the code
+    rq.oriented = 1;
+    rq.code = flip ? orientation_compose(orientation, HIPDEC_XF_MIRROR, 1) : orientation;
+    if (rq.code & 1) { rq.ow = d->height; rq.oh = d->width; }
+    rq.pitch = pitch ? pitch : (size_t)d->width * (d->layout == HIPDEC_TENSOR_NHWC ? 3 : 1);
+    flip = 0;
+  }
+  rq.sH = cf == 1 || cf == 2 ? 1 : 0; rq.sV = cf == 1 ? 1 : 0;
   rq.left = left; rq.top = top; rq.rw = rw; rq.rh = rh; rq.flip = flip; rq.nhwc = d->layout == HIPDEC_TENSOR_NHWC;
   for (int c = 0; c < 3; c++) { rq.scale[c] = d->scale[c]; rq.bias[c] = d->bias[c]; }
   struct Scope { ~Scope() { color_tensor_clear(); } } scope;
@@ -839,12 +869,26 @@ void hipdec_tensor_stats(uint64_t* tensors, uint64_t* entries)
   if (entries) *entries = g_tensor_entries.load();
 }
 
-int hipdec_batch_to_tensor(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, int n_entries, void* out_dev, size_t out_bytes,
-                           void* stream)
+}  // extern "C"
+
+namespace {
+// the orientation list of an oriented call (NULL: all 0)
+int check_orientations(const char* who, const char* what, const int* orientations, int n)
+{
+  for (int e = 0; orientations && e < n; e++)
+    if (orientations[e] < 0 || orientations[e] > 7) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: %s %d: orientation %d is not 0 .. 7", who, what, e, orientations[e]);
+  return 0;
+}
+
+// hipdec_batch_to_tensor, and - oriented - hipdec_batch_to_tensor_oriented: the same checks, windows and planner rules; the oriented form records its blocks
+// for the k_oriented_* kernels (color.hip) and keeps them in a parameter array of its own
+int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations, bool oriented, int n_entries,
+                         void* out_dev, size_t out_bytes, void* stream)
 {
   if (!b || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: bad arguments");
   size_t bytes = 0;
   if (int rc = tensor_check_desc("to_tensor", desc, n_entries, &bytes)) return rc;
+  if (oriented) if (int rc = check_orientations("to_tensor_oriented", "entry", orientations, n_entries)) return rc;
   if (!entries && n_entries != (int)b->pics.size())
     return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: %d entries without an entry list, the batch has %d items", n_entries, (int)b->pics.size());
   if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
@@ -867,17 +911,106 @@ int hipdec_batch_to_tensor(hipdec_batch* b, const hipdec_tensor_desc* desc, cons
       hipdec_nclx nclx{1, I.colour_primaries, I.transfer_characteristics, I.matrix_coeffs, I.full_range_flag};
       if (!rc) rc = tensor_record_entry("to_tensor", b->arena + P.off_out[0], P.out_stride[0], b->arena + P.off_out[1], P.out_stride[1], b->arena + P.off_out[2], P.out_stride[2],
                                         P.out_width, P.out_height, b->wide ? I.bit_depth_luma : 8, P.chroma_format_idc, &nclx, &nclx, desc, left, top, rw, rh,
-                                        entries ? entries[e].flip : 0, (uint8_t*)out_dev + (size_t)e * entry_bytes);
+                                        entries ? entries[e].flip : 0, (uint8_t*)out_dev + (size_t)e * entry_bytes,
+                                        oriented ? (orientations ? orientations[e] : 0) : -1);
       if (rc) { color_tensor_abort(); return rc; }
     }
     const size_t slot = b->runs ? (b->runs - 1) % (b->ev.size() / kEv) : 0;
     hipEvent_t* ev = b->ev.data() + kEv * slot;
     HIPDEC_CHECK_HIP(hipEventRecord(ev[6], s));
-    int rc = color_tensor_launch(b->color_tensor, desc->filter, desc->dtype, s);
+    int rc = color_tensor_launch(oriented ? b->color_oriented : b->color_tensor, desc->filter, desc->dtype, s);
     HIPDEC_CHECK_HIP(hipEventRecord(ev[7], s));
     if (!rc && b->runs) b->colour_timed[slot] = 1;
     b->mark_done(s);
     if (!rc) { g_tensor_calls++; g_tensor_entries += (uint64_t)n_entries; }
+    return rc;
+  });
+}
+
+// what the RGB forms of the oriented output decide for one picture from the arguments alone (before a device is touched)
+int rgb_oriented_check_item(const char* who, int i, int out_chroma, int code, int ow, int oh, int filter, size_t stride)
+{
+  if (out_chroma != 10) return set_error(HIPDEC_ERR_UNSUPPORTED, "%s: out_chroma %d (interleaved RGB24, 10, is the oriented form)", who, out_chroma);
+  if (code < 0 || code > 7) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: item %d: orientation %d is not 0 .. 7", who, i, code);
+  if (ow < 1 || oh < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: item %d: output size %d x %d", who, i, ow, oh);
+  if (filter != HIPDEC_SCALE_NEAREST && filter != HIPDEC_SCALE_BOX) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown filter %d", who, filter);
+  if (stride < (size_t)ow * 3) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: item %d: out_stride %zu is smaller than a row of %zu bytes", who, i, stride, (size_t)ow * 3);
+  return 0;
+}
+
+// one picture of an oriented RGB call: a U8 / NHWC entry over the whole picture whose rows are out_stride apart
+int rgb_oriented_record(const char* who, const RgbSource& S, int code, int ow, int oh, int filter, void* out_dev, size_t out_stride)
+{
+  if (S.max_pixels && (uint64_t)ow * (uint64_t)oh > S.max_pixels)
+    return set_error(HIPDEC_ERR_LIMIT, "%s: output of %d x %d pixels exceeds max_image_size_pixels", who, ow, oh);
+  hipdec_tensor_desc d;
+  memset(&d, 0, sizeof(d));
+  d.width = ow; d.height = oh; d.dtype = HIPDEC_TENSOR_U8; d.layout = HIPDEC_TENSOR_NHWC; d.filter = filter;
+  for (int c = 0; c < 3; c++) d.scale[c] = 1.0f;
+  const hipdec_image_info& I = *S.info;
+  hipdec_nclx nclx{1, I.colour_primaries, I.transfer_characteristics, I.matrix_coeffs, I.full_range_flag};
+  return tensor_record_entry(who, S.plane[0], S.stride[0], S.plane[1], S.stride[1], S.plane[2], S.stride[2], S.width, S.height, S.wide ? I.bit_depth_luma : 8,
+                             S.chroma_format_idc, &nclx, &nclx, &d, 0, 0, S.width, S.height, 0, out_dev, code, out_stride);
+}
+}  // namespace
+
+extern "C" {
+
+int hipdec_orientation_compose(int orientation, int op, int arg)
+{
+  const int c = orientation_compose(orientation, op, arg);
+  if (c < 0) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "orientation_compose: orientation %d, op %d, arg %d", orientation, op, arg), -1;
+  return c;
+}
+
+// EXIF 1 .. 8: identity, mirror horizontal, half turn, mirror vertical, transpose, quarter turn clockwise, anti-transpose, quarter turn counter-clockwise
+int hipdec_orientation_from_exif(int exif)
+{
+  static const int code[8] = {0, 4, 2, 6, 7, 3, 5, 1};
+  if (exif < 1 || exif > 8) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "orientation_from_exif: %d is not 1 .. 8", exif), -1;
+  return code[exif - 1];
+}
+
+int hipdec_batch_to_tensor(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, int n_entries, void* out_dev, size_t out_bytes,
+                           void* stream)
+{
+  return batch_to_tensor_impl(b, desc, entries, nullptr, false, n_entries, out_dev, out_bytes, stream);
+}
+
+int hipdec_batch_to_tensor_oriented(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations, int n_entries,
+                                    void* out_dev, size_t out_bytes, void* stream)
+{
+  return batch_to_tensor_impl(b, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream);
+}
+
+int hipdec_batch_to_rgb_scaled_oriented_all(hipdec_batch* b, int out_chroma, const int* orientations, const int* out_widths, const int* out_heights, int filter,
+                                            void* const* outs_dev, const size_t* out_strides, void* stream)
+{
+  const char* who = "to_rgb_scaled_oriented_all";
+  if (!b || !out_widths || !out_heights || !outs_dev || !out_strides) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  const int n = (int)b->pics.size();
+  for (int i = 0; i < n; i++) {
+    if (!outs_dev[i]) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: item %d: no output", who, i);
+    if (int rc = rgb_oriented_check_item(who, i, out_chroma, orientations ? orientations[i] : 0, out_widths[i], out_heights[i], filter, out_strides[i])) return rc;
+  }
+  DeviceScope scope(b->device);
+  if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: the batch's arena was handed to another batch", who);
+  return guarded(who, [&]() -> int {
+    hipStream_t s = follow_stream(b, stream);
+    color_tensor_begin();
+    for (int i = 0; i < n; i++) {
+      const PicParams& P = b->params[i];
+      const RgbSource S{{b->arena + P.off_out[0], b->arena + P.off_out[1], b->arena + P.off_out[2]}, {P.out_stride[0], P.out_stride[1], P.out_stride[2]},
+                        P.out_width, P.out_height, P.chroma_format_idc, b->wide, &b->pics[i].info, b->max_pixels};
+      if (int rc = rgb_oriented_record(who, S, orientations ? orientations[i] : 0, out_widths[i], out_heights[i], filter, outs_dev[i], out_strides[i])) { color_tensor_abort(); return rc; }
+    }
+    const size_t slot = b->runs ? (b->runs - 1) % (b->ev.size() / kEv) : 0;
+    hipEvent_t* ev = b->ev.data() + kEv * slot;
+    HIPDEC_CHECK_HIP(hipEventRecord(ev[6], s));
+    int rc = color_tensor_launch(b->color_oriented, filter, HIPDEC_TENSOR_U8, s);
+    HIPDEC_CHECK_HIP(hipEventRecord(ev[7], s));
+    if (!rc && b->runs) b->colour_timed[slot] = 1;
+    b->mark_done(s);
     return rc;
   });
 }

@@ -26,6 +26,7 @@ struct hipdec_album {
   uint32_t max_rows = 0;                 // of any job: sizes the launch
   hipEvent_t paste_ev[2] = {nullptr, nullptr};   // around the paste launch of the last run
   ColorBatchState color, color_scaled, color_tensor;   // parameter blocks of the three output stages (their own, as hipdec_batch's)
+  ColorBatchState color_oriented;                      // ... and of the oriented forms
   uint64_t max_pixels = 0;
   bool ran = false;
   ~hipdec_album()
@@ -36,6 +37,7 @@ struct hipdec_album {
     color_batch_state_free(color);
     color_batch_state_free(color_scaled);
     color_batch_state_free(color_tensor);
+    color_batch_state_free(color_oriented);
     if (canvas) arena_release(canvas, canvas_capacity);
   }
 };
@@ -273,13 +275,17 @@ int hipdec_album_to_rgb_scaled_all(hipdec_album* a, int out_chroma, const int* o
   return rc;
 }
 
-// hipdec_batch_to_tensor over the canvases: entry.item names a photo, the window lies in its output size
-int hipdec_album_to_tensor(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, int n_entries, void* out_dev, size_t out_bytes,
-                           void* stream)
+}  // extern "C"
+
+namespace {
+// hipdec_batch_to_tensor over the canvases: entry.item names a photo, the window lies in its output size; oriented: as batch_to_tensor_impl
+int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations, bool oriented, int n_entries,
+                         void* out_dev, size_t out_bytes, void* stream)
 {
   if (!a || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_tensor: bad arguments");
   size_t bytes = 0;
   if (int rc = tensor_check_desc("album_to_tensor", desc, n_entries, &bytes)) return rc;
+  if (oriented) if (int rc = check_orientations("album_to_tensor_oriented", "entry", orientations, n_entries)) return rc;
   const int n_photos = (int)a->photos.size();
   if (!entries && n_entries != n_photos)
     return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_tensor: %d entries without an entry list, the album has %d photos", n_entries, n_photos);
@@ -302,10 +308,52 @@ int hipdec_album_to_tensor(hipdec_album* a, const hipdec_tensor_desc* desc, cons
       hipdec_nclx nclx{1, I.colour_primaries, I.transfer_characteristics, I.matrix_coeffs, I.full_range_flag};
       if (!rc) rc = tensor_record_entry("album_to_tensor", S.plane[0], S.stride[0], S.plane[1], S.stride[1], S.plane[2], S.stride[2], S.width, S.height,
                                         S.wide ? I.bit_depth_luma : 8, S.chroma_format_idc, &nclx, &nclx, desc, left, top, rw, rh, entries ? entries[e].flip : 0,
-                                        (uint8_t*)out_dev + (size_t)e * entry_bytes);
+                                        (uint8_t*)out_dev + (size_t)e * entry_bytes, oriented ? (orientations ? orientations[e] : 0) : -1);
       if (rc) { color_tensor_abort(); return rc; }
     }
-    const int rc = color_tensor_launch(a->color_tensor, desc->filter, desc->dtype, s);
+    const int rc = color_tensor_launch(oriented ? a->color_oriented : a->color_tensor, desc->filter, desc->dtype, s);
+    b->mark_done(s);
+    return rc;
+  });
+}
+}  // namespace
+
+extern "C" {
+
+int hipdec_album_to_tensor(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, int n_entries, void* out_dev, size_t out_bytes,
+                           void* stream)
+{
+  return album_to_tensor_impl(a, desc, entries, nullptr, false, n_entries, out_dev, out_bytes, stream);
+}
+
+int hipdec_album_to_tensor_oriented(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations, int n_entries,
+                                    void* out_dev, size_t out_bytes, void* stream)
+{
+  return album_to_tensor_impl(a, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream);
+}
+
+// hipdec_batch_to_rgb_scaled_oriented_all over the canvases
+int hipdec_album_to_rgb_scaled_oriented_all(hipdec_album* a, int out_chroma, const int* orientations, const int* out_widths, const int* out_heights, int filter,
+                                            void* const* outs_dev, const size_t* out_strides, void* stream)
+{
+  const char* who = "album_to_rgb_scaled_oriented_all";
+  if (!a || !out_widths || !out_heights || !outs_dev || !out_strides) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  const int n = (int)a->photos.size();
+  for (int p = 0; p < n; p++) {
+    if (!outs_dev[p]) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: photo %d: no output", who, p);
+    if (int rc = rgb_oriented_check_item(who, p, out_chroma, orientations ? orientations[p] : 0, out_widths[p], out_heights[p], filter, out_strides[p])) return rc;
+  }
+  DeviceScope scope(a->device);
+  return guarded(who, [&]() -> int {
+    hipdec_batch* b = a->batch.get();
+    hipStream_t s = follow_stream(b, stream);
+    color_tensor_begin();
+    for (int p = 0; p < n; p++)
+      if (int rc = rgb_oriented_record(who, album_source(a, p), orientations ? orientations[p] : 0, out_widths[p], out_heights[p], filter, outs_dev[p], out_strides[p])) {
+        color_tensor_abort();
+        return rc;
+      }
+    const int rc = color_tensor_launch(a->color_oriented, filter, HIPDEC_TENSOR_U8, s);
     b->mark_done(s);
     return rc;
   });

@@ -93,7 +93,9 @@ int scale_planes_launch(PlaneScaleParams* jobs, int n, int bytes_per_sample, int
 // Tensor output (color.hip).  As a scale request: the NEXT hipdec_color_* entry point that ends in interleaved RGB24 (8-bit value) or little-endian RRGGBB
 // (native-depth value) records a tensor block instead of launching - its `out` is the entry's first element - and color_tensor_launch() sends the recorded
 // blocks out as ONE launch.  The window is in luma samples of the planes handed in; sH / sV are their chroma shifts (box presents them as 4:4:4).
-struct TensorRequest { int ow, oh, sH, sV, left, top, rw, rh, flip, nhwc; float scale[3], bias[3]; };
+// Oriented output: `oriented` sends the block to the k_oriented_* kernels - ow x oh is then the PRE-orientation size, `code` the hipdec_orientation with the
+// entry's flip folded in, `pitch` the elements from one displayed row to the next.
+struct TensorRequest { int ow, oh, sH, sV, left, top, rw, rh, flip, nhwc; float scale[3], bias[3]; int oriented, code; size_t pitch; };
 void color_tensor_request(const TensorRequest& r);
 void color_tensor_clear();
 bool color_tensor_pending();

@@ -72,6 +72,14 @@ def _bind(lib):
     lib.hipdec_album_stats.restype = None
     lib.hipdec_album_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
     lib.hipdec_album_paste_timing_us.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.hipdec_orientation_compose.argtypes = [ci, ci, ci]
+    lib.hipdec_orientation_from_exif.argtypes = [ci]
+    lib.hipdec_batch_to_tensor_oriented.argtypes = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), C.POINTER(ci), ci, vp, sz, vp]
+    lib.hipdec_album_to_tensor_oriented.argtypes = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), C.POINTER(ci), ci, vp, sz, vp]
+    lib.hipdec_batch_to_rgb_scaled_oriented_all.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(vp), C.POINTER(sz), vp]
+    lib.hipdec_album_to_rgb_scaled_oriented_all.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(vp), C.POINTER(sz), vp]
+    lib.hipdec_oriented_stats.restype = None
+    lib.hipdec_oriented_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
     lib._dec_bound = True
     return lib
 
@@ -234,6 +242,67 @@ def pipeline_stats():
 SCALE_NEAREST, SCALE_BOX = 0, 1   # hipdec_scale_filter
 
 
+# hipdec_orientation: code = r + 4 * m - the stored picture rotated counter-clockwise by r quarter turns, then mirrored horizontally if m
+ORIENT_0, ORIENT_CCW90, ORIENT_180, ORIENT_CCW270 = 0, 1, 2, 3
+ORIENT_MIRROR, ORIENT_CCW90_MIRROR, ORIENT_180_MIRROR, ORIENT_CCW270_MIRROR = 4, 5, 6, 7
+XF_ROTATE_CCW, XF_MIRROR = 0, 1                                                # hipdec_transform_op
+
+
+def orientation_compose(orientation, op, arg):
+    """the code of "apply op (XF_ROTATE_CCW with 90 / 180 / 270, XF_MIRROR with 0 vertical / 1 horizontal) to the displayed picture of `orientation`"
+    (hipdec_orientation_compose; host only): folds an item's 'irot' / 'imir' list, in 'ipma' order, into one code"""
+    code = _bind(load_library()).hipdec_orientation_compose(orientation, op, arg)
+    if code < 0:
+        raise ValueError("orientation_compose(%r, %r, %r)" % (orientation, op, arg))
+    return code
+
+
+def orientation_from_exif(exif):
+    """the code of EXIF orientation 1 .. 8 (hipdec_orientation_from_exif; host only)"""
+    code = _bind(load_library()).hipdec_orientation_from_exif(exif)
+    if code < 0:
+        raise ValueError("EXIF orientation %r is not 1 .. 8" % (exif,))
+    return code
+
+
+def oriented_size(code, width, height):
+    """the displayed size of a stored picture of width x height"""
+    return (height, width) if code & 1 else (width, height)
+
+
+def stored_window(code, stored_width, stored_height, left, top, width, height):
+    """A window given in DISPLAYED coordinates (left, top, width, height inside the displayed picture of a stored_width x stored_height picture with
+    orientation `code`) as the (left, top, width, height) in the stored picture that a tensor entry needs: the oriented result of that entry shows
+    exactly the displayed window."""
+    dw, dh = oriented_size(code, stored_width, stored_height)
+    if width < 1 or height < 1 or left < 0 or top < 0 or left + width > dw or top + height > dh:
+        raise ValueError("window %d x %d at (%d, %d) leaves the displayed picture of %d x %d" % (width, height, left, top, dw, dh))
+    r, m = code & 3, code >> 2
+    if m:                                   # undo the mirror of the displayed picture
+        left = dw - left - width
+    # undo r quarter turns counter-clockwise, one at a time: out(X, Y) = in(w - 1 - Y, X) on a w x h picture that becomes h x w
+    w, h = dw, dh
+    for _ in range(r):
+        left, top, width, height = h - top - height, left, height, width
+        w, h = h, w
+    return left, top, width, height
+
+
+def oriented_stats():
+    """(launches of the oriented kernels, entries they wrote, entries with a quarter turn) since load"""
+    lib = _bind(load_library())
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    lib.hipdec_oriented_stats(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def _orientation_array(orientations, n):
+    codes = [int(c) for c in orientations]
+    if len(codes) != n:
+        raise ValueError("%d orientations for %d entries" % (len(codes), n))
+    return (C.c_int * n)(*codes)
+
+
 def fit_within(width, height, size):
     """The thumbnail size examples/heif_thumbnailer.cc:172-186 computes: the image as it is when both sides fit into `size`, else the longer
     side becomes `size` and the other one follows with integer division (which may give 0: the thumbnailer refuses that, and so does
@@ -245,9 +314,14 @@ def fit_within(width, height, size):
     return width * size // height, size
 
 
-def _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream):
-    """Batch.to_tensor / Album.to_tensor: the description, the output buffer (DeviceBuffer or torch.Tensor) and the stream, then `call`"""
+def _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations=None):
+    """Batch.to_tensor / Album.to_tensor: the description, the output buffer (DeviceBuffer or torch.Tensor) and the stream, then `call` (the oriented
+    entry point when `orientations` is given)"""
     n = self.n if entries is None else len(entries)
+    if orientations is not None:
+        codes = _orientation_array(orientations, n)
+        oriented = call
+        call = lambda h, desc, arr, n, ptr, room, stream: oriented(h, desc, arr, codes, n, ptr, room, stream)
     d0 = self.info(0)
     max_value = (1 << d0["bit_depth_luma"]) - 1 if (dtype != "uint8" and d0["bit_depth_luma"] > 8) else 255
     sc, bi = tensor_scale_bias(mean, std, scale, bias, max_value)
@@ -476,13 +550,18 @@ class Batch:
         self._srgb_ptrs = (C.c_void_p * self.n)(*[buf.ptr for buf, _, _ in self._srgb])
         self._srgb_strides = (C.c_size_t * self.n)(*[stride for _, stride, _ in self._srgb])
 
-    def to_rgb_scaled_all(self, filter=SCALE_BOX, stream=None):
-        """asynchronous: every item scaled to its pre-allocated size, ONE launch"""
+    def to_rgb_scaled_all(self, filter=SCALE_BOX, stream=None, orientations=None):
+        """asynchronous: every item scaled to its pre-allocated size, ONE launch.  orientations: one hipdec_orientation code per item - the sizes given to
+        alloc_rgb_scaled() are then sizes of the DISPLAYED pictures (RGB24 only)"""
+        if orientations is not None:
+            check(self._lib.hipdec_batch_to_rgb_scaled_oriented_all(self._h, self._srgb_chroma, _orientation_array(orientations, self.n), self._srgb_w, self._srgb_h,
+                                                                    filter, self._srgb_ptrs, self._srgb_strides, stream))
+            return
         check(self._lib.hipdec_batch_to_rgb_scaled_all(self._h, self._srgb_chroma, self._srgb_w, self._srgb_h, filter, self._srgb_ptrs,
                                                        self._srgb_strides, stream))
 
     def to_tensor(self, size, entries=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, filter=SCALE_BOX, out=None,
-                  stream=None):
+                  stream=None, orientations=None):
         """asynchronous: crop windows of the decoded pictures, scaled to size = (width, height), optionally flipped, as ONE dense tensor of shape
         (N, 3, height, width) ("NCHW") or (N, height, width, 3) ("NHWC") written by one fused kernel (hipdec_batch_to_tensor).
 
@@ -495,7 +574,11 @@ class Batch:
         max_value = 255, or 2^bits - 1 of item 0 for float dtypes from sources above 8 bits.
         out: a DeviceBuffer of at least the tensor's bytes (returned as it is; tensor_to_host() reads it back as a NumPy array), or a contiguous
         CUDA / HIP torch.Tensor of the tensor's shape and dtype (its data_ptr() is written; the stream defaults to torch's current stream - when that
-        is torch's legacy default stream the call waits on the host instead), or None: a torch tensor where torch sees a GPU, a DeviceBuffer elsewhere."""
+        is torch's legacy default stream the call waits on the host instead), or None: a torch tensor where torch sees a GPU, a DeviceBuffer elsewhere.
+        orientations: one hipdec_orientation code per entry (hipdec_batch_to_tensor_oriented): `size` is then the size of the DISPLAYED sample, windows
+        stay in the stored picture (stored_window() maps a displayed window), and an entry's flip mirrors the displayed sample."""
+        if orientations is not None:
+            return _to_tensor(self, self._lib.hipdec_batch_to_tensor_oriented, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations)
         return _to_tensor(self, self._lib.hipdec_batch_to_tensor, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
 
     def tensor_to_host(self):
@@ -667,8 +750,12 @@ class Album:
         self._srgb_ptrs = (C.c_void_p * self.n)(*[buf.ptr for buf, _, _ in self._srgb])
         self._srgb_strides = (C.c_size_t * self.n)(*[stride for _, stride, _ in self._srgb])
 
-    def to_rgb_scaled_all(self, filter=SCALE_BOX, stream=None):
-        """asynchronous: every photo scaled to its pre-allocated size, ONE launch"""
+    def to_rgb_scaled_all(self, filter=SCALE_BOX, stream=None, orientations=None):
+        """asynchronous: every photo scaled to its pre-allocated size, ONE launch; orientations: as Batch.to_rgb_scaled_all"""
+        if orientations is not None:
+            check(self._lib.hipdec_album_to_rgb_scaled_oriented_all(self._h, self._srgb_chroma, _orientation_array(orientations, self.n), self._srgb_w, self._srgb_h,
+                                                                    filter, self._srgb_ptrs, self._srgb_strides, stream))
+            return
         check(self._lib.hipdec_album_to_rgb_scaled_all(self._h, self._srgb_chroma, self._srgb_w, self._srgb_h, filter, self._srgb_ptrs,
                                                        self._srgb_strides, stream))
 
@@ -678,8 +765,10 @@ class Album:
         return buf.to_numpy((h, stride), np.uint8)
 
     def to_tensor(self, size, entries=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, filter=SCALE_BOX, out=None,
-                  stream=None):
+                  stream=None, orientations=None):
         """Batch.to_tensor over the composed photos: an entry's item names a photo, its window lies in the photo's output size"""
+        if orientations is not None:
+            return _to_tensor(self, self._lib.hipdec_album_to_tensor_oriented, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations)
         return _to_tensor(self, self._lib.hipdec_album_to_tensor, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
 
     tensor_to_host = Batch.tensor_to_host
