@@ -9,6 +9,8 @@
  *                                                     (the size rule of libheif's examples/heif_thumbnailer.cc:172-186, area-averaged on the device)
  *   ./decode_batch --thumb 256 --orient 1 item0.hevc  the previews as they are DISPLAYED for orientation code 0 .. 7 (hipdec_orientation: what the host folded the
  *                                                     items' 'irot' / 'imir' into with hipdec_orientation_compose), still ONE launch: the rotation is in its store
+ *   ./decode_batch --thumb 256 --filter bicubic ...   the previews with another filter: box (the default) | nearest | bilinear | bicubic - the last two are
+ *                                                     PIL.Image.resize bit for bit (HIPDEC_SCALE_BILINEAR / HIPDEC_SCALE_BICUBIC); after --orient where both are given
  *   ./decode_batch --tensor 224 item0.hevc ...        ends in ONE launch that writes a float16 N x 3 x 224 x 224 tensor: the centred square of every item,
  *                                                     area-averaged, (V / 255 - mean) / std with the usual ImageNet constants
  *   ./decode_batch --album 16 6x8 tile0.hevc ...      the items are TILES: 16 grid photos of 6 x 8 tiles (tile t of photo k is item (k * 48 + t) mod n; the
@@ -96,13 +98,22 @@ int main(int argc, char** argv)
     if (orient < 0 || orient > 7 || (argv[2][0] < '0' || argv[2][0] > '7') || argv[2][1]) argc = 0;
     else { argv += 2; argc -= 2; }
   }
+  int filter = HIPDEC_SCALE_BOX;
+  if (thumb && argc >= 2 && !strcmp(argv[1], "--filter")) {
+    static const struct { const char* name; int value; } filters[4] = {{"box", HIPDEC_SCALE_BOX}, {"nearest", HIPDEC_SCALE_NEAREST}, {"bilinear", HIPDEC_SCALE_BILINEAR},
+                                                                      {"bicubic", HIPDEC_SCALE_BICUBIC}};
+    int k = 4;
+    if (argc >= 3) for (k = 0; k < 4 && strcmp(argv[2], filters[k].name); k++) {}
+    if (k == 4) argc = 0;                                          /* no or an unknown name: usage */
+    else { filter = filters[k].value; argv += 2; argc -= 2; }
+  }
   int tensor = 0;
   if (!thumb && argc >= 2 && !strcmp(argv[1], "--tensor")) {
     tensor = argc >= 3 ? atoi(argv[2]) : 0;
     if (tensor < 1) argc = 0;
     else { argv += 2; argc -= 2; }
   }
-  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
   const int n = argc - 1;
   const void** data = (const void**)calloc((size_t)n, sizeof(void*));
   size_t* sizes = (size_t*)calloc((size_t)n, sizeof(size_t));
@@ -161,8 +172,8 @@ int main(int argc, char** argv)
       outs[i] = hipdec_malloc(strides[i] * (size_t)hs[i]);
       if (!outs[i]) { fprintf(stderr, "%s\n", hipdec_last_error()); return 1; }
     }
-    const int rc = orient < 0 ? hipdec_batch_to_rgb_scaled_all(prev, 10, ws, hs, HIPDEC_SCALE_BOX, (void* const*)outs, strides, NULL)
-                              : hipdec_batch_to_rgb_scaled_oriented_all(prev, 10, codes, ws, hs, HIPDEC_SCALE_BOX, (void* const*)outs, strides, NULL);
+    const int rc = orient < 0 ? hipdec_batch_to_rgb_scaled_all(prev, 10, ws, hs, filter, (void* const*)outs, strides, NULL)
+                              : hipdec_batch_to_rgb_scaled_oriented_all(prev, 10, codes, ws, hs, filter, (void* const*)outs, strides, NULL);
     if (rc || hipdec_batch_status(prev)) {
       fprintf(stderr, "%s\n", hipdec_last_error());
       return 1;

@@ -431,8 +431,33 @@ HIPDEC_API int hipdec_plane_crop(const void* in, size_t in_stride, int w, int h,
  *                        the chroma planes; the output chroma planes have the subsampled size of the output image ((w + 1) / 2 ...).  Up-scaling is allowed.
  *  HIPDEC_SCALE_BOX      area average (not in the reference), integer-exact.  A plane of pw x ph samples goes to qw x qh: output sample (ox, oy) is
  *                        (S + n / 2) / n, S the sum of the input samples in [x0, x1) x [y0, y1), x0 = ox * pw / qw, x1 = (ox + 1) * pw / qw (x0 + 1 where that
- *                        left the range empty), the same in y, n = (x1 - x0) * (y1 - y0); 64-bit products, integer division.  Each plane uses ITS OWN pw, ph. */
-typedef enum hipdec_scale_filter { HIPDEC_SCALE_NEAREST = 0, HIPDEC_SCALE_BOX = 1 } hipdec_scale_filter;
+ *                        left the range empty), the same in y, n = (x1 - x0) * (y1 - y0); 64-bit products, integer division.  Each plane uses ITS OWN pw, ph.
+ * Two more filters are taken by the tensor forms and the interleaved RGB24 forms further down, NOT by the plane-level calls of this section
+ * (hipdec_image_scale, hipdec_plane_scale, hipdec_batch_read_plane_scaled keep refusing them as unknown filters):
+ *  HIPDEC_SCALE_BILINEAR, HIPDEC_SCALE_BICUBIC   Pillow's 8-bit resampler (PIL.Image.resize with BILINEAR / BICUBIC; src/libImaging/Resample.c), bit for bit.
+ *  For an entry with window rw x rh at (left, top) and pre-orientation output ow x oh:
+ *      V = resample(full[top : top + rh, left : left + rw], ow, oh),
+ *  `full` the interleaved 8-bit RGB picture hipdec_batch_to_rgb writes for out_chroma 10 (nearest-neighbour chroma, the planner's op, to-SDR for sources above
+ *  8 bits) - that is Image.fromarray(full).crop(window).resize((ow, oh), filter).  The window is the image: nothing outside it is read.  The flip, the float
+ *  stage and the orientation apply to V exactly as they do for the other filters.  resample is separable, the horizontal pass first, the intermediate rounded
+ *  and clipped to 8 bits between the passes.  Per axis, n_in input and n_out output samples, all in IEEE double without contraction:
+ *      scale = (double)n_in / n_out;  fs = max(scale, 1.0);  support = S * fs   (S = 1.0 bilinear, 2.0 bicubic);  ss = 1.0 / fs
+ *      for xx in [0, n_out):  center = (xx + 0.5) * scale
+ *          xmin = max((int)(center - support + 0.5), 0);   xmax = min((int)(center + support + 0.5), n_in);   n = xmax - xmin
+ *          w[x] = f((x + xmin - center + 0.5) * ss), x in [0, n);   ww = w[0] + w[1] + ... in that order;   if (ww != 0.0) w[x] /= ww
+ *          k[x] = (int)(w[x] * 4194304.0 + (w[x] < 0 ? -0.5 : 0.5))                 (2^22; the conversion truncates toward zero)
+ *          out[xx] = clip((2^21 + sum_x in[xmin + x] * k[x]) >> 22, 0, 255)         (int32 accumulation, arithmetic shift)
+ *      bilinear  f(x): x = |x|;  x < 1 ? 1.0 - x : 0.0
+ *      bicubic   f(x): x = |x|, a = -0.5;  x < 1: ((a + 2.0) * x - (a + 3.0)) * x * x + 1;   x < 2: (((x - 5) * x + 8) * x - 4) * a;   else 0.0
+ *  (Pillow skips a pass whose axis keeps its size; both filters give the identity kernel there.)  A monochrome source gives R = G = B.  Sources above 8 bits
+ *  are taken with HIPDEC_TENSOR_U8 and by the RGB24 forms; a float dtype from such a source would need a native-depth definition Pillow does not have and is
+ *  HIPDEC_ERR_UNSUPPORTED.  The RGB forms take these filters for out_chroma 10 only (any other: HIPDEC_ERR_UNSUPPORTED).  The coefficient tables are computed
+ *  on the host, one per distinct (n_in, n_out) of a call, and uploaded with one copy; a call whose tables exceed 64 MiB is HIPDEC_ERR_LIMIT before anything
+ *  is launched (a table holds about 2 * S * n_in + 3 * n_out 32-bit values: a 4096-sample axis to 224 with bicubic is 66 KB). */
+typedef enum hipdec_scale_filter { HIPDEC_SCALE_NEAREST = 0, HIPDEC_SCALE_BOX = 1, HIPDEC_SCALE_BILINEAR = 16, HIPDEC_SCALE_BICUBIC = 17 } hipdec_scale_filter;
+/* Host only (no device is touched): the taps of output sample out_index along an axis of in_size -> out_size samples as the kernel receives them.  Returns their
+ * count n (< 0: error), *first = xmin, coeffs[0 .. min(n, capacity)) = k[].  filter: HIPDEC_SCALE_BILINEAR or HIPDEC_SCALE_BICUBIC. */
+HIPDEC_API int hipdec_resample_taps(int in_size, int out_size, int filter, int out_index, int* first, int32_t* coeffs, int capacity);
 /* Every plane of `in` (host or device pointers as `on_device` says; host planes the decoder handed over are found device-resident) to out_width x out_height,
  * into the planes `out` brings (same on_device convention; NULL where `in` has none); out->width / height / chroma / bit_depth are filled in.  The chroma
  * format is kept: chroma planes come out at the subsampled size of the output image. */
@@ -450,6 +475,7 @@ HIPDEC_API int hipdec_plane_scale(const void* in, size_t in_stride, int in_w, in
  *           out(x, y) = full(x * W / out_width, y * H / out_height); only the sampled pixels are read.
  *  box:     the bytes of hipdec_color_convert (nearest-neighbour upsampling has nothing to do) on the three planes box-scaled to out_width x out_height each,
  *           i.e. on a 4:4:4 image of the input's bit depth and VUI colour description.
+ *  bilinear / bicubic (out_chroma 10 only): resample(full, out_width, out_height) as defined above, `full` the bytes of hipdec_batch_to_rgb.
  * HIPDEC_ERR_LIMIT when the batch was created with max_image_size_pixels and out_width x out_height exceeds it.  Asynchronous on `stream`. */
 HIPDEC_API int hipdec_batch_to_rgb_scaled(hipdec_batch* b, int i, int out_chroma, int out_width, int out_height, int filter, void* out_dev, size_t out_stride,
                                           void* stream);
@@ -475,6 +501,8 @@ HIPDEC_API int hipdec_batch_read_plane_scaled(hipdec_batch* b, int i, int c, int
  *  HIPDEC_SCALE_BOX      the box definition above applied to each plane CROPPED to the window, with that plane's own cropped size: luma columns
  *                        [left, left + rw), chroma columns [left >> sH, ((left + rw - 1) >> sH) + 1), the same in y with sV; then the colour conversion
  *                        of hipdec_color_convert on the three averaged planes as a 4:4:4 image.  For the whole picture: hipdec_batch_to_rgb_scaled BOX.
+ *  HIPDEC_SCALE_BILINEAR / HIPDEC_SCALE_BICUBIC   V = resample(full[window], ow, oh), Pillow's resampler as defined with hipdec_scale_filter; 8-bit component
+ *                        values only (a float dtype from a source above 8 bits: HIPDEC_ERR_UNSUPPORTED).
  *  The component value V is the out_chroma 10 value (8 bits; sources above 8 bits go through to-SDR) for 8-bit sources and for HIPDEC_TENSOR_U8 from any
  *  source; float dtypes from sources above 8 bits get the native-depth value out_chroma 14 would store (0 .. 2^bits - 1: fold 1 / 1023 into `scale`).
  * Float stage: (float)V * scale[c] + bias[c] in fp32 - a multiply, then an add, each rounded once - and for F16 / BF16 the IEEE round-to-nearest-even
@@ -506,7 +534,8 @@ HIPDEC_API int hipdec_image_to_tensor(const hipdec_color_image* in, const hipdec
 HIPDEC_API void hipdec_tensor_stats(uint64_t* tensors, uint64_t* entries);
 /* Debug inspection: plane `plane` (0 .. 2) of entry `entry` as the kernel of the batch's LAST hipdec_batch_to_tensor received it - the device pointer and
  * stride of the PLANE and the window of it that is scaled.  A window is carried as an offset and never moves the pointer, so the box kernel's aligned
- * 32- / 64-bit row loads start at a 4-sample boundary of the plane whatever the window's parity. */
+ * 32- / 64-bit row loads start at a 4-sample boundary of the plane whatever the window's parity.  (Calls with the bilinear / bicubic filters keep their blocks
+ * apart and are not what this call shows.) */
 HIPDEC_API int hipdec_batch_tensor_block(hipdec_batch* b, int entry, int plane, const void** plane_dev, size_t* plane_stride, int* x, int* y, int* width,
                                          int* height);
 

@@ -83,6 +83,7 @@ def plan(bpp, chroma, nclx, target_chroma, upsampling=UPSAMPLING_BILINEAR, only_
 
 
 SCALE_NEAREST, SCALE_BOX = 0, 1   # hipdec_scale_filter
+SCALE_BILINEAR, SCALE_BICUBIC = 16, 17   # ... Pillow's 8-bit resampler bit for bit: the tensor and RGB24 forms only, not image_scale()
 
 
 class ColorImage(C.Structure):
@@ -99,7 +100,8 @@ def subsampled_size(width, height, chroma):
 def image_scale(planes, bpp, chroma, width, height, filter=SCALE_BOX, alpha=None):
     """heif_image_scale_image() on the GPU (hipdec_image_scale).  planes: [Y] or [Y, Cb, Cr] NumPy arrays, alpha: an optional plane of the
     luma size; chroma: 0 (monochrome) / CHROMA_420 / CHROMA_422 / CHROMA_444.  Returns the scaled planes in the same order (alpha last).
-    SCALE_NEAREST is the reference's arithmetic bit for bit, SCALE_BOX the area average defined in include/heif_hipdec.h."""
+    SCALE_NEAREST is the reference's arithmetic bit for bit, SCALE_BOX the area average defined in include/heif_hipdec.h (the plane-level call
+    takes these two only)."""
     lib = load_library()
     lib.hipdec_image_scale.argtypes = [C.POINTER(ColorImage), C.c_int, C.c_int, C.c_int, C.POINTER(ColorImage)]
     dt = np.uint16 if bpp > 8 else np.uint8
@@ -127,7 +129,8 @@ def image_to_tensor(planes, bpp, chroma, nclx, size, entries=None, dtype="float1
     """Batch.to_tensor for one image that is not a batch item (hipdec_image_to_tensor): planes [Y] or [Y, Cb, Cr] NumPy arrays of `bpp` bits, chroma
     0 / CHROMA_420 / CHROMA_422 / CHROMA_444, nclx (primaries, transfer, matrix, full_range) or None.  entries: (left, top, width, height[, flip])
     windows, or None for the whole image.  Returns the tensor as a NumPy array (bfloat16 as uint16 bits).  dtype, layout, mean / std / scale / bias
-    as Batch.to_tensor states them (max_value = 2^bpp - 1 for float dtypes from more than 8 bits, else 255)."""
+    as Batch.to_tensor states them (max_value = 2^bpp - 1 for float dtypes from more than 8 bits, else 255).  filter: SCALE_NEAREST, SCALE_BOX, or
+    SCALE_BILINEAR / SCALE_BICUBIC (PIL.Image.resize bit for bit on the 8-bit RGB picture; from more than 8 bits dtype "uint8" only)."""
     from . import decoder as dec
     lib = dec._bind(load_library())
     dt = np.uint16 if bpp > 8 else np.uint8

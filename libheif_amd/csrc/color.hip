@@ -21,6 +21,8 @@
 #include <cstring>
 #include <vector>
 #include <atomic>
+#include <map>
+#include <utility>
 
 namespace {
 
@@ -819,6 +821,188 @@ __global__ __launch_bounds__(256) void k_oriented_nearest(const OrientedParams* 
 }
 
 // the plane scalers: blockIdx.z selects the plane (all planes of an image, or of all items of a batch, are ONE launch)
+// ---- Pillow's bilinear / bicubic resampling of 8-bit pictures (HIPDEC_SCALE_BILINEAR / _BICUBIC, include/heif_hipdec.h), bit for bit: two separable passes
+// with integer coefficients of 22 fractional bits, the horizontal result rounded and clipped to 8 bits before the vertical pass.  The coefficient tables come
+// from the host (resample_table_fill below): n_out records (first tap, tap count), then n_out rows of `stride` coefficients.
+// A workgroup of 256 threads owns kResTR output rows x at most kResTC output columns of the PRE-orientation picture P of one entry.  It walks the source rows
+// its vertical taps cover, kResSR at a time:
+//   stage   the source columns the run's horizontal taps cover - at most kResSpan per chunk, from a 4-sample boundary of the plane - are read as the full-size
+//           kernel reads them (one aligned load of four luma samples, nearest-neighbour chroma) and converted with convert4<Pix, LO_RGB24>, the statement
+//           hipdec_batch_to_rgb's picture is made of; one packed 32-bit word per pixel goes to LDS.  Every source pixel is converted once per band.
+//   H       thread (column c, source row j) adds its taps that lie inside the chunk (int32, carried across chunks: a row of 4096 samples to 1 is legal),
+//           rounds, clips and leaves the 8-bit triple in LDS.
+//   V       thread (column c, row group g) feeds that triple into the sums of its four output rows; the row group is the wave, so the vertical records and
+//           coefficients are wave-uniform.  The sums stay in registers across all source rows of the band: no bound on the number of taps on either axis.
+// The finished band goes through LDS to store_oriented4 in 4-pixel groups along DISPLAYED rows (for a quarter turn: four rows of P at one column), so flip,
+// layout, dtype, pitch and orientation are the oriented kernels' store path; the unoriented calls use code 0 (4 with a flip) and a dense pitch.
+// LDS: 4 * 1024 * 4 + 4 * 64 * 4 + 16 * 65 * 4 = 21568 bytes - seven workgroups per CU.  Both tap loops are runtime loops.
+constexpr int kResTC = 64, kResTR = 16, kResSR = 4, kResSpan = 1024;
+constexpr uint64_t kResampleTableBytes = 64ull << 20;   // bound on the tables of one call (include/heif_hipdec.h): HIPDEC_ERR_LIMIT above it
+
+struct ResampleParams {
+  OrientedParams o;         // o.t.ow x o.t.oh: the size of P; o.t.tile: output columns per workgroup (<= kResTC); o.t.flip is 0
+  const int32_t* xt;        // the table of the horizontal axis (o.t.rw -> o.t.ow) and its coefficient row stride
+  const int32_t* yt;        // ... of the vertical axis (o.t.rh -> o.t.oh)
+  int xstride, ystride;
+};
+
+// four pixels of plane row yy from plane column x0 (a multiple of 4, inside the picture), as rgb_block loads them
+template <typename Pix>
+__device__ __forceinline__ void resample_load4(const ColorParams& p, int sH, int sV, bool mono, int x0, int yy, int (&Y)[4], int (&CB)[4], int (&CR)[4])
+{
+  const int npx = min(4, p.w - x0);
+  HIPDEC_GLOBAL const Pix* yrow = (HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.y + (size_t)yy * p.ys) + x0;
+  if (npx == 4 && sizeof(Pix) == 1 && (((uintptr_t)yrow) & 3) == 0) {
+    const uint32_t v = *(HIPDEC_GLOBAL const uint32_t*)yrow;
+    Y[0] = v & 255; Y[1] = (v >> 8) & 255; Y[2] = (v >> 16) & 255; Y[3] = v >> 24;
+  } else if (npx == 4 && sizeof(Pix) == 2 && (((uintptr_t)yrow) & 7) == 0) {
+    const uint2 v = *(HIPDEC_GLOBAL const uint2*)yrow;
+    Y[0] = v.x & 0xffff; Y[1] = v.x >> 16; Y[2] = v.y & 0xffff; Y[3] = v.y >> 16;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; i++) Y[i] = i < npx ? yrow[i] : 0;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) { CB[i] = 0; CR[i] = 0; }
+  if (mono) return;
+  HIPDEC_GLOBAL const Pix* cbrow = (HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.cb + (size_t)(yy >> sV) * p.cbs);
+  HIPDEC_GLOBAL const Pix* crrow = (HIPDEC_GLOBAL const Pix*)((HIPDEC_GLOBAL const uint8_t*)p.cr + (size_t)(yy >> sV) * p.crs);
+  if (sH) {
+    const int c0 = x0 >> 1;
+    const int cbA = cbrow[c0], crA = crrow[c0];
+    int cbB = cbA, crB = crA;
+    if (npx > 2) { cbB = cbrow[c0 + 1]; crB = crrow[c0 + 1]; }
+    CB[0] = CB[1] = cbA; CB[2] = CB[3] = cbB;
+    CR[0] = CR[1] = crA; CR[2] = CR[3] = crB;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; i++) if (i < npx) { CB[i] = cbrow[x0 + i]; CR[i] = crrow[x0 + i]; }
+  }
+}
+
+__device__ __forceinline__ uint32_t resample_pack(const int (&s)[3])
+{
+  return (uint32_t)clip_i(s[0] >> 22, 255) | ((uint32_t)clip_i(s[1] >> 22, 255) << 8) | ((uint32_t)clip_i(s[2] >> 22, 255) << 16);
+}
+
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) void k_resample(const ResampleParams* __restrict__ ps)
+{
+  __shared__ uint32_t src[kResSR][kResSpan];
+  __shared__ uint32_t hrow[kResSR][kResTC];
+  __shared__ uint32_t otile[kResTR][kResTC + 1];
+  const ResampleParams rp = ps[blockIdx.z];   // wave-uniform: scalar loads into SGPRs
+  const OrientedParams& op = rp.o;
+  const TensorParams& tp = op.t;
+  const ColorParams& p = tp.c;
+  const int tid = threadIdx.x, c = tid & (kResTC - 1), rg = tid / kResTC;   // rg: the wave - source row of the chunk in H, row group of the band in V
+  const int tile = max(1, min(tp.tile, kResTC));
+  const int ox0 = blockIdx.x * tile;
+  if (ox0 >= tp.ow) return;                               // (the whole workgroup)
+  const int ncol = min(tile, tp.ow - ox0);
+  const bool mono = p.arith == AR_MONO;
+  const int quarter = op.code & 1, fx = ((op.code >> 1) ^ (op.code >> 2)) & 1, fy = ((op.code >> 1) ^ op.code) & 1;
+  HIPDEC_GLOBAL const int32_t* xt = (HIPDEC_GLOBAL const int32_t*)rp.xt;
+  HIPDEC_GLOBAL const int32_t* yt = (HIPDEC_GLOBAL const int32_t*)rp.yt;
+  HIPDEC_GLOBAL const int32_t* xk = xt + 2 * (size_t)tp.ow;
+  HIPDEC_GLOBAL const int32_t* yk = yt + 2 * (size_t)tp.oh;
+  // plane columns [base, send) hold every tap of the run (first taps and ends do not decrease along an axis); base is a 4-sample boundary of the plane
+  const int base = (tp.left + xt[2 * ox0]) & ~3;
+  const int send = tp.left + xt[2 * (ox0 + ncol - 1)] + xt[2 * (ox0 + ncol - 1) + 1];
+  const int nchunks = (send - base + kResSpan - 1) / kResSpan;
+  const bool hascol = c < ncol;
+  const int cx = ox0 + (hascol ? c : 0);
+  const int xa = tp.left + xt[2 * cx], xn = hascol ? xt[2 * cx + 1] : 0;   // this thread's column: its first tap as a plane column, and its tap count
+  HIPDEC_GLOBAL const int32_t* kx = xk + (size_t)cx * (size_t)rp.xstride;
+  for (int oy0 = blockIdx.y * kResTR; oy0 < tp.oh; oy0 += gridDim.y * kResTR) {
+    const int nrow = min(kResTR, tp.oh - oy0);
+    const int srow0 = yt[2 * oy0], srow1 = yt[2 * (oy0 + nrow - 1)] + yt[2 * (oy0 + nrow - 1) + 1];   // window rows [srow0, srow1) hold every tap of the band
+    int ymin[4], yn[4], acc[4][3];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int r = rg * 4 + i;
+      ymin[i] = r < nrow ? wave_uniform(yt[2 * (oy0 + r)]) : 0;
+      yn[i] = r < nrow ? wave_uniform(yt[2 * (oy0 + r) + 1]) : 0;
+      acc[i][0] = acc[i][1] = acc[i][2] = 1 << 21;
+    }
+    for (int sr = srow0; sr < srow1; sr += kResSR) {
+      int h[3] = {1 << 21, 1 << 21, 1 << 21};
+      for (int k = 0; k < nchunks; k++) {
+        const int cs = base + k * kResSpan;
+        if (k) __syncthreads();                           // H has finished with the previous chunk
+        const int x0 = cs + tid * 4;
+        if (x0 < send) {
+#pragma unroll
+          for (int j = 0; j < kResSR; j++) {
+            if (sr + j >= srow1) break;
+            int Y[4], CB[4], CR[4], R[4], G[4], B[4];
+            resample_load4<Pix>(p, tp.sH, tp.sV, mono, x0, tp.top + sr + j, Y, CB, CR);
+            convert4<Pix, LO_RGB24>(p, Y, CB, CR, R, G, B);
+#pragma unroll
+            for (int i = 0; i < 4; i++) src[j][tid * 4 + i] = (uint32_t)R[i] | ((uint32_t)G[i] << 8) | ((uint32_t)B[i] << 16);
+          }
+        }
+        __syncthreads();
+        if (sr + rg < srow1) {
+          const int lo = max(xa, cs), hi = min(xa + xn, cs + kResSpan);
+          for (int x = lo; x < hi; x++) {
+            const uint32_t v = src[rg][x - cs];
+            const int kk = kx[x - xa];
+            h[0] += (int)(v & 255u) * kk; h[1] += (int)((v >> 8) & 255u) * kk; h[2] += (int)((v >> 16) & 255u) * kk;
+          }
+        }
+      }
+      hrow[rg][c] = resample_pack(h);                     // rounded and clipped to 8 bits BEFORE the vertical pass
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < kResSR; j++) {
+        const int sy = sr + j;
+        if (sy >= srow1) break;
+        const uint32_t v = hrow[j][c];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int t = sy - ymin[i];
+          if ((unsigned)t < (unsigned)yn[i]) {
+            const int kk = yk[(size_t)(oy0 + rg * 4 + i) * (size_t)rp.ystride + (size_t)t];
+            acc[i][0] += (int)(v & 255u) * kk; acc[i][1] += (int)((v >> 8) & 255u) * kk; acc[i][2] += (int)((v >> 16) & 255u) * kk;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) otile[rg * 4 + i][c] = resample_pack(acc[i]);
+    __syncthreads();
+    if (!quarter) {   // 4-pixel groups of row oy or H - 1 - oy, columns forward or reversed
+      const uint32_t ng = ((uint32_t)ncol + 3u) >> 2, total = ng * (uint32_t)nrow;
+      for (uint32_t idx = (uint32_t)tid; idx < total; idx += 256u) {
+        const uint32_t r = idx / ng, g = idx - r * ng;
+        int R[4], G[4], B[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {                     // (past the run's last pixel: inside the tile row, not stored)
+          const uint32_t s = otile[r][g * 4u + (uint32_t)i];
+          R[i] = (int)(s & 255u); G[i] = (int)((s >> 8) & 255u); B[i] = (int)((s >> 16) & 255u);
+        }
+        const int oy = oy0 + (int)r;
+        store_oriented4<DT>(op, tp.ow, tp.oh, fx, ox0 + (int)g * 4, fy ? tp.oh - 1 - oy : oy, min(4, ncol - (int)g * 4), R, G, B);
+      }
+    } else {          // a row of P is a displayed column: four rows of P at column x are four neighbours of displayed row Y
+      const uint32_t ng = ((uint32_t)nrow + 3u) >> 2, total = ng * (uint32_t)ncol;
+      for (uint32_t idx = (uint32_t)tid; idx < total; idx += 256u) {
+        const uint32_t cc = idx / ng, g = idx - cc * ng;
+        int R[4], G[4], B[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {                     // (past the band's last row: inside the tile, not stored)
+          const uint32_t s = otile[g * 4u + (uint32_t)i][cc];
+          R[i] = (int)(s & 255u); G[i] = (int)((s >> 8) & 255u); B[i] = (int)((s >> 16) & 255u);
+        }
+        const int x = ox0 + (int)cc;
+        store_oriented4<DT>(op, tp.oh, tp.ow, fx, oy0 + (int)g * 4, fy ? tp.ow - 1 - x : x, min(4, nrow - (int)g * 4), R, G, B);
+      }
+    }
+    __syncthreads();                                      // the tile is written again by the next band
+  }
+}
+
 template <typename Pix>
 __global__ __launch_bounds__(256) void k_scale_plane_nearest(const hipdec::PlaneScaleParams* __restrict__ ps)
 {
@@ -1161,8 +1345,91 @@ thread_local std::vector<CapturedScaled> t_captured_scaled;
 // the recorded blocks go out as one launch (hipdec::color_tensor_launch).  Taken and checked like a scale request.
 struct TensorReq { bool on = false; hipdec::TensorRequest r; };
 thread_local TensorReq t_tensor;
-struct CapturedTensor { TensorParams p; int wide; int oriented, code; uint64_t pitch; };   // oriented: for the k_oriented_* kernels, with a code and a row pitch
+struct CapturedTensor { TensorParams p; int wide; int oriented, code; uint64_t pitch; int resample; };   // oriented: for the k_oriented_* kernels, with a code and a row pitch; resample: the filter, for k_resample (code and pitch are set for every entry)
 thread_local std::vector<CapturedTensor> t_captured_tensor;
+
+// ---- the coefficient tables of HIPDEC_SCALE_BILINEAR / _BICUBIC: Pillow's precompute_coeffs + normalize_coeffs_8bpc (src/libImaging/Resample.c), statement
+// by statement as include/heif_hipdec.h gives them.  IEEE double, no contraction (this file is built with -ffp-contract=off): the ORDER of operations is
+// part of the definition.
+double resample_filter_value(int filter, double x)
+{
+  if (x < 0.0) x = -x;
+  if (filter == HIPDEC_SCALE_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
+  const double a = -0.5;
+  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+  return 0.0;
+}
+
+struct ResampleAxis {
+  double scale, support, ss;
+  int n_in, filter, stride;   // stride: taps an output sample can have ((int)ceil(support) * 2 + 1, Pillow's ksize)
+};
+ResampleAxis resample_axis_of(int n_in, int n_out, int filter)
+{
+  ResampleAxis a;
+  a.n_in = n_in; a.filter = filter;
+  a.scale = (double)n_in / n_out;
+  const double fs = a.scale < 1.0 ? 1.0 : a.scale;
+  a.support = (filter == HIPDEC_SCALE_BILINEAR ? 1.0 : 2.0) * fs;
+  a.ss = 1.0 / fs;
+  a.stride = (int)std::ceil(a.support) * 2 + 1;
+  return a;
+}
+
+// the taps of output sample xx: *first = xmin, k[0 .. n) the coefficients (k and w hold a.stride elements); returns n
+int resample_taps_of(const ResampleAxis& a, int xx, int* first, int32_t* k, double* w)
+{
+  const double center = (xx + 0.5) * a.scale;
+  int xmin = (int)(center - a.support + 0.5);
+  if (xmin < 0) xmin = 0;
+  int xmax = (int)(center + a.support + 0.5);
+  if (xmax > a.n_in) xmax = a.n_in;
+  int n = xmax - xmin;
+  if (n > a.stride) n = a.stride;   // (cannot happen: ceil(support) * 2 + 1 covers the range)
+  double ww = 0.0;
+  for (int x = 0; x < n; x++) {
+    w[x] = resample_filter_value(a.filter, (x + xmin - center + 0.5) * a.ss);
+    ww += w[x];
+  }
+  for (int x = 0; x < n; x++) {
+    if (ww != 0.0) w[x] /= ww;
+    k[x] = (int)(w[x] * 4194304.0 + (w[x] < 0 ? -0.5 : 0.5));
+  }
+  *first = xmin;
+  return n < 0 ? 0 : n;
+}
+
+// ints of the table of an axis: n_out records (first, count), then n_out rows of `stride` coefficients
+uint64_t resample_table_ints(int n_in, int n_out, int filter)
+{
+  return (uint64_t)n_out * (2ull + (uint64_t)resample_axis_of(n_in, n_out, filter).stride);
+}
+
+void resample_table_fill(int n_in, int n_out, int filter, int32_t* t)
+{
+  const ResampleAxis a = resample_axis_of(n_in, n_out, filter);
+  std::vector<double> w((size_t)a.stride);
+  int32_t* k = t + 2 * (size_t)n_out;
+  for (int xx = 0; xx < n_out; xx++, k += a.stride) {
+    int first = 0;
+    const int n = resample_taps_of(a, xx, &first, k, w.data());
+    for (int x = n; x < a.stride; x++) k[x] = 0;
+    t[2 * (size_t)xx] = first; t[2 * (size_t)xx + 1] = n;
+  }
+}
+
+// output columns per workgroup of k_resample: as many (whole 4-pixel groups, at most kResTC) as have their taps inside one staged chunk of kResSpan columns
+int resample_tile_of(int n_in, int n_out, int filter)
+{
+  const ResampleAxis a = resample_axis_of(n_in, n_out, filter);
+  double t = ((double)kResSpan - 6.0 - 2.0 * a.support) / a.scale;
+  if (t > kResTC) t = kResTC;
+  if (t < 1) t = 1;                                     // taps wider than the chunk: the kernel's chunk loop
+  int ti = (int)t;
+  if (ti >= 4) ti &= ~3;
+  return ti;
+}
 
 int box_tile_of(int pw, int qw)
 {
@@ -1221,14 +1488,17 @@ int record_tensor(const ColorParams& p)
   tp.c = p; tp.ow = r.ow; tp.oh = r.oh; tp.sH = r.sH; tp.sV = r.sV;
   tp.left = r.left; tp.top = r.top; tp.rw = r.rw; tp.rh = r.rh; tp.flip = r.flip ? 1 : 0; tp.nhwc = r.nhwc ? 1 : 0;
   for (int c = 0; c < 3; c++) { tp.scale[c] = r.scale[c]; tp.bias[c] = r.bias[c]; }
-  tp.tile = box_tile_of(r.rw, r.ow);
-  if (r.oriented) {   // (r.ow x r.oh: the pre-orientation size; the quarter-turn stage holds kOrientedTile columns)
+  tp.tile = r.resample ? resample_tile_of(r.rw, r.ow, r.resample) : box_tile_of(r.rw, r.ow);
+  if (r.resample) {
+    if constexpr (LAYOUT != LO_RGB24) return hipdec::set_error(HIPDEC_ERR_UNSUPPORTED, "resampled output: 8-bit component values only");
+    tp.flip = 0;      // folded into the code
+  } else if (r.oriented) {   // (r.ow x r.oh: the pre-orientation size; the quarter-turn stage holds kOrientedTile columns)
     const int cap = sizeof(Pix) == 1 ? OrientedTile<uint8_t, TD_U8>::TC : OrientedTile<uint16_t, TD_U8>::TC;
     tp.tile = tp.tile < cap ? tp.tile : cap;
     tp.flip = 0;      // folded into the code
   }
   t_tensor.on = false;   // taken
-  t_captured_tensor.push_back(CapturedTensor{tp, sizeof(Pix) == 2, r.oriented ? 1 : 0, r.code, (uint64_t)r.pitch});
+  t_captured_tensor.push_back(CapturedTensor{tp, sizeof(Pix) == 2, r.oriented ? 1 : 0, r.code, (uint64_t)r.pitch, r.resample});
   return 0;
   }
 }
@@ -1525,6 +1795,78 @@ int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
   g_oriented_entries += (uint64_t)caps.size(); g_oriented_quarter += quarter;
   return 0;
 }
+
+// HIPDEC_SCALE_BILINEAR / _BICUBIC: the recorded blocks with their coefficient tables as ONE launch of k_resample.  The tables of a call are deduplicated by
+// (input samples, output samples) - the filter is the call's - and travel behind the parameter blocks in the same buffer, so ONE asynchronous copy brings
+// both to the device and the staging memory is kept as the other launches keep theirs (st.host, st.prev).
+template <typename Pix, int DT>
+void launch_resample_grid(const ResampleParams* dev, int n, int tiles, int bands, hipStream_t s)
+{
+  dim3 block(256), grid(tiles, bands < 65535 ? bands : 65535, n);
+  hipLaunchKernelGGL((k_resample<Pix, DT>), grid, block, 0, s, dev);
+}
+
+int resample_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int filter, int dtype, hipStream_t s)
+{
+  std::map<std::pair<int, int>, uint64_t> where;   // axis -> the table's first int
+  uint64_t ints = 0;
+  auto want = [&](int n_in, int n_out) {
+    if (where.emplace(std::make_pair(n_in, n_out), ints).second) ints += resample_table_ints(n_in, n_out, filter);
+  };
+  int max_tiles = 0, max_bands = 0;
+  uint64_t quarter = 0;
+  for (const auto& c : caps) {
+    if (c.wide != caps[0].wide) return set_error(HIPDEC_ERR_UNSUPPORTED, "resampled output: the entries mix 8-bit and wider sources");
+    if (c.resample != filter) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "resampled output: the entries were recorded for filter %d, the launch is for %d", c.resample, filter);
+    want(c.p.rw, c.p.ow); want(c.p.rh, c.p.oh);
+    if (ints > kResampleTableBytes / 4)
+      return set_error(HIPDEC_ERR_LIMIT, "resampled output: the coefficient tables of this call exceed %llu bytes", (unsigned long long)kResampleTableBytes);
+    const int tile = c.p.tile < kResTC ? (c.p.tile > 0 ? c.p.tile : 1) : kResTC;   // (as the kernel reads it)
+    const int tiles = (c.p.ow + tile - 1) / tile, bands = (c.p.oh + kResTR - 1) / kResTR;
+    max_tiles = tiles > max_tiles ? tiles : max_tiles; max_bands = bands > max_bands ? bands : max_bands;
+    quarter += (uint64_t)(c.code & 1);
+  }
+  const size_t params_bytes = (caps.size() * sizeof(ResampleParams) + 15) & ~(size_t)15;
+  const size_t bytes = params_bytes + (size_t)ints * sizeof(int32_t);
+  std::vector<uint8_t> host(bytes);
+  for (const auto& w : where) resample_table_fill(w.first.first, w.first.second, filter, (int32_t*)(host.data() + params_bytes) + w.second);
+  if (st.dev_bytes < bytes) {
+    if (st.dev) arena_release(st.dev, st.dev_bytes);
+    st.dev = nullptr; st.dev_bytes = 0; st.host.clear();
+    HIPDEC_CHECK_HIP(arena_acquire(&st.dev, bytes, &st.dev_bytes));
+  }
+  const int32_t* tables_dev = (const int32_t*)((const uint8_t*)st.dev + params_bytes);
+  for (size_t i = 0; i < caps.size(); i++) {
+    const CapturedTensor& c = caps[i];
+    ResampleParams rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.o.t = c.p; rp.o.code = c.code; rp.o.rb = kResTR; rp.o.pitch = c.pitch;
+    rp.xt = tables_dev + where[std::make_pair(c.p.rw, c.p.ow)]; rp.xstride = resample_axis_of(c.p.rw, c.p.ow, filter).stride;
+    rp.yt = tables_dev + where[std::make_pair(c.p.rh, c.p.oh)]; rp.ystride = resample_axis_of(c.p.rh, c.p.oh, filter).stride;
+    memcpy(host.data() + i * sizeof(ResampleParams), &rp, sizeof(rp));
+  }
+  if (st.host != host) {   // steady state (same windows, sizes, codes and output): nothing to upload
+    st.prev.swap(st.host);
+    st.host.swap(host);
+    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), bytes, hipMemcpyHostToDevice, s));
+  }
+  for (size_t first = 0; first < caps.size(); first += 65535) {
+    const ResampleParams* dev = (const ResampleParams*)st.dev + first;
+    const int n = (int)(caps.size() - first < 65535 ? caps.size() - first : 65535);
+    switch (caps[0].wide * 4 + dtype) {
+#define X(DT) case DT: launch_resample_grid<uint8_t, DT>(dev, n, max_tiles, max_bands, s); break; \
+              case 4 + DT: launch_resample_grid<uint16_t, DT>(dev, n, max_tiles, max_bands, s); break;
+      X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
+#undef X
+      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "resampled output: unknown dtype %d", dtype);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "resample kernel launch: %s", hipGetErrorString(e));
+    if (caps[0].oriented) g_oriented_launches++;
+  }
+  if (caps[0].oriented) { g_oriented_entries += (uint64_t)caps.size(); g_oriented_quarter += quarter; }
+  return 0;
+}
 }  // namespace
 
 // the tensor blocks recorded on this thread since color_tensor_begin() as ONE launch (a grid's z extent is 65535: more entries take as few launches as that allows)
@@ -1533,6 +1875,7 @@ int color_tensor_launch(ColorBatchState& st, int filter, int dtype, hipStream_t 
   std::vector<CapturedTensor> caps;
   caps.swap(t_captured_tensor);
   if (caps.empty()) return 0;
+  if (caps[0].resample) return resample_launch(caps, st, filter, dtype, s);   // (the filter is the call's: all entries, or none)
   if (caps[0].oriented) return oriented_launch(caps, st, filter, dtype, s);   // (a call's entries are all oriented, or none is)
   int max_tiles = 0;
   for (const auto& c : caps) {
@@ -1624,6 +1967,21 @@ void color_batch_state_free(ColorBatchState& st)
 using namespace hipdec;
 
 extern "C" {
+
+int hipdec_resample_taps(int in_size, int out_size, int filter, int out_index, int* first, int32_t* coeffs, int capacity)
+{
+  if (filter != HIPDEC_SCALE_BILINEAR && filter != HIPDEC_SCALE_BICUBIC) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "resample_taps: filter %d has no taps (bilinear 16, bicubic 17)", filter);
+  if (in_size < 1 || out_size < 1 || out_index < 0 || out_index >= out_size || !first || capacity < 0 || (capacity > 0 && !coeffs))
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "resample_taps: bad arguments");
+  return guarded("resample_taps", [&]() -> int {
+    const ResampleAxis a = resample_axis_of(in_size, out_size, filter);
+    std::vector<double> w((size_t)a.stride);
+    std::vector<int32_t> k((size_t)a.stride);
+    const int n = resample_taps_of(a, out_index, first, k.data(), w.data());
+    for (int x = 0; x < n && x < capacity; x++) coeffs[x] = k[x];
+    return n;
+  });
+}
 
 void hipdec_oriented_stats(uint64_t* launches, uint64_t* entries, uint64_t* quarter_turn_entries)
 {

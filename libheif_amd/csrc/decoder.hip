@@ -661,6 +661,8 @@ namespace {
 // hipdec_batch_to_rgb, and - with a scale request - hipdec_batch_to_rgb_scaled: the same argument checks and planner rules; the request makes the colour
 // entry points end in the fused scale + colour kernel (color.hip).  Box presents the planes as the 4:4:4 image they are scaled to.
 struct ScaleRequest { int ow, oh, filter; };
+// the Pillow-exact filters (include/heif_hipdec.h): taken by the tensor forms and the RGB24 forms, through k_resample (color.hip)
+inline bool resample_filter(int filter) { return filter == HIPDEC_SCALE_BILINEAR || filter == HIPDEC_SCALE_BICUBIC; }
 int copy_rows_to_host(void* dst, size_t dst_stride, const void* dsrc, size_t src_stride, size_t row_bytes, int rows, hipStream_t s);   // decoder_color_boundary.inc
 // The planes one picture hands to the colour entry points: a decoded item of a batch (hipdec_batch_to_rgb*), or the composed canvas of a photo of an
 // album (hipdec_album_to_rgb*, decoder_album.inc).  info: the VUI colour description and the bit depth.
@@ -785,13 +787,22 @@ int tensor_check_desc(const char* who, const hipdec_tensor_desc* d, int n_entrie
   if (d->width < 1 || d->height < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: output size %d x %d", who, d->width, d->height);
   if (d->dtype < HIPDEC_TENSOR_U8 || d->dtype > HIPDEC_TENSOR_BF16) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown dtype %d", who, d->dtype);
   if (d->layout != HIPDEC_TENSOR_NCHW && d->layout != HIPDEC_TENSOR_NHWC) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown layout %d", who, d->layout);
-  if (d->filter != HIPDEC_SCALE_NEAREST && d->filter != HIPDEC_SCALE_BOX) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown filter %d", who, d->filter);
+  if (d->filter != HIPDEC_SCALE_NEAREST && d->filter != HIPDEC_SCALE_BOX && !resample_filter(d->filter))
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown filter %d", who, d->filter);
   if (d->dtype != HIPDEC_TENSOR_U8)
     for (int c = 0; c < 3; c++)
       if (!std::isfinite(d->scale[c]) || !std::isfinite(d->bias[c])) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: scale / bias of channel %d is not finite", who, c);
   const uint64_t per = 3ull * (uint64_t)d->width * (uint64_t)d->height * tensor_elem_bytes(d->dtype);   // (evaluated before the check below, which keeps it far from 2^64)
   if ((uint64_t)d->width * (uint64_t)d->height > (1ull << 40) || per > (~0ull) / (uint64_t)n_entries) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: tensor too large", who);
   *bytes = (size_t)(per * (uint64_t)n_entries);
+  return 0;
+}
+
+// bilinear / bicubic are defined on the 8-bit picture (Pillow has no native-depth form): a float dtype from a source above 8 bits is refused
+int tensor_check_resample_depth(const char* who, const hipdec_tensor_desc* d, int bits)
+{
+  if (resample_filter(d->filter) && bits > 8 && d->dtype != HIPDEC_TENSOR_U8)
+    return set_error(HIPDEC_ERR_UNSUPPORTED, "%s: filter %d from a %d-bit source is defined for HIPDEC_TENSOR_U8 only (the 8-bit picture is what is resampled)", who, d->filter, bits);
   return 0;
 }
 
@@ -814,9 +825,16 @@ int tensor_record_entry(const char* who, const uint8_t* y, size_t ys, const uint
                         const hipdec_nclx* nclx, const hipdec_nclx* nclx_after_sdr, const hipdec_tensor_desc* d, int left, int top, int rw, int rh, int flip, void* elem0,
                         int orientation = -1, size_t pitch = 0)
 {
+  if (int rc = tensor_check_resample_depth(who, d, bits)) return rc;
   TensorRequest rq;
   memset(&rq, 0, sizeof(rq));
   rq.ow = d->width; rq.oh = d->height;
+  rq.resample = resample_filter(d->filter) ? d->filter : 0;
+  if (orientation < 0 && rq.resample) {   // k_resample stores through the oriented path: an unoriented entry is code 0 (the mirror with a flip) and a dense pitch
+    rq.code = flip ? HIPDEC_ORIENT_MIRROR : HIPDEC_ORIENT_0;
+    rq.pitch = pitch ? pitch : (size_t)d->width * (d->layout == HIPDEC_TENSOR_NHWC ? 3 : 1);
+    flip = 0;
+  }
   if (orientation >= 0) {   // oriented output: d->width x height is the DISPLAYED size, the kernels work on the pre-orientation picture; the flip becomes part of the code
     rq.oriented = 1;
     rq.code = flip ? orientation_compose(orientation, HIPDEC_XF_MIRROR, 1) : orientation;
@@ -918,7 +936,8 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
     const size_t slot = b->runs ? (b->runs - 1) % (b->ev.size() / kEv) : 0;
     hipEvent_t* ev = b->ev.data() + kEv * slot;
     HIPDEC_CHECK_HIP(hipEventRecord(ev[6], s));
-    int rc = color_tensor_launch(oriented ? b->color_oriented : b->color_tensor, desc->filter, desc->dtype, s);
+    // (resampled entries are not hipdec_batch_tensor_block's blocks: they go with the oriented ones)
+    int rc = color_tensor_launch(oriented || resample_filter(desc->filter) ? b->color_oriented : b->color_tensor, desc->filter, desc->dtype, s);
     HIPDEC_CHECK_HIP(hipEventRecord(ev[7], s));
     if (!rc && b->runs) b->colour_timed[slot] = 1;
     b->mark_done(s);
@@ -933,12 +952,13 @@ int rgb_oriented_check_item(const char* who, int i, int out_chroma, int code, in
   if (out_chroma != 10) return set_error(HIPDEC_ERR_UNSUPPORTED, "%s: out_chroma %d (interleaved RGB24, 10, is the oriented form)", who, out_chroma);
   if (code < 0 || code > 7) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: item %d: orientation %d is not 0 .. 7", who, i, code);
   if (ow < 1 || oh < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: item %d: output size %d x %d", who, i, ow, oh);
-  if (filter != HIPDEC_SCALE_NEAREST && filter != HIPDEC_SCALE_BOX) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown filter %d", who, filter);
+  if (filter != HIPDEC_SCALE_NEAREST && filter != HIPDEC_SCALE_BOX && !resample_filter(filter)) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown filter %d", who, filter);
   if (stride < (size_t)ow * 3) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: item %d: out_stride %zu is smaller than a row of %zu bytes", who, i, stride, (size_t)ow * 3);
   return 0;
 }
 
-// one picture of an oriented RGB call: a U8 / NHWC entry over the whole picture whose rows are out_stride apart
+// one picture of an oriented RGB call: a U8 / NHWC entry over the whole picture whose rows are out_stride apart (code -1: the same entry for an unoriented
+// call with a resampling filter, which has no other way to a row pitch)
 int rgb_oriented_record(const char* who, const RgbSource& S, int code, int ow, int oh, int filter, void* out_dev, size_t out_stride)
 {
   if (S.max_pixels && (uint64_t)ow * (uint64_t)oh > S.max_pixels)
@@ -951,6 +971,42 @@ int rgb_oriented_record(const char* who, const RgbSource& S, int code, int ow, i
   hipdec_nclx nclx{1, I.colour_primaries, I.transfer_characteristics, I.matrix_coeffs, I.full_range_flag};
   return tensor_record_entry(who, S.plane[0], S.stride[0], S.plane[1], S.stride[1], S.plane[2], S.stride[2], S.width, S.height, S.wide ? I.bit_depth_luma : 8,
                              S.chroma_format_idc, &nclx, &nclx, &d, 0, 0, S.width, S.height, 0, out_dev, code, out_stride);
+}
+
+// hipdec_batch_to_rgb_scaled (item `first`) and hipdec_batch_to_rgb_scaled_all (all items) with a resampling filter: the pictures as U8 / NHWC entries whose
+// rows are out_stride apart, ONE launch of k_resample.  Interleaved RGB24 only; what the arguments alone decide is refused before the batch is looked at.
+int batch_rgb_resample(const char* who, hipdec_batch* b, int first, bool all, int out_chroma, const int* ows, const int* ohs, int filter, void* const* outs,
+                       const size_t* strides, void* stream)
+{
+  if (out_chroma != 10) return set_error(HIPDEC_ERR_UNSUPPORTED, "%s: out_chroma %d with filter %d (bilinear / bicubic write interleaved RGB24, out_chroma 10)", who, out_chroma, filter);
+  if (!b || !ows || !ohs || !outs || !strides || (!all && (first < 0 || first >= (int)b->pics.size()))) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  const int n = all ? (int)b->pics.size() : 1;
+  for (int i = 0; i < n; i++) {
+    if (!outs[i]) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: item %d: no output", who, first + i);
+    if (int rc = rgb_oriented_check_item(who, first + i, out_chroma, 0, ows[i], ohs[i], filter, strides[i])) return rc;
+  }
+  DeviceScope scope(b->device);
+  if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: the batch's arena was handed to another batch", who);
+  return guarded(who, [&]() -> int {
+    hipStream_t s = follow_stream(b, stream);
+    color_tensor_begin();
+    for (int i = 0; i < n; i++) {
+      const PicParams& P = b->params[first + i];
+      const RgbSource S{{b->arena + P.off_out[0], b->arena + P.off_out[1], b->arena + P.off_out[2]}, {P.out_stride[0], P.out_stride[1], P.out_stride[2]},
+                        P.out_width, P.out_height, P.chroma_format_idc, b->wide, &b->pics[first + i].info, b->max_pixels};
+      if (int rc = rgb_oriented_record(who, S, -1, ows[i], ohs[i], filter, outs[i], strides[i])) { color_tensor_abort(); return rc; }
+    }
+    const size_t slot = b->runs ? (b->runs - 1) % (b->ev.size() / kEv) : 0;
+    hipEvent_t* ev = b->ev.data() + kEv * slot;
+    if (all) HIPDEC_CHECK_HIP(hipEventRecord(ev[6], s));
+    int rc = color_tensor_launch(b->color_oriented, filter, HIPDEC_TENSOR_U8, s);
+    if (all) {
+      HIPDEC_CHECK_HIP(hipEventRecord(ev[7], s));
+      if (!rc && b->runs) b->colour_timed[slot] = 1;
+    }
+    b->mark_done(s);
+    return rc;
+  });
 }
 }  // namespace
 
@@ -1028,6 +1084,7 @@ int hipdec_batch_to_rgb(hipdec_batch* b, int i, int out_chroma, void* out_dev, s
 
 int hipdec_batch_to_rgb_scaled(hipdec_batch* b, int i, int out_chroma, int out_width, int out_height, int filter, void* out_dev, size_t out_stride, void* stream)
 {
+  if (resample_filter(filter)) return batch_rgb_resample("to_rgb_scaled", b, i, false, out_chroma, &out_width, &out_height, filter, &out_dev, &out_stride, stream);
   const ScaleRequest rq{out_width, out_height, filter};
   return batch_to_rgb_impl(b, i, out_chroma, out_dev, out_stride, stream, &rq);
 }
@@ -1035,6 +1092,7 @@ int hipdec_batch_to_rgb_scaled(hipdec_batch* b, int i, int out_chroma, int out_w
 int hipdec_batch_to_rgb_scaled_all(hipdec_batch* b, int out_chroma, const int* out_widths, const int* out_heights, int filter, void* const* outs_dev,
                                    const size_t* out_strides, void* stream)
 {
+  if (resample_filter(filter)) return batch_rgb_resample("to_rgb_scaled_all", b, 0, true, out_chroma, out_widths, out_heights, filter, outs_dev, out_strides, stream);
   if (!b || !out_widths || !out_heights || !outs_dev || !out_strides) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb_scaled_all: bad arguments");
   DeviceScope scope(b->device);
   if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_rgb_scaled_all: the batch's arena was handed to another batch");

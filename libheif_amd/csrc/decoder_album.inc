@@ -54,6 +54,9 @@ RgbSource album_source(const hipdec_album* a, int p)
                    ph.out_w, ph.out_h, a->chroma_format_idc, a->bits > 8, &a->batch->pics[(size_t)ph.first_tile].info, a->max_pixels};
 }
 
+int album_rgb_entries(const char* who, hipdec_album* a, int out_chroma, const int* orientations, bool oriented, const int* out_widths, const int* out_heights, int filter,
+                      void* const* outs_dev, const size_t* out_strides, void* stream);   // (below)
+
 }  // namespace
 
 extern "C" {
@@ -259,6 +262,10 @@ int hipdec_album_to_rgb_all(hipdec_album* a, int out_chroma, void* const* outs_d
 int hipdec_album_to_rgb_scaled_all(hipdec_album* a, int out_chroma, const int* out_widths, const int* out_heights, int filter, void* const* outs_dev,
                                    const size_t* out_strides, void* stream)
 {
+  if (resample_filter(filter)) {   // bilinear / bicubic: the photos as U8 / NHWC entries of ONE k_resample launch, as the oriented form records them
+    if (out_chroma != 10) return set_error(HIPDEC_ERR_UNSUPPORTED, "album_to_rgb_scaled_all: out_chroma %d with filter %d (bilinear / bicubic write interleaved RGB24, out_chroma 10)", out_chroma, filter);
+    return album_rgb_entries("album_to_rgb_scaled_all", a, out_chroma, nullptr, false, out_widths, out_heights, filter, outs_dev, out_strides, stream);
+  }
   if (!a || !out_widths || !out_heights || !outs_dev || !out_strides) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_rgb_scaled_all: bad arguments");
   DeviceScope scope(a->device);
   hipdec_batch* b = a->batch.get();
@@ -278,6 +285,32 @@ int hipdec_album_to_rgb_scaled_all(hipdec_album* a, int out_chroma, const int* o
 }  // extern "C"
 
 namespace {
+// hipdec_batch_to_rgb_scaled_oriented_all over the canvases; oriented false: the unoriented call with a resampling filter (no code, not counted as oriented)
+int album_rgb_entries(const char* who, hipdec_album* a, int out_chroma, const int* orientations, bool oriented, const int* out_widths, const int* out_heights, int filter,
+                      void* const* outs_dev, const size_t* out_strides, void* stream)
+{
+  if (!a || !out_widths || !out_heights || !outs_dev || !out_strides) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  const int n = (int)a->photos.size();
+  for (int p = 0; p < n; p++) {
+    if (!outs_dev[p]) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: photo %d: no output", who, p);
+    if (int rc = rgb_oriented_check_item(who, p, out_chroma, orientations ? orientations[p] : 0, out_widths[p], out_heights[p], filter, out_strides[p])) return rc;
+  }
+  DeviceScope scope(a->device);
+  return guarded(who, [&]() -> int {
+    hipdec_batch* b = a->batch.get();
+    hipStream_t s = follow_stream(b, stream);
+    color_tensor_begin();
+    for (int p = 0; p < n; p++)
+      if (int rc = rgb_oriented_record(who, album_source(a, p), oriented ? (orientations ? orientations[p] : 0) : -1, out_widths[p], out_heights[p], filter, outs_dev[p], out_strides[p])) {
+        color_tensor_abort();
+        return rc;
+      }
+    const int rc = color_tensor_launch(a->color_oriented, filter, HIPDEC_TENSOR_U8, s);
+    b->mark_done(s);
+    return rc;
+  });
+}
+
 // hipdec_batch_to_tensor over the canvases: entry.item names a photo, the window lies in its output size; oriented: as batch_to_tensor_impl
 int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations, bool oriented, int n_entries,
                          void* out_dev, size_t out_bytes, void* stream)
@@ -311,7 +344,7 @@ int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const 
                                         (uint8_t*)out_dev + (size_t)e * entry_bytes, oriented ? (orientations ? orientations[e] : 0) : -1);
       if (rc) { color_tensor_abort(); return rc; }
     }
-    const int rc = color_tensor_launch(oriented ? a->color_oriented : a->color_tensor, desc->filter, desc->dtype, s);
+    const int rc = color_tensor_launch(oriented || resample_filter(desc->filter) ? a->color_oriented : a->color_tensor, desc->filter, desc->dtype, s);
     b->mark_done(s);
     return rc;
   });
@@ -332,31 +365,10 @@ int hipdec_album_to_tensor_oriented(hipdec_album* a, const hipdec_tensor_desc* d
   return album_to_tensor_impl(a, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream);
 }
 
-// hipdec_batch_to_rgb_scaled_oriented_all over the canvases
 int hipdec_album_to_rgb_scaled_oriented_all(hipdec_album* a, int out_chroma, const int* orientations, const int* out_widths, const int* out_heights, int filter,
                                             void* const* outs_dev, const size_t* out_strides, void* stream)
 {
-  const char* who = "album_to_rgb_scaled_oriented_all";
-  if (!a || !out_widths || !out_heights || !outs_dev || !out_strides) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
-  const int n = (int)a->photos.size();
-  for (int p = 0; p < n; p++) {
-    if (!outs_dev[p]) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: photo %d: no output", who, p);
-    if (int rc = rgb_oriented_check_item(who, p, out_chroma, orientations ? orientations[p] : 0, out_widths[p], out_heights[p], filter, out_strides[p])) return rc;
-  }
-  DeviceScope scope(a->device);
-  return guarded(who, [&]() -> int {
-    hipdec_batch* b = a->batch.get();
-    hipStream_t s = follow_stream(b, stream);
-    color_tensor_begin();
-    for (int p = 0; p < n; p++)
-      if (int rc = rgb_oriented_record(who, album_source(a, p), orientations ? orientations[p] : 0, out_widths[p], out_heights[p], filter, outs_dev[p], out_strides[p])) {
-        color_tensor_abort();
-        return rc;
-      }
-    const int rc = color_tensor_launch(a->color_oriented, filter, HIPDEC_TENSOR_U8, s);
-    b->mark_done(s);
-    return rc;
-  });
+  return album_rgb_entries("album_to_rgb_scaled_oriented_all", a, out_chroma, orientations, true, out_widths, out_heights, filter, outs_dev, out_strides, stream);
 }
 
 void hipdec_album_stats(uint64_t* albums, uint64_t* photos, uint64_t* paste_launches)

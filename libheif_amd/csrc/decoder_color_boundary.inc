@@ -787,6 +787,7 @@ int hipdec_image_to_tensor(const hipdec_color_image* in, const hipdec_nclx* nclx
     for (int e = 0; entries && e < n_entries; e++)
       if (int rc = tensor_window("image_to_tensor", entries + e, e, w, h, &left, &top, &rw, &rh)) return rc;
   }
+  if (int rc = tensor_check_resample_depth("image_to_tensor", desc, in->bit_depth)) return rc;
   if (int rc = ensure_init()) return rc;
   return guarded("image_to_tensor", [&]() -> int {
     hipStream_t s = stream_acquire_priority();

@@ -95,7 +95,8 @@ int scale_planes_launch(PlaneScaleParams* jobs, int n, int bytes_per_sample, int
 // blocks out as ONE launch.  The window is in luma samples of the planes handed in; sH / sV are their chroma shifts (box presents them as 4:4:4).
 // Oriented output: `oriented` sends the block to the k_oriented_* kernels - ow x oh is then the PRE-orientation size, `code` the hipdec_orientation with the
 // entry's flip folded in, `pitch` the elements from one displayed row to the next.
-struct TensorRequest { int ow, oh, sH, sV, left, top, rw, rh, flip, nhwc; float scale[3], bias[3]; int oriented, code; size_t pitch; };
+struct TensorRequest { int ow, oh, sH, sV, left, top, rw, rh, flip, nhwc; float scale[3], bias[3]; int oriented, code; size_t pitch;
+                       int resample; /* HIPDEC_SCALE_BILINEAR / _BICUBIC: the block is recorded for k_resample, code and pitch set for every entry (0: no) */ };
 void color_tensor_request(const TensorRequest& r);
 void color_tensor_clear();
 bool color_tensor_pending();

@@ -240,6 +240,22 @@ def pipeline_stats():
 
 
 SCALE_NEAREST, SCALE_BOX = 0, 1   # hipdec_scale_filter
+SCALE_BILINEAR, SCALE_BICUBIC = 16, 17   # ... PIL.Image.resize(BILINEAR / BICUBIC) bit for bit (to_tensor, to_rgb_scaled*; not planes_scaled)
+
+
+def resample_taps(in_size, out_size, filter, out_index):
+    """(first input sample, [coefficients with 22 fractional bits]) of output sample out_index along an axis of in_size -> out_size samples, as the
+    SCALE_BILINEAR / SCALE_BICUBIC kernel receives them (hipdec_resample_taps; host only)"""
+    lib = load_library()
+    lib.hipdec_resample_taps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int32), C.c_int]
+    lib.hipdec_resample_taps.restype = C.c_int
+    first = C.c_int()
+    n = lib.hipdec_resample_taps(in_size, out_size, filter, out_index, C.byref(first), None, 0)
+    if n < 0:
+        raise ValueError("resample_taps(%r, %r, %r, %r)" % (in_size, out_size, filter, out_index))
+    k = (C.c_int32 * max(n, 1))()
+    check(min(lib.hipdec_resample_taps(in_size, out_size, filter, out_index, C.byref(first), k, n), 0))
+    return first.value, list(k[:n])
 
 
 # hipdec_orientation: code = r + 4 * m - the stored picture rotated counter-clockwise by r quarter turns, then mirrored horizontally if m
@@ -530,7 +546,8 @@ class Batch:
         check(self._lib.hipdec_batch_run_rgb(self._h, self._rgb_chroma, self._rgb_ptrs, self._rgb_strides, stream))
 
     def to_rgb_scaled(self, i, width, height, filter=SCALE_BOX, out_chroma=10):
-        """item i as interleaved rows of width x height pixels straight from its decoded planes (one fused scale + colour kernel)"""
+        """item i as interleaved rows of width x height pixels straight from its decoded planes (one fused scale + colour kernel).  filter: SCALE_NEAREST,
+        SCALE_BOX, or - out_chroma 10 only - SCALE_BILINEAR / SCALE_BICUBIC (PIL.Image.resize of to_rgb(i, 10), bit for bit)"""
         bpp = {10: 3, 11: 4, 12: 6, 14: 6}[out_chroma]
         buf = DeviceBuffer(max(1, width) * max(1, height) * bpp)
         check(self._lib.hipdec_batch_to_rgb_scaled(self._h, i, out_chroma, width, height, filter, buf.ptr, width * bpp, None))
@@ -552,7 +569,8 @@ class Batch:
 
     def to_rgb_scaled_all(self, filter=SCALE_BOX, stream=None, orientations=None):
         """asynchronous: every item scaled to its pre-allocated size, ONE launch.  orientations: one hipdec_orientation code per item - the sizes given to
-        alloc_rgb_scaled() are then sizes of the DISPLAYED pictures (RGB24 only)"""
+        alloc_rgb_scaled() are then sizes of the DISPLAYED pictures (RGB24 only).  filter: SCALE_NEAREST, SCALE_BOX, or - RGB24 only - SCALE_BILINEAR /
+        SCALE_BICUBIC (PIL.Image.resize bit for bit)"""
         if orientations is not None:
             check(self._lib.hipdec_batch_to_rgb_scaled_oriented_all(self._h, self._srgb_chroma, _orientation_array(orientations, self.n), self._srgb_w, self._srgb_h,
                                                                     filter, self._srgb_ptrs, self._srgb_strides, stream))
@@ -576,7 +594,9 @@ class Batch:
         CUDA / HIP torch.Tensor of the tensor's shape and dtype (its data_ptr() is written; the stream defaults to torch's current stream - when that
         is torch's legacy default stream the call waits on the host instead), or None: a torch tensor where torch sees a GPU, a DeviceBuffer elsewhere.
         orientations: one hipdec_orientation code per entry (hipdec_batch_to_tensor_oriented): `size` is then the size of the DISPLAYED sample, windows
-        stay in the stored picture (stored_window() maps a displayed window), and an entry's flip mirrors the displayed sample."""
+        stay in the stored picture (stored_window() maps a displayed window), and an entry's flip mirrors the displayed sample.
+        filter: SCALE_NEAREST, SCALE_BOX, or SCALE_BILINEAR / SCALE_BICUBIC: V = PIL.Image.resize of the window of the 8-bit RGB picture (to_rgb(i, 10)),
+        bit for bit - what torchvision's Resize / RandomResizedCrop compute on PIL images; from sources above 8 bits with dtype "uint8" only."""
         if orientations is not None:
             return _to_tensor(self, self._lib.hipdec_batch_to_tensor_oriented, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations)
         return _to_tensor(self, self._lib.hipdec_batch_to_tensor, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
