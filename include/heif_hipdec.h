@@ -622,6 +622,53 @@ HIPDEC_API int hipdec_album_to_rgb_scaled_oriented_all(hipdec_album* a, int out_
 /* counters since load: launches of the oriented kernels, the entries they wrote, and how many of those had a quarter turn (odd r) */
 HIPDEC_API void hipdec_oriented_stats(uint64_t* launches, uint64_t* entries, uint64_t* quarter_turn_entries);
 
+/* ---- placed tensor output: letterbox and pad-to-size in the fused kernels ---------------------------------------------------------------------------------
+ * The tensor forms above stretch every window to the one common desc->width x height.  Detection, segmentation, OCR and vision-language loaders keep the
+ * aspect ratio (letterbox to 640 x 640 with grey 114) or pad to a common size (nested tensors with a padding mask, pad-to-max of a bucket).  These calls
+ * write each sample into a rectangle of a larger canvas and fill the rest, in the same launch set: no scaled intermediate, no canvas fill, no copies.
+ *
+ * THE DEFINITION OF THE RESULT.  desc->width x height is the size of the CANVAS of every entry; layout, dtypes and hipdec_tensor_bytes are unchanged.
+ * For entry e with rectangle pl = places[e] (the rectangle of the DISPLAYED sample inside the canvas):
+ *  - Inside the rectangle the canvas holds, element for element, what hipdec_batch_to_tensor_oriented writes for the same entry (item, window, flip),
+ *    orientation code, filter, dtype, scale and bias with desc->width / height replaced by pl.width / pl.height: canvas element (c, pl.y + Y, pl.x + X) is
+ *    element (c, Y, X) of that result.  The pre-orientation size is swapped for an odd number of quarter turns exactly as that call defines it; the flip
+ *    mirrors the sample inside its rectangle, not the canvas.  All filters, codes, dtypes and both layouts are taken; whatever the oriented call refuses
+ *    for a sample of pl.width x pl.height is refused here with the same status.
+ *  - Everywhere else the canvas holds the fill element of its channel:
+ *      HIPDEC_FILL_COMPONENT  value[c] is an integral component value V in the range a pixel can have (0 .. 255; 0 .. 2^bits - 1 for a float dtype from a
+ *                             source above 8 bits).  The element is what a pixel of that value gets: (float)V * scale[c] + bias[c], narrowed as pixels
+ *                             are; V itself for HIPDEC_TENSOR_U8.  "Pad with 114, then normalise" is bit-identical to normalising a padded picture.
+ *      HIPDEC_FILL_ELEMENT    value[c] is the element itself: stored as fp32, or narrowed to F16 / BF16 with the round-to-nearest-even statement of the
+ *                             pixels (subnormals included); for HIPDEC_TENSOR_U8 an integer in 0 .. 255.  Zero-after-normalisation padding.
+ *    fill NULL: component 0 in every channel.
+ *  - mask_dev (may be NULL): a dense n_entries x height x width uint8 tensor, 1 where the canvas element is margin, 0 inside the rectangle.  Every byte of
+ *    it is written.
+ * places NULL: every rectangle is the whole canvas; with mask_dev NULL as well the call IS hipdec_batch_to_tensor_oriented, byte for byte and launch for
+ * launch.  orientations NULL: all 0.  entries NULL: as in the sibling calls.
+ * Refused before a device is touched, HIPDEC_ERR_INVALID_ARGUMENT: a rectangle with a non-positive side or one that leaves the canvas (the entry is named),
+ * a non-finite fill, a component fill that is not integral or out of range, an unknown domain, a non-zero `reserved`, a U8 element fill that is not an
+ * integer in 0 .. 255, out_bytes below hipdec_tensor_bytes, a code outside 0 .. 7.  Canvas width * height above max_image_size_pixels: HIPDEC_ERR_LIMIT.
+ * (A component fill above 255 with a float dtype is held against the bit depth of the entries' sources: refused before anything is launched.)
+ * Launches: the picture part through the oriented / resampling kernels with the canvas row as pitch and the canvas plane as plane stride; the margins of ALL
+ * entries - and the mask - in ONE launch of k_canvas_margin (65535 entries per launch).  The two write disjoint elements, every canvas element exactly once.
+ * A call without margins and without a mask launches no margin kernel.  Device time: slot [5] of hipdec_batch_slot_kernel_timing_us, both launches. */
+typedef struct hipdec_tensor_place { int x, y, width, height; } hipdec_tensor_place;
+typedef enum hipdec_fill_domain { HIPDEC_FILL_COMPONENT = 0, HIPDEC_FILL_ELEMENT = 1 } hipdec_fill_domain;
+typedef struct hipdec_tensor_fill { float value[3]; int domain; int reserved; } hipdec_tensor_fill;
+HIPDEC_API int hipdec_batch_to_tensor_placed(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                             const hipdec_tensor_place* places, const hipdec_tensor_fill* fill, void* mask_dev, int n_entries, void* out_dev,
+                                             size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_album_to_tensor_placed(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                             const hipdec_tensor_place* places, const hipdec_tensor_fill* fill, void* mask_dev, int n_entries, void* out_dev,
+                                             size_t out_bytes, void* stream);
+/* Host only, 64-bit integer arithmetic.  The rectangle of a displayed sample of src_width x src_height fitted into the canvas with its aspect ratio kept:
+ * with !upscale a source that fits both ways keeps its size; otherwise, if src_width * canvas_height >= src_height * canvas_width, width = canvas_width and
+ * height = max(1, (src_height * canvas_width + src_width / 2) / src_width), else the mirror-image rule with height = canvas_height.  anchor 0: top-left;
+ * 1: centred, x = (canvas_width - width) / 2 rounding down, the same for y.  A non-positive size or an unknown anchor: -1, hipdec_last_error says why. */
+HIPDEC_API int hipdec_letterbox_place(int src_width, int src_height, int canvas_width, int canvas_height, int upscale, int anchor, hipdec_tensor_place* out);
+/* counters since load: placed calls, their entries, launches of the margin kernel */
+HIPDEC_API void hipdec_placed_stats(uint64_t* calls, uint64_t* entries, uint64_t* margin_launches);
+
 /* counters since load: images through hipdec_image_transform, grid canvases handed out by hipdec_grid_read_plane_tracked (hipdec_image_scale counts in
  * hipdec_image_scale_stats) */
 HIPDEC_API void hipdec_image_ops_stats(uint64_t* transforms, uint64_t* grid_canvases);

@@ -592,10 +592,12 @@ __global__ __launch_bounds__(256) void k_tensor_nearest(const TensorParams* __re
 // An entry's flip is folded into the code by the host, the code is wave-uniform, and entries of all eight codes share a launch.
 struct OrientedParams {
   TensorParams t;     // t.ow x t.oh: the size of P; t.flip is 0; t.c.o0: the entry's first element
-  int code;           // hipdec_orientation, 0 .. 7
-  int rb;             // box: rows of P a workgroup takes at a time - the kernel's RB for a quarter turn, fewer (more workgroups) where rows stay rows
-  uint64_t pitch;     // elements from one DISPLAYED row to the next (dense for tensors, out_stride for RGB24)
+  uint16_t code;      // hipdec_orientation, 0 .. 7
+  uint16_t rb;        // box: rows of P a workgroup takes at a time - the kernel's RB for a quarter turn, fewer (more workgroups) where rows stay rows
+  int plane_rows;     // NCHW: a channel plane is plane_rows * pitch elements - the displayed rows for a dense sample, the canvas' rows for a placed one
+  uint64_t pitch;     // elements from one DISPLAYED row to the next (dense for tensors, out_stride for RGB24, the canvas row for placed tensors)
 };
+static_assert(sizeof(OrientedParams) == sizeof(TensorParams) + 16, "the block keeps the size it had before the plane stride: code and rb share a word with it");
 
 // store_tensor4's shape with a row pitch: a 4-pixel group of displayed row `row` (of dh rows of dw pixels) whose pixels are columns x0 .. x0 + npx - 1 before
 // the reversal `rev` (column x goes to dw - 1 - x).  Vector stores where the group is whole and its destination aligned, element stores otherwise.
@@ -614,7 +616,7 @@ __device__ __forceinline__ void store_oriented4(const OrientedParams& op, int dw
     v[1][i] = tensor_elem<DT>(rev ? G[3 - i] : G[i], tp.scale[1], tp.bias[1]);
     v[2][i] = tensor_elem<DT>(rev ? B[3 - i] : B[i], tp.scale[2], tp.bias[2]);
   }
-  const size_t dw = (size_t)dw_, pitch = (size_t)op.pitch, plane = (size_t)dh_ * pitch;
+  const size_t dw = (size_t)dw_, pitch = (size_t)op.pitch, plane = (size_t)op.plane_rows * pitch;
   const size_t xs = rev ? dw - (size_t)npx - (size_t)x0 : (size_t)x0;   // the group's first column in memory
   HIPDEC_GLOBAL E* o = (HIPDEC_GLOBAL E*)tp.c.o0 + (size_t)row * pitch;
   if (tp.nhwc) {
@@ -709,7 +711,7 @@ __global__ __launch_bounds__(256) void k_oriented_box(const OrientedParams* __re
   const int cw = ((tp.left + tp.rw - 1) >> tp.sH) - cl + 1, ch = ((tp.top + tp.rh - 1) >> tp.sV) - ct + 1;
   const int fcw = (p.w + (1 << tp.sH) - 1) >> tp.sH;
   const BoxPlane pl[3] = {{p.y, p.ys, tp.rw, tp.rh, p.w, tp.left, tp.top}, {p.cb, p.cbs, cw, ch, fcw, cl, ct}, {p.cr, p.crs, cw, ch, fcw, cl, ct}};
-  const int rb = max(1, min(op.rb, RB));                  // (the stage has RB rows whatever the block says)
+  const int rb = max(1, min((int)op.rb, RB));                  // (the stage has RB rows whatever the block says)
   for (int yb = blockIdx.y * rb; yb < tp.oh; yb += gridDim.y * rb) {
     const int nrows = min(rb, tp.oh - yb);
     for (int r = 0; r < nrows; r++) {
@@ -754,7 +756,7 @@ __global__ __launch_bounds__(256) void k_oriented_box(const OrientedParams* __re
       }
     } else {
       const uint32_t total = n * (uint32_t)nox;
-      const size_t plane = (size_t)tp.ow * pitch;          // the displayed picture has t.ow rows
+      const size_t plane = (size_t)op.plane_rows * pitch;   // (the displayed picture's t.ow rows, or the canvas')
       for (uint32_t idx = (uint32_t)tid; idx < total; idx += 256u) {
         const uint32_t c = idx / n, j = idx - c * n;
         const int x = oxA + (int)c;
@@ -817,6 +819,104 @@ __global__ __launch_bounds__(256) void k_oriented_nearest(const OrientedParams* 
     }
     tensor_convert4<Pix>(p, Y, CB, CR, R, G, B);
     store_oriented4<DT>(op, dw, dh, 0, X0, Yd, npx, R, G, B);
+  }
+}
+
+// ---- placed tensor output (include/heif_hipdec.h hipdec_batch_to_tensor_placed): the oriented / resampling kernels write an entry's sample into its
+// rectangle of the canvas - o0 the rectangle's first element, pitch the canvas row, plane the canvas plane - and k_canvas_margin writes everything else:
+// the fill element of each channel outside the rectangle and, where asked for, the whole mask (1 outside, 0 inside).  ONE launch for all entries of a call,
+// blockIdx.z the entry.  Store-only, no LDS.
+// Shape: an entry's canvas is one run of 3 * W * H elements, cut into the 16-byte blocks of MEMORY it touches (the first and last may be partial); a lane owns
+// one block at a time, finds (channel, row, column) of its first element with two divisions (32-bit while the entry has fewer than 2^31 elements) and walks
+// its 16 / 8 / 4 elements from there with compares only.  A block that is margin throughout - the rows above and below the rectangle, and, since the run
+// right of the rectangle in one row continues as the run left of it in the next, most of what lies beside it - goes out as ONE 16-byte store; a block the
+// rectangle's edge or the entry's end cuts goes out element by element, margin elements only; a block inside the rectangle is not touched.  Consecutive lanes
+// own consecutive blocks, so a wave's vector stores cover 1 KiB of consecutive memory.
+// Bytes: the margin's elements once (plus W * H mask bytes), nothing read but the parameter block.
+template <int DT>
+__device__ __forceinline__ uint32_t canvas_fill_elem(const hipdec::CanvasMargin& m, float value, float scale, float bias)
+{
+  if (m.domain == HIPDEC_FILL_COMPONENT) return tensor_elem<DT>((int)value, scale, bias);   // what a pixel of that component value gets
+  if (DT == TD_U8) return (uint32_t)(int)value;
+  if (DT == TD_F32) return __builtin_bit_cast(uint32_t, value);
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(HIPDEC_HOST_EMU)
+  if (DT == TD_F16) return __builtin_bit_cast(uint16_t, (_Float16)value);
+  return __builtin_bit_cast(uint16_t, (__bf16)value);
+#else
+  return DT == TD_F16 ? f32_to_f16_rne(__builtin_bit_cast(uint32_t, value)) : f32_to_bf16_rne(__builtin_bit_cast(uint32_t, value));
+#endif
+}
+
+// MASK: `base` is the entry's W * H mask bytes - one plane, 1 outside the rectangle and 0 inside, every byte written
+template <typename E, bool MASK, typename Idx>
+__device__ __forceinline__ void canvas_margin_blocks(const hipdec::CanvasMargin& m, HIPDEC_GLOBAL E* base, uint32_t f0, uint32_t f1, uint32_t f2)
+{
+  constexpr int N = 16 / (int)sizeof(E), PER = 4 / (int)sizeof(E);
+  constexpr uint32_t kAll = N == 16 ? 0xffffu : (N == 8 ? 0xffu : 0xfu);
+  const bool nhwc = !MASK && m.nhwc;
+  const int W = m.W, H = m.H, x0 = m.x, x1 = m.x + m.w, y0 = m.y, y1 = m.y + m.h;
+  const Idx px = (Idx)W * (Idx)H, total = MASK ? px : px * 3;
+  const uintptr_t addr = (uintptr_t)base;
+  const bool aligned = (addr & (sizeof(E) - 1)) == 0;                 // (an output that is not even element-aligned takes element stores throughout)
+  const uint32_t lead = (uint32_t)((addr & 15) / sizeof(E));          // elements between the 16-byte boundary below the entry and its first element
+  HIPDEC_GLOBAL E* origin = base - lead;
+  const Idx nblocks = (total + lead + (Idx)(N - 1)) / (Idx)N;
+  for (Idx j = (Idx)blockIdx.x * 256u + threadIdx.x; j < nblocks; j += (Idx)gridDim.x * 256u) {
+    const Idx v0 = j * (Idx)N;
+    const uint32_t skip = v0 < (Idx)lead ? lead - (uint32_t)v0 : 0u;  // (block 0 only: its elements in front of the entry)
+    Idx e = v0 + skip - lead;
+    int c, y, x;
+    if (nhwc) {
+      const Idx pix = e / 3u, row = pix / (Idx)W;
+      c = (int)(e - pix * 3u); y = (int)row; x = (int)(pix - row * (Idx)W);
+    } else {
+      const Idx pl = e / px, r = e - pl * px, row = r / (Idx)W;
+      c = (int)pl; y = (int)row; x = (int)(r - row * (Idx)W);
+    }
+    uint32_t w[4] = {0u, 0u, 0u, 0u}, bits = 0u;
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+      if ((uint32_t)i >= skip && e < total) {
+        const bool in = y >= y0 && y < y1 && x >= x0 && x < x1;
+        const uint32_t el = MASK ? (in ? 0u : 1u) : (c == 0 ? f0 : (c == 1 ? f1 : f2));
+        w[i / PER] |= el << (8u * (uint32_t)sizeof(E) * (uint32_t)(i % PER));
+        if (MASK || !in) bits |= 1u << i;
+        e++;
+        if (nhwc) {
+          if (++c == 3) { c = 0; if (++x == W) { x = 0; y++; } }
+        } else if (++x == W) {
+          x = 0;
+          if (++y == H) { y = 0; c++; }
+        }
+      }
+    }
+    HIPDEC_GLOBAL E* d = origin + v0;
+    if (bits == kAll && aligned) {
+      uint4 v; v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+      *(HIPDEC_GLOBAL uint4*)d = v;
+    } else if (bits) {
+#pragma unroll
+      for (int i = 0; i < N; i++)
+        if ((bits >> i) & 1u) d[i] = (E)(w[i / PER] >> (8u * (uint32_t)sizeof(E) * (uint32_t)(i % PER)));
+    }
+  }
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void k_canvas_margin(const hipdec::CanvasMargin* __restrict__ ms)
+{
+  typedef typename TensorElem<DT>::T E;
+  const hipdec::CanvasMargin m = ms[blockIdx.z];   // wave-uniform: scalar loads into SGPRs
+  const bool small = (uint64_t)m.W * (uint64_t)m.H * 3ull < (1ull << 31);
+  if (m.margin) {
+    const uint32_t f0 = canvas_fill_elem<DT>(m, m.value[0], m.scale[0], m.bias[0]), f1 = canvas_fill_elem<DT>(m, m.value[1], m.scale[1], m.bias[1]),
+                   f2 = canvas_fill_elem<DT>(m, m.value[2], m.scale[2], m.bias[2]);
+    if (small) canvas_margin_blocks<E, false, uint32_t>(m, (HIPDEC_GLOBAL E*)m.o0, f0, f1, f2);
+    else canvas_margin_blocks<E, false, uint64_t>(m, (HIPDEC_GLOBAL E*)m.o0, f0, f1, f2);
+  }
+  if (m.mask) {
+    if (small) canvas_margin_blocks<uint8_t, true, uint32_t>(m, (HIPDEC_GLOBAL uint8_t*)m.mask, 0u, 0u, 0u);
+    else canvas_margin_blocks<uint8_t, true, uint64_t>(m, (HIPDEC_GLOBAL uint8_t*)m.mask, 0u, 0u, 0u);
   }
 }
 
@@ -1345,7 +1445,7 @@ thread_local std::vector<CapturedScaled> t_captured_scaled;
 // the recorded blocks go out as one launch (hipdec::color_tensor_launch).  Taken and checked like a scale request.
 struct TensorReq { bool on = false; hipdec::TensorRequest r; };
 thread_local TensorReq t_tensor;
-struct CapturedTensor { TensorParams p; int wide; int oriented, code; uint64_t pitch; int resample; };   // oriented: for the k_oriented_* kernels, with a code and a row pitch; resample: the filter, for k_resample (code and pitch are set for every entry)
+struct CapturedTensor { TensorParams p; int wide; int oriented, code; uint64_t pitch; int plane_rows; int resample; };   // oriented: for the k_oriented_* kernels, with a code, a row pitch and the rows of a channel plane; resample: the filter, for k_resample (code and pitch are set for every entry)
 thread_local std::vector<CapturedTensor> t_captured_tensor;
 
 // ---- the coefficient tables of HIPDEC_SCALE_BILINEAR / _BICUBIC: Pillow's precompute_coeffs + normalize_coeffs_8bpc (src/libImaging/Resample.c), statement
@@ -1498,7 +1598,7 @@ int record_tensor(const ColorParams& p)
     tp.flip = 0;      // folded into the code
   }
   t_tensor.on = false;   // taken
-  t_captured_tensor.push_back(CapturedTensor{tp, sizeof(Pix) == 2, r.oriented ? 1 : 0, r.code, (uint64_t)r.pitch, r.resample});
+  t_captured_tensor.push_back(CapturedTensor{tp, sizeof(Pix) == 2, r.oriented ? 1 : 0, r.code, (uint64_t)r.pitch, r.plane_rows, r.resample});
   return 0;
   }
 }
@@ -1765,7 +1865,7 @@ int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
   for (size_t i = 0; i < caps.size(); i++) {
     OrientedParams op;
     memset(&op, 0, sizeof(op));
-    op.t = caps[i].p; op.code = caps[i].code; op.rb = block_rows(caps[i]); op.pitch = caps[i].pitch;
+    op.t = caps[i].p; op.code = (uint16_t)caps[i].code; op.rb = (uint16_t)block_rows(caps[i]); op.pitch = caps[i].pitch; op.plane_rows = caps[i].plane_rows;
     memcpy(host.data() + i * sizeof(OrientedParams), &op, sizeof(op));
   }
   if (st.dev_bytes < bytes) {
@@ -1840,7 +1940,7 @@ int resample_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
     const CapturedTensor& c = caps[i];
     ResampleParams rp;
     memset(&rp, 0, sizeof(rp));
-    rp.o.t = c.p; rp.o.code = c.code; rp.o.rb = kResTR; rp.o.pitch = c.pitch;
+    rp.o.t = c.p; rp.o.code = (uint16_t)c.code; rp.o.rb = (uint16_t)kResTR; rp.o.pitch = c.pitch; rp.o.plane_rows = c.plane_rows;
     rp.xt = tables_dev + where[std::make_pair(c.p.rw, c.p.ow)]; rp.xstride = resample_axis_of(c.p.rw, c.p.ow, filter).stride;
     rp.yt = tables_dev + where[std::make_pair(c.p.rh, c.p.oh)]; rp.ystride = resample_axis_of(c.p.rh, c.p.oh, filter).stride;
     memcpy(host.data() + i * sizeof(ResampleParams), &rp, sizeof(rp));
@@ -1909,6 +2009,56 @@ int color_tensor_launch(ColorBatchState& st, int filter, int dtype, hipStream_t 
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "tensor kernel launch: %s", hipGetErrorString(e));
+  }
+  return 0;
+}
+
+// ---- placed tensor output: the margins (and masks) of all entries of a call as ONE launch of k_canvas_margin; the blocks are kept and re-uploaded only
+// when they change, as the picture blocks are
+std::atomic<uint64_t> g_placed_calls{0}, g_placed_entries{0}, g_placed_margin_launches{0};
+void placed_note_call(uint64_t entries) { g_placed_calls++; g_placed_entries += entries; }
+
+int canvas_margin_launch(ColorBatchState& st, const CanvasMargin* blocks, int n, int dtype, hipStream_t s)
+{
+  bool any = false;
+  uint64_t max_elems = 0;
+  for (int i = 0; i < n; i++) {
+    if (!blocks[i].margin && !blocks[i].mask) continue;
+    any = true;
+    const uint64_t elems = 3ull * (uint64_t)blocks[i].W * (uint64_t)blocks[i].H;
+    max_elems = elems > max_elems ? elems : max_elems;
+  }
+  if (!any) return 0;
+  const size_t bytes = (size_t)n * sizeof(CanvasMargin);
+  std::vector<uint8_t> host(bytes);
+  memcpy(host.data(), blocks, bytes);
+  if (st.dev_bytes < bytes) {
+    if (st.dev) arena_release(st.dev, st.dev_bytes);
+    st.dev = nullptr; st.dev_bytes = 0; st.host.clear();
+    HIPDEC_CHECK_HIP(arena_acquire(&st.dev, bytes, &st.dev_bytes));
+  }
+  if (st.host != host) {   // steady state (same rectangles, fill and output): nothing to upload
+    st.prev.swap(st.host);
+    st.host.swap(host);
+    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), bytes, hipMemcpyHostToDevice, s));
+  }
+  // a lane owns one 16-byte block at a time: an entry touches at most elements / (elements per block) + 2 of them (the kernel's loop strides over what the
+  // grid leaves; a mask has fewer)
+  const uint64_t per = dtype == TD_U8 ? 16 : (dtype == TD_F32 ? 4 : 8);
+  const uint64_t gx = (max_elems / per + 2 + 255) / 256;
+  for (int first = 0; first < n; first += 65535) {
+    const CanvasMargin* dev = (const CanvasMargin*)st.dev + first;
+    dim3 block(256), grid((unsigned)(gx < 65536 ? gx : 65536), 1, (unsigned)(n - first < 65535 ? n - first : 65535));
+    switch (dtype) {
+      case TD_U8: hipLaunchKernelGGL((k_canvas_margin<TD_U8>), grid, block, 0, s, dev); break;
+      case TD_F32: hipLaunchKernelGGL((k_canvas_margin<TD_F32>), grid, block, 0, s, dev); break;
+      case TD_F16: hipLaunchKernelGGL((k_canvas_margin<TD_F16>), grid, block, 0, s, dev); break;
+      case TD_BF16: hipLaunchKernelGGL((k_canvas_margin<TD_BF16>), grid, block, 0, s, dev); break;
+      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "placed output: unknown dtype %d", dtype);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "margin kernel launch: %s", hipGetErrorString(e));
+    g_placed_margin_launches++;
   }
   return 0;
 }
@@ -1988,6 +2138,13 @@ void hipdec_oriented_stats(uint64_t* launches, uint64_t* entries, uint64_t* quar
   if (launches) *launches = g_oriented_launches.load();
   if (entries) *entries = g_oriented_entries.load();
   if (quarter_turn_entries) *quarter_turn_entries = g_oriented_quarter.load();
+}
+
+void hipdec_placed_stats(uint64_t* calls, uint64_t* entries, uint64_t* margin_launches)
+{
+  if (calls) *calls = g_placed_calls.load();
+  if (entries) *entries = g_placed_entries.load();
+  if (margin_launches) *margin_launches = g_placed_margin_launches.load();
 }
 
 void hipdec_color_coefficients(const hipdec_nclx* nclx, float out[4]) { if (out) coefficients(nclx, out); }   // (nclx NULL: the reference's defaults)

@@ -64,6 +64,7 @@ struct hipdec_batch : BatchLayout {
   ColorBatchState color_scaled; // ... and of hipdec_batch_to_rgb_scaled_all (its own, so that a host alternating the two uploads nothing in the steady state)
   ColorBatchState color_tensor; // ... and of hipdec_batch_to_tensor
   ColorBatchState color_oriented; // ... and of the oriented forms (hipdec_batch_to_tensor_oriented, hipdec_batch_to_rgb_scaled_oriented_all)
+  ColorBatchState color_margin;   // ... and the margin blocks of hipdec_batch_to_tensor_placed
   uint64_t max_pixels = 0;      // the limit given at creation (0: none): scaled outputs are held against it as well
   // decoder path (plugin): the output planes of every item staged in pinned host memory by ONE set of asynchronous copies behind the
   // kernels, so that N decoder instances sharing the batch do not queue N x 3 pageable device-to-host copies (stage_planes_to_host)
@@ -126,6 +127,7 @@ struct hipdec_batch : BatchLayout {
     color_batch_state_free(color_scaled);
     color_batch_state_free(color_tensor);
     color_batch_state_free(color_oriented);
+    color_batch_state_free(color_margin);
     if (arena) arena_release(arena, arena_capacity);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : chain_events) if (e) (void)hipEventDestroy(e);
@@ -823,7 +825,7 @@ int tensor_window(const char* who, const hipdec_tensor_entry* e, int idx, int w,
 // presents the planes as the 4:4:4 image they are scaled to.  The entry point records the block (color.hip); elem0: the entry's first element.
 int tensor_record_entry(const char* who, const uint8_t* y, size_t ys, const uint8_t* cb, size_t cbs, const uint8_t* cr, size_t crs, int w, int h, int bits, int cf,
                         const hipdec_nclx* nclx, const hipdec_nclx* nclx_after_sdr, const hipdec_tensor_desc* d, int left, int top, int rw, int rh, int flip, void* elem0,
-                        int orientation = -1, size_t pitch = 0)
+                        int orientation = -1, size_t pitch = 0, int plane_rows = 0)
 {
   if (int rc = tensor_check_resample_depth(who, d, bits)) return rc;
   TensorRequest rq;
@@ -842,6 +844,7 @@ int tensor_record_entry(const char* who, const uint8_t* y, size_t ys, const uint
     rq.pitch = pitch ? pitch : (size_t)d->width * (d->layout == HIPDEC_TENSOR_NHWC ? 3 : 1);
     flip = 0;
   }
+  rq.plane_rows = plane_rows ? plane_rows : d->height;   // (d->height: the displayed rows)
   rq.sH = cf == 1 || cf == 2 ? 1 : 0; rq.sV = cf == 1 ? 1 : 0;
   rq.left = left; rq.top = top; rq.rw = rw; rq.rh = rh; rq.flip = flip; rq.nhwc = d->layout == HIPDEC_TENSOR_NHWC;
   for (int c = 0; c < 3; c++) { rq.scale[c] = d->scale[c]; rq.bias[c] = d->bias[c]; }
@@ -898,18 +901,84 @@ int check_orientations(const char* who, const char* what, const int* orientation
   return 0;
 }
 
+// ---- placed tensor output (hipdec_batch_to_tensor_placed / hipdec_album_to_tensor_placed): what the two forms share
+struct PlacedArgs { const hipdec_tensor_place* places; const hipdec_tensor_fill* fill; void* mask; };
+
+// what the arguments alone decide (the description has passed tensor_check_desc)
+int placed_check(const char* who, const hipdec_tensor_desc* d, const PlacedArgs& pa, int n_entries)
+{
+  for (int e = 0; pa.places && e < n_entries; e++) {
+    const hipdec_tensor_place& pl = pa.places[e];
+    if (pl.width < 1 || pl.height < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: rectangle size %d x %d", who, e, pl.width, pl.height);
+    if (pl.x < 0 || pl.y < 0 || (int64_t)pl.x + pl.width > d->width || (int64_t)pl.y + pl.height > d->height)
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: rectangle %d x %d at (%d, %d) leaves the canvas of %d x %d", who, e, pl.width, pl.height, pl.x, pl.y,
+                       d->width, d->height);
+  }
+  if (!pa.fill) return 0;
+  const hipdec_tensor_fill& f = *pa.fill;
+  if (f.domain != HIPDEC_FILL_COMPONENT && f.domain != HIPDEC_FILL_ELEMENT) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown fill domain %d", who, f.domain);
+  if (f.reserved) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: fill.reserved is %d, not 0", who, f.reserved);
+  for (int c = 0; c < 3; c++) {
+    const float v = f.value[c];
+    if (!std::isfinite(v)) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: fill of channel %d is not finite", who, c);
+    const bool integral = v == std::floor(v);
+    if (f.domain == HIPDEC_FILL_COMPONENT) {   // (above 255 with a float dtype: held against the sources' bit depth by placed_check_component)
+      if (!integral || v < 0.0f || v > (d->dtype == HIPDEC_TENSOR_U8 ? 255.0f : 65535.0f))
+        return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: component fill %g of channel %d is not an integer a pixel can have", who, (double)v, c);
+    } else if (d->dtype == HIPDEC_TENSOR_U8 && (!integral || v < 0.0f || v > 255.0f)) {
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: element fill %g of channel %d is not an integer in 0 .. 255", who, (double)v, c);
+    }
+  }
+  return 0;
+}
+
+// a component fill against the range of the component values entry e gets: 0 .. 255, or 0 .. 2^bits - 1 for a float dtype from a source above 8 bits
+int placed_check_component(const char* who, const hipdec_tensor_desc* d, const PlacedArgs& pa, int e, int bits)
+{
+  if (!pa.fill || pa.fill->domain != HIPDEC_FILL_COMPONENT) return 0;
+  const float top = (float)((1 << (d->dtype != HIPDEC_TENSOR_U8 && bits > 8 ? bits : 8)) - 1);
+  for (int c = 0; c < 3; c++)
+    if (pa.fill->value[c] > top)
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: component fill %g of channel %d is above %g, the largest value of its source", who, e,
+                       (double)pa.fill->value[c], c, (double)top);
+  return 0;
+}
+
+// entry e of a placed call: *sample is the description of the sample in its rectangle, *elem0 the rectangle's first element, *m the entry's margin block
+void placed_entry(const hipdec_tensor_desc* d, const PlacedArgs& pa, int e, void* out_dev, size_t entry_bytes, hipdec_tensor_desc* sample, void** elem0, CanvasMargin* m)
+{
+  const hipdec_tensor_place whole{0, 0, d->width, d->height};
+  const hipdec_tensor_place& pl = pa.places ? pa.places[e] : whole;
+  const size_t k = d->layout == HIPDEC_TENSOR_NHWC ? 3 : 1;
+  uint8_t* canvas = (uint8_t*)out_dev + (size_t)e * entry_bytes;
+  *sample = *d;
+  sample->width = pl.width; sample->height = pl.height;
+  *elem0 = canvas + ((size_t)pl.y * (size_t)d->width + (size_t)pl.x) * k * tensor_elem_bytes(d->dtype);
+  memset(m, 0, sizeof(*m));
+  m->o0 = canvas;
+  m->mask = pa.mask ? (uint8_t*)pa.mask + (size_t)e * (size_t)d->width * (size_t)d->height : nullptr;
+  m->W = d->width; m->H = d->height; m->x = pl.x; m->y = pl.y; m->w = pl.width; m->h = pl.height;
+  m->nhwc = d->layout == HIPDEC_TENSOR_NHWC;
+  m->domain = pa.fill ? pa.fill->domain : HIPDEC_FILL_COMPONENT;
+  m->margin = pl.width != d->width || pl.height != d->height;
+  for (int c = 0; c < 3; c++) { m->value[c] = pa.fill ? pa.fill->value[c] : 0.0f; m->scale[c] = d->scale[c]; m->bias[c] = d->bias[c]; }
+}
+
 // hipdec_batch_to_tensor, and - oriented - hipdec_batch_to_tensor_oriented: the same checks, windows and planner rules; the oriented form records its blocks
 // for the k_oriented_* kernels (color.hip) and keeps them in a parameter array of its own
+// Placed (pa; always oriented): the sample goes into its rectangle of the canvas desc describes, k_canvas_margin (color.hip) writes the rest.
 int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations, bool oriented, int n_entries,
-                         void* out_dev, size_t out_bytes, void* stream)
+                         void* out_dev, size_t out_bytes, void* stream, const PlacedArgs* pa = nullptr)
 {
   if (!b || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: bad arguments");
   size_t bytes = 0;
   if (int rc = tensor_check_desc("to_tensor", desc, n_entries, &bytes)) return rc;
   if (oriented) if (int rc = check_orientations("to_tensor_oriented", "entry", orientations, n_entries)) return rc;
+  if (pa) if (int rc = placed_check("to_tensor_placed", desc, *pa, n_entries)) return rc;
+  if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
+  // (everything above is decided without reading the handle)
   if (!entries && n_entries != (int)b->pics.size())
     return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: %d entries without an entry list, the batch has %d items", n_entries, (int)b->pics.size());
-  if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
   DeviceScope scope(b->device);
   if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: the batch's arena was handed to another batch");
   if (b->max_pixels && (uint64_t)desc->width * (uint64_t)desc->height > b->max_pixels)
@@ -917,6 +986,7 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
   return guarded("to_tensor", [&]() -> int {
     hipStream_t s = follow_stream(b, stream);
     const size_t entry_bytes = bytes / (size_t)n_entries;
+    std::vector<CanvasMargin> margins(pa ? (size_t)n_entries : 0);
     color_tensor_begin();
     for (int e = 0; e < n_entries; e++) {
       const int i = entries ? entries[e].item : e;
@@ -927,10 +997,18 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
       int rc = tensor_window("to_tensor", entries ? entries + e : nullptr, e, P.out_width, P.out_height, &left, &top, &rw, &rh);
       // the decoder reports the VUI colour description exactly as the libde265 plugin would attach it (hipdec_batch_to_rgb hands it on as it is)
       hipdec_nclx nclx{1, I.colour_primaries, I.transfer_characteristics, I.matrix_coeffs, I.full_range_flag};
+      hipdec_tensor_desc sample = *desc;
+      void* elem0 = (uint8_t*)out_dev + (size_t)e * entry_bytes;
+      size_t pitch = 0;
+      int plane_rows = 0;
+      if (pa) {
+        if (!rc) rc = placed_check_component("to_tensor_placed", desc, *pa, e, b->wide ? I.bit_depth_luma : 8);
+        placed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0, &margins[(size_t)e]);
+        pitch = (size_t)desc->width * (desc->layout == HIPDEC_TENSOR_NHWC ? 3 : 1); plane_rows = desc->height;
+      }
       if (!rc) rc = tensor_record_entry("to_tensor", b->arena + P.off_out[0], P.out_stride[0], b->arena + P.off_out[1], P.out_stride[1], b->arena + P.off_out[2], P.out_stride[2],
-                                        P.out_width, P.out_height, b->wide ? I.bit_depth_luma : 8, P.chroma_format_idc, &nclx, &nclx, desc, left, top, rw, rh,
-                                        entries ? entries[e].flip : 0, (uint8_t*)out_dev + (size_t)e * entry_bytes,
-                                        oriented ? (orientations ? orientations[e] : 0) : -1);
+                                        P.out_width, P.out_height, b->wide ? I.bit_depth_luma : 8, P.chroma_format_idc, &nclx, &nclx, &sample, left, top, rw, rh,
+                                        entries ? entries[e].flip : 0, elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows);
       if (rc) { color_tensor_abort(); return rc; }
     }
     const size_t slot = b->runs ? (b->runs - 1) % (b->ev.size() / kEv) : 0;
@@ -938,10 +1016,12 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
     HIPDEC_CHECK_HIP(hipEventRecord(ev[6], s));
     // (resampled entries are not hipdec_batch_tensor_block's blocks: they go with the oriented ones)
     int rc = color_tensor_launch(oriented || resample_filter(desc->filter) ? b->color_oriented : b->color_tensor, desc->filter, desc->dtype, s);
+    if (!rc && pa) rc = canvas_margin_launch(b->color_margin, margins.data(), n_entries, desc->dtype, s);   // (disjoint elements: no order between the two but the stream's)
     HIPDEC_CHECK_HIP(hipEventRecord(ev[7], s));
     if (!rc && b->runs) b->colour_timed[slot] = 1;
     b->mark_done(s);
     if (!rc) { g_tensor_calls++; g_tensor_entries += (uint64_t)n_entries; }
+    if (!rc && pa) placed_note_call((uint64_t)n_entries);
     return rc;
   });
 }
@@ -1037,6 +1117,30 @@ int hipdec_batch_to_tensor_oriented(hipdec_batch* b, const hipdec_tensor_desc* d
                                     void* out_dev, size_t out_bytes, void* stream)
 {
   return batch_to_tensor_impl(b, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream);
+}
+
+int hipdec_batch_to_tensor_placed(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                  const hipdec_tensor_place* places, const hipdec_tensor_fill* fill, void* mask_dev, int n_entries, void* out_dev, size_t out_bytes,
+                                  void* stream)
+{
+  const PlacedArgs pa{places, fill, mask_dev};
+  return batch_to_tensor_impl(b, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, &pa);
+}
+
+int hipdec_letterbox_place(int src_width, int src_height, int canvas_width, int canvas_height, int upscale, int anchor, hipdec_tensor_place* out)
+{
+  if (!out || src_width < 1 || src_height < 1 || canvas_width < 1 || canvas_height < 1)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "letterbox_place: source %d x %d into canvas %d x %d", src_width, src_height, canvas_width, canvas_height), -1;
+  if (anchor != 0 && anchor != 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "letterbox_place: anchor %d (0 top-left, 1 centred)", anchor), -1;
+  const int64_t sw = src_width, sh = src_height, cw = canvas_width, ch = canvas_height;
+  int64_t w, h;
+  if (!upscale && sw <= cw && sh <= ch) { w = sw; h = sh; }
+  else if (sw * ch >= sh * cw) { w = cw; h = (sh * cw + sw / 2) / sw; h = h < 1 ? 1 : h; }
+  else { h = ch; w = (sw * ch + sh / 2) / sh; w = w < 1 ? 1 : w; }
+  out->width = (int)w; out->height = (int)h;
+  out->x = anchor ? (int)((cw - w) / 2) : 0;
+  out->y = anchor ? (int)((ch - h) / 2) : 0;
+  return 0;
 }
 
 int hipdec_batch_to_rgb_scaled_oriented_all(hipdec_batch* b, int out_chroma, const int* orientations, const int* out_widths, const int* out_heights, int filter,

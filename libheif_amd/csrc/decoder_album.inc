@@ -27,6 +27,7 @@ struct hipdec_album {
   hipEvent_t paste_ev[2] = {nullptr, nullptr};   // around the paste launch of the last run
   ColorBatchState color, color_scaled, color_tensor;   // parameter blocks of the three output stages (their own, as hipdec_batch's)
   ColorBatchState color_oriented;                      // ... and of the oriented forms
+  ColorBatchState color_margin;                        // ... and the margin blocks of hipdec_album_to_tensor_placed
   uint64_t max_pixels = 0;
   bool ran = false;
   ~hipdec_album()
@@ -38,6 +39,7 @@ struct hipdec_album {
     color_batch_state_free(color_scaled);
     color_batch_state_free(color_tensor);
     color_batch_state_free(color_oriented);
+    color_batch_state_free(color_margin);
     if (canvas) arena_release(canvas, canvas_capacity);
   }
 };
@@ -311,18 +313,20 @@ int album_rgb_entries(const char* who, hipdec_album* a, int out_chroma, const in
   });
 }
 
-// hipdec_batch_to_tensor over the canvases: entry.item names a photo, the window lies in its output size; oriented: as batch_to_tensor_impl
+// hipdec_batch_to_tensor over the canvases: entry.item names a photo, the window lies in its output size; oriented and placed (pa): as batch_to_tensor_impl
 int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations, bool oriented, int n_entries,
-                         void* out_dev, size_t out_bytes, void* stream)
+                         void* out_dev, size_t out_bytes, void* stream, const PlacedArgs* pa = nullptr)
 {
   if (!a || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_tensor: bad arguments");
   size_t bytes = 0;
   if (int rc = tensor_check_desc("album_to_tensor", desc, n_entries, &bytes)) return rc;
   if (oriented) if (int rc = check_orientations("album_to_tensor_oriented", "entry", orientations, n_entries)) return rc;
+  if (pa) if (int rc = placed_check("album_to_tensor_placed", desc, *pa, n_entries)) return rc;
+  if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
+  // (everything above is decided without reading the handle)
   const int n_photos = (int)a->photos.size();
   if (!entries && n_entries != n_photos)
     return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_tensor: %d entries without an entry list, the album has %d photos", n_entries, n_photos);
-  if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
   DeviceScope scope(a->device);
   if (a->max_pixels && (uint64_t)desc->width * (uint64_t)desc->height > a->max_pixels)
     return set_error(HIPDEC_ERR_LIMIT, "album_to_tensor: output of %d x %d pixels exceeds max_image_size_pixels", desc->width, desc->height);
@@ -330,6 +334,7 @@ int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const 
     hipdec_batch* b = a->batch.get();
     hipStream_t s = follow_stream(b, stream);
     const size_t entry_bytes = bytes / (size_t)n_entries;
+    std::vector<CanvasMargin> margins(pa ? (size_t)n_entries : 0);
     color_tensor_begin();
     for (int e = 0; e < n_entries; e++) {
       const int p = entries ? entries[e].item : e;
@@ -339,13 +344,24 @@ int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const 
       int left, top, rw, rh;
       int rc = tensor_window("album_to_tensor", entries ? entries + e : nullptr, e, S.width, S.height, &left, &top, &rw, &rh);
       hipdec_nclx nclx{1, I.colour_primaries, I.transfer_characteristics, I.matrix_coeffs, I.full_range_flag};
+      hipdec_tensor_desc sample = *desc;
+      void* elem0 = (uint8_t*)out_dev + (size_t)e * entry_bytes;
+      size_t pitch = 0;
+      int plane_rows = 0;
+      if (pa) {
+        if (!rc) rc = placed_check_component("album_to_tensor_placed", desc, *pa, e, S.wide ? I.bit_depth_luma : 8);
+        placed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0, &margins[(size_t)e]);
+        pitch = (size_t)desc->width * (desc->layout == HIPDEC_TENSOR_NHWC ? 3 : 1); plane_rows = desc->height;
+      }
       if (!rc) rc = tensor_record_entry("album_to_tensor", S.plane[0], S.stride[0], S.plane[1], S.stride[1], S.plane[2], S.stride[2], S.width, S.height,
-                                        S.wide ? I.bit_depth_luma : 8, S.chroma_format_idc, &nclx, &nclx, desc, left, top, rw, rh, entries ? entries[e].flip : 0,
-                                        (uint8_t*)out_dev + (size_t)e * entry_bytes, oriented ? (orientations ? orientations[e] : 0) : -1);
+                                        S.wide ? I.bit_depth_luma : 8, S.chroma_format_idc, &nclx, &nclx, &sample, left, top, rw, rh, entries ? entries[e].flip : 0,
+                                        elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows);
       if (rc) { color_tensor_abort(); return rc; }
     }
-    const int rc = color_tensor_launch(oriented || resample_filter(desc->filter) ? a->color_oriented : a->color_tensor, desc->filter, desc->dtype, s);
+    int rc = color_tensor_launch(oriented || resample_filter(desc->filter) ? a->color_oriented : a->color_tensor, desc->filter, desc->dtype, s);
+    if (!rc && pa) rc = canvas_margin_launch(a->color_margin, margins.data(), n_entries, desc->dtype, s);
     b->mark_done(s);
+    if (!rc && pa) placed_note_call((uint64_t)n_entries);
     return rc;
   });
 }
@@ -363,6 +379,14 @@ int hipdec_album_to_tensor_oriented(hipdec_album* a, const hipdec_tensor_desc* d
                                     void* out_dev, size_t out_bytes, void* stream)
 {
   return album_to_tensor_impl(a, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream);
+}
+
+int hipdec_album_to_tensor_placed(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                  const hipdec_tensor_place* places, const hipdec_tensor_fill* fill, void* mask_dev, int n_entries, void* out_dev, size_t out_bytes,
+                                  void* stream)
+{
+  const PlacedArgs pa{places, fill, mask_dev};
+  return album_to_tensor_impl(a, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, &pa);
 }
 
 int hipdec_album_to_rgb_scaled_oriented_all(hipdec_album* a, int out_chroma, const int* orientations, const int* out_widths, const int* out_heights, int filter,

@@ -94,8 +94,9 @@ int scale_planes_launch(PlaneScaleParams* jobs, int n, int bytes_per_sample, int
 // (native-depth value) records a tensor block instead of launching - its `out` is the entry's first element - and color_tensor_launch() sends the recorded
 // blocks out as ONE launch.  The window is in luma samples of the planes handed in; sH / sV are their chroma shifts (box presents them as 4:4:4).
 // Oriented output: `oriented` sends the block to the k_oriented_* kernels - ow x oh is then the PRE-orientation size, `code` the hipdec_orientation with the
-// entry's flip folded in, `pitch` the elements from one displayed row to the next.
-struct TensorRequest { int ow, oh, sH, sV, left, top, rw, rh, flip, nhwc; float scale[3], bias[3]; int oriented, code; size_t pitch;
+// entry's flip folded in, `pitch` the elements from one displayed row to the next, `plane_rows` the rows of a channel plane (NCHW: the plane is
+// plane_rows * pitch elements; a dense sample: its displayed rows, a placed one: the canvas' rows).
+struct TensorRequest { int ow, oh, sH, sV, left, top, rw, rh, flip, nhwc; float scale[3], bias[3]; int oriented, code; size_t pitch; int plane_rows;
                        int resample; /* HIPDEC_SCALE_BILINEAR / _BICUBIC: the block is recorded for k_resample, code and pitch set for every entry (0: no) */ };
 void color_tensor_request(const TensorRequest& r);
 void color_tensor_clear();
@@ -104,6 +105,23 @@ void color_tensor_begin();
 void color_tensor_abort();
 int color_tensor_launch(ColorBatchState& st, int filter, int dtype, hipStream_t s);
 int color_tensor_inspect(const ColorBatchState& st, int entry, int plane, const void** plane_dev, size_t* stride, int* x, int* y, int* w, int* h);
+
+// Placed tensor output (color.hip k_canvas_margin): everything of an entry's canvas outside its rectangle, and its mask, for all entries in ONE launch.
+// One block per entry; the kernel computes the fill elements itself (tensor_elem<DT> / the RNE narrowing), so they cannot differ from a pixel's.
+struct CanvasMargin {
+  uint8_t* o0;             // the canvas' first element
+  uint8_t* mask;           // the entry's W * H mask bytes, or NULL
+  int W, H;                // the canvas
+  int x, y, w, h;          // the rectangle
+  int nhwc;
+  int domain;              // hipdec_fill_domain
+  int margin;              // the rectangle is not the whole canvas
+  int reserved;
+  float value[3], scale[3], bias[3];
+};
+// launches when an entry has a margin or a mask (nothing otherwise); dtype: hipdec_tensor_dtype
+int canvas_margin_launch(ColorBatchState& st, const CanvasMargin* blocks, int n, int dtype, hipStream_t s);
+void placed_note_call(uint64_t entries);   // hipdec_placed_stats
 
 // The paste of an album of grid photos (transform.hip k_album_paste): one job per (tile, plane), already clipped to the photo's output size by the host
 // (a job clipped to nothing is not emitted); the job table lives in device memory and all jobs go out as ONE launch.

@@ -80,6 +80,12 @@ def _bind(lib):
     lib.hipdec_album_to_rgb_scaled_oriented_all.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(vp), C.POINTER(sz), vp]
     lib.hipdec_oriented_stats.restype = None
     lib.hipdec_oriented_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
+    placed = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), C.POINTER(ci), C.POINTER(TensorPlace), C.POINTER(TensorFill), vp, ci, vp, sz, vp]
+    lib.hipdec_batch_to_tensor_placed.argtypes = placed
+    lib.hipdec_album_to_tensor_placed.argtypes = placed
+    lib.hipdec_letterbox_place.argtypes = [ci, ci, ci, ci, ci, ci, C.POINTER(TensorPlace)]
+    lib.hipdec_placed_stats.restype = None
+    lib.hipdec_placed_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
     lib._dec_bound = True
     return lib
 
@@ -100,6 +106,17 @@ class TensorEntry(C.Structure):
     _fields_ = [("item", C.c_int), ("left", C.c_int), ("top", C.c_int), ("width", C.c_int), ("height", C.c_int), ("flip", C.c_int)]
 
 
+class TensorPlace(C.Structure):
+    """hipdec_tensor_place"""
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("width", C.c_int), ("height", C.c_int)]
+
+
+class TensorFill(C.Structure):
+    """hipdec_tensor_fill"""
+    _fields_ = [("value", C.c_float * 3), ("domain", C.c_int), ("reserved", C.c_int)]
+
+
+FILL_DOMAINS = {"component": 0, "element": 1}                                 # hipdec_fill_domain
 TENSOR_DTYPES = {"uint8": 0, "float32": 1, "float16": 2, "bfloat16": 3}       # hipdec_tensor_dtype
 TENSOR_LAYOUTS = {"NCHW": 0, "NHWC": 1}                                       # hipdec_tensor_layout
 _TENSOR_NUMPY = {"uint8": np.uint8, "float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}   # (NumPy has no bfloat16: its bits)
@@ -319,6 +336,58 @@ def _orientation_array(orientations, n):
     return (C.c_int * n)(*codes)
 
 
+def tensor_places(places, n=None):
+    """a ctypes array of hipdec_tensor_place from (x, y, width, height) tuples or TensorPlace objects"""
+    places = list(places)
+    if n is not None and len(places) != n:
+        raise ValueError("%d places for %d entries" % (len(places), n))
+    arr = (TensorPlace * len(places))()
+    for k, p in enumerate(places):
+        arr[k] = p if isinstance(p, TensorPlace) else TensorPlace(*(int(v) for v in p))
+    return arr
+
+
+def tensor_fill(fill, fill_domain="component"):
+    """hipdec_tensor_fill from a number or three per channel; fill_domain "component" (a pixel's component value, normalised as pixels are) or "element"
+    (the tensor element itself)"""
+    if fill_domain not in FILL_DOMAINS:
+        raise ValueError("fill_domain must be 'component' or 'element'")
+    f = TensorFill()
+    v = np.broadcast_to(np.asarray(fill, np.float32), (3,))
+    for c in range(3):
+        f.value[c] = float(v[c])
+    f.domain = FILL_DOMAINS[fill_domain]
+    return f
+
+
+_ANCHORS = {"topleft": 0, "center": 1}
+
+
+def letterbox_place(src_size, canvas_size, upscale=True, anchor="center"):
+    """(x, y, width, height): the rectangle of a displayed sample of src_size = (width, height) fitted into canvas_size = (width, height) with its aspect
+    ratio kept (hipdec_letterbox_place; host only).  upscale False: a source that fits both ways keeps its size.  anchor "center" or "topleft"."""
+    if anchor not in _ANCHORS:
+        raise ValueError("anchor must be 'center' or 'topleft'")
+    pl = TensorPlace()
+    if _bind(load_library()).hipdec_letterbox_place(int(src_size[0]), int(src_size[1]), int(canvas_size[0]), int(canvas_size[1]), int(bool(upscale)), _ANCHORS[anchor],
+                                                     C.byref(pl)) != 0:
+        raise ValueError("letterbox_place(%r, %r)" % (tuple(src_size), tuple(canvas_size)))
+    return pl.x, pl.y, pl.width, pl.height
+
+
+def letterbox_places(sizes, canvas_size, upscale=True, anchor="center"):
+    """letterbox_place for a list of DISPLAYED sizes (oriented_size() of the stored ones): the `places` of a to_tensor call"""
+    return [letterbox_place(s, canvas_size, upscale, anchor) for s in sizes]
+
+
+def placed_stats():
+    """(placed to_tensor calls, their entries, launches of the margin kernel) since load"""
+    lib = _bind(load_library())
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    lib.hipdec_placed_stats(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
 def fit_within(width, height, size):
     """The thumbnail size examples/heif_thumbnailer.cc:172-186 computes: the image as it is when both sides fit into `size`, else the longer
     side becomes `size` and the other one follows with integer division (which may give 0: the thumbnailer refuses that, and so does
@@ -330,11 +399,20 @@ def fit_within(width, height, size):
     return width * size // height, size
 
 
-def _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations=None):
+def _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations=None, placed=None):
     """Batch.to_tensor / Album.to_tensor: the description, the output buffer (DeviceBuffer or torch.Tensor) and the stream, then `call` (the oriented
-    entry point when `orientations` is given)"""
+    entry point when `orientations` is given; the placed one with placed = (places, fill, fill_domain, mask))"""
     n = self.n if entries is None else len(entries)
-    if orientations is not None:
+    self._tensor_mask = None      # (the mask of THIS call, or none: tensor_mask_to_host() never hands back an earlier call's)
+    last_mask = None
+    if placed is not None:
+        places, fill, fill_domain, mask = placed
+        codes = None if orientations is None else _orientation_array(orientations, n)
+        parr = None if places is None else tensor_places(places, n)
+        f = None if fill is None else tensor_fill(fill, fill_domain)
+        placed_call, mask_ptr = call, [None]
+        call = lambda h, desc, arr, n, ptr, room, stream: placed_call(h, desc, arr, codes, parr, f, mask_ptr[0], n, ptr, room, stream)
+    elif orientations is not None:
         codes = _orientation_array(orientations, n)
         oriented = call
         call = lambda h, desc, arr, n, ptr, room, stream: oriented(h, desc, arr, codes, n, ptr, room, stream)
@@ -370,7 +448,28 @@ def _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias,
                 # on the host - what torch has queued for `out` first, and the tensor is complete when this call returns
                 ts.synchronize()
                 host_wait = True
+    if placed is not None and mask is not None and mask is not False:
+        mshape = (n, int(size[1]), int(size[0]))
+        if mask is True:
+            if isinstance(out, DeviceBuffer):
+                mask = DeviceBuffer(max(int(np.prod(mshape)), 1))
+            else:
+                import torch
+                mask = torch.empty(mshape, dtype=torch.uint8, device=out.device)
+        if isinstance(mask, DeviceBuffer):
+            if mask.nbytes < int(np.prod(mshape)):
+                raise ValueError("mask has %d bytes, the mask tensor has %d" % (mask.nbytes, int(np.prod(mshape))))
+            mask_ptr[0] = mask.ptr
+        else:
+            import torch
+            if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype != torch.uint8:
+                raise TypeError("mask must be True, a DeviceBuffer or a CUDA / HIP torch.Tensor of uint8")
+            if tuple(mask.shape) != mshape or not mask.is_contiguous():
+                raise ValueError("mask must be contiguous with shape %s" % (mshape,))
+            mask_ptr[0] = mask.data_ptr()
+        last_mask = (mask, mshape, stream)
     check(call(self._h, C.byref(desc), arr, n, ptr, room, stream))
+    self._tensor_mask = last_mask
     if host_wait:
         check(self._lib.hipdec_stream_synchronize(None))
     self._tensor = (out, shape, _TENSOR_NUMPY[dtype], stream)
@@ -579,7 +678,7 @@ class Batch:
                                                        self._srgb_strides, stream))
 
     def to_tensor(self, size, entries=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, filter=SCALE_BOX, out=None,
-                  stream=None, orientations=None):
+                  stream=None, orientations=None, places=None, fill=None, fill_domain="component", mask=None):
         """asynchronous: crop windows of the decoded pictures, scaled to size = (width, height), optionally flipped, as ONE dense tensor of shape
         (N, 3, height, width) ("NCHW") or (N, height, width, 3) ("NHWC") written by one fused kernel (hipdec_batch_to_tensor).
 
@@ -596,7 +695,19 @@ class Batch:
         orientations: one hipdec_orientation code per entry (hipdec_batch_to_tensor_oriented): `size` is then the size of the DISPLAYED sample, windows
         stay in the stored picture (stored_window() maps a displayed window), and an entry's flip mirrors the displayed sample.
         filter: SCALE_NEAREST, SCALE_BOX, or SCALE_BILINEAR / SCALE_BICUBIC: V = PIL.Image.resize of the window of the 8-bit RGB picture (to_rgb(i, 10)),
-        bit for bit - what torchvision's Resize / RandomResizedCrop compute on PIL images; from sources above 8 bits with dtype "uint8" only."""
+        bit for bit - what torchvision's Resize / RandomResizedCrop compute on PIL images; from sources above 8 bits with dtype "uint8" only.
+        places / fill / mask (hipdec_batch_to_tensor_placed; any of them selects it): `size` is then the size of the CANVAS of every entry, places one
+        (x, y, width, height) rectangle per entry - the displayed sample is written there at that size (letterbox_places()), None: the whole canvas -
+        and the rest of the canvas holds `fill`: a number or three per channel, with fill_domain "component" a pixel's component value (normalised as
+        pixels are: fill=114 is the usual grey) or "element" the tensor element itself (0.0: zero after normalisation); default component 0.
+        mask: a DeviceBuffer or a uint8 torch.Tensor of shape (N, height, width), or True to allocate one - 1 where the canvas is padding, 0 inside the
+        rectangle (tensor_mask_to_host() reads the mask of the LAST call back; it raises when that call wrote none).  The mask is written on the stream the
+        tensor is written on: `stream`, or - stream None - torch's current stream when `out` is a torch.Tensor and the library's own stream when `out`
+        is a DeviceBuffer, whatever the mask is; a torch mask next to a DeviceBuffer `out` therefore needs `stream=` (or synchronize()) to be ordered
+        with torch's work."""
+        if places is not None or fill is not None or mask is not None:
+            return _to_tensor(self, self._lib.hipdec_batch_to_tensor_placed, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations,
+                              (places, fill, fill_domain, mask))
         if orientations is not None:
             return _to_tensor(self, self._lib.hipdec_batch_to_tensor_oriented, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations)
         return _to_tensor(self, self._lib.hipdec_batch_to_tensor, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
@@ -611,6 +722,16 @@ class Batch:
         t = out.view(torch.int16) if dt == np.uint16 else out
         a = t.cpu().numpy()
         return a.view(np.uint16) if dt == np.uint16 else a
+
+    def tensor_mask_to_host(self):
+        """the mask of the last placed to_tensor() as a NumPy uint8 array of shape (N, height, width); waits for its stream"""
+        if getattr(self, "_tensor_mask", None) is None:
+            raise RuntimeError("tensor_mask_to_host: the last to_tensor() wrote no mask (mask= was not given, or there has been no call)")
+        mask, shape, stream = self._tensor_mask
+        check(self._lib.hipdec_stream_synchronize(stream))
+        if isinstance(mask, DeviceBuffer):
+            return mask.to_numpy(shape, np.uint8)
+        return mask.cpu().numpy()
 
     def tensor_block(self, entry, plane):
         """debug inspection (hipdec_batch_tensor_block): (device pointer, stride, x, y, width, height) of a plane of an entry of the last to_tensor()"""
@@ -785,13 +906,17 @@ class Album:
         return buf.to_numpy((h, stride), np.uint8)
 
     def to_tensor(self, size, entries=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, filter=SCALE_BOX, out=None,
-                  stream=None, orientations=None):
+                  stream=None, orientations=None, places=None, fill=None, fill_domain="component", mask=None):
         """Batch.to_tensor over the composed photos: an entry's item names a photo, its window lies in the photo's output size"""
+        if places is not None or fill is not None or mask is not None:
+            return _to_tensor(self, self._lib.hipdec_album_to_tensor_placed, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations,
+                              (places, fill, fill_domain, mask))
         if orientations is not None:
             return _to_tensor(self, self._lib.hipdec_album_to_tensor_oriented, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations)
         return _to_tensor(self, self._lib.hipdec_album_to_tensor, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
 
     tensor_to_host = Batch.tensor_to_host
+    tensor_mask_to_host = Batch.tensor_mask_to_host
 
     def paste_timing_us(self):
         """device time of the paste launch of the last run(), microseconds"""
