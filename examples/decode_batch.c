@@ -9,6 +9,10 @@
  *                                                     (the size rule of libheif's examples/heif_thumbnailer.cc:172-186, area-averaged on the device)
  *   ./decode_batch --thumb 256 --orient 1 item0.hevc  the previews as they are DISPLAYED for orientation code 0 .. 7 (hipdec_orientation: what the host folded the
  *                                                     items' 'irot' / 'imir' into with hipdec_orientation_compose), still ONE launch: the rotation is in its store
+ *   ./decode_batch --thumb 448 --patches 14:2 ...      instead of previews, ONE launch writes the batch as the packed sequence of patch tokens native-resolution
+ *                                                     vision encoders take (hipdec_batch_to_tensor_packed): every item at its own preview size rounded down to a
+ *                                                     multiple of P * M, uint8 tokens of 3 * P * P elements in Conv2d weight order, merge groups of M x M;
+ *                                                     last among the --thumb options
  *   ./decode_batch --thumb 256 --filter bicubic ...   the previews with another filter: box (the default) | nearest | bilinear | bicubic - the last two are
  *                                                     PIL.Image.resize bit for bit (HIPDEC_SCALE_BILINEAR / HIPDEC_SCALE_BICUBIC); after --orient where both are given
  *   ./decode_batch --tensor 224 item0.hevc ...        ends in ONE launch that writes a float16 N x 3 x 224 x 224 tensor: the centred square of every item,
@@ -107,13 +111,20 @@ int main(int argc, char** argv)
     if (k == 4) argc = 0;                                          /* no or an unknown name: usage */
     else { filter = filters[k].value; argv += 2; argc -= 2; }
   }
+  int patch = 0, merge = 1;
+  if (thumb && argc >= 2 && !strcmp(argv[1], "--patches")) {
+    char tail = 0;
+    const int got = argc >= 3 ? sscanf(argv[2], "%d:%d%c", &patch, &merge, &tail) : 0;
+    if ((got != 1 && got != 2) || patch < 1 || patch > 256 || merge < 1 || merge > 16) argc = 0;   /* no or a bad P[:M]: usage */
+    else { argv += 2; argc -= 2; }
+  }
   int tensor = 0;
   if (!thumb && argc >= 2 && !strcmp(argv[1], "--tensor")) {
     tensor = argc >= 3 ? atoi(argv[2]) : 0;
     if (tensor < 1) argc = 0;
     else { argv += 2; argc -= 2; }
   }
-  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] [--patches P[:M]] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
   const int n = argc - 1;
   const void** data = (const void**)calloc((size_t)n, sizeof(void*));
   size_t* sizes = (size_t*)calloc((size_t)n, sizeof(size_t));
@@ -167,10 +178,44 @@ int main(int argc, char** argv)
         if (dw > dh) { hs[i] = (int)((long long)dh * thumb / dw); ws[i] = thumb; }
         else { ws[i] = (int)((long long)dw * thumb / dh); hs[i] = thumb; }
       }
+      if (patch) { ws[i] -= ws[i] % (patch * merge); hs[i] -= hs[i] % (patch * merge); }   /* choosing the sizes is the caller's: here, rounded down */
       if (ws[i] < 1 || hs[i] < 1) { fprintf(stderr, "%s: zero thumbnail output size\n", argv[1 + i]); return 1; }
+      if (patch) continue;
       strides[i] = (size_t)ws[i] * 3;
       outs[i] = hipdec_malloc(strides[i] * (size_t)hs[i]);
       if (!outs[i]) { fprintf(stderr, "%s\n", hipdec_last_error()); return 1; }
+    }
+    if (patch) {                                                   /* the packed sequence of the whole batch: one launch, one buffer */
+      hipdec_tensor_desc d;
+      memset(&d, 0, sizeof d);                                     /* width = height = 0: the sizes are per sample */
+      d.dtype = HIPDEC_TENSOR_U8; d.layout = HIPDEC_TENSOR_NCHW; d.filter = filter;
+      const hipdec_tensor_patches pt = {patch, merge, {0, 0}};
+      uint64_t* offs = (uint64_t*)calloc((size_t)n, sizeof(uint64_t));
+      uint32_t* toks = (uint32_t*)calloc((size_t)n, sizeof(uint32_t));
+      hipdec_tensor_sample* sm = (hipdec_tensor_sample*)calloc((size_t)n, sizeof(hipdec_tensor_sample));
+      uint64_t total = 0;
+      if (hipdec_tensor_packed_layout(&pt, ws, hs, n, offs, toks, &total)) { fprintf(stderr, "%s\n", hipdec_last_error()); return 1; }
+      for (int i = 0; i < n; i++) { sm[i].width = ws[i]; sm[i].height = hs[i]; sm[i].offset = offs[i]; }
+      void* seq = hipdec_malloc((size_t)total);
+      uint8_t* host = (uint8_t*)malloc((size_t)total);
+      if (!seq || !host || hipdec_batch_to_tensor_packed(prev, &d, NULL, codes, sm, &pt, n, seq, (size_t)total, NULL) || hipdec_batch_status(prev) ||
+          hipdec_memcpy_d2h(host, seq, (size_t)total)) {
+        fprintf(stderr, "%s\n", hipdec_last_error());
+        return 1;
+      }
+      unsigned long long all = 0, tokens = 0;
+      for (int i = 0; i < n; i++) {
+        unsigned long long sum = 0;
+        for (uint64_t k = 0; k < 3ull * (uint64_t)ws[i] * (uint64_t)hs[i]; k++) sum += host[offs[i] + k];
+        printf("%s: %u tokens of %dx%d at %dx%d, byte sum %llu\n", argv[1 + i], toks[i], patch, patch, ws[i], hs[i], sum);
+        all += sum; tokens += toks[i];
+      }
+      printf("packed sequence: %llu tokens x %d elements, byte sum %llu\n", tokens, 3 * patch * patch, all);
+      free(host); hipdec_free(seq); free(offs); free(toks); free(sm);
+      free(ws); free(hs); free(codes); free(outs); free(strides);
+      hipdec_batch_free(prev);
+      hipdec_shutdown();
+      return 0;
     }
     const int rc = orient < 0 ? hipdec_batch_to_rgb_scaled_all(prev, 10, ws, hs, filter, (void* const*)outs, strides, NULL)
                               : hipdec_batch_to_rgb_scaled_oriented_all(prev, 10, codes, ws, hs, filter, (void* const*)outs, strides, NULL);

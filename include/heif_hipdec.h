@@ -669,6 +669,55 @@ HIPDEC_API int hipdec_letterbox_place(int src_width, int src_height, int canvas_
 /* counters since load: placed calls, their entries, launches of the margin kernel */
 HIPDEC_API void hipdec_placed_stats(uint64_t* calls, uint64_t* entries, uint64_t* margin_launches);
 
+/* ---- packed tensor output: per-sample sizes and patch sequences in one launch ---------------------------------------------------------------------------
+ * Native-resolution vision encoders (Qwen2-VL / 2.5-VL, SigLIP2 NaFlex, Pixtral, NaViT-style packing) take no common size: each photo keeps its aspect
+ * ratio, is resized to its own w x h - a multiple of the patch size - and the batch is ONE packed sequence of patch tokens, [sum of tokens, 3 * P * P].
+ * The tensor forms above take one desc->width x height for all entries and the placed form pads to one canvas; these calls take a size and an offset per
+ * entry and write either dense samples or the patch sequence itself, all entries in one launch.  desc->width and desc->height must be 0 (the sizes are per
+ * sample); dtype, layout, filter, scale and bias mean what they mean in the sibling calls.
+ *
+ * THE DEFINITION OF THE RESULT.  For entry e with samples[e] = (w, h, offset):
+ *  - S[c][Y][X] is the element hipdec_batch_to_tensor_oriented writes at (c, Y, X) for the same entry (item, window, flip), orientation code, filter, dtype,
+ *    scale and bias with desc->width / height = w / h.  Everything that call defines is untouched: integer stage, float stage, to-SDR rules, the size swap
+ *    for an odd number of quarter turns, the flip of the displayed sample.
+ *  - The sample occupies exactly the 3 * w * h elements out[offset .. offset + 3wh) (offset counts ELEMENTS of desc->dtype).
+ *  - patch == 0, or patches NULL: the sample is stored densely in desc->layout,
+ *      NCHW  out[offset + (c * h + Y) * w + X]          NHWC  out[offset + (Y * w + X) * 3 + c]
+ *  - patch == P >= 1 with merge == m: w and h are multiples of P * m; with gw = w / P, gy = Y / P, gx = X / P, py = Y % P, px = X % P the token index is
+ *      t = ((gy / m) * (gw / m) + gx / m) * m * m + (gy % m) * m + gx % m
+ *    (m == 1: row-major gy * gw + gx; m == 2: the order Qwen2-VL's image processor emits), the position inside the token
+ *      NCHW  k = (c * P + py) * P + px     the flattened Conv2d(3, D, P, P) weight order
+ *      NHWC  k = (py * P + px) * 3 + c     NaFlex / big_vision patchify order
+ *    and the element goes to out[offset + t * 3 * P * P + k].  As array expressions over the dense sample S (NCHW, shape [3, h, w], gh = h / P):
+ *      m == 1, NHWC:  S.transpose(1, 2, 0).reshape(gh, P, gw, P, 3).transpose(0, 2, 1, 3, 4).reshape(gh * gw, P * P * 3)
+ *      m == 2, NCHW:  S.reshape(3, gh / 2, 2, P, gw / 2, 2, P).transpose(1, 4, 2, 5, 0, 3, 6).reshape(gh * gw, 3 * P * P)
+ * Every element of a sample's range is written exactly once and nothing else in `out` is written: gaps the caller leaves between samples stay as they were.
+ * Entries of all sizes, codes and resampling-table sizes share one launch (65535 entries per launch, as in the siblings): ONE kernel launch for BOX and
+ * NEAREST, one launch plus the one table upload of the resampling path for BILINEAR / BICUBIC.  Device time: slot [5] of hipdec_batch_slot_kernel_timing_us.
+ * Refused before a device is touched, HIPDEC_ERR_INVALID_ARGUMENT, naming the entry where one is at fault: samples NULL; desc->width or height non-zero; a
+ * sample with a non-positive side; patch < 0 or > 256; merge < 1 or > 16; merge != 1 with patch == 0; a non-zero `reserved`; a side that is not a multiple
+ * of patch * merge; offset + 3wh above out_bytes / sizeof(element); two samples whose element ranges overlap; a code outside 0 .. 7; everything else the
+ * oriented call refuses on its arguments alone.  w * h above max_image_size_pixels: HIPDEC_ERR_LIMIT.  What the oriented call refuses from the sources -
+ * mixed 8-bit and wider entries, a float dtype from a source above 8 bits with BILINEAR / BICUBIC, resampling tables above 64 MiB - is refused with the same
+ * status before anything is launched.
+ * Out of scope: choosing the sizes stays with the caller, as reading `irot` does (Qwen's smart_resize and NaFlex's search over scales are float rules of
+ * other projects); Qwen's duplicated temporal axis; margins and masks (a packed sample has none); the single-image form. */
+typedef struct hipdec_tensor_sample { int width, height; uint64_t offset; } hipdec_tensor_sample;   /* DISPLAYED size; index of the sample's first element in out */
+typedef struct hipdec_tensor_patches { int patch, merge, reserved[2]; } hipdec_tensor_patches;      /* patch 0: dense samples; merge >= 1 */
+HIPDEC_API int hipdec_batch_to_tensor_packed(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                             const hipdec_tensor_sample* samples, const hipdec_tensor_patches* patches, int n_entries, void* out_dev,
+                                             size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_album_to_tensor_packed(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                             const hipdec_tensor_sample* samples, const hipdec_tensor_patches* patches, int n_entries, void* out_dev,
+                                             size_t out_bytes, void* stream);
+/* Host only: offsets[e] of samples packed back to back in entry order, tokens[e] per sample ((w / patch) * (h / patch); 0 for dense samples) and the total
+ * element count (any of the three may be NULL).  A refused argument - a bad `patches`, a non-positive side, a side that is no multiple of patch * merge -
+ * returns -1 and hipdec_last_error says why. */
+HIPDEC_API int hipdec_tensor_packed_layout(const hipdec_tensor_patches* patches, const int* widths, const int* heights, int n, uint64_t* offsets,
+                                           uint32_t* tokens, uint64_t* total_elements);
+/* counters since load: packed calls, their entries, and how many of those were written as patch sequences */
+HIPDEC_API void hipdec_packed_stats(uint64_t* calls, uint64_t* entries, uint64_t* patch_entries);
+
 /* counters since load: images through hipdec_image_transform, grid canvases handed out by hipdec_grid_read_plane_tracked (hipdec_image_scale counts in
  * hipdec_image_scale_stats) */
 HIPDEC_API void hipdec_image_ops_stats(uint64_t* transforms, uint64_t* grid_canvases);

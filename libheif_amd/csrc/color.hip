@@ -653,6 +653,123 @@ __device__ __forceinline__ void store_oriented4(const OrientedParams& op, int dw
   }
 }
 
+// ---- packed tensor output, patch sequences (include/heif_hipdec.h hipdec_batch_to_tensor_packed): the sample of an entry is stored as tokens of P x P
+// pixels - token t of the sample starts at element t * 3 * P * P of it - instead of rows.  The element offset of displayed pixel (Y, X), channel 0, is a
+// sum of a row part and a column part: with gy = Y / P, py = Y % P, gx = X / P, px = X % P and the merge size m
+//   t * 3PP = ((gy / m) * (gw / m) + gx / m) * m * m * 3PP + ((gy % m) * m + gx % m) * 3PP
+//   rowoff(Y) = (gy / m) * rowtok + (gy % m) * mtok + py * prow          rowtok = (gw / m) * m * m * 3PP, mtok = m * 3PP, prow = P * pxs
+//   coloff(X) = (gx / m) * tokm + (gx % m) * tok + px * pxs              tokm = m * m * 3PP, tok = 3PP
+// where pxs is the distance of horizontal neighbours inside a token (1 in Conv2d weight order, 3 in NaFlex order) and chs the distance of the channels
+// (P * P, or 1).  Everything in the block is wave-uniform and computed by the host; the divisions by P and m are a multiply-high with floor(2^32 / d) and
+// one correction step (exact for every 32-bit dividend: the estimate is short by at most one), five VALU operations each.
+struct PatchInfo {
+  uint32_t P, m;
+  uint32_t magicP, magicM;   // min(floor(2^32 / d), 2^32 - 1)
+  uint32_t tok, tokm, mtok;
+  uint32_t prow, pxs, chs;
+  uint64_t rowtok;
+};
+static_assert(sizeof(PatchInfo) == 48, "the blocks behind it stay 16-byte multiples");
+struct PatchParams { OrientedParams in; PatchInfo b; };
+
+__device__ __forceinline__ uint32_t patch_divmod(uint32_t n, uint32_t d, uint32_t magic, uint32_t& rem)
+{
+  uint32_t q = (uint32_t)(((uint64_t)n * (uint64_t)magic) >> 32);
+  rem = n - q * d;
+  if (rem >= d) { q++; rem -= d; }
+  return q;
+}
+__device__ __forceinline__ size_t patch_rowoff(const PatchInfo& b, uint32_t Y)
+{
+  uint32_t py, ry;
+  const uint32_t gy = patch_divmod(Y, b.P, b.magicP, py), my = patch_divmod(gy, b.m, b.magicM, ry);
+  return (size_t)my * (size_t)b.rowtok + (size_t)(ry * b.mtok + py * b.prow);
+}
+__device__ __forceinline__ size_t patch_coloff(const PatchInfo& b, uint32_t X)
+{
+  uint32_t px, rx;
+  const uint32_t gx = patch_divmod(X, b.P, b.magicP, px), mx = patch_divmod(gx, b.m, b.magicM, rx);
+  return (size_t)mx * (size_t)b.tokm + (size_t)(rx * b.tok + px * b.pxs);
+}
+
+// store_oriented4's shape in token order.  A whole group whose first column in memory is a multiple of 4 lies inside one patch when P % 4 == 0: there it is
+// what the dense store has - one vector store per channel (the channels P * P apart) or one run of 12 elements - behind the same runtime alignment test.
+// Every other group - any other P, a ragged or unaligned group - takes element stores with the patch found per pixel (the row part once).
+template <int DT>
+__device__ __forceinline__ void store_patch4(const OrientedParams& op, const PatchInfo& b, int dw_, int rev, int x0, int row, int npx, const int (&R)[4],
+                                             const int (&G)[4], const int (&B)[4])
+{
+  typedef typename TensorElem<DT>::T E;
+  typedef TensorQuad<DT> Q;
+  typedef typename Q::V V;
+  const TensorParams& tp = op.t;
+  uint32_t v[3][4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    v[0][i] = tensor_elem<DT>(rev ? R[3 - i] : R[i], tp.scale[0], tp.bias[0]);
+    v[1][i] = tensor_elem<DT>(rev ? G[3 - i] : G[i], tp.scale[1], tp.bias[1]);
+    v[2][i] = tensor_elem<DT>(rev ? B[3 - i] : B[i], tp.scale[2], tp.bias[2]);
+  }
+  const uint32_t dw = (uint32_t)dw_;
+  const uint32_t xs = rev ? dw - (uint32_t)npx - (uint32_t)x0 : (uint32_t)x0;   // the group's first column in memory
+  HIPDEC_GLOBAL E* o = (HIPDEC_GLOBAL E*)tp.c.o0 + patch_rowoff(b, (uint32_t)row);
+  if (npx == 4 && ((b.P | xs) & 3u) == 0) {
+    HIPDEC_GLOBAL E* d = o + patch_coloff(b, xs);
+    if (tp.nhwc) {
+      if ((((uintptr_t)d) & (4 * sizeof(E) - 1)) == 0) {
+        ((HIPDEC_GLOBAL V*)d)[0] = Q::pack(v[0][0], v[1][0], v[2][0], v[0][1]);
+        ((HIPDEC_GLOBAL V*)d)[1] = Q::pack(v[1][1], v[2][1], v[0][2], v[1][2]);
+        ((HIPDEC_GLOBAL V*)d)[2] = Q::pack(v[2][2], v[0][3], v[1][3], v[2][3]);
+        return;
+      }
+    } else {
+      HIPDEC_GLOBAL E* g = d + b.chs;
+      HIPDEC_GLOBAL E* bl = g + b.chs;
+      if (((((uintptr_t)d) | ((uintptr_t)g) | ((uintptr_t)bl)) & (4 * sizeof(E) - 1)) == 0) {
+        *(HIPDEC_GLOBAL V*)d = Q::pack(v[0][0], v[0][1], v[0][2], v[0][3]);
+        *(HIPDEC_GLOBAL V*)g = Q::pack(v[1][0], v[1][1], v[1][2], v[1][3]);
+        *(HIPDEC_GLOBAL V*)bl = Q::pack(v[2][0], v[2][1], v[2][2], v[2][3]);
+        return;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    if (i >= npx) break;
+    const int k = rev ? 3 - i : i;                                   // where pixel x0 + i sits in v
+    const uint32_t col = rev ? dw - 1u - (uint32_t)(x0 + i) : (uint32_t)(x0 + i);
+    HIPDEC_GLOBAL E* d = o + patch_coloff(b, col);
+    d[0] = (E)v[0][k]; d[b.chs] = (E)v[1][k]; d[2 * b.chs] = (E)v[2][k];
+  }
+}
+
+// The store policies of the nearest and resampling kernel bodies: the dense one is the store the kernels have had (rows of `pitch` elements), the blocked
+// one writes token order.  A policy is an argument of the body the way LAYOUT is one of rgb_block.
+// Block: the parameter block the kernel reads (the body loads it, as the kernels did); inner(): the block the body works on.
+template <typename Blk> struct DenseStore {
+  typedef Blk Block;
+  __device__ __forceinline__ explicit DenseStore(const Blk&) {}
+  static __device__ __forceinline__ const Blk& inner(const Blk& k) { return k; }
+  template <int DT>
+  __device__ __forceinline__ void group4(const OrientedParams& op, int dw, int dh, int rev, int x0, int row, int npx, const int (&R)[4], const int (&G)[4],
+                                         const int (&B)[4]) const
+  {
+    store_oriented4<DT>(op, dw, dh, rev, x0, row, npx, R, G, B);
+  }
+};
+template <typename Blk> struct PatchStore {   // Blk: PatchParams, or PatchResampleParams - {the dense block `in`, PatchInfo b}
+  typedef Blk Block;
+  const PatchInfo& b;
+  __device__ __forceinline__ explicit PatchStore(const Blk& k) : b(k.b) {}
+  static __device__ __forceinline__ auto inner(const Blk& k) -> decltype((k.in)) { return k.in; }
+  template <int DT>
+  __device__ __forceinline__ void group4(const OrientedParams& op, int dw, int, int rev, int x0, int row, int npx, const int (&R)[4], const int (&G)[4],
+                                         const int (&B)[4]) const
+  {
+    store_patch4<DT>(op, b, dw, rev, x0, row, npx, R, G, B);
+  }
+};
+
 // The quarter-turn store of the box kernel.  The box stage has to walk SOURCE rows (box_columns lives on aligned row loads), but a row of P is a COLUMN of
 // the displayed picture: stored as it is computed, every element would open a 64-byte segment of its own.  So a workgroup takes RB consecutive rows of P for
 // its tile of at most TC columns, stages the converted integer components in LDS (one row of the stage per row of P, one 32-bit word per pixel where the
@@ -772,24 +889,129 @@ __global__ __launch_bounds__(256) void k_oriented_box(const OrientedParams* __re
   }
 }
 
+// k_oriented_box with the blocked store: the box kernel of a patch sequence.  Its integer stage is k_oriented_box's, statement for statement; the two texts
+// differ in the store only.  (k_oriented_box is not built from a body shared with this kernel, as k_oriented_nearest and k_resample are from theirs: as a
+// wrapper of one it allocated 122 / 170 VGPRs where it has 119 / 166 - the difference is lanes that hold spilled SGPRs - and left the 168 step of the 16-bit
+// kernel.)  The patch constants are read where the store needs them, behind the box stage, not held in SGPRs across it: the stage is where the kernel's
+// register pressure peaks.
+//   row-preserving codes:  4-pixel groups through store_patch4.
+//   quarter turns:         column x of the tile is displayed row Y and receives a run of RB pixels, as in k_oriented_box; in token order the run is cut where
+//                          it crosses a patch: consecutive lanes stay on consecutive elements inside each piece of P pixels (3 * P elements in NaFlex
+//                          order), and the pieces of one run lie a token apart.  The patch of an element is found per element.
+__device__ __forceinline__ PatchInfo patch_info_late(const PatchParams* q)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(HIPDEC_HOST_EMU)
+  asm volatile("" : "+s"(q));   // (the loads stay behind this point)
+#endif
+  return q->b;
+}
+
+// (the occupancy step is stated - four workgroups per CU for 8-bit samples, 128 VGPRs; three for 16-bit ones, 168 - so that the scheduler orders the store for
+// registers: left to itself it took 130 - 132 / 180 for the float dtypes)
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(Pix) == 1 ? 4 : 3))) void k_patch_box(const PatchParams* __restrict__ ps)
+{
+  typedef OrientedTile<Pix, DT> T;
+  typedef OrientedStage<T::kNarrow> St;
+  typedef typename TensorElem<DT>::T E;
+  constexpr int RB = T::RB, TC = T::TC;
+  __shared__ typename BoxAcc<Pix>::T colsum[3][kBoxSpan];
+  __shared__ typename St::S stage[RB][TC + 1];
+  const OrientedParams op = ps[blockIdx.z].in;   // wave-uniform: scalar loads into SGPRs
+  const TensorParams& tp = op.t;
+  const ColorParams& p = tp.c;
+  const int tid = threadIdx.x;
+  const int oxA = blockIdx.x * tp.tile;
+  if (oxA >= tp.ow) return;                               // (the whole workgroup)
+  const int nox = min(tp.tile, tp.ow - oxA);              // <= TC: the host caps the tile
+  const bool mono = p.arith == AR_MONO;
+  const int quarter = op.code & 1, fx = ((op.code >> 1) ^ (op.code >> 2)) & 1, fy = ((op.code >> 1) ^ op.code) & 1;
+  const int cl = tp.left >> tp.sH, ct = tp.top >> tp.sV;
+  const int cw = ((tp.left + tp.rw - 1) >> tp.sH) - cl + 1, ch = ((tp.top + tp.rh - 1) >> tp.sV) - ct + 1;
+  const int fcw = (p.w + (1 << tp.sH) - 1) >> tp.sH;
+  const BoxPlane pl[3] = {{p.y, p.ys, tp.rw, tp.rh, p.w, tp.left, tp.top}, {p.cb, p.cbs, cw, ch, fcw, cl, ct}, {p.cr, p.crs, cw, ch, fcw, cl, ct}};
+  const int rb = max(1, min((int)op.rb, RB));                  // (the stage has RB rows whatever the block says)
+  for (int yb = blockIdx.y * rb; yb < tp.oh; yb += gridDim.y * rb) {
+    const int nrows = min(rb, tp.oh - yb);
+    for (int r = 0; r < nrows; r++) {
+      uint32_t v[3];
+      box_tile<Pix, 3, true>(pl, mono ? 1 : 3, tp.ow, tp.oh, oxA, nox, yb + r, colsum, v);
+      if (tid < nox) {                                    // the owner of column oxA + tid converts its own pixel (four copies of it: one statement of the arithmetic)
+        const int Y[4] = {(int)v[0], (int)v[0], (int)v[0], (int)v[0]}, CB[4] = {(int)v[1], (int)v[1], (int)v[1], (int)v[1]}, CR[4] = {(int)v[2], (int)v[2], (int)v[2], (int)v[2]};
+        int R[4], G[4], B[4];
+        tensor_convert4<Pix>(p, Y, CB, CR, R, G, B);
+        stage[r][tid] = St::pack(R[0], G[0], B[0]);
+      }
+      __syncthreads();                                    // colsum is written again by the next row; after the last one the stage is complete
+    }
+    const PatchInfo b = patch_info_late(ps + blockIdx.z);
+    if (!quarter) {
+      const uint32_t ng = ((uint32_t)nox + 3u) >> 2, total = ng * (uint32_t)nrows;
+#pragma unroll 1
+      for (uint32_t idx = (uint32_t)tid; idx < total; idx += 256u) {
+        const uint32_t r = idx / ng, g = idx - r * ng;
+        int R[4], G[4], B[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {                     // (past the tile's last pixel: inside the padded stage row, not stored)
+          const typename St::S s = stage[r][g * 4u + (uint32_t)i];
+          R[i] = St::get(s, 0); G[i] = St::get(s, 1); B[i] = St::get(s, 2);
+        }
+        const int oy = yb + (int)r;
+        store_patch4<DT>(op, b, tp.ow, fx, oxA + (int)g * 4, fy ? tp.oh - 1 - oy : oy, min(4, nox - (int)g * 4), R, G, B);
+      }
+      __syncthreads();                                    // the stage is written again by the next block of rows
+      continue;
+    }
+    // rows yb .. yb + nrows - 1 of P are displayed columns xrun .. xrun + nrows - 1 (in reverse order where fx), column x of P is displayed row Y
+    const uint32_t n = (uint32_t)nrows, xrun = (uint32_t)(fx ? tp.oh - yb - nrows : yb);
+    HIPDEC_GLOBAL E* o = (HIPDEC_GLOBAL E*)p.o0;
+    if (tp.nhwc) {
+      const uint32_t per = 3u * n, total = per * (uint32_t)nox;
+#pragma unroll 1
+      for (uint32_t idx = (uint32_t)tid; idx < total; idx += 256u) {
+        const uint32_t c = idx / per, e = idx - c * per, j = e / 3u, k = e - 3u * j;
+        const int x = oxA + (int)c;
+        const int val = St::get(stage[fx ? n - 1u - j : j][c], k);
+        o[patch_rowoff(b, (uint32_t)(fy ? tp.ow - 1 - x : x)) + patch_coloff(b, xrun + j) + k] =
+            (E)tensor_elem<DT>(val, k == 0 ? tp.scale[0] : (k == 1 ? tp.scale[1] : tp.scale[2]), k == 0 ? tp.bias[0] : (k == 1 ? tp.bias[1] : tp.bias[2]));
+      }
+    } else {
+      const uint32_t total = n * (uint32_t)nox;
+#pragma unroll 1
+      for (uint32_t idx = (uint32_t)tid; idx < total; idx += 256u) {
+        const uint32_t c = idx / n, j = idx - c * n;
+        const int x = oxA + (int)c;
+        const typename St::S s = stage[fx ? n - 1u - j : j][c];
+        HIPDEC_GLOBAL E* d = o + patch_rowoff(b, (uint32_t)(fy ? tp.ow - 1 - x : x)) + patch_coloff(b, xrun + j);
+        d[0] = (E)tensor_elem<DT>(St::get(s, 0), tp.scale[0], tp.bias[0]);
+        d[b.chs] = (E)tensor_elem<DT>(St::get(s, 1), tp.scale[1], tp.bias[1]);
+        d[2 * b.chs] = (E)tensor_elem<DT>(St::get(s, 2), tp.scale[2], tp.bias[2]);
+      }
+    }
+    __syncthreads();                                      // the stage is written again by the next block of rows
+  }
+}
+
 // Nearest neighbour runs in OUTPUT space for all eight codes: a lane owns four pixels of a DISPLAYED row, maps each back to its pixel (x, y) of P and from
 // there to the source sample k_tensor_nearest reads, and stores them with store_tensor4's shape.  The stores are as coalesced as the unoriented kernel's; the
 // reads of a quarter turn walk down source columns, which a down-scaling nearest kernel - it reads one sample in (scale factor)^2 - does sparsely either way.
 // No LDS.
-template <typename Pix, int DT>
-__global__ __launch_bounds__(256) void k_oriented_nearest(const OrientedParams* __restrict__ ps)
+template <typename Pix, int DT, typename Store>
+__device__ __forceinline__ void oriented_nearest_body(const typename Store::Block* ps, const int tx, const int ty)   // tx, ty: threadIdx.x / .y, as in oriented_box_body
 {
-  const OrientedParams op = ps[blockIdx.z];
+  const typename Store::Block blk = ps[blockIdx.z];
+  const OrientedParams& op = Store::inner(blk);
+  const Store st(blk);
   const TensorParams& tp = op.t;
   const ColorParams& p = tp.c;
   const int quarter = op.code & 1, fx = ((op.code >> 1) ^ (op.code >> 2)) & 1, fy = ((op.code >> 1) ^ op.code) & 1;
   const int dw = quarter ? tp.oh : tp.ow, dh = quarter ? tp.ow : tp.oh;   // the displayed size
-  const int X0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  const int X0 = (blockIdx.x * blockDim.x + tx) * 4;
   if (X0 >= dw) return;
   const int npx = min(4, dw - X0);
   const bool mono = p.arith == AR_MONO;
   const int ra = quarter ? tp.rh : tp.rw, rc = quarter ? tp.rw : tp.rh;   // the window's extent along a displayed row, and across the rows
-  for (int Yd = blockIdx.y * blockDim.y + threadIdx.y; Yd < dh; Yd += gridDim.y * blockDim.y) {
+  for (int Yd = blockIdx.y * blockDim.y + ty; Yd < dh; Yd += gridDim.y * blockDim.y) {
     const int c = fy ? dh - 1 - Yd : Yd;
     const int sc = (int)((uint64_t)c * (uint64_t)rc / (uint64_t)dh);
     int Y[4], CB[4], CR[4], R[4], G[4], B[4];
@@ -818,8 +1040,20 @@ __global__ __launch_bounds__(256) void k_oriented_nearest(const OrientedParams* 
       }
     }
     tensor_convert4<Pix>(p, Y, CB, CR, R, G, B);
-    store_oriented4<DT>(op, dw, dh, 0, X0, Yd, npx, R, G, B);
+    st.template group4<DT>(op, dw, dh, 0, X0, Yd, npx, R, G, B);
   }
+}
+
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) void k_oriented_nearest(const OrientedParams* __restrict__ ps)
+{
+  oriented_nearest_body<Pix, DT, DenseStore<OrientedParams>>(ps, threadIdx.x, threadIdx.y);
+}
+
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) void k_patch_nearest(const PatchParams* __restrict__ ps)
+{
+  oriented_nearest_body<Pix, DT, PatchStore<PatchParams>>(ps, threadIdx.x, threadIdx.y);
 }
 
 // ---- placed tensor output (include/heif_hipdec.h hipdec_batch_to_tensor_placed): the oriented / resampling kernels write an entry's sample into its
@@ -985,17 +1219,19 @@ __device__ __forceinline__ uint32_t resample_pack(const int (&s)[3])
   return (uint32_t)clip_i(s[0] >> 22, 255) | ((uint32_t)clip_i(s[1] >> 22, 255) << 8) | ((uint32_t)clip_i(s[2] >> 22, 255) << 16);
 }
 
-template <typename Pix, int DT>
-__global__ __launch_bounds__(256) void k_resample(const ResampleParams* __restrict__ ps)
+template <typename Pix, int DT, typename Store>
+__device__ __forceinline__ void resample_body(const typename Store::Block* ps, const int tid)   // tid: threadIdx.x, as in oriented_box_body
 {
   __shared__ uint32_t src[kResSR][kResSpan];
   __shared__ uint32_t hrow[kResSR][kResTC];
   __shared__ uint32_t otile[kResTR][kResTC + 1];
-  const ResampleParams rp = ps[blockIdx.z];   // wave-uniform: scalar loads into SGPRs
+  const typename Store::Block blk = ps[blockIdx.z];   // wave-uniform: scalar loads into SGPRs
+  const ResampleParams& rp = Store::inner(blk);
+  const Store st(blk);
   const OrientedParams& op = rp.o;
   const TensorParams& tp = op.t;
   const ColorParams& p = tp.c;
-  const int tid = threadIdx.x, c = tid & (kResTC - 1), rg = tid / kResTC;   // rg: the wave - source row of the chunk in H, row group of the band in V
+  const int c = tid & (kResTC - 1), rg = tid / kResTC;   // rg: the wave - source row of the chunk in H, row group of the band in V   // rg: the wave - source row of the chunk in H, row group of the band in V
   const int tile = max(1, min(tp.tile, kResTC));
   const int ox0 = blockIdx.x * tile;
   if (ox0 >= tp.ow) return;                               // (the whole workgroup)
@@ -1083,7 +1319,7 @@ __global__ __launch_bounds__(256) void k_resample(const ResampleParams* __restri
           R[i] = (int)(s & 255u); G[i] = (int)((s >> 8) & 255u); B[i] = (int)((s >> 16) & 255u);
         }
         const int oy = oy0 + (int)r;
-        store_oriented4<DT>(op, tp.ow, tp.oh, fx, ox0 + (int)g * 4, fy ? tp.oh - 1 - oy : oy, min(4, ncol - (int)g * 4), R, G, B);
+        st.template group4<DT>(op, tp.ow, tp.oh, fx, ox0 + (int)g * 4, fy ? tp.oh - 1 - oy : oy, min(4, ncol - (int)g * 4), R, G, B);
       }
     } else {          // a row of P is a displayed column: four rows of P at column x are four neighbours of displayed row Y
       const uint32_t ng = ((uint32_t)nrow + 3u) >> 2, total = ng * (uint32_t)ncol;
@@ -1096,11 +1332,26 @@ __global__ __launch_bounds__(256) void k_resample(const ResampleParams* __restri
           R[i] = (int)(s & 255u); G[i] = (int)((s >> 8) & 255u); B[i] = (int)((s >> 16) & 255u);
         }
         const int x = ox0 + (int)cc;
-        store_oriented4<DT>(op, tp.oh, tp.ow, fx, oy0 + (int)g * 4, fy ? tp.ow - 1 - x : x, min(4, nrow - (int)g * 4), R, G, B);
+        st.template group4<DT>(op, tp.oh, tp.ow, fx, oy0 + (int)g * 4, fy ? tp.ow - 1 - x : x, min(4, nrow - (int)g * 4), R, G, B);
       }
     }
     __syncthreads();                                      // the tile is written again by the next band
   }
+}
+
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) void k_resample(const ResampleParams* __restrict__ ps)
+{
+  resample_body<Pix, DT, DenseStore<ResampleParams>>(ps, threadIdx.x);
+}
+
+// the resampler of a patch sequence: its quarter-turn write-out already goes in 4-pixel groups along displayed rows (bands of kResTR = 16 rows of P start at
+// multiples of 16), so the blocked group store serves both write-outs
+struct PatchResampleParams { ResampleParams in; PatchInfo b; };
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) void k_patch_resample(const PatchResampleParams* __restrict__ ps)
+{
+  resample_body<Pix, DT, PatchStore<PatchResampleParams>>(ps, threadIdx.x);
 }
 
 template <typename Pix>
@@ -1445,7 +1696,7 @@ thread_local std::vector<CapturedScaled> t_captured_scaled;
 // the recorded blocks go out as one launch (hipdec::color_tensor_launch).  Taken and checked like a scale request.
 struct TensorReq { bool on = false; hipdec::TensorRequest r; };
 thread_local TensorReq t_tensor;
-struct CapturedTensor { TensorParams p; int wide; int oriented, code; uint64_t pitch; int plane_rows; int resample; };   // oriented: for the k_oriented_* kernels, with a code, a row pitch and the rows of a channel plane; resample: the filter, for k_resample (code and pitch are set for every entry)
+struct CapturedTensor { TensorParams p; int wide; int oriented, code; uint64_t pitch; int plane_rows; int resample; int patch, merge; /* patch > 0: a patch sequence, for the k_patch_* kernels */ };   // oriented: for the k_oriented_* kernels, with a code, a row pitch and the rows of a channel plane; resample: the filter, for k_resample (code and pitch are set for every entry)
 thread_local std::vector<CapturedTensor> t_captured_tensor;
 
 // ---- the coefficient tables of HIPDEC_SCALE_BILINEAR / _BICUBIC: Pillow's precompute_coeffs + normalize_coeffs_8bpc (src/libImaging/Resample.c), statement
@@ -1598,7 +1849,7 @@ int record_tensor(const ColorParams& p)
     tp.flip = 0;      // folded into the code
   }
   t_tensor.on = false;   // taken
-  t_captured_tensor.push_back(CapturedTensor{tp, sizeof(Pix) == 2, r.oriented ? 1 : 0, r.code, (uint64_t)r.pitch, r.plane_rows, r.resample});
+  t_captured_tensor.push_back(CapturedTensor{tp, sizeof(Pix) == 2, r.oriented ? 1 : 0, r.code, (uint64_t)r.pitch, r.plane_rows, r.resample, r.patch, r.merge});
   return 0;
   }
 }
@@ -1843,6 +2094,35 @@ void launch_oriented_grid(const OrientedParams* dev, int n, int filter, int ow, 
   }
 }
 
+// the blocked store's constants of an entry (PatchInfo above): its displayed width is a multiple of patch * merge
+PatchInfo patch_info_of(const CapturedTensor& c)
+{
+  PatchInfo b;
+  memset(&b, 0, sizeof(b));
+  const uint32_t P = (uint32_t)c.patch, m = (uint32_t)c.merge, dw = (uint32_t)(c.code & 1 ? c.p.oh : c.p.ow);
+  auto magic = [](uint32_t d) { const uint64_t v = (1ull << 32) / d; return (uint32_t)(v > 0xffffffffull ? 0xffffffffull : v); };
+  b.P = P; b.m = m; b.magicP = magic(P); b.magicM = magic(m);
+  b.tok = 3u * P * P; b.tokm = m * m * b.tok; b.mtok = m * b.tok;
+  b.pxs = c.p.nhwc ? 3u : 1u; b.chs = c.p.nhwc ? 1u : P * P; b.prow = P * b.pxs;
+  b.rowtok = (uint64_t)(dw / P / m) * (uint64_t)b.tokm;
+  return b;
+}
+
+template <typename Pix, int DT>
+void launch_patch_grid(const PatchParams* dev, int n, int filter, int ow, int oh, int gy_box, int tiles, hipStream_t s)
+{
+  if (filter == HIPDEC_SCALE_BOX) {
+    dim3 block(256), grid(tiles, gy_box < 65535 ? gy_box : 65535, n);
+    hipLaunchKernelGGL((k_patch_box<Pix, DT>), grid, block, 0, s, dev);
+  } else {
+    const int gy = (oh + 3) / 4;
+    dim3 block(64, 4), grid(((ow + 3) / 4 + 63) / 64, gy < 16384 ? gy : 16384, n);
+    hipLaunchKernelGGL((k_patch_nearest<Pix, DT>), grid, block, 0, s, dev);
+  }
+}
+
+std::atomic<uint64_t> g_packed_calls{0}, g_packed_entries{0}, g_packed_patch_entries{0};
+
 // the oriented form of color_tensor_launch: entries of all codes and (RGB form) sizes share the launch, so the grid covers the largest of each extent
 int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int filter, int dtype, hipStream_t s)
 {
@@ -1860,13 +2140,19 @@ int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
     max_dw = dw > max_dw ? dw : max_dw; max_dh = dh > max_dh ? dh : max_dh; max_blocks = blocks > max_blocks ? blocks : max_blocks;
     quarter += (uint64_t)(c.code & 1);
   }
-  const size_t bytes = caps.size() * sizeof(OrientedParams);
+  const bool blocked = caps[0].patch > 0;   // (a call's entries are all patch sequences, or none is): PatchParams blocks for the k_patch_* kernels
+  const size_t block_bytes = blocked ? sizeof(PatchParams) : sizeof(OrientedParams);
+  const size_t bytes = caps.size() * block_bytes;
   std::vector<uint8_t> host(bytes);
   for (size_t i = 0; i < caps.size(); i++) {
     OrientedParams op;
     memset(&op, 0, sizeof(op));
     op.t = caps[i].p; op.code = (uint16_t)caps[i].code; op.rb = (uint16_t)block_rows(caps[i]); op.pitch = caps[i].pitch; op.plane_rows = caps[i].plane_rows;
-    memcpy(host.data() + i * sizeof(OrientedParams), &op, sizeof(op));
+    memcpy(host.data() + i * block_bytes, &op, sizeof(op));
+    if (blocked) {
+      const PatchInfo b = patch_info_of(caps[i]);
+      memcpy(host.data() + i * block_bytes + offsetof(PatchParams, b), &b, sizeof(b));
+    }
   }
   if (st.dev_bytes < bytes) {
     if (st.dev) arena_release(st.dev, st.dev_bytes);
@@ -1880,8 +2166,16 @@ int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
   }
   for (size_t first = 0; first < caps.size(); first += 65535) {
     const OrientedParams* dev = (const OrientedParams*)st.dev + first;
+    const PatchParams* pdev = (const PatchParams*)st.dev + first;
     const int n = (int)(caps.size() - first < 65535 ? caps.size() - first : 65535);
-    switch (caps[0].wide * 4 + dtype) {
+    if (blocked) switch (caps[0].wide * 4 + dtype) {
+#define X(DT) case DT: launch_patch_grid<uint8_t, DT>(pdev, n, filter, max_dw, max_dh, max_blocks, max_tiles, s); break; \
+              case 4 + DT: launch_patch_grid<uint16_t, DT>(pdev, n, filter, max_dw, max_dh, max_blocks, max_tiles, s); break;
+      X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
+#undef X
+      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "oriented output: unknown dtype %d", dtype);
+    }
+    else switch (caps[0].wide * 4 + dtype) {
 #define X(DT) case DT: launch_oriented_grid<uint8_t, DT>(dev, n, filter, max_dw, max_dh, max_blocks, max_tiles, s); break; \
               case 4 + DT: launch_oriented_grid<uint16_t, DT>(dev, n, filter, max_dw, max_dh, max_blocks, max_tiles, s); break;
       X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
@@ -1905,6 +2199,12 @@ void launch_resample_grid(const ResampleParams* dev, int n, int tiles, int bands
   dim3 block(256), grid(tiles, bands < 65535 ? bands : 65535, n);
   hipLaunchKernelGGL((k_resample<Pix, DT>), grid, block, 0, s, dev);
 }
+template <typename Pix, int DT>
+void launch_patch_resample_grid(const PatchResampleParams* dev, int n, int tiles, int bands, hipStream_t s)
+{
+  dim3 block(256), grid(tiles, bands < 65535 ? bands : 65535, n);
+  hipLaunchKernelGGL((k_patch_resample<Pix, DT>), grid, block, 0, s, dev);
+}
 
 int resample_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int filter, int dtype, hipStream_t s)
 {
@@ -1926,7 +2226,9 @@ int resample_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
     max_tiles = tiles > max_tiles ? tiles : max_tiles; max_bands = bands > max_bands ? bands : max_bands;
     quarter += (uint64_t)(c.code & 1);
   }
-  const size_t params_bytes = (caps.size() * sizeof(ResampleParams) + 15) & ~(size_t)15;
+  const bool blocked = caps[0].patch > 0;   // (as in oriented_launch): PatchResampleParams blocks for k_patch_resample
+  const size_t block_bytes = blocked ? sizeof(PatchResampleParams) : sizeof(ResampleParams);
+  const size_t params_bytes = (caps.size() * block_bytes + 15) & ~(size_t)15;
   const size_t bytes = params_bytes + (size_t)ints * sizeof(int32_t);
   std::vector<uint8_t> host(bytes);
   for (const auto& w : where) resample_table_fill(w.first.first, w.first.second, filter, (int32_t*)(host.data() + params_bytes) + w.second);
@@ -1943,7 +2245,11 @@ int resample_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
     rp.o.t = c.p; rp.o.code = (uint16_t)c.code; rp.o.rb = (uint16_t)kResTR; rp.o.pitch = c.pitch; rp.o.plane_rows = c.plane_rows;
     rp.xt = tables_dev + where[std::make_pair(c.p.rw, c.p.ow)]; rp.xstride = resample_axis_of(c.p.rw, c.p.ow, filter).stride;
     rp.yt = tables_dev + where[std::make_pair(c.p.rh, c.p.oh)]; rp.ystride = resample_axis_of(c.p.rh, c.p.oh, filter).stride;
-    memcpy(host.data() + i * sizeof(ResampleParams), &rp, sizeof(rp));
+    memcpy(host.data() + i * block_bytes, &rp, sizeof(rp));
+    if (blocked) {
+      const PatchInfo b = patch_info_of(c);
+      memcpy(host.data() + i * block_bytes + offsetof(PatchResampleParams, b), &b, sizeof(b));
+    }
   }
   if (st.host != host) {   // steady state (same windows, sizes, codes and output): nothing to upload
     st.prev.swap(st.host);
@@ -1952,8 +2258,16 @@ int resample_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
   }
   for (size_t first = 0; first < caps.size(); first += 65535) {
     const ResampleParams* dev = (const ResampleParams*)st.dev + first;
+    const PatchResampleParams* pdev = (const PatchResampleParams*)st.dev + first;
     const int n = (int)(caps.size() - first < 65535 ? caps.size() - first : 65535);
-    switch (caps[0].wide * 4 + dtype) {
+    if (blocked) switch (caps[0].wide * 4 + dtype) {
+#define X(DT) case DT: launch_patch_resample_grid<uint8_t, DT>(pdev, n, max_tiles, max_bands, s); break; \
+              case 4 + DT: launch_patch_resample_grid<uint16_t, DT>(pdev, n, max_tiles, max_bands, s); break;
+      X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
+#undef X
+      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "resampled output: unknown dtype %d", dtype);
+    }
+    else switch (caps[0].wide * 4 + dtype) {
 #define X(DT) case DT: launch_resample_grid<uint8_t, DT>(dev, n, max_tiles, max_bands, s); break; \
               case 4 + DT: launch_resample_grid<uint16_t, DT>(dev, n, max_tiles, max_bands, s); break;
       X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
@@ -2017,6 +2331,7 @@ int color_tensor_launch(ColorBatchState& st, int filter, int dtype, hipStream_t 
 // when they change, as the picture blocks are
 std::atomic<uint64_t> g_placed_calls{0}, g_placed_entries{0}, g_placed_margin_launches{0};
 void placed_note_call(uint64_t entries) { g_placed_calls++; g_placed_entries += entries; }
+void packed_note_call(uint64_t entries, bool patches) { g_packed_calls++; g_packed_entries += entries; if (patches) g_packed_patch_entries += entries; }
 
 int canvas_margin_launch(ColorBatchState& st, const CanvasMargin* blocks, int n, int dtype, hipStream_t s)
 {
@@ -2138,6 +2453,13 @@ void hipdec_oriented_stats(uint64_t* launches, uint64_t* entries, uint64_t* quar
   if (launches) *launches = g_oriented_launches.load();
   if (entries) *entries = g_oriented_entries.load();
   if (quarter_turn_entries) *quarter_turn_entries = g_oriented_quarter.load();
+}
+
+void hipdec_packed_stats(uint64_t* calls, uint64_t* entries, uint64_t* patch_entries)
+{
+  if (calls) *calls = g_packed_calls.load();
+  if (entries) *entries = g_packed_entries.load();
+  if (patch_entries) *patch_entries = g_packed_patch_entries.load();
 }
 
 void hipdec_placed_stats(uint64_t* calls, uint64_t* entries, uint64_t* margin_launches)

@@ -65,6 +65,7 @@ struct hipdec_batch : BatchLayout {
   ColorBatchState color_tensor; // ... and of hipdec_batch_to_tensor
   ColorBatchState color_oriented; // ... and of the oriented forms (hipdec_batch_to_tensor_oriented, hipdec_batch_to_rgb_scaled_oriented_all)
   ColorBatchState color_margin;   // ... and the margin blocks of hipdec_batch_to_tensor_placed
+  ColorBatchState color_packed;   // ... and of hipdec_batch_to_tensor_packed
   uint64_t max_pixels = 0;      // the limit given at creation (0: none): scaled outputs are held against it as well
   // decoder path (plugin): the output planes of every item staged in pinned host memory by ONE set of asynchronous copies behind the
   // kernels, so that N decoder instances sharing the batch do not queue N x 3 pageable device-to-host copies (stage_planes_to_host)
@@ -128,6 +129,7 @@ struct hipdec_batch : BatchLayout {
     color_batch_state_free(color_tensor);
     color_batch_state_free(color_oriented);
     color_batch_state_free(color_margin);
+    color_batch_state_free(color_packed);
     if (arena) arena_release(arena, arena_capacity);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : chain_events) if (e) (void)hipEventDestroy(e);
@@ -825,11 +827,12 @@ int tensor_window(const char* who, const hipdec_tensor_entry* e, int idx, int w,
 // presents the planes as the 4:4:4 image they are scaled to.  The entry point records the block (color.hip); elem0: the entry's first element.
 int tensor_record_entry(const char* who, const uint8_t* y, size_t ys, const uint8_t* cb, size_t cbs, const uint8_t* cr, size_t crs, int w, int h, int bits, int cf,
                         const hipdec_nclx* nclx, const hipdec_nclx* nclx_after_sdr, const hipdec_tensor_desc* d, int left, int top, int rw, int rh, int flip, void* elem0,
-                        int orientation = -1, size_t pitch = 0, int plane_rows = 0)
+                        int orientation = -1, size_t pitch = 0, int plane_rows = 0, int patch = 0, int merge = 1)
 {
   if (int rc = tensor_check_resample_depth(who, d, bits)) return rc;
   TensorRequest rq;
   memset(&rq, 0, sizeof(rq));
+  rq.patch = patch; rq.merge = merge;
   rq.ow = d->width; rq.oh = d->height;
   rq.resample = resample_filter(d->filter) ? d->filter : 0;
   if (orientation < 0 && rq.resample) {   // k_resample stores through the oriented path: an unoriented entry is code 0 (the mirror with a flip) and a dense pitch
@@ -964,25 +967,100 @@ void placed_entry(const hipdec_tensor_desc* d, const PlacedArgs& pa, int e, void
   for (int c = 0; c < 3; c++) { m->value[c] = pa.fill ? pa.fill->value[c] : 0.0f; m->scale[c] = d->scale[c]; m->bias[c] = d->bias[c]; }
 }
 
+// ---- packed tensor output (hipdec_batch_to_tensor_packed / hipdec_album_to_tensor_packed): what the two forms and hipdec_tensor_packed_layout share
+struct PackedArgs { const hipdec_tensor_sample* samples; int patch, merge; };
+
+int packed_check_patches(const char* who, const hipdec_tensor_patches* p)
+{
+  if (!p) return 0;
+  if (p->patch < 0 || p->patch > 256) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: patch %d is not 0 .. 256", who, p->patch);
+  if (p->merge < 1 || p->merge > 16) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: merge %d is not 1 .. 16", who, p->merge);
+  if (p->patch == 0 && p->merge != 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: merge %d without patches (dense samples take merge 1)", who, p->merge);
+  if (p->reserved[0] || p->reserved[1]) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: patches.reserved is not 0", who);
+  return 0;
+}
+
+int packed_check_size(const char* who, int e, int w, int h, int patch, int merge)
+{
+  if (w < 1 || h < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: sample size %d x %d", who, e, w, h);
+  if (patch && (w % (patch * merge) || h % (patch * merge)))
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: sample size %d x %d is not a multiple of patch * merge = %d", who, e, w, h, patch * merge);
+  return 0;
+}
+
+// what the arguments alone decide: the description has passed tensor_check_desc with a size of 1 x 1; *pk is filled from `patches`
+int packed_check(const char* who, const hipdec_tensor_desc* d, const hipdec_tensor_sample* samples, const hipdec_tensor_patches* patches, int n_entries, size_t out_bytes,
+                 PackedArgs* pk)
+{
+  if (!samples) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: no samples", who);
+  if (int rc = packed_check_patches(who, patches)) return rc;
+  pk->samples = samples; pk->patch = patches ? patches->patch : 0; pk->merge = patches ? patches->merge : 1;
+  const uint64_t room = (uint64_t)out_bytes / tensor_elem_bytes(d->dtype);
+  std::vector<std::pair<uint64_t, int>> order((size_t)n_entries);
+  for (int e = 0; e < n_entries; e++) {
+    const hipdec_tensor_sample& sm = samples[e];
+    if (int rc = packed_check_size(who, e, sm.width, sm.height, pk->patch, pk->merge)) return rc;
+    const uint64_t len = 3ull * (uint64_t)sm.width * (uint64_t)sm.height;
+    if (sm.offset > room || len > room - sm.offset)
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: sample of %llu elements at offset %llu leaves the output of %llu elements", who, e,
+                       (unsigned long long)len, (unsigned long long)sm.offset, (unsigned long long)room);
+    order[(size_t)e] = std::make_pair(sm.offset, e);
+  }
+  std::sort(order.begin(), order.end());
+  for (int k = 0; k + 1 < n_entries; k++) {
+    const hipdec_tensor_sample& a = samples[order[(size_t)k].second];
+    if (a.offset + 3ull * (uint64_t)a.width * (uint64_t)a.height > order[(size_t)k + 1].first)
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: its elements overlap those of entry %d", who, order[(size_t)k + 1].second, order[(size_t)k].second);
+  }
+  return 0;
+}
+
+struct PackedSpec { const hipdec_tensor_sample* samples; const hipdec_tensor_patches* patches; };   // as the caller gave them
+
+// entry e of a packed call: *sample is the description of the sample at its own size, *elem0 its first element
+void packed_entry(const hipdec_tensor_desc* d, const PackedArgs& pk, int e, void* out_dev, hipdec_tensor_desc* sample, void** elem0)
+{
+  *sample = *d;
+  sample->width = pk.samples[e].width; sample->height = pk.samples[e].height;
+  *elem0 = (uint8_t*)out_dev + (size_t)pk.samples[e].offset * tensor_elem_bytes(d->dtype);
+}
+
+// the description of a packed call: the sizes are per sample, so its own must be 0; *unit is the copy the description's other checks see
+int packed_check_desc(const char* who, const hipdec_tensor_desc* d, hipdec_tensor_desc* unit)
+{
+  if (!d) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  if (d->width || d->height) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: desc size %d x %d: the sizes are per sample, desc->width and height must be 0", who, d->width, d->height);
+  *unit = *d;
+  unit->width = unit->height = 1;
+  return 0;
+}
+
 // hipdec_batch_to_tensor, and - oriented - hipdec_batch_to_tensor_oriented: the same checks, windows and planner rules; the oriented form records its blocks
 // for the k_oriented_* kernels (color.hip) and keeps them in a parameter array of its own
 // Placed (pa; always oriented): the sample goes into its rectangle of the canvas desc describes, k_canvas_margin (color.hip) writes the rest.
 int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations, bool oriented, int n_entries,
-                         void* out_dev, size_t out_bytes, void* stream, const PlacedArgs* pa = nullptr)
+                         void* out_dev, size_t out_bytes, void* stream, const PlacedArgs* pa = nullptr, const PackedSpec* ps = nullptr)
 {
   if (!b || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: bad arguments");
   size_t bytes = 0;
-  if (int rc = tensor_check_desc("to_tensor", desc, n_entries, &bytes)) return rc;
+  hipdec_tensor_desc unit;
+  PackedArgs pk{nullptr, 0, 1};
+  if (ps) if (int rc = packed_check_desc("to_tensor_packed", desc, &unit)) return rc;
+  if (int rc = tensor_check_desc("to_tensor", ps ? &unit : desc, n_entries, &bytes)) return rc;
   if (oriented) if (int rc = check_orientations("to_tensor_oriented", "entry", orientations, n_entries)) return rc;
   if (pa) if (int rc = placed_check("to_tensor_placed", desc, *pa, n_entries)) return rc;
-  if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
+  if (ps) { if (int rc = packed_check("to_tensor_packed", desc, ps->samples, ps->patches, n_entries, out_bytes, &pk)) return rc; }
+  else if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
   // (everything above is decided without reading the handle)
   if (!entries && n_entries != (int)b->pics.size())
     return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: %d entries without an entry list, the batch has %d items", n_entries, (int)b->pics.size());
   DeviceScope scope(b->device);
   if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: the batch's arena was handed to another batch");
-  if (b->max_pixels && (uint64_t)desc->width * (uint64_t)desc->height > b->max_pixels)
+  if (!ps && b->max_pixels && (uint64_t)desc->width * (uint64_t)desc->height > b->max_pixels)
     return set_error(HIPDEC_ERR_LIMIT, "to_tensor: output of %d x %d pixels exceeds max_image_size_pixels", desc->width, desc->height);
+  for (int e = 0; ps && b->max_pixels && e < n_entries; e++)
+    if ((uint64_t)pk.samples[e].width * (uint64_t)pk.samples[e].height > b->max_pixels)
+      return set_error(HIPDEC_ERR_LIMIT, "to_tensor_packed: entry %d: sample of %d x %d pixels exceeds max_image_size_pixels", e, pk.samples[e].width, pk.samples[e].height);
   return guarded("to_tensor", [&]() -> int {
     hipStream_t s = follow_stream(b, stream);
     const size_t entry_bytes = bytes / (size_t)n_entries;
@@ -1006,22 +1084,24 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
         placed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0, &margins[(size_t)e]);
         pitch = (size_t)desc->width * (desc->layout == HIPDEC_TENSOR_NHWC ? 3 : 1); plane_rows = desc->height;
       }
+      if (ps) packed_entry(desc, pk, e, out_dev, &sample, &elem0);   // (its own size, dense pitch and plane: the defaults of the sample's description)
       if (!rc) rc = tensor_record_entry("to_tensor", b->arena + P.off_out[0], P.out_stride[0], b->arena + P.off_out[1], P.out_stride[1], b->arena + P.off_out[2], P.out_stride[2],
                                         P.out_width, P.out_height, b->wide ? I.bit_depth_luma : 8, P.chroma_format_idc, &nclx, &nclx, &sample, left, top, rw, rh,
-                                        entries ? entries[e].flip : 0, elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows);
+                                        entries ? entries[e].flip : 0, elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows, pk.patch, pk.merge);
       if (rc) { color_tensor_abort(); return rc; }
     }
     const size_t slot = b->runs ? (b->runs - 1) % (b->ev.size() / kEv) : 0;
     hipEvent_t* ev = b->ev.data() + kEv * slot;
     HIPDEC_CHECK_HIP(hipEventRecord(ev[6], s));
     // (resampled entries are not hipdec_batch_tensor_block's blocks: they go with the oriented ones)
-    int rc = color_tensor_launch(oriented || resample_filter(desc->filter) ? b->color_oriented : b->color_tensor, desc->filter, desc->dtype, s);
+    int rc = color_tensor_launch(ps ? b->color_packed : (oriented || resample_filter(desc->filter) ? b->color_oriented : b->color_tensor), desc->filter, desc->dtype, s);
     if (!rc && pa) rc = canvas_margin_launch(b->color_margin, margins.data(), n_entries, desc->dtype, s);   // (disjoint elements: no order between the two but the stream's)
     HIPDEC_CHECK_HIP(hipEventRecord(ev[7], s));
     if (!rc && b->runs) b->colour_timed[slot] = 1;
     b->mark_done(s);
     if (!rc) { g_tensor_calls++; g_tensor_entries += (uint64_t)n_entries; }
     if (!rc && pa) placed_note_call((uint64_t)n_entries);
+    if (!rc && ps) packed_note_call((uint64_t)n_entries, pk.patch > 0);
     return rc;
   });
 }
@@ -1125,6 +1205,33 @@ int hipdec_batch_to_tensor_placed(hipdec_batch* b, const hipdec_tensor_desc* des
 {
   const PlacedArgs pa{places, fill, mask_dev};
   return batch_to_tensor_impl(b, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, &pa);
+}
+
+int hipdec_batch_to_tensor_packed(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                  const hipdec_tensor_sample* samples, const hipdec_tensor_patches* patches, int n_entries, void* out_dev, size_t out_bytes, void* stream)
+{
+  const PackedSpec ps{samples, patches};
+  return batch_to_tensor_impl(b, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, nullptr, &ps);
+}
+
+int hipdec_tensor_packed_layout(const hipdec_tensor_patches* patches, const int* widths, const int* heights, int n, uint64_t* offsets, uint32_t* tokens,
+                                uint64_t* total_elements)
+{
+  if (!widths || !heights || n < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_packed_layout: bad arguments"), -1;
+  if (packed_check_patches("tensor_packed_layout", patches)) return -1;
+  const int patch = patches ? patches->patch : 0, merge = patches ? patches->merge : 1;
+  uint64_t at = 0;
+  for (int e = 0; e < n; e++) {
+    if (packed_check_size("tensor_packed_layout", e, widths[e], heights[e], patch, merge)) return -1;
+    const uint64_t len = 3ull * (uint64_t)widths[e] * (uint64_t)heights[e];
+    const uint64_t tok = patch ? (uint64_t)(widths[e] / patch) * (uint64_t)(heights[e] / patch) : 0;
+    if (tok > 0xffffffffull || len > ~0ull - at) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_packed_layout: entry %d: the sequence is too long", e), -1;
+    if (offsets) offsets[e] = at;
+    if (tokens) tokens[e] = (uint32_t)tok;
+    at += len;
+  }
+  if (total_elements) *total_elements = at;
+  return 0;
 }
 
 int hipdec_letterbox_place(int src_width, int src_height, int canvas_width, int canvas_height, int upscale, int anchor, hipdec_tensor_place* out)

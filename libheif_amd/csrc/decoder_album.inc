@@ -28,6 +28,7 @@ struct hipdec_album {
   ColorBatchState color, color_scaled, color_tensor;   // parameter blocks of the three output stages (their own, as hipdec_batch's)
   ColorBatchState color_oriented;                      // ... and of the oriented forms
   ColorBatchState color_margin;                        // ... and the margin blocks of hipdec_album_to_tensor_placed
+  ColorBatchState color_packed;                        // ... and of hipdec_album_to_tensor_packed
   uint64_t max_pixels = 0;
   bool ran = false;
   ~hipdec_album()
@@ -40,6 +41,7 @@ struct hipdec_album {
     color_batch_state_free(color_tensor);
     color_batch_state_free(color_oriented);
     color_batch_state_free(color_margin);
+    color_batch_state_free(color_packed);
     if (canvas) arena_release(canvas, canvas_capacity);
   }
 };
@@ -315,21 +317,28 @@ int album_rgb_entries(const char* who, hipdec_album* a, int out_chroma, const in
 
 // hipdec_batch_to_tensor over the canvases: entry.item names a photo, the window lies in its output size; oriented and placed (pa): as batch_to_tensor_impl
 int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations, bool oriented, int n_entries,
-                         void* out_dev, size_t out_bytes, void* stream, const PlacedArgs* pa = nullptr)
+                         void* out_dev, size_t out_bytes, void* stream, const PlacedArgs* pa = nullptr, const PackedSpec* ps = nullptr)
 {
   if (!a || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_tensor: bad arguments");
   size_t bytes = 0;
-  if (int rc = tensor_check_desc("album_to_tensor", desc, n_entries, &bytes)) return rc;
+  hipdec_tensor_desc unit;
+  PackedArgs pk{nullptr, 0, 1};
+  if (ps) if (int rc = packed_check_desc("album_to_tensor_packed", desc, &unit)) return rc;
+  if (int rc = tensor_check_desc("album_to_tensor", ps ? &unit : desc, n_entries, &bytes)) return rc;
   if (oriented) if (int rc = check_orientations("album_to_tensor_oriented", "entry", orientations, n_entries)) return rc;
   if (pa) if (int rc = placed_check("album_to_tensor_placed", desc, *pa, n_entries)) return rc;
-  if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
+  if (ps) { if (int rc = packed_check("album_to_tensor_packed", desc, ps->samples, ps->patches, n_entries, out_bytes, &pk)) return rc; }
+  else if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
   // (everything above is decided without reading the handle)
   const int n_photos = (int)a->photos.size();
   if (!entries && n_entries != n_photos)
     return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_tensor: %d entries without an entry list, the album has %d photos", n_entries, n_photos);
   DeviceScope scope(a->device);
-  if (a->max_pixels && (uint64_t)desc->width * (uint64_t)desc->height > a->max_pixels)
+  if (!ps && a->max_pixels && (uint64_t)desc->width * (uint64_t)desc->height > a->max_pixels)
     return set_error(HIPDEC_ERR_LIMIT, "album_to_tensor: output of %d x %d pixels exceeds max_image_size_pixels", desc->width, desc->height);
+  for (int e = 0; ps && a->max_pixels && e < n_entries; e++)
+    if ((uint64_t)pk.samples[e].width * (uint64_t)pk.samples[e].height > a->max_pixels)
+      return set_error(HIPDEC_ERR_LIMIT, "album_to_tensor_packed: entry %d: sample of %d x %d pixels exceeds max_image_size_pixels", e, pk.samples[e].width, pk.samples[e].height);
   return guarded("album_to_tensor", [&]() -> int {
     hipdec_batch* b = a->batch.get();
     hipStream_t s = follow_stream(b, stream);
@@ -353,15 +362,17 @@ int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const 
         placed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0, &margins[(size_t)e]);
         pitch = (size_t)desc->width * (desc->layout == HIPDEC_TENSOR_NHWC ? 3 : 1); plane_rows = desc->height;
       }
+      if (ps) packed_entry(desc, pk, e, out_dev, &sample, &elem0);
       if (!rc) rc = tensor_record_entry("album_to_tensor", S.plane[0], S.stride[0], S.plane[1], S.stride[1], S.plane[2], S.stride[2], S.width, S.height,
                                         S.wide ? I.bit_depth_luma : 8, S.chroma_format_idc, &nclx, &nclx, &sample, left, top, rw, rh, entries ? entries[e].flip : 0,
-                                        elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows);
+                                        elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows, pk.patch, pk.merge);
       if (rc) { color_tensor_abort(); return rc; }
     }
-    int rc = color_tensor_launch(oriented || resample_filter(desc->filter) ? a->color_oriented : a->color_tensor, desc->filter, desc->dtype, s);
+    int rc = color_tensor_launch(ps ? a->color_packed : (oriented || resample_filter(desc->filter) ? a->color_oriented : a->color_tensor), desc->filter, desc->dtype, s);
     if (!rc && pa) rc = canvas_margin_launch(a->color_margin, margins.data(), n_entries, desc->dtype, s);
     b->mark_done(s);
     if (!rc && pa) placed_note_call((uint64_t)n_entries);
+    if (!rc && ps) packed_note_call((uint64_t)n_entries, pk.patch > 0);
     return rc;
   });
 }
@@ -387,6 +398,13 @@ int hipdec_album_to_tensor_placed(hipdec_album* a, const hipdec_tensor_desc* des
 {
   const PlacedArgs pa{places, fill, mask_dev};
   return album_to_tensor_impl(a, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, &pa);
+}
+
+int hipdec_album_to_tensor_packed(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                  const hipdec_tensor_sample* samples, const hipdec_tensor_patches* patches, int n_entries, void* out_dev, size_t out_bytes, void* stream)
+{
+  const PackedSpec ps{samples, patches};
+  return album_to_tensor_impl(a, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, nullptr, &ps);
 }
 
 int hipdec_album_to_rgb_scaled_oriented_all(hipdec_album* a, int out_chroma, const int* orientations, const int* out_widths, const int* out_heights, int filter,

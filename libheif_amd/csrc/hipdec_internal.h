@@ -96,8 +96,11 @@ int scale_planes_launch(PlaneScaleParams* jobs, int n, int bytes_per_sample, int
 // Oriented output: `oriented` sends the block to the k_oriented_* kernels - ow x oh is then the PRE-orientation size, `code` the hipdec_orientation with the
 // entry's flip folded in, `pitch` the elements from one displayed row to the next, `plane_rows` the rows of a channel plane (NCHW: the plane is
 // plane_rows * pitch elements; a dense sample: its displayed rows, a placed one: the canvas' rows).
+// Packed output, patch sequences: `patch` > 0 sends the (oriented) block to the k_patch_* kernels, which store the sample as tokens of patch x patch pixels in
+// groups of merge x merge (hipdec_batch_to_tensor_packed); pitch and plane_rows are then not read.
 struct TensorRequest { int ow, oh, sH, sV, left, top, rw, rh, flip, nhwc; float scale[3], bias[3]; int oriented, code; size_t pitch; int plane_rows;
-                       int resample; /* HIPDEC_SCALE_BILINEAR / _BICUBIC: the block is recorded for k_resample, code and pitch set for every entry (0: no) */ };
+                       int resample; /* HIPDEC_SCALE_BILINEAR / _BICUBIC: the block is recorded for k_resample, code and pitch set for every entry (0: no) */
+                       int patch, merge; };
 void color_tensor_request(const TensorRequest& r);
 void color_tensor_clear();
 bool color_tensor_pending();
@@ -122,6 +125,7 @@ struct CanvasMargin {
 // launches when an entry has a margin or a mask (nothing otherwise); dtype: hipdec_tensor_dtype
 int canvas_margin_launch(ColorBatchState& st, const CanvasMargin* blocks, int n, int dtype, hipStream_t s);
 void placed_note_call(uint64_t entries);   // hipdec_placed_stats
+void packed_note_call(uint64_t entries, bool patches);   // hipdec_packed_stats
 
 // The paste of an album of grid photos (transform.hip k_album_paste): one job per (tile, plane), already clipped to the photo's output size by the host
 // (a job clipped to nothing is not emitted); the job table lives in device memory and all jobs go out as ONE launch.

@@ -86,6 +86,13 @@ def _bind(lib):
     lib.hipdec_letterbox_place.argtypes = [ci, ci, ci, ci, ci, ci, C.POINTER(TensorPlace)]
     lib.hipdec_placed_stats.restype = None
     lib.hipdec_placed_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
+    packed = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), C.POINTER(ci), C.POINTER(TensorSample), C.POINTER(TensorPatches), ci, vp, sz, vp]
+    lib.hipdec_batch_to_tensor_packed.argtypes = packed
+    lib.hipdec_album_to_tensor_packed.argtypes = packed
+    lib.hipdec_tensor_packed_layout.argtypes = [C.POINTER(TensorPatches), C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                                C.POINTER(C.c_uint64)]
+    lib.hipdec_packed_stats.restype = None
+    lib.hipdec_packed_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
     lib._dec_bound = True
     return lib
 
@@ -114,6 +121,16 @@ class TensorPlace(C.Structure):
 class TensorFill(C.Structure):
     """hipdec_tensor_fill"""
     _fields_ = [("value", C.c_float * 3), ("domain", C.c_int), ("reserved", C.c_int)]
+
+
+class TensorSample(C.Structure):
+    """hipdec_tensor_sample"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("offset", C.c_uint64)]
+
+
+class TensorPatches(C.Structure):
+    """hipdec_tensor_patches"""
+    _fields_ = [("patch", C.c_int), ("merge", C.c_int), ("reserved", C.c_int * 2)]
 
 
 FILL_DOMAINS = {"component": 0, "element": 1}                                 # hipdec_fill_domain
@@ -386,6 +403,102 @@ def placed_stats():
     a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
     lib.hipdec_placed_stats(C.byref(a), C.byref(b), C.byref(c))
     return a.value, b.value, c.value
+
+
+def packed_layout(sizes, patch=0, merge=1):
+    """(offsets, tokens, total elements) of samples of the DISPLAYED sizes (width, height) packed back to back in entry order
+    (hipdec_tensor_packed_layout; host only): offsets[e] is the index of sample e's first element, tokens[e] its (width / patch) * (height / patch) patch
+    tokens (0 for dense samples, patch 0).  A size that is no multiple of patch * merge raises ValueError."""
+    lib = _bind(load_library())
+    n = len(sizes)
+    ws, hs = (C.c_int * n)(*(int(s[0]) for s in sizes)), (C.c_int * n)(*(int(s[1]) for s in sizes))
+    offs, toks, total = (C.c_uint64 * n)(), (C.c_uint32 * n)(), C.c_uint64()
+    pt = TensorPatches(int(patch), int(merge))
+    if lib.hipdec_tensor_packed_layout(C.byref(pt), ws, hs, n, offs, toks, C.byref(total)) != 0:
+        raise ValueError("packed_layout: %s" % lib.hipdec_last_error().decode())
+    return list(offs), list(toks), total.value
+
+
+def packed_stats():
+    """(packed to_tensor calls, their entries, entries written as patch sequences) since load"""
+    lib = _bind(load_library())
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    lib.hipdec_packed_stats(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def _to_tensor_packed(self, call, sizes, entries, patch, merge, dtype, layout, mean, std, scale, bias, filter, orientations, offsets, out, stream):
+    """Batch.to_tensor_packed / Album.to_tensor_packed: the samples, the 1-D output buffer (DeviceBuffer or torch.Tensor) and the stream, then `call`"""
+    n = self.n if entries is None else len(entries)
+    sizes = [(int(w), int(h)) for w, h in sizes]
+    if len(sizes) != n:
+        raise ValueError("%d sizes for %d entries" % (len(sizes), n))
+    patch, merge = int(patch), int(merge)
+    if offsets is None:
+        offsets, _, total = packed_layout(sizes, patch, merge)
+    else:
+        offsets = [int(o) for o in offsets]
+        if len(offsets) != n:
+            raise ValueError("%d offsets for %d entries" % (len(offsets), n))
+        total = max(o + 3 * w * h for o, (w, h) in zip(offsets, sizes))
+    samples = (TensorSample * n)(*(TensorSample(w, h, o) for (w, h), o in zip(sizes, offsets)))
+    pt = TensorPatches(patch, merge)
+    codes = None if orientations is None else _orientation_array(orientations, n)
+    d0 = self.info(0)
+    max_value = (1 << d0["bit_depth_luma"]) - 1 if (dtype != "uint8" and d0["bit_depth_luma"] > 8) else 255
+    sc, bi = tensor_scale_bias(mean, std, scale, bias, max_value)
+    desc = tensor_desc((0, 0), dtype, layout, filter, sc, bi)
+    item = np.dtype(_TENSOR_NUMPY[dtype]).itemsize
+    arr = None if entries is None else tensor_entries(entries)
+    host_wait = False
+    if out is None:
+        torch = _torch_gpu()
+        out = torch.empty((total,), dtype=getattr(torch, dtype), device="cuda") if torch is not None else DeviceBuffer(max(total * item, 1))
+    if isinstance(out, DeviceBuffer):
+        ptr, room = out.ptr, out.nbytes
+    else:
+        import torch
+        if not isinstance(out, torch.Tensor) or not out.is_cuda:
+            raise TypeError("out must be a DeviceBuffer or a CUDA / HIP torch.Tensor")
+        if out.dim() != 1 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous 1-D tensor")
+        if out.dtype != getattr(torch, dtype):
+            raise ValueError("out has dtype %s, the tensor has %s" % (out.dtype, dtype))
+        ptr, room = out.data_ptr(), out.numel() * item
+        if stream is None:
+            ts = torch.cuda.current_stream(out.device)
+            stream = ts.cuda_stream or None
+            if stream is None:   # (torch's legacy default stream: ordered on the host, as in to_tensor)
+                ts.synchronize()
+                host_wait = True
+    check(call(self._h, C.byref(desc), arr, codes, samples, C.byref(pt), n, ptr, room, stream))
+    if host_wait:
+        check(self._lib.hipdec_stream_synchronize(None))
+    self._tensor_packed = (out, room // item, _TENSOR_NUMPY[dtype], stream, sizes, offsets, patch, layout)
+    grids = [(h // patch, w // patch) for w, h in sizes] if patch else None
+    return out, offsets, grids
+
+
+def _tensor_packed_to_host(self):
+    """the last to_tensor_packed() result on the host; waits for its stream.  Patch sequences: one array [tokens, 3 * patch * patch], the samples' tokens in
+    entry order (gaps between samples left out).  Dense samples: (flat, view) - the whole output as a flat array, and view(e), sample e of it in the shape
+    of its layout, (3, height, width) or (height, width, 3).  bfloat16 comes as uint16 bit patterns."""
+    out, elems, dt, stream, sizes, offsets, patch, layout = self._tensor_packed
+    check(self._lib.hipdec_stream_synchronize(stream))
+    if isinstance(out, DeviceBuffer):
+        flat = out.to_numpy((elems,), dt)
+    else:
+        import torch
+        t = out.view(torch.int16) if dt == np.uint16 else out
+        flat = t.cpu().numpy()
+        flat = flat.view(np.uint16) if dt == np.uint16 else flat
+    if patch:
+        return np.concatenate([flat[o:o + 3 * w * h] for o, (w, h) in zip(offsets, sizes)]).reshape(-1, 3 * patch * patch)
+
+    def view(e):
+        w, h = sizes[e]
+        return flat[offsets[e]:offsets[e] + 3 * w * h].reshape((3, h, w) if layout == "NCHW" else (h, w, 3))
+    return flat, view
 
 
 def fit_within(width, height, size):
@@ -712,6 +825,22 @@ class Batch:
             return _to_tensor(self, self._lib.hipdec_batch_to_tensor_oriented, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations)
         return _to_tensor(self, self._lib.hipdec_batch_to_tensor, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
 
+    def to_tensor_packed(self, sizes, entries=None, patch=0, merge=1, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None,
+                         filter=SCALE_BOX, orientations=None, offsets=None, out=None, stream=None):
+        """asynchronous: every entry at its OWN displayed size sizes[e] = (width, height), all entries in one launch into one 1-D output
+        (hipdec_batch_to_tensor_packed) - what native-resolution vision encoders take.  Sample e is what to_tensor(sizes[e], ..., orientations=) writes for
+        the entry, stored from element offsets[e] on: densely in `layout` (patch 0), or as the sequence of its patch tokens (patch P >= 1, sizes multiples
+        of P * merge): token t = ((gy // m) * (gw // m) + gx // m) * m * m + (gy % m) * m + gx % m of patch (gy, gx), inside a token Conv2d weight order
+        (c, py, px) for "NCHW" and big_vision / NaFlex order (py, px, c) for "NHWC".  merge 2 is the token order of Qwen2-VL's image processor.
+        offsets None: the samples back to back in entry order (packed_layout()).  Choosing the sizes stays with the caller.
+        out: a DeviceBuffer, or a 1-D torch.Tensor (written on torch's current stream unless `stream` is given); None allocates one.
+        Returns (out, offsets, grids) with grids[e] = (height / P, width / P) for patches, None for dense samples; out[offsets[0]:].view(-1, 3 * P * P)
+        of back-to-back samples is the packed sequence.  tensor_packed_to_host() reads the result back."""
+        return _to_tensor_packed(self, self._lib.hipdec_batch_to_tensor_packed, sizes, entries, patch, merge, dtype, layout, mean, std, scale, bias, filter,
+                                 orientations, offsets, out, stream)
+
+    tensor_packed_to_host = _tensor_packed_to_host
+
     def tensor_to_host(self):
         """the last to_tensor() result as a NumPy array of the tensor's shape (bfloat16 as uint16 bit patterns); waits for its stream"""
         out, shape, dt, stream = self._tensor
@@ -917,6 +1046,14 @@ class Album:
 
     tensor_to_host = Batch.tensor_to_host
     tensor_mask_to_host = Batch.tensor_mask_to_host
+
+    def to_tensor_packed(self, sizes, entries=None, patch=0, merge=1, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None,
+                         filter=SCALE_BOX, orientations=None, offsets=None, out=None, stream=None):
+        """Batch.to_tensor_packed over the composed photos"""
+        return _to_tensor_packed(self, self._lib.hipdec_album_to_tensor_packed, sizes, entries, patch, merge, dtype, layout, mean, std, scale, bias, filter,
+                                 orientations, offsets, out, stream)
+
+    tensor_packed_to_host = _tensor_packed_to_host
 
     def paste_timing_us(self):
         """device time of the paste launch of the last run(), microseconds"""
