@@ -701,7 +701,7 @@ HIPDEC_API void hipdec_placed_stats(uint64_t* calls, uint64_t* entries, uint64_t
  * mixed 8-bit and wider entries, a float dtype from a source above 8 bits with BILINEAR / BICUBIC, resampling tables above 64 MiB - is refused with the same
  * status before anything is launched.
  * Out of scope: choosing the sizes stays with the caller, as reading `irot` does (Qwen's smart_resize and NaFlex's search over scales are float rules of
- * other projects); Qwen's duplicated temporal axis; margins and masks (a packed sample has none); the single-image form. */
+ * other projects); Qwen's duplicated temporal axis (hipdec_clips_to_tensor_packed below writes it); margins and masks (a packed sample has none); the single-image form. */
 typedef struct hipdec_tensor_sample { int width, height; uint64_t offset; } hipdec_tensor_sample;   /* DISPLAYED size; index of the sample's first element in out */
 typedef struct hipdec_tensor_patches { int patch, merge, reserved[2]; } hipdec_tensor_patches;      /* patch 0: dense samples; merge >= 1 */
 HIPDEC_API int hipdec_batch_to_tensor_packed(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
@@ -717,6 +717,87 @@ HIPDEC_API int hipdec_tensor_packed_layout(const hipdec_tensor_patches* patches,
                                            uint32_t* tokens, uint64_t* total_elements);
 /* counters since load: packed calls, their entries, and how many of those were written as patch sequences */
 HIPDEC_API void hipdec_packed_stats(uint64_t* calls, uint64_t* entries, uint64_t* patch_entries);
+
+/* ---- clips: the samples of several sequence tracks as ONE launch set, frames resident in device memory, video tensors ---------------------------------
+ * A video loader wants a clip: T sampled frames of a track, one crop window and one flip for the whole clip, resized and normalised, as N x T x 3 x H x W,
+ * N x 3 x T x H x W or token sequences.  A hipdec_clips object takes the samples of n_tracks tracks, decodes them as one launch set - the set the look-ahead
+ * chains of hipdec_decoder objects share, built directly: no decoder objects, no coalescer - and keeps every picture in device memory; the tensor stage of
+ * the batch calls above then serves its frames.
+ *
+ * SAMPLES.  Track t's samples are sample_counts[t] consecutive entries of samples[] / sample_sizes[] (track 0's first), in DECODING order, each one access
+ * unit in the framing of hipdec_decoder_push_data ([u32 BE length][NAL]...).  A track's first sample carries the parameter sets and is a random-access
+ * picture; later samples may repeat or replace parameter sets.  Each track starts from a fresh sequence state.
+ * FRAMES.  The frames of a track are its output pictures in OUTPUT order - the order hipdec_decoder_next_picture releases them in with `flush`: coded video
+ * sequence by coded video sequence (an IDR picture starts one), each in picture-order-count order.  Pictures with pic_output_flag == 0 are decoded but are
+ * not frames; RASL pictures 8.3.3 drops are neither.  hipdec_clip_frame: `item` is the frame's item in the borrowed batch, `sample` the index of its sample
+ * within the track, `poc` its picture order count, `sequence` the index of its coded video sequence within the track (from 0).
+ * Refused by hipdec_clips_create before a device is touched, the message naming `track %d` (and `sample %d` where one is at fault): a NULL argument or a
+ * non-positive count (HIPDEC_ERR_INVALID_ARGUMENT); broken framing (HIPDEC_ERR_END_OF_DATA); a sample that is not exactly one coded picture; more samples in
+ * all than the chain limit (1024, HIPDEC_CHAIN_MAX_PICTURES: HIPDEC_ERR_LIMIT); and, with the status the front end gives, a sample it refuses, a first
+ * sample without parameter sets, a P / B picture whose reference is not among the track's samples, 8-bit tracks beside wider ones.
+ * hipdec_clips_run is asynchronous as hipdec_batch_run is, hipdec_clips_status synchronises as hipdec_batch_status does.
+ * THE BORROWED BATCH.  hipdec_clips_batch returns the launch set as a hipdec_batch, valid until hipdec_clips_free: every hipdec_batch_* read, colour,
+ * scaled, tensor, placed and packed call serves frames through it with item = hipdec_clip_frame.item.  hipdec_batch_run on it is refused with
+ * HIPDEC_ERR_INVALID_ARGUMENT; hipdec_batch_free on it does nothing. */
+typedef struct hipdec_clips hipdec_clips;
+typedef struct hipdec_clip_frame { int item, sample, poc, sequence; hipdec_image_info info; } hipdec_clip_frame;
+HIPDEC_API int hipdec_clips_create(hipdec_clips** out, int n_tracks, const int* sample_counts, const void* const* samples, const size_t* sample_sizes,
+                                   uint64_t max_image_size_pixels);
+HIPDEC_API void hipdec_clips_free(hipdec_clips* c);
+HIPDEC_API int hipdec_clips_run(hipdec_clips* c, void* stream);
+HIPDEC_API int hipdec_clips_status(hipdec_clips* c);
+HIPDEC_API int hipdec_clips_track_count(const hipdec_clips* c);                /* a NULL object: HIPDEC_ERR_INVALID_ARGUMENT (negative) */
+HIPDEC_API int hipdec_clips_frame_count(const hipdec_clips* c, int track);     /* a NULL object or a track outside the object's: HIPDEC_ERR_INVALID_ARGUMENT */
+HIPDEC_API int hipdec_clips_frame(const hipdec_clips* c, int track, int frame, hipdec_clip_frame* out);
+HIPDEC_API int hipdec_clips_frame_plane(hipdec_clips* c, int track, int frame, int plane, const void** dptr, size_t* stride);
+HIPDEC_API int hipdec_clips_read_plane(hipdec_clips* c, int track, int frame, int plane, void* dst_host, size_t dst_stride);
+HIPDEC_API hipdec_batch* hipdec_clips_batch(hipdec_clips* c);
+/* counters since load: launch sets built, their tracks, their frames, clip tensor calls, and the frames that went through the strided box kernel */
+HIPDEC_API void hipdec_clips_stats(uint64_t* sets, uint64_t* tracks, uint64_t* frames, uint64_t* tensor_calls, uint64_t* strided_box_entries);
+
+/* CLIP TENSORS.  Entry e is a clip of T = clip->frames frames of track entries[e].item: frames[e * T + k], k = 0 .. T - 1, are frame indices of that track
+ * (they may repeat and come in any order); the entry's window, flip and orientation code hold for all T frames.
+ * THE DEFINITION OF THE RESULT.  F(e, k)[c][y][x] is, element for element, what hipdec_batch_to_tensor_oriented writes on the borrowed batch for the entry
+ * (item of frame frames[e * T + k] of track entries[e].item, the entry's window and flip), the entry's code, and `desc` as given (filter, dtype, scale,
+ * bias, width, height).  With W x H = desc->width x desc->height the output is n_entries * T * 3 * H * W elements without padding:
+ *   HIPDEC_CLIP_FRAME_MAJOR,   NCHW  (N T C H W):  out[(((e * T + k) * 3 + c) * H + y) * W + x]
+ *   HIPDEC_CLIP_FRAME_MAJOR,   NHWC  (N T H W C):  out[(((e * T + k) * H + y) * W + x) * 3 + c]
+ *   HIPDEC_CLIP_CHANNEL_MAJOR, NCHW  (N C T H W):  out[(((e * 3 + c) * T + k) * H + y) * W + x]
+ *   HIPDEC_CLIP_CHANNEL_MAJOR with NHWC: refused.
+ * All four filters, all dtypes and all eight codes; the native-depth rule for float dtypes from sources above 8 bits and the refusal of floats from such
+ * sources with BILINEAR / BICUBIC hold as in the oriented call.
+ * Launches: BILINEAR / BICUBIC one launch plus its table upload, NEAREST one launch; BOX entries whose code with the flip folded in is 0 or 4 go through
+ * the strided box kernel (the unoriented box kernel's stage with a row pitch and a plane stride), the other codes through the oriented box kernel: at most
+ * two launches.  Device time: slot [5] of hipdec_batch_slot_kernel_timing_us of the borrowed batch.
+ * Refused before the handle is read, HIPDEC_ERR_INVALID_ARGUMENT, naming the entry: `frames` NULL; T < 1; a non-zero `reserved`; temporal_patch > 1 (or
+ * < 0); an unknown order; and - once the handle is read - a track or a frame index outside the object's.  Everything else as the oriented call refuses it.
+ *
+ * TOKEN SEQUENCES WITH A TEMPORAL PATCH (hipdec_clips_to_tensor_packed).  desc->width and height must be 0; samples[e] = (w, h, offset) is the displayed
+ * size of clip e's frames and the element offset of the clip, which occupies exactly the 3 * T * w * h elements from there.
+ *  - patch == 0 (or patches NULL): the clip is dense, in the orders above, at its own size; temporal_patch must be 0 or 1.
+ *  - patch == P, merge == m, temporal_patch == Tp >= 1 (0 counts as 1): T % Tp == 0, the order is frame-major.  With gw = w / P, gh = h / P and gy, gx, py,
+ *    px as in hipdec_batch_to_tensor_packed, the spatial token index is ts = ((gy / m) * (gw / m) + gx / m) * m * m + (gy % m) * m + gx % m, the token of the
+ *    clip t = (k / Tp) * gh * gw + ts, the position inside the token
+ *      NCHW  j = ((c * Tp + k % Tp) * P + py) * P + px          NHWC  j = (((k % Tp) * P + py) * P + px) * 3 + c
+ *    and the element goes to out[offset + t * 3 * Tp * P * P + j].  For a clip S[T, 3, h, w] with Tp = 2, m = 2 (NCHW) this restates
+ *      S.reshape(T/2, 2, 3, gh/2, 2, P, gw/2, 2, P).transpose(0, 3, 6, 4, 7, 2, 1, 5, 8).reshape(T/2 * gh * gw, 3 * 2 * P * P)
+ *    the order Qwen2-VL's processor emits for video; a still becomes its image tokens with frames = {0, 0}.
+ * Refused as the packed call refuses (the element range of a clip is 3 * T * w * h; overlap of two clips' ranges names the entry), and: T % Tp != 0;
+ * Tp < 0 or Tp > 16; channel-major order with patches.
+ * Out of scope: reading samples out of a container (stsz / ctts / moov parsing), choosing sizes, skipping the decode of pictures nobody sampled, audio, the
+ * libheif hook, pipelining several hipdec_clips objects against each other. */
+typedef enum { HIPDEC_CLIP_FRAME_MAJOR = 0, HIPDEC_CLIP_CHANNEL_MAJOR = 1 } hipdec_clip_order;
+typedef struct hipdec_clip_desc { int frames /* T >= 1 */, order /* hipdec_clip_order */, temporal_patch /* 0 or 1 for dense clips */, reserved /* 0 */; } hipdec_clip_desc;
+HIPDEC_API int hipdec_clips_to_tensor(hipdec_clips* c, const hipdec_tensor_desc* desc, const hipdec_clip_desc* clip, const hipdec_tensor_entry* entries,
+                                      const int* frames, const int* orientations, int n_entries, void* out_dev, size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_clips_to_tensor_packed(hipdec_clips* c, const hipdec_tensor_desc* desc, const hipdec_clip_desc* clip, const hipdec_tensor_entry* entries,
+                                             const int* frames, const int* orientations, const hipdec_tensor_sample* samples,
+                                             const hipdec_tensor_patches* patches, int n_entries, void* out_dev, size_t out_bytes, void* stream);
+/* Host only, the clip form of hipdec_tensor_packed_layout: offsets[e] of clips of `frames` frames packed back to back in entry order (3 * frames * w * h
+ * elements each), tokens[e] per clip ((frames / Tp) * (w / patch) * (h / patch); 0 for dense clips) and the total element count (any of the three may be
+ * NULL).  A refused argument returns -1 and hipdec_last_error says why. */
+HIPDEC_API int hipdec_clip_packed_layout(const hipdec_clip_desc* clip, const hipdec_tensor_patches* patches, const int* widths, const int* heights, int n,
+                                         uint64_t* offsets, uint32_t* tokens, uint64_t* total_elements);
 
 /* counters since load: images through hipdec_image_transform, grid canvases handed out by hipdec_grid_read_plane_tracked (hipdec_image_scale counts in
  * hipdec_image_scale_stats) */

@@ -17,6 +17,7 @@
 // Float parity: compiled with -ffp-contract=off; the reference build (x86-64 baseline) has no FMA.
 #include "hipdec_internal.h"
 #include "color_device.h"
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -650,6 +651,48 @@ __device__ __forceinline__ void store_oriented4(const OrientedParams& op, int dw
       HIPDEC_GLOBAL E* d = o + col;
       d[0] = (E)v[0][k]; d[plane] = (E)v[1][k]; d[2 * plane] = (E)v[2][k];
     }
+  }
+}
+
+// ---- clip output (include/heif_hipdec.h hipdec_clips_to_tensor): the box kernel of the frames of a clip whose rows stay rows and whose row order stays -
+// folded codes 0 and 4.  A frame of an N x C x T x H x W clip has its channel planes T * H rows apart, so it needs the row pitch and the plane stride of the
+// oriented store, but nothing of k_oriented_box's quarter-turn stage, which caps the column tile at 96 / 64 and stages every pixel in LDS a second time.
+// The integer stage is k_tensor_box's, statement for statement - the same box_tile, tile choice (up to 256 columns), LDS and flip as a store index - and
+// the store is store_oriented4: vector stores behind its run-time alignment test (a plane stride that is no multiple of four elements leaves the G and B
+// planes unaligned: element stores).  A sibling text, as k_patch_box is one of k_oriented_box: k_tensor_box's code object does not change.
+// (the occupancy step is stated, as for k_patch_box: left to itself the scheduler took 176 VGPRs for the float dtypes from 16-bit samples, past the 168 step)
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(Pix) == 1 ? 4 : 3))) void k_clip_box(const OrientedParams* __restrict__ ps)
+{
+  __shared__ typename BoxAcc<Pix>::T colsum[3][kBoxSpan];
+  __shared__ uint32_t avg[3][256];
+  const OrientedParams op = ps[blockIdx.z];   // wave-uniform: scalar loads into SGPRs
+  const TensorParams& tp = op.t;
+  const ColorParams& p = tp.c;
+  const int tid = threadIdx.x;
+  const int oxA = blockIdx.x * tp.tile;
+  if (oxA >= tp.ow) return;                               // (the whole workgroup)
+  const int nox = min(tp.tile, tp.ow - oxA);
+  const bool mono = p.arith == AR_MONO;
+  const int fx = (op.code >> 2) & 1;                      // code 0 or 4: the mirror is the only thing left of the orientation
+  const int cl = tp.left >> tp.sH, ct = tp.top >> tp.sV;
+  const int cw = ((tp.left + tp.rw - 1) >> tp.sH) - cl + 1, ch = ((tp.top + tp.rh - 1) >> tp.sV) - ct + 1;
+  const int fcw = (p.w + (1 << tp.sH) - 1) >> tp.sH;
+  const BoxPlane pl[3] = {{p.y, p.ys, tp.rw, tp.rh, p.w, tp.left, tp.top}, {p.cb, p.cbs, cw, ch, fcw, cl, ct}, {p.cr, p.crs, cw, ch, fcw, cl, ct}};
+  for (int oy = blockIdx.y; oy < tp.oh; oy += gridDim.y) {
+    uint32_t v[3];
+    box_tile<Pix, 3, true>(pl, mono ? 1 : 3, tp.ow, tp.oh, oxA, nox, oy, colsum, v);
+    avg[0][tid] = v[0]; avg[1][tid] = v[1]; avg[2][tid] = v[2];
+    __syncthreads();
+    if (tid * 4 < nox) {
+      const int npx = min(4, nox - tid * 4);
+      int Y[4], CB[4], CR[4], R[4], G[4], B[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) { Y[i] = (int)avg[0][(tid * 4 + i) & 255]; CB[i] = (int)avg[1][(tid * 4 + i) & 255]; CR[i] = (int)avg[2][(tid * 4 + i) & 255]; }
+      tensor_convert4<Pix>(p, Y, CB, CR, R, G, B);
+      store_oriented4<DT>(op, tp.ow, tp.oh, fx, oxA + tid * 4, oy, npx, R, G, B);
+    }
+    __syncthreads();                                      // avg and colsum are written again by the next row
   }
 }
 
@@ -1696,7 +1739,7 @@ thread_local std::vector<CapturedScaled> t_captured_scaled;
 // the recorded blocks go out as one launch (hipdec::color_tensor_launch).  Taken and checked like a scale request.
 struct TensorReq { bool on = false; hipdec::TensorRequest r; };
 thread_local TensorReq t_tensor;
-struct CapturedTensor { TensorParams p; int wide; int oriented, code; uint64_t pitch; int plane_rows; int resample; int patch, merge; /* patch > 0: a patch sequence, for the k_patch_* kernels */ };   // oriented: for the k_oriented_* kernels, with a code, a row pitch and the rows of a channel plane; resample: the filter, for k_resample (code and pitch are set for every entry)
+struct CapturedTensor { TensorParams p; int wide; int oriented, code; uint64_t pitch; int plane_rows; int resample; int patch, merge; /* patch > 0: a patch sequence, for the k_patch_* kernels */ int tpatch, strided; /* clips: frames per token; the entry goes to k_clip_box */ };   // oriented: for the k_oriented_* kernels, with a code, a row pitch and the rows of a channel plane; resample: the filter, for k_resample (code and pitch are set for every entry)
 thread_local std::vector<CapturedTensor> t_captured_tensor;
 
 // ---- the coefficient tables of HIPDEC_SCALE_BILINEAR / _BICUBIC: Pillow's precompute_coeffs + normalize_coeffs_8bpc (src/libImaging/Resample.c), statement
@@ -1843,13 +1886,16 @@ int record_tensor(const ColorParams& p)
   if (r.resample) {
     if constexpr (LAYOUT != LO_RGB24) return hipdec::set_error(HIPDEC_ERR_UNSUPPORTED, "resampled output: 8-bit component values only");
     tp.flip = 0;      // folded into the code
+  } else if (r.oriented && r.strided_box) {   // k_clip_box: k_tensor_box's tile, no quarter-turn stage to fit
+    tp.flip = 0;      // folded into the code
   } else if (r.oriented) {   // (r.ow x r.oh: the pre-orientation size; the quarter-turn stage holds kOrientedTile columns)
     const int cap = sizeof(Pix) == 1 ? OrientedTile<uint8_t, TD_U8>::TC : OrientedTile<uint16_t, TD_U8>::TC;
     tp.tile = tp.tile < cap ? tp.tile : cap;
     tp.flip = 0;      // folded into the code
   }
   t_tensor.on = false;   // taken
-  t_captured_tensor.push_back(CapturedTensor{tp, sizeof(Pix) == 2, r.oriented ? 1 : 0, r.code, (uint64_t)r.pitch, r.plane_rows, r.resample, r.patch, r.merge});
+  t_captured_tensor.push_back(CapturedTensor{tp, sizeof(Pix) == 2, r.oriented ? 1 : 0, r.code, (uint64_t)r.pitch, r.plane_rows, r.resample, r.patch, r.merge, r.tpatch > 1 ? r.tpatch : 1,
+                                             r.oriented && !r.resample && !r.patch && r.strided_box ? 1 : 0});
   return 0;
   }
 }
@@ -2102,8 +2148,9 @@ PatchInfo patch_info_of(const CapturedTensor& c)
   const uint32_t P = (uint32_t)c.patch, m = (uint32_t)c.merge, dw = (uint32_t)(c.code & 1 ? c.p.oh : c.p.ow);
   auto magic = [](uint32_t d) { const uint64_t v = (1ull << 32) / d; return (uint32_t)(v > 0xffffffffull ? 0xffffffffull : v); };
   b.P = P; b.m = m; b.magicP = magic(P); b.magicM = magic(m);
-  b.tok = 3u * P * P; b.tokm = m * m * b.tok; b.mtok = m * b.tok;
-  b.pxs = c.p.nhwc ? 3u : 1u; b.chs = c.p.nhwc ? 1u : P * P; b.prow = P * b.pxs;
+  const uint32_t Tp = c.tpatch > 1 ? (uint32_t)c.tpatch : 1u;   // a clip's token holds Tp frames: the frame's place in it is part of the entry's first element
+  b.tok = 3u * Tp * P * P; b.tokm = m * m * b.tok; b.mtok = m * b.tok;
+  b.pxs = c.p.nhwc ? 3u : 1u; b.chs = c.p.nhwc ? 1u : Tp * P * P; b.prow = P * b.pxs;
   b.rowtok = (uint64_t)(dw / P / m) * (uint64_t)b.tokm;
   return b;
 }
@@ -2122,6 +2169,7 @@ void launch_patch_grid(const PatchParams* dev, int n, int filter, int ow, int oh
 }
 
 std::atomic<uint64_t> g_packed_calls{0}, g_packed_entries{0}, g_packed_patch_entries{0};
+std::atomic<uint64_t> g_clip_box_entries{0};
 
 // the oriented form of color_tensor_launch: entries of all codes and (RGB form) sizes share the launch, so the grid covers the largest of each extent
 int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int filter, int dtype, hipStream_t s)
@@ -2131,9 +2179,18 @@ int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
   // rows of P per workgroup: the kernel's RB where a row of P becomes a column (the length of a contiguous run), 16 where rows stay rows (more workgroups)
   const int RB = !caps[0].wide || dtype == TD_U8 ? OrientedTile<uint8_t, TD_U8>::RB : OrientedTile<uint16_t, TD_F32>::RB;
   auto block_rows = [&](const CapturedTensor& c) { return c.code & 1 ? RB : 16; };
-  for (const auto& c : caps) {
+  // clips: the box entries for k_clip_box come first in the block array and go out as a launch of their own, with k_tensor_box's grid
+  size_t n_clip = 0;
+  int clip_tiles = 0, clip_oh = 0;
+  if (filter == HIPDEC_SCALE_BOX) {
+    std::stable_partition(caps.begin(), caps.end(), [](const CapturedTensor& c) { return c.strided != 0; });
+    while (n_clip < caps.size() && caps[n_clip].strided) n_clip++;
+  }
+  for (size_t i = 0; i < caps.size(); i++) {
+    const CapturedTensor& c = caps[i];
     if (c.wide != caps[0].wide) return set_error(HIPDEC_ERR_UNSUPPORTED, "oriented output: the entries mix 8-bit and wider sources");
     const int tiles = (c.p.ow + c.p.tile - 1) / c.p.tile;
+    if (i < n_clip) { clip_tiles = tiles > clip_tiles ? tiles : clip_tiles; clip_oh = c.p.oh > clip_oh ? c.p.oh : clip_oh; continue; }
     const int dw = c.code & 1 ? c.p.oh : c.p.ow, dh = c.code & 1 ? c.p.ow : c.p.oh;
     max_tiles = tiles > max_tiles ? tiles : max_tiles;
     const int blocks = (c.p.oh + block_rows(c) - 1) / block_rows(c);
@@ -2164,7 +2221,22 @@ int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
     st.host.swap(host);
     HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), bytes, hipMemcpyHostToDevice, s));
   }
-  for (size_t first = 0; first < caps.size(); first += 65535) {
+  for (size_t first = 0; first < n_clip; first += 65535) {
+    const OrientedParams* dev = (const OrientedParams*)st.dev + first;
+    dim3 block(256), grid(clip_tiles, clip_oh < 65535 ? clip_oh : 65535, (unsigned)(n_clip - first < 65535 ? n_clip - first : 65535));
+    switch (caps[0].wide * 4 + dtype) {
+#define X(DT) case DT: hipLaunchKernelGGL((k_clip_box<uint8_t, DT>), grid, block, 0, s, dev); break; \
+              case 4 + DT: hipLaunchKernelGGL((k_clip_box<uint16_t, DT>), grid, block, 0, s, dev); break;
+      X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
+#undef X
+      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "clip output: unknown dtype %d", dtype);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "clip kernel launch: %s", hipGetErrorString(e));
+    g_oriented_launches++;
+  }
+  g_clip_box_entries += (uint64_t)n_clip;
+  for (size_t first = n_clip; first < caps.size(); first += 65535) {
     const OrientedParams* dev = (const OrientedParams*)st.dev + first;
     const PatchParams* pdev = (const PatchParams*)st.dev + first;
     const int n = (int)(caps.size() - first < 65535 ? caps.size() - first : 65535);
@@ -2331,6 +2403,7 @@ int color_tensor_launch(ColorBatchState& st, int filter, int dtype, hipStream_t 
 // when they change, as the picture blocks are
 std::atomic<uint64_t> g_placed_calls{0}, g_placed_entries{0}, g_placed_margin_launches{0};
 void placed_note_call(uint64_t entries) { g_placed_calls++; g_placed_entries += entries; }
+uint64_t clip_box_entries() { return g_clip_box_entries.load(); }
 void packed_note_call(uint64_t entries, bool patches) { g_packed_calls++; g_packed_entries += entries; if (patches) g_packed_patch_entries += entries; }
 
 int canvas_margin_launch(ColorBatchState& st, const CanvasMargin* blocks, int n, int dtype, hipStream_t s)

@@ -58,6 +58,7 @@ struct hipdec_batch : BatchLayout {
   uint64_t runs = 0;
   hipStream_t last_stream = nullptr;
   bool ran = false;
+  bool borrowed = false;        // owned by a hipdec_clips object (decoder_clips.inc): hipdec_batch_free leaves it alone, hipdec_batch_run is refused
   bool retired = false;         // its arena went to another batch (hipdec_batch_create_recycling): only status / timing / free remain
   uint32_t wave_share = 1;      // the CABAC work pool of this batch takes 1 / wave_share of the wave budget (launch sets of the decoder path overlap in pairs)
   ColorBatchState color;        // parameter blocks of hipdec_batch_to_rgb_all
@@ -566,7 +567,7 @@ int hipdec_batch_create_recycling(hipdec_batch** out, int n, const void* const* 
   });
 }
 
-void hipdec_batch_free(hipdec_batch* b) { delete b; }
+void hipdec_batch_free(hipdec_batch* b) { if (b && b->borrowed) return; delete b; }
 int hipdec_batch_count(const hipdec_batch* b) { return b ? (int)b->pics.size() : 0; }
 
 int hipdec_batch_info(const hipdec_batch* b, int i, hipdec_image_info* info)
@@ -579,6 +580,7 @@ int hipdec_batch_info(const hipdec_batch* b, int i, hipdec_image_info* info)
 int hipdec_batch_run(hipdec_batch* b, void* stream)
 {
   if (!b) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "batch_run: NULL batch");
+  if (b->borrowed) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "batch_run: the batch is borrowed from a hipdec_clips object (hipdec_clips_run runs it)");
   DeviceScope scope(b->device);
   if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "batch_run: the batch's arena was handed to another batch");
   if (int rc = ensure_init()) return rc;
@@ -827,7 +829,7 @@ int tensor_window(const char* who, const hipdec_tensor_entry* e, int idx, int w,
 // presents the planes as the 4:4:4 image they are scaled to.  The entry point records the block (color.hip); elem0: the entry's first element.
 int tensor_record_entry(const char* who, const uint8_t* y, size_t ys, const uint8_t* cb, size_t cbs, const uint8_t* cr, size_t crs, int w, int h, int bits, int cf,
                         const hipdec_nclx* nclx, const hipdec_nclx* nclx_after_sdr, const hipdec_tensor_desc* d, int left, int top, int rw, int rh, int flip, void* elem0,
-                        int orientation = -1, size_t pitch = 0, int plane_rows = 0, int patch = 0, int merge = 1)
+                        int orientation = -1, size_t pitch = 0, int plane_rows = 0, int patch = 0, int merge = 1, int tpatch = 1, bool* strided_box = nullptr)
 {
   if (int rc = tensor_check_resample_depth(who, d, bits)) return rc;
   TensorRequest rq;
@@ -847,6 +849,10 @@ int tensor_record_entry(const char* who, const uint8_t* y, size_t ys, const uint
     rq.pitch = pitch ? pitch : (size_t)d->width * (d->layout == HIPDEC_TENSOR_NHWC ? 3 : 1);
     flip = 0;
   }
+  // clips (decoder_clips.inc; *strided_box in: the call may take k_clip_box, out: this entry does): a box entry whose rows stay rows in their order
+  rq.tpatch = tpatch;
+  if (strided_box) *strided_box = *strided_box && rq.oriented && !rq.resample && !patch && d->filter == HIPDEC_SCALE_BOX && (rq.code == HIPDEC_ORIENT_0 || rq.code == HIPDEC_ORIENT_MIRROR);
+  rq.strided_box = strided_box && *strided_box;
   rq.plane_rows = plane_rows ? plane_rows : d->height;   // (d->height: the displayed rows)
   rq.sH = cf == 1 || cf == 2 ? 1 : 0; rq.sV = cf == 1 ? 1 : 0;
   rq.left = left; rq.top = top; rq.rw = rw; rq.rh = rh; rq.flip = flip; rq.nhwc = d->layout == HIPDEC_TENSOR_NHWC;
@@ -1527,3 +1533,4 @@ int hipdec_probe(const void* data, size_t size, uint64_t max_image_size_pixels, 
 #include "decoder_color_boundary.inc"  // resident planes, colour planner, hipdec_color_convert, image transforms
 #include "decoder_grid.inc"            // grid photos over the node's GPUs
 #include "decoder_album.inc"           // albums of grid photos: one launch set, one fused paste
+#include "decoder_clips.inc"           // clips: the samples of several sequence tracks as one launch set, video tensors

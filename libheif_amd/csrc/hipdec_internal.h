@@ -100,7 +100,9 @@ int scale_planes_launch(PlaneScaleParams* jobs, int n, int bytes_per_sample, int
 // groups of merge x merge (hipdec_batch_to_tensor_packed); pitch and plane_rows are then not read.
 struct TensorRequest { int ow, oh, sH, sV, left, top, rw, rh, flip, nhwc; float scale[3], bias[3]; int oriented, code; size_t pitch; int plane_rows;
                        int resample; /* HIPDEC_SCALE_BILINEAR / _BICUBIC: the block is recorded for k_resample, code and pitch set for every entry (0: no) */
-                       int patch, merge; };
+                       int patch, merge;
+                       int tpatch;        /* clips (hipdec_clips_to_tensor_packed): frames per token, a token is 3 * tpatch * patch * patch elements (0 / 1: a still's) */
+                       int strided_box;   /* clips: a box entry whose folded code is 0 or 4 goes to k_clip_box - k_tensor_box's stage, the oriented store - not k_oriented_box */ };
 void color_tensor_request(const TensorRequest& r);
 void color_tensor_clear();
 bool color_tensor_pending();
@@ -126,6 +128,7 @@ struct CanvasMargin {
 int canvas_margin_launch(ColorBatchState& st, const CanvasMargin* blocks, int n, int dtype, hipStream_t s);
 void placed_note_call(uint64_t entries);   // hipdec_placed_stats
 void packed_note_call(uint64_t entries, bool patches);   // hipdec_packed_stats
+uint64_t clip_box_entries();   // entries that have gone through k_clip_box (hipdec_clips_stats)
 
 // The paste of an album of grid photos (transform.hip k_album_paste): one job per (tile, plane), already clipped to the photo's output size by the host
 // (a job clipped to nothing is not emitted); the job table lives in device memory and all jobs go out as ONE launch.

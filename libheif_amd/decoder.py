@@ -93,6 +93,26 @@ def _bind(lib):
                                                 C.POINTER(C.c_uint64)]
     lib.hipdec_packed_stats.restype = None
     lib.hipdec_packed_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
+    if hasattr(lib, "hipdec_clips_create"):   # (tools/ab_bench.sh loads an older branch's library through this module: it has no clips, and Clips() says so)
+        lib.hipdec_clips_create.argtypes = [C.POINTER(vp), ci, C.POINTER(ci), C.POINTER(C.c_char_p), C.POINTER(sz), C.c_uint64]
+        lib.hipdec_clips_free.argtypes = [vp]
+        lib.hipdec_clips_free.restype = None
+        lib.hipdec_clips_run.argtypes = [vp, vp]
+        lib.hipdec_clips_status.argtypes = [vp]
+        lib.hipdec_clips_track_count.argtypes = [vp]
+        lib.hipdec_clips_frame_count.argtypes = [vp, ci]
+        lib.hipdec_clips_frame.argtypes = [vp, ci, ci, C.POINTER(ClipFrame)]
+        lib.hipdec_clips_frame_plane.argtypes = [vp, ci, ci, ci, C.POINTER(vp), C.POINTER(sz)]
+        lib.hipdec_clips_read_plane.argtypes = [vp, ci, ci, ci, vp, sz]
+        lib.hipdec_clips_batch.restype = vp
+        lib.hipdec_clips_batch.argtypes = [vp]
+        lib.hipdec_clips_stats.restype = None
+        lib.hipdec_clips_stats.argtypes = [C.POINTER(C.c_uint64)] * 5
+        lib.hipdec_clips_to_tensor.argtypes = [vp, C.POINTER(TensorDesc), C.POINTER(ClipDesc), C.POINTER(TensorEntry), C.POINTER(ci), C.POINTER(ci), ci, vp, sz, vp]
+        lib.hipdec_clips_to_tensor_packed.argtypes = [vp, C.POINTER(TensorDesc), C.POINTER(ClipDesc), C.POINTER(TensorEntry), C.POINTER(ci), C.POINTER(ci),
+                                                      C.POINTER(TensorSample), C.POINTER(TensorPatches), ci, vp, sz, vp]
+        lib.hipdec_clip_packed_layout.argtypes = [C.POINTER(ClipDesc), C.POINTER(TensorPatches), C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib._dec_bound = True
     return lib
 
@@ -133,7 +153,18 @@ class TensorPatches(C.Structure):
     _fields_ = [("patch", C.c_int), ("merge", C.c_int), ("reserved", C.c_int * 2)]
 
 
-FILL_DOMAINS = {"component": 0, "element": 1}                                 # hipdec_fill_domain
+class ClipFrame(C.Structure):
+    """hipdec_clip_frame"""
+    _fields_ = [("item", C.c_int), ("sample", C.c_int), ("poc", C.c_int), ("sequence", C.c_int), ("info", ImageInfo)]
+
+
+class ClipDesc(C.Structure):
+    """hipdec_clip_desc"""
+    _fields_ = [("frames", C.c_int), ("order", C.c_int), ("temporal_patch", C.c_int), ("reserved", C.c_int)]
+
+
+CLIP_ORDERS = {"TCHW": (0, "NCHW"), "THWC": (0, "NHWC"), "CTHW": (1, "NCHW")}   # (hipdec_clip_order, layout of a frame)
+FILL_DOMAINS = {"component": 0, "element": 1}                                # hipdec_fill_domain
 TENSOR_DTYPES = {"uint8": 0, "float32": 1, "float16": 2, "bfloat16": 3}       # hipdec_tensor_dtype
 TENSOR_LAYOUTS = {"NCHW": 0, "NHWC": 1}                                       # hipdec_tensor_layout
 _TENSOR_NUMPY = {"uint8": np.uint8, "float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}   # (NumPy has no bfloat16: its bits)
@@ -1065,6 +1096,237 @@ class Album:
         if self._h:
             self._lib.hipdec_album_free(self._h)
             self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+# ---- clips (video loaders): include/heif_hipdec.h hipdec_clips_* ------------------------------------------------------------------------------------------
+def clips_stats():
+    """(launch sets built, their tracks, their frames, clip tensor calls, frames through the strided box kernel) since load"""
+    lib = _bind(load_library())
+    v = [C.c_uint64() for _ in range(5)]
+    lib.hipdec_clips_stats(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def uniform_frames(frame_count, T, stride=1, start=0, pad="repeat_last"):
+    """T frame indices start, start + stride, ... of a track of frame_count frames - the usual uniform sampling of a video loader.  Indices past the last
+    frame: pad "repeat_last" clamps them to it, "loop" wraps them around, "error" raises ValueError."""
+    frame_count, T, stride, start = int(frame_count), int(T), int(stride), int(start)
+    if frame_count < 1 or T < 1 or stride < 1 or start < 0 or start >= frame_count:
+        raise ValueError("uniform_frames: frame_count %d, T %d, stride %d, start %d" % (frame_count, T, stride, start))
+    idx = [start + k * stride for k in range(T)]
+    if pad == "repeat_last":
+        return [min(i, frame_count - 1) for i in idx]
+    if pad == "loop":
+        return [i % frame_count for i in idx]
+    if pad == "error":
+        if idx[-1] >= frame_count:
+            raise ValueError("uniform_frames: frame %d of a track of %d" % (idx[-1], frame_count))
+        return idx
+    raise ValueError("pad must be repeat_last, loop or error")
+
+
+def clip_packed_layout(sizes, T, patch=0, merge=1, temporal_patch=1):
+    """(offsets, tokens, total elements) of clips of T frames of the DISPLAYED sizes (width, height) packed back to back in entry order
+    (hipdec_clip_packed_layout; host only): tokens[e] = (T / temporal_patch) * (width / patch) * (height / patch), 0 for dense clips."""
+    lib = _bind(load_library())
+    n = len(sizes)
+    ws, hs = (C.c_int * n)(*(int(s[0]) for s in sizes)), (C.c_int * n)(*(int(s[1]) for s in sizes))
+    offs, toks, total = (C.c_uint64 * n)(), (C.c_uint32 * n)(), C.c_uint64()
+    pt = TensorPatches(int(patch), int(merge))
+    cd = ClipDesc(int(T), 0, int(temporal_patch), 0)
+    if lib.hipdec_clip_packed_layout(C.byref(cd), C.byref(pt), ws, hs, n, offs, toks, C.byref(total)) != 0:
+        raise ValueError("clip_packed_layout: %s" % lib.hipdec_last_error().decode())
+    return list(offs), list(toks), total.value
+
+
+class _BorrowedBatch(Batch):
+    """Clips.batch: the launch set of a Clips object as a Batch.  Not owned - free() and __del__ do nothing, run() is refused by the library - and
+    valid as long as the Clips object is (Clips.free() clears the handle)."""
+
+    def __init__(self, lib, handle, n):
+        self._lib, self._h, self.n = lib, C.c_void_p(handle), n
+
+    def free(self):
+        pass
+
+    def __del__(self):
+        pass
+
+
+class Clips:
+    """The samples of several sequence tracks decoded by ONE launch set, every picture resident in device memory, and video tensors from them
+    (hipdec_clips_*).  tracks: a list of tracks, each a list of samples (bytes) in decoding order, in the framing of HipDecoder.push_data; a track's first
+    sample carries the parameter sets.  The FRAMES of a track are its output pictures in output order."""
+
+    def __init__(self, tracks, max_image_size_pixels=0):
+        self._lib = _bind(load_library())
+        self._keep = [bytes(s) for t in tracks for s in t]
+        n = len(self._keep)
+        counts = (C.c_int * max(len(tracks), 1))(*[len(t) for t in tracks])
+        arr = (C.c_char_p * max(n, 1))(*self._keep)
+        sizes = (C.c_size_t * max(n, 1))(*[len(s) for s in self._keep])
+        self._h = C.c_void_p()
+        check(self._lib.hipdec_clips_create(C.byref(self._h), len(tracks), counts, arr, sizes, int(max_image_size_pixels)))
+        self.n_tracks = self._lib.hipdec_clips_track_count(self._h)
+        bh = self._lib.hipdec_clips_batch(self._h)
+        self.batch = _BorrowedBatch(self._lib, bh, self._lib.hipdec_batch_count(bh))
+
+    def run(self, stream=None):
+        check(self._lib.hipdec_clips_run(self._h, stream))
+
+    def status(self):
+        check(self._lib.hipdec_clips_status(self._h))
+
+    def frame_count(self, t):
+        n = self._lib.hipdec_clips_frame_count(self._h, t)
+        if n < 0:
+            check(n)
+        return n
+
+    def frame(self, t, f):
+        """{"item", "sample", "poc", "sequence"} and the picture's info fields"""
+        cf = ClipFrame()
+        check(self._lib.hipdec_clips_frame(self._h, t, f, C.byref(cf)))
+        d = _info_dict(cf.info)
+        d.update(item=cf.item, sample=cf.sample, poc=cf.poc, sequence=cf.sequence)
+        return d
+
+    def info(self, i=0):
+        return self.batch.info(i)
+
+    def planes(self, t, f):
+        d = self.frame(t, f)
+        dt = np.uint16 if d["bit_depth_luma"] > 8 else np.uint8
+        out = []
+        for c in range(3 if d["chroma_format_idc"] else 1):
+            w, h = (d["width"], d["height"]) if c == 0 else (d["chroma_width"], d["chroma_height"])
+            a = np.empty((h, w), dt)
+            check(self._lib.hipdec_clips_read_plane(self._h, t, f, c, a.ctypes.data, w * a.itemsize))
+            out.append(a)
+        return out
+
+    def _frames_array(self, frames, n, T):
+        flat = [int(f) for clip in frames for f in clip] if len(frames) and hasattr(frames[0], "__len__") else [int(f) for f in frames]
+        if len(flat) != n * T:
+            raise ValueError("%d frame indices for %d clips of %d frames" % (len(flat), n, T))
+        return (C.c_int * len(flat))(*flat)
+
+    def to_tensor(self, size, T, entries, frames, order="TCHW", dtype="float16", mean=None, std=None, scale=None, bias=None, filter=1, orientations=None,
+                  out=None, stream=None):
+        """asynchronous: one clip of T frames per entry as ONE dense tensor (hipdec_clips_to_tensor).  entries: (track, left, top, width, height[, flip])
+        tuples - one window and one flip for the whole clip; frames: T frame indices of the entry's track per entry (uniform_frames()), nested or flat.
+        order: "TCHW" (N, T, 3, H, W), "CTHW" (N, 3, T, H, W) or "THWC" (N, T, H, W, 3).  Everything else as Batch.to_tensor; each frame is what
+        Clips.batch.to_tensor(..., orientations=) writes for the frame's item."""
+        if order not in CLIP_ORDERS:
+            raise ValueError("order must be one of %s" % sorted(CLIP_ORDERS))
+        T = int(T)
+        co, layout = CLIP_ORDERS[order]
+        n = len(entries)
+        W, H = int(size[0]), int(size[1])
+        shape = {"TCHW": (n, T, 3, H, W), "CTHW": (n, 3, T, H, W), "THWC": (n, T, H, W, 3)}[order]
+        cd = ClipDesc(T, co, 0, 0)
+        fr = self._frames_array(frames, n, T)
+        codes = None if orientations is None else _orientation_array(orientations, n)
+        call = lambda h, desc, arr, n_, ptr, room, s: self._lib.hipdec_clips_to_tensor(h, desc, C.byref(cd), arr, fr, codes, n_, ptr, room, s)
+        return self._go(call, (W, H), shape, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
+
+    def _go(self, call, size, shape, entries, dtype, layout, mean, std, scale, bias, filter, out, stream):
+        d0 = self.batch.info(0)
+        max_value = (1 << d0["bit_depth_luma"]) - 1 if (dtype != "uint8" and d0["bit_depth_luma"] > 8) else 255
+        sc, bi = tensor_scale_bias(mean, std, scale, bias, max_value)
+        desc = tensor_desc(size, dtype, layout, filter, sc, bi)
+        item = np.dtype(_TENSOR_NUMPY[dtype]).itemsize
+        nbytes = int(np.prod(shape)) * item
+        arr = tensor_entries(entries)
+        host_wait = False
+        if out is None:
+            torch = _torch_gpu()
+            out = torch.empty(shape, dtype=getattr(torch, dtype), device="cuda") if torch is not None else DeviceBuffer(max(nbytes, 1))
+        if isinstance(out, DeviceBuffer):
+            ptr, room = out.ptr, out.nbytes
+        else:
+            import torch
+            if not isinstance(out, torch.Tensor) or not out.is_cuda:
+                raise TypeError("out must be a DeviceBuffer or a CUDA / HIP torch.Tensor")
+            if len(shape) == 1:   # token sequences and packed clips: a 1-D tensor that may be longer than the clips (gaps and a tail stay as they are)
+                if out.dim() != 1 or out.numel() < shape[0]:
+                    raise ValueError("out must be a 1-D tensor of at least %d elements" % shape[0])
+            elif tuple(out.shape) != tuple(shape):
+                raise ValueError("out has shape %s, the tensor has %s" % (tuple(out.shape), tuple(shape)))
+            if out.dtype != getattr(torch, dtype):
+                raise ValueError("out has dtype %s, the tensor has %s" % (out.dtype, dtype))
+            if not out.is_contiguous():
+                raise ValueError("out must be contiguous")
+            ptr, room = out.data_ptr(), out.numel() * item
+            if stream is None:
+                ts = torch.cuda.current_stream(out.device)
+                stream = ts.cuda_stream or None
+                if stream is None:   # (torch's legacy default stream: ordered on the host, as in Batch.to_tensor)
+                    ts.synchronize()
+                    host_wait = True
+        check(call(self._h, C.byref(desc), arr, len(entries), ptr, room, stream))
+        if host_wait:
+            check(self._lib.hipdec_stream_synchronize(None))
+        self._tensor = (out, tuple(shape), _TENSOR_NUMPY[dtype], stream)
+        return out
+
+    def to_tokens(self, sizes, T, entries, frames, patch, merge=1, temporal_patch=1, layout="NCHW", order="TCHW", dtype="float16", mean=None, std=None,
+                  scale=None, bias=None, filter=1, orientations=None, offsets=None, out=None, stream=None):
+        """asynchronous: one clip per entry at its OWN displayed size sizes[e] = (width, height) into one 1-D output (hipdec_clips_to_tensor_packed): token
+        sequences with a temporal patch (patch P >= 1: a token is 3 * temporal_patch * P * P elements, (c, k, py, px) for "NCHW" and (k, py, px, c) for
+        "NHWC"; merge 2 with temporal_patch 2 is the order of Qwen2-VL's video tokens), or dense clips in `order` (patch 0).  offsets None: back to back
+        (clip_packed_layout()).  Returns (out, offsets, grids), grids[e] = (T / temporal_patch, height / P, width / P) for patches, None for dense clips."""
+        T, patch, merge, Tp = int(T), int(patch), int(merge), int(temporal_patch)
+        n = len(entries)
+        sizes = [(int(w), int(h)) for w, h in sizes]
+        if len(sizes) != n:
+            raise ValueError("%d sizes for %d entries" % (len(sizes), n))
+        if patch == 0 and order != "TCHW":
+            if order not in CLIP_ORDERS:
+                raise ValueError("order must be one of %s" % sorted(CLIP_ORDERS))
+            co, layout = CLIP_ORDERS[order]
+        else:
+            co = 0
+        if offsets is None:
+            offsets, _, total = clip_packed_layout(sizes, T, patch, merge, Tp)
+        else:
+            offsets = [int(o) for o in offsets]
+            if len(offsets) != n:
+                raise ValueError("%d offsets for %d entries" % (len(offsets), n))
+            total = max(o + 3 * T * w * h for o, (w, h) in zip(offsets, sizes))
+        samples = (TensorSample * n)(*(TensorSample(w, h, o) for (w, h), o in zip(sizes, offsets)))
+        pt = TensorPatches(patch, merge)
+        cd = ClipDesc(T, co, Tp, 0)
+        fr = self._frames_array(frames, n, T)
+        codes = None if orientations is None else _orientation_array(orientations, n)
+        call = lambda h, desc, arr, n_, ptr, room, s: self._lib.hipdec_clips_to_tensor_packed(h, desc, C.byref(cd), arr, fr, codes, samples, C.byref(pt), n_, ptr,
+                                                                                              room, s)
+        out = self._go(call, (0, 0), (total,), entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
+        grids = [(T // max(Tp, 1), h // patch, w // patch) for w, h in sizes] if patch else None
+        return out, offsets, grids
+
+    def tensor_to_host(self):
+        """the last to_tensor() / to_tokens() result as a NumPy array of its shape (bfloat16 as uint16 bit patterns); waits for its stream"""
+        out, shape, dt, stream = self._tensor
+        check(self._lib.hipdec_stream_synchronize(stream))
+        if isinstance(out, DeviceBuffer):
+            return out.to_numpy(shape, dt)
+        import torch
+        t = out.view(torch.int16) if dt == np.uint16 else out
+        a = (t[:shape[0]] if len(shape) == 1 else t).cpu().numpy()
+        return a.view(np.uint16) if dt == np.uint16 else a
+
+    def free(self):
+        if self._h:
+            self._lib.hipdec_clips_free(self._h)
+            self._h = C.c_void_p()
+            self.batch._h = C.c_void_p()
 
     def __del__(self):
         try:
