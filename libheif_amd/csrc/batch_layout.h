@@ -24,6 +24,7 @@ struct BatchLayout {
   std::vector<ReconWave> recon_waves;
   bool wide = false;  // samples wider than 8 bit -> uint16 planes
   bool any_inter = false;   // the batch holds a P picture: the parser build with the inter syntax, k_motion and k_mc run
+  bool general_chroma = false;   // the batch holds a 4:2:2 or 4:4:4 picture (such pictures and P pictures are reconstructed without the plan, recon_kernel.hip)
   int max_w = 0, max_h = 0, max_ow = 0, max_oh = 0, max_ctbs = 0;
   // ---- chains (sequence tracks with look-ahead): the items are consecutive samples of a track in decoding order - of ONE track, or of
   //      several tracks whose decoder instances asked at the same time (`tracks`).  The CABAC parser and the residual kernel run over all of them at
@@ -49,7 +50,8 @@ struct BatchLayout {
     int first = 0, count = 0;                   // pixel steps: the items
     uint32_t first_rwave = 0, num_rwaves = 0;   // pixel steps: their reconstruction wavefronts
     uint32_t first_row = 0, num_rows = 0;       // motion steps: their rows in the RowDesc table
-    int max_w = 0, max_h = 0, max_ow = 0, max_oh = 0;
+    bool general_chroma = false;   // the batch holds a 4:2:2 or 4:4:4 picture (such pictures and P pictures are reconstructed without the plan, recon_kernel.hip)
+  int max_w = 0, max_h = 0, max_ow = 0, max_oh = 0;
     bool any_inter = false;
     int motion_need = 0;                        // pixel steps: motion steps [0, motion_need) hold the motion fields of the step's pictures
   };

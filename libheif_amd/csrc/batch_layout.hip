@@ -268,6 +268,7 @@ int layout_core(BatchLayout& b, const size_t* sizes, std::string& err_out)
     PicParams& P = b.params[i];
     P.width = S.pic_width; P.height = S.pic_height;
     P.chroma_format_idc = S.chroma_format_idc;
+    if (S.chroma_format_idc >= 2) b.general_chroma = true;
     const int csw = (S.chroma_format_idc == 1 || S.chroma_format_idc == 2) ? 1 : 0, csh = S.chroma_format_idc == 1 ? 1 : 0;   // log2 SubWidthC, log2 SubHeightC (6.2)
     P.cwidth = S.chroma_format_idc ? S.pic_width >> csw : 0; P.cheight = S.chroma_format_idc ? S.pic_height >> csh : 0;
     P.out_width = pp.info.width; P.out_height = pp.info.height; P.out_cwidth = pp.info.chroma_width; P.out_cheight = pp.info.chroma_height;
@@ -356,6 +357,12 @@ int layout_core(BatchLayout& b, const size_t* sizes, std::string& err_out)
     P.off_u_ipm = off; off = align_up(off + nunits, 256);
     P.off_u_ipmc = off; off = align_up(off + nunits, 256);
     P.off_u_qp = off; off = align_up(off + nunits, 256);
+    // reconstruction plan (k_recon_plan): worst case one luma block per 4x4 unit and one chroma block per 8x8 luma area
+    P.off_plan = P.off_plan_cnt = 0;
+    if (!P.is_inter && P.chroma_format_idc < 2) {
+      P.off_plan = off; off = align_up(off + (nunits + nunits / 4) * sizeof(PlanRecord), 256);
+      P.off_plan_cnt = off; off = align_up(off + nctb * sizeof(uint32_t), 256);
+    }
     P.off_msyn = P.off_mf = off;
     if (P.is_inter) {
       P.off_msyn = off; off = align_up(off + nunits * sizeof(MotionSyntax), 256);

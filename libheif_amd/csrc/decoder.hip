@@ -398,7 +398,7 @@ int launch_all(hipdec_batch& b, hipStream_t s, const void* fused_rgb_params = nu
     ra.inter_from_plane = inter_residual_in_mc() ? 1u : 0u;
     if (int rc = step("motion + mc")) return rc;
   }
-  if (!parse_only) launch_recon(ra, b.wide, ps, b.any_inter);
+  if (!parse_only) launch_recon(ra, b.wide, ps, b.any_inter, b.general_chroma ? 1 : 0);
   HIPDEC_CHECK_HIP(hipEventRecord(ev[3], ps));
   if (int rc = step("recon")) return rc;
   if (!parse_only) launch_deblock(fa, n, b.max_w, b.max_h, b.wide, ps, !b.any_inter && !pa.general_chroma);

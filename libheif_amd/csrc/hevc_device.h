@@ -169,7 +169,21 @@ struct PicParams {
   uint64_t off_reftab;            // RefFrame[16]
   uint64_t off_msyn;              // MotionSyntax[ctbs * units_per_ctb]
   uint64_t off_mf;                // MotionUnit[ctbs * units_per_ctb]
+  // ---- reconstruction plan (intra pictures with 4:0:0 / 4:2:0 sampling; 0 / unused otherwise): k_recon_plan writes it, the wavefront reads it
+  uint64_t off_plan;              // PlanRecord[ctbs * plan_stride]: per CTB the luma list (units_per_ctb slots) followed by the chroma list (units_per_ctb / 4 slots)
+  uint64_t off_plan_cnt;          // uint32[ctbs]: records in the CTB's luma list | records in its chroma list << 16
 };
+
+// One transform block of the reconstruction plan (recon_kernel.hip): what the wavefront needs to reconstruct it, in z-scan order per CTB and plane group.
+//   w0: bits 0..3 / 4..7 the block's x / y inside the CTB in units of 4 component samples, 8..10 log2 of its size, 11 its reference samples are smoothed
+//       (8.4.4.2.3: luma blocks from 8x8 up, by mode), 12..16 NL, 17..21 NT, 22 the above region is available, 23 the above-left sample is, 24..31 the z index of
+//       the block's first 4x4 luma unit (a quad of 4x4 luma blocks: of the quad) - the residual sits at that index
+//   w1: bits 0..7 the intra mode of the component(s) (as the unit map carries it), 8..15 the u_flags byte of the unit the block's flags come from
+//   Availability of the neighbouring samples (8.4.4.2.2, constrained intra prediction off) in units of 4 component samples: NL samples of the left
+//   column are available counted from the block's top edge downward (left, then below-left: 0 .. 2 * size / 4); NT samples of the top row counted
+//   rightward from the block's left edge if the above region is available, else from its right edge (above-right only: a slice that starts in the CTB row above)
+struct PlanRecord { uint32_t w0, w1; };
+static_assert(sizeof(PlanRecord) == 8, "PlanRecord layout");
 
 struct CtbInfo {
   uint16_t slice_idx;   // index into the picture's SliceParams

@@ -50,7 +50,10 @@ void launch_mc(const FilterArgs& a, int n_pics, int max_w, int max_h, bool wide,
 inline bool inter_residual_in_mc() { static const bool per_block = getenv("HIPDEC_INTER_RECON_PER_BLOCK") != nullptr; return !per_block; }
 void launch_parse_general(const ParseArgs& a, bool throughput, hipStream_t s);   // parse_kernel_general.hip: batches with 4:2:2 / 4:4:4 pictures
 void launch_residual(const FilterArgs& a, int n_pics, int max_ctbs, bool general_chroma /* the batch holds 4:2:2 / 4:4:4 pictures */, hipStream_t s);
-void launch_recon(const ReconArgs& a, bool wide, hipStream_t s, bool inter = false /* the batch holds P pictures */);
+// general_chroma: the batch holds 4:2:2 / 4:4:4 pictures (BatchLayout::general_chroma).  Batches with neither those nor P pictures run k_recon_plan in front of
+// the wavefront, which then reads the plan; -1 (a caller that does not know) counts as 1.
+void launch_recon(const ReconArgs& a, bool wide, hipStream_t s, bool inter = false /* the batch holds P pictures */, int general_chroma = -1);
+int recon_plan_launched();   // 1: the calling thread's last launch_recon ran the plan kernel
 // one_pass: the batch holds intra pictures with 4:0:0 / 4:2:0 sampling only - both edge directions in one pass (k_deblock_fused)
 void launch_deblock(const FilterArgs& a, int n_pics, int max_w, int max_h, bool wide, hipStream_t s, bool one_pass = false);
 // may_keep = false: no picture of the batch has lossless CUs or unfiltered PCM units (8.7.3 "samples stay as they are"): the kernel variant without those paths
@@ -93,7 +96,7 @@ inline void launch_chain_pixels(const BatchLayout& L, uint8_t* arena, int k, hip
   if (st.any_inter) launch_mc(fa, st.count, st.max_w, st.max_h, L.wide, s, inter_residual_in_mc());
   ReconArgs ra{pics, (const ReconWave*)(arena + L.off_rwaves) + st.first_rwave, st.num_rwaves, arena, (uint32_t*)(arena + L.off_row_progress),
                (uint32_t*)(arena + L.off_ticket) + BatchLayout::chain_ticket(k), status, inter_residual_in_mc() ? 1u : 0u};
-  launch_recon(ra, L.wide, s, L.any_inter);
+  launch_recon(ra, L.wide, s, L.any_inter, L.general_chroma ? 1 : 0);
   launch_deblock(fa, st.count, st.max_w, st.max_h, L.wide, s);
   bool may_keep = false, restricted = false;
   for (int i = st.first; i < st.first + st.count; i++) {

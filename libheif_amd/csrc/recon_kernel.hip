@@ -17,6 +17,9 @@
 //   * the CTB being reconstructed lives in LDS (tile(s) + top / left borders + reference-sample line(s), one packed
 //     word per 4x4 unit, a bitmap of the units decoded so far), so gathering, substitution, smoothing and
 //     prediction never touch HBM; the finished CTB leaves LDS once with row-contiguous stores.
+//   * which blocks a CTB holds and which of their neighbouring samples are available does not depend on samples: for intra pictures with 4:0:0 / 4:2:0
+//     sampling k_recon_plan works it out for all CTBs at once in front of the wavefront, which then reads 8-byte records by scalar loads and needs neither
+//     the unit words nor the bitmap (P / B and 4:2:2 / 4:4:4 pictures keep them: the `_inter` builds).
 //   * the kernel is VALU-issue bound (a 4x4 block uses 16 of the lanes but costs whole wave instructions), so the
 //     block path avoids quarter-rate multiplies (v_mul_i32_i24), constant-memory tables (packed immediates) and
 //     anything that waits on global memory besides the prefetched residual.
@@ -80,7 +83,9 @@ constexpr uint64_t smooth_mode_mask(int n)
   return m;
 }
 
-template <typename Pix>
+// PLAN: the build that reads the reconstruction plan (k_recon_plan below) - availability and the unit words come with the plan's records,
+// the two maps at the end shrink to one element
+template <typename Pix, bool PLAN>
 struct ReconLds {
   Pix tile[64 * 64];        // the CTB of this wave's component
   uint32_t top_raw[72];     // words of the line buffer covering x_ctb - 1 .. x_ctb + 2 * ctb - 1 (+ one pad word in front)
@@ -89,11 +94,32 @@ struct ReconLds {
   // availability of the neighbourhood in 4x4-luma units, one row of bits per unit row: row uy + 1, bit ux + 1 for the
   // units ux, uy in [-1, 2 * units_per_side): row 0 / bit 0 are the borders owned by the neighbouring CTBs, rows and bits
   // past the CTB stay 0 (not decoded yet), a unit of the CTB is set when its block has been reconstructed
-  uint64_t avrow[33];
+  uint64_t avrow[PLAN ? 1 : 33];
   // per 4x4-luma unit (z order): log2 TU size | UM_OUTSIDE / UM_INVALID | UF_* flags << 8 | intra mode of this component << 16 |
   // unit x << 24 | unit y << 28
-  uint32_t m_unit[256];
+  uint32_t m_unit[PLAN ? 1 : 256];
 };
+
+// Availability of a block's neighbouring samples as the plan carries it (PlanRecord, hevc_device.h), in units of 4 component samples: nl samples of
+// the left column counted from the block's top edge downward, nt of the top row counted rightward from the block's left edge (above != 0) or from its
+// right edge, the above-left sample; smooth: 8.4.4.2.3 applies to the block (size and mode).  Unused (zero) in the builds that walk the bitmap.
+struct PlanAvail { int nl, nt, above, corner, smooth; };
+// bits [lo, lo + len) of a 64-bit word, clipped to it (lo may be negative)
+__device__ __forceinline__ uint64_t bit_run(int lo, int len)
+{
+  const int a = lo < 0 ? 0 : lo, b = lo + len > 64 ? 64 : lo + len;
+  return b > a ? (~0ull >> (64 - (b - a))) << a : 0ull;
+}
+// the available reference samples e in [64 j, 64 j + 64) of an n x n block in scan order (left column bottom-up: e < 2n, corner: e = 2n, top row)
+__device__ __forceinline__ uint64_t plan_mask(const PlanAvail& V, int n, int j)
+{
+  const int n2 = 2 * n;
+  // up to 8x8 all 4n + 1 samples sit in word 0 and nothing needs clipping (nl, nt <= n / 2): three bit-field masks
+  if (n <= 8) return j ? 0ull : ((((1ull << (4 * V.nl)) - 1ull) << (n2 - 4 * V.nl)) | ((uint64_t)V.corner << n2) | (((1ull << (4 * V.nt)) - 1ull) << (n2 + 1 + (V.above ? 0 : n))));
+  return bit_run(n2 - 4 * V.nl - 64 * j, 4 * V.nl) | bit_run(n2 - 64 * j, V.corner) | bit_run(n2 + 1 + (V.above ? 0 : n) - 64 * j, 4 * V.nt);
+}
+// the last sample of the top row (e = 4n, handled apart by the forms whose passes end before it): available when the top run reaches it
+__device__ __forceinline__ int plan_last(const PlanAvail& V, int n) { return V.nt == (V.above ? n >> 1 : n >> 2); }
 
 constexpr uint32_t UM_OUTSIDE = 16u, UM_INVALID = 32u;   // unit-word bits 4 / 5 (ReconLds::m_unit): the unit lies outside the picture / carries an impossible transform size
 
@@ -139,6 +165,26 @@ __device__ __forceinline__ void drain_stores()
 #endif
 }
 
+// The plan is written by the kernel in front of this one and only read here: loads through the constant address space, which the compiler turns into
+// scalar loads when the address is wave-uniform (a plain global load of the arena stays a vector load: the kernel also stores into the arena)
+__device__ __forceinline__ uint32_t plan_load32(const uint32_t* p)
+{
+#ifndef HIPDEC_HOST_EMU
+  return *(const __attribute__((address_space(4))) uint32_t*)(uintptr_t)p;
+#else
+  return *p;
+#endif
+}
+__device__ __forceinline__ uint2 plan_load64(const PlanRecord* p)
+{
+#ifndef HIPDEC_HOST_EMU
+  const uint64_t v = *(const __attribute__((address_space(4))) uint64_t*)(uintptr_t)p;
+  return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
+#else
+  return make_uint2(p->w0, p->w1);
+#endif
+}
+
 struct Ctx {
   int lane;
   int ctbc, lg_ctbc;  // CTB size in component samples (and its log2)
@@ -158,7 +204,7 @@ struct Ctx {
 // the units of an inter coded block become available to the intra blocks behind them (not with constrained_intra_pred_flag: their samples stay "not
 // available for intra prediction", 8.4.4.2.2)
 template <typename Pix>
-__device__ __forceinline__ void mark_inter_available(ReconLds<Pix>& L, const Ctx& C, int xb, int yb, int log2n, int ushx, int ushy)
+__device__ __forceinline__ void mark_inter_available(ReconLds<Pix, false>& L, const Ctx& C, int xb, int yb, int log2n, int ushx, int ushy)
 {
   if (!C.cip) {
     const int n = 1 << log2n;
@@ -169,7 +215,7 @@ __device__ __forceinline__ void mark_inter_available(ReconLds<Pix>& L, const Ctx
 }
 
 template <typename Pix>
-__device__ __forceinline__ void reconstruct_inter_block(ReconLds<Pix>& L, const Ctx& C, Pix* tile, const Pix* pred, uint32_t pstride, int xb, int yb, int log2n, int cbf,
+__device__ __forceinline__ void reconstruct_inter_block(ReconLds<Pix, false>& L, const Ctx& C, Pix* tile, const Pix* pred, uint32_t pstride, int xb, int yb, int log2n, int cbf,
                                                         const int16_t* res, int l, int LW, int ushx, int ushy)
 {
   const int n = 1 << log2n, nn = n * n, lg_ctbc = C.lg_ctbc, maxv = C.maxv;
@@ -184,8 +230,10 @@ __device__ __forceinline__ void reconstruct_inter_block(ReconLds<Pix>& L, const 
 
 // One transform block: prediction (+ residual) into the LDS tile.
 //   (xb, yb): block origin inside the CTB in component samples; log2n: block size
-template <typename Pix>
-__device__ __forceinline__ void reconstruct_block(ReconLds<Pix>& L, const Ctx& C, const Pix* top, int xb, int yb, int log2n, int mode, int cbf, const int16_t* res)
+//   V: the availability from the plan (PLAN builds; the others read the bitmap L.avrow and mark the block in it)
+template <typename Pix, bool PLAN>
+__device__ __forceinline__ void reconstruct_block(ReconLds<Pix, PLAN>& L, const Ctx& C, const Pix* top, int xb, int yb, int log2n, int mode, int cbf, const int16_t* res,
+                                                  const PlanAvail& V)
 {
   const int lane = C.lane;
   const int n = 1 << log2n, n2 = 2 * n, N = 4 * n + 1, nn = n * n;
@@ -219,19 +267,21 @@ __device__ __forceinline__ void reconstruct_block(ReconLds<Pix>& L, const Ctx& C
     const int px = is_left ? -1 : e - n2 - 1, py = is_left ? n2 - 1 - e : -1;
     const int X = xb + px, Y = yb + py;
     int a = 0;
-    if (e < N) a = (int)((L.avrow[(Y >> C.ush) + 1] >> ((X >> C.ush) + 1)) & 1u);
+    if constexpr (PLAN) { m[j] = plan_mask(V, n, j); a = (int)((m[j] >> lane) & 1u); }
+    else if (e < N) a = (int)((L.avrow[(Y >> C.ush) + 1] >> ((X >> C.ush) + 1)) & 1u);
     if (a) {
       const Pix* src = Y < 0 ? &top[X + 1] : (X < 0 ? &L.left[Y] : &tile[(Y << lg_ctbc) + X]);
       ref0[e] = (uint16_t)*src;
     }
     av[j] = a;
-    m[j] = __ballot(a);
+    if constexpr (!PLAN) m[j] = __ballot(a);
   }
   int ax = 1;          // availability of the extra sample (blocks below 16x16 have none: counts as present)
   const int has_x = n >= 16;
   if (has_x) {
     const int X = xb + n2 - 1, Y = yb - 1;
-    ax = (int)((L.avrow[(Y >> C.ush) + 1] >> ((X >> C.ush) + 1)) & 1u);
+    if constexpr (PLAN) ax = plan_last(V, n);
+    else ax = (int)((L.avrow[(Y >> C.ush) + 1] >> ((X >> C.ush) + 1)) & 1u);
     if (ax && lane == 0) ref0[N - 1] = (uint16_t)(Y < 0 ? top[X + 1] : tile[(Y << lg_ctbc) + X]);
   }
   lds_sync();
@@ -274,10 +324,10 @@ __device__ __forceinline__ void reconstruct_block(ReconLds<Pix>& L, const Ctx& C
   // accessors in scan order: left column p[-1][k-1] = ref[2n - k], top row p[k-1][-1] = ref[2n + k]
   const uint16_t* ref = ref0;
   // ---- 8.4.4.2.3 smoothing of the reference samples (luma; chroma too with ChromaArrayType 3) ----
-  if (C.smooth && n != 4) {
+  if (PLAN ? V.smooth != 0 : (C.smooth && n != 4)) {
     constexpr uint64_t k8 = smooth_mode_mask(8), k16 = smooth_mode_mask(16), k32 = smooth_mode_mask(32);
     const uint64_t filtered_modes = n == 8 ? k8 : (n == 16 ? k16 : k32);
-    if ((filtered_modes >> (mode & 63)) & 1ull) {
+    if (PLAN || ((filtered_modes >> (mode & 63)) & 1ull)) {
       int strong = 0;
       if (C.strong && n == 32) {
         const int c0 = ref[n2], tl = ref[0], tm = ref[n], rt = ref[N - 1], rm = ref[n2 + n];  // corner, p[-1][63], p[-1][31], p[63][-1], p[31][-1]
@@ -377,7 +427,7 @@ __device__ __forceinline__ void reconstruct_block(ReconLds<Pix>& L, const Ctx& C
 #undef RT
 #undef NEXT_RES
   // ---- the block's units are decoded now ----
-  {
+  if constexpr (!PLAN) {
     const int k = n >> C.ush;    // units per side (>= 1)
     if (lane < k) lds_or(&L.avrow[(yb >> C.ush) + 1 + lane], ((1ull << k) - 1ull) << ((xb >> C.ush) + 1));
   }
@@ -389,8 +439,9 @@ __device__ __forceinline__ void reconstruct_block(ReconLds<Pix>& L, const Ctx& C
 // wave shuffles - and the prediction reads them with ds_bpermute instead of through a reference line in LDS: no line to write, no passes over 64 j + lane,
 // no LDS round trips between the stages (the general form's four wave-level LDS fences per block were most of a small block's latency, its run-time
 // sizes a third of its instructions).  Every sample of the block is one lane (16 or 64 of them).  Same arithmetic as reconstruct_block.
-template <typename Pix, int LG>
-__device__ __forceinline__ void reconstruct_block_reg(ReconLds<Pix>& L, const Ctx& C, const Pix* top, int xb, int yb, int mode, int cbf, const int16_t* res)
+template <typename Pix, int LG, bool PLAN>
+__device__ __forceinline__ void reconstruct_block_reg(ReconLds<Pix, PLAN>& L, const Ctx& C, const Pix* top, int xb, int yb, int mode, int cbf, const int16_t* res,
+                                                      const PlanAvail& V)
 {
   constexpr int n = 1 << LG, n2 = 2 * n, N = 4 * n + 1, nn = n * n;
   static_assert(N <= 64 && nn <= 64, "one lane per reference sample and per block sample");
@@ -403,10 +454,12 @@ __device__ __forceinline__ void reconstruct_block_reg(ReconLds<Pix>& L, const Ct
   const int is_left = e < n2;
   const int X = xb + (is_left ? -1 : e - n2 - 1), Y = yb + (is_left ? n2 - 1 - e : -1);
   int a = 0;
-  if (e < N) a = (int)((L.avrow[(Y >> C.ush) + 1] >> ((X >> C.ush) + 1)) & 1u);
+  uint64_t m;
+  if constexpr (PLAN) { m = plan_mask(V, n, 0); a = (int)((m >> lane) & 1u); }
+  else if (e < N) a = (int)((L.avrow[(Y >> C.ush) + 1] >> ((X >> C.ush) + 1)) & 1u);
   int r = 0;
   if (a) r = (int)(Y < 0 ? top[X + 1] : (X < 0 ? L.left[Y] : tile[(Y << lg_ctbc) + X]));
-  const uint64_t m = __ballot(a);
+  if constexpr (!PLAN) m = __ballot(a);
   if (m != (1ull << N) - 1ull) {   // (wave-uniform) substitution
     if (m == 0) r = 1 << (C.bit_depth - 1);
     else {
@@ -417,9 +470,9 @@ __device__ __forceinline__ void reconstruct_block_reg(ReconLds<Pix>& L, const Ct
     }
   }
   // ---- 8.4.4.2.3 smoothing (8x8; 4x4 blocks are never filtered): [1 2 1] on everything but the two ends ----
-  if (LG == 3 && C.smooth) {
+  if (LG == 3 && (PLAN ? V.smooth != 0 : C.smooth != 0)) {
     constexpr uint64_t k8 = smooth_mode_mask(8);
-    if ((k8 >> (mode & 63)) & 1ull) {
+    if (PLAN || ((k8 >> (mode & 63)) & 1ull)) {
       const int lo = __shfl(r, lane - 1), hi = __shfl(r, lane + 1);
       const int f = (lo + 2 * r + hi + 2) >> 2;
       r = (e == 0 || e >= N - 1) ? r : f;
@@ -464,7 +517,7 @@ __device__ __forceinline__ void reconstruct_block_reg(ReconLds<Pix>& L, const Ct
   if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0);   // a PCM unit's "residual" is the sample itself
   if (lane < nn) tile[((yb + y) << lg_ctbc) + xb + x] = (Pix)v;
   // ---- the block's units are decoded now ----
-  {
+  if constexpr (!PLAN) {
     const int k = n >> C.ush;    // units per side (>= 1)
     if (lane < k) lds_or(&L.avrow[(yb >> C.ush) + 1 + lane], ((1ull << k) - 1ull) << ((xb >> C.ush) + 1));
   }
@@ -476,9 +529,9 @@ __device__ __forceinline__ void reconstruct_block_reg(ReconLds<Pix>& L, const Ct
 // the samples, the residuals and the coded-block flags differ — so one instruction stream reconstructs both blocks.
 //   LDS: the Cr tile sits behind the Cb tile (each 1 << lg_ctbc wide, 1 << lg_ctbh tall), left borders at left[0..63] / left[64..127], reference lines
 //   at refbuf0[1 + 67 h ...];  `top`, `cbf` and `res` are this lane's half's.
-template <typename Pix>
-__device__ __forceinline__ void reconstruct_chroma_pair(ReconLds<Pix>& L, const Ctx& C, const Pix* top, int xb, int yb, int log2n, int mode, int cbf,
-                                                        const int16_t* res)
+template <typename Pix, bool PLAN>
+__device__ __forceinline__ void reconstruct_chroma_pair(ReconLds<Pix, PLAN>& L, const Ctx& C, const Pix* top, int xb, int yb, int log2n, int mode, int cbf,
+                                                        const int16_t* res, const PlanAvail& V)
 {
   const int lane = C.lane, l = lane & 31, h = lane >> 5;
   const int n = 1 << log2n, n2 = 2 * n, N = 4 * n + 1, nn = n * n;
@@ -500,6 +553,7 @@ __device__ __forceinline__ void reconstruct_chroma_pair(ReconLds<Pix>& L, const 
   // ---- reference samples: e = l + 32 j for J = 1 (2 for 16x16) passes; blocks from 8x8 up have the extra sample e = 4n ----
   const int J = n == 16 ? 2 : 1;
   uint64_t m0 = 0;        // availability over e < 64 (identical in both halves: taken from the Cb lanes)
+  if constexpr (PLAN) m0 = plan_mask(V, n, 0) & (J == 2 ? ~0ull : 0xffffffffull);
   int av[2] = {0, 0};
 #pragma unroll
   for (int j = 0; j < 2; j++) {
@@ -509,19 +563,21 @@ __device__ __forceinline__ void reconstruct_chroma_pair(ReconLds<Pix>& L, const 
     const int px = is_left ? -1 : e - n2 - 1, py = is_left ? n2 - 1 - e : -1;
     const int X = xb + px, Y = yb + py;
     int a = 0;
-    if (e < N) a = (int)((L.avrow[(Y >> ushy) + 1] >> ((X >> 1) + 1)) & 1u);
+    if constexpr (PLAN) a = (int)((m0 >> e) & 1u);
+    else if (e < N) a = (int)((L.avrow[(Y >> ushy) + 1] >> ((X >> 1) + 1)) & 1u);
     if (a) {
       const Pix* src = Y < 0 ? &top[X + 1] : (X < 0 ? &left[Y] : &tile[(Y << lg_ctbc) + X]);
       ref0[e] = (uint16_t)*src;
     }
     av[j] = a;
-    m0 |= (__ballot(a) & 0xffffffffull) << (32 * j);
+    if constexpr (!PLAN) m0 |= (__ballot(a) & 0xffffffffull) << (32 * j);
   }
   int ax = 1;
   const int has_x = n >= 8;
   if (has_x) {
     const int X = xb + n2 - 1, Y = yb - 1;
-    ax = (int)((L.avrow[(Y >> ushy) + 1] >> ((X >> 1) + 1)) & 1u);
+    if constexpr (PLAN) ax = plan_last(V, n);
+    else ax = (int)((L.avrow[(Y >> ushy) + 1] >> ((X >> 1) + 1)) & 1u);
     if (ax && l == 0) ref0[N - 1] = (uint16_t)(Y < 0 ? top[X + 1] : tile[(Y << lg_ctbc) + X]);
   }
   lds_sync();
@@ -607,7 +663,7 @@ __device__ __forceinline__ void reconstruct_chroma_pair(ReconLds<Pix>& L, const 
 #undef RL
 #undef RT
 #undef NEXT_RES
-  {
+  if constexpr (!PLAN) {
     const int k = n >> 1, rows = n >> ushy;    // units per row of the block, unit rows (4:2:2: a 4x4 block is two units wide and one tall)
     if (lane < rows) lds_or(&L.avrow[(yb >> ushy) + 1 + lane], ((1ull << k) - 1ull) << ((xb >> 1) + 1));
   }
@@ -616,8 +672,9 @@ __device__ __forceinline__ void reconstruct_chroma_pair(ReconLds<Pix>& L, const 
 
 // The 4x4 blocks of the chroma pair register-resident (reconstruct_block_reg's scheme in each half of the wave: 17 reference samples and 16 block
 // samples per half; 4:2:0 / 4:2:2 chroma has neither reference smoothing nor boundary filters)
-template <typename Pix>
-__device__ __forceinline__ void reconstruct_chroma_pair_reg4(ReconLds<Pix>& L, const Ctx& C, const Pix* top, int xb, int yb, int mode, int cbf, const int16_t* res)
+template <typename Pix, bool PLAN>
+__device__ __forceinline__ void reconstruct_chroma_pair_reg4(ReconLds<Pix, PLAN>& L, const Ctx& C, const Pix* top, int xb, int yb, int mode, int cbf, const int16_t* res,
+                                                             const PlanAvail& V)
 {
   constexpr int LG = 2, n = 4, n2 = 8, N = 17, nn = 16;
   const int lane = C.lane, l = lane & 31, hb = lane & 32;   // hb: the first lane of this lane's half
@@ -630,10 +687,12 @@ __device__ __forceinline__ void reconstruct_chroma_pair_reg4(ReconLds<Pix>& L, c
   const int is_left = e < n2;
   const int X = xb + (is_left ? -1 : e - n2 - 1), Y = yb + (is_left ? n2 - 1 - e : -1);
   int a = 0;
-  if (e < N) a = (int)((L.avrow[(Y >> ushy) + 1] >> ((X >> 1) + 1)) & 1u);
+  uint32_t m;
+  if constexpr (PLAN) { m = (uint32_t)plan_mask(V, n, 0); a = (int)((m >> l) & 1u); }
+  else if (e < N) a = (int)((L.avrow[(Y >> ushy) + 1] >> ((X >> 1) + 1)) & 1u);
   int r = 0;
   if (a) r = (int)(Y < 0 ? top[X + 1] : (X < 0 ? left[Y] : tile[(Y << lg_ctbc) + X]));
-  const uint32_t m = (uint32_t)__ballot(a);   // availability is the same in both halves: the Cb lanes' bits
+  if constexpr (!PLAN) m = (uint32_t)__ballot(a);   // availability is the same in both halves: the Cb lanes' bits
   if (m != (1u << N) - 1u) {
     if (m == 0) r = 1 << (C.bit_depth - 1);
     else {
@@ -667,7 +726,7 @@ __device__ __forceinline__ void reconstruct_chroma_pair_reg4(ReconLds<Pix>& L, c
   }
   if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0);   // a PCM unit's "residual" is the sample itself
   if (l < nn) tile[((yb + y) << lg_ctbc) + xb + x] = (Pix)v;
-  {
+  if constexpr (!PLAN) {
     const int k = n >> 1, rows = n >> ushy;    // units per row of the block, unit rows (4:2:2: a 4x4 block is two units wide and one tall)
     if (lane < (rows > 0 ? rows : 1)) lds_or(&L.avrow[(yb >> ushy) + 1 + lane], ((1ull << k) - 1ull) << ((xb >> 1) + 1));
   }
@@ -680,9 +739,12 @@ __device__ __forceinline__ void reconstruct_chroma_pair_reg4(ReconLds<Pix>& L, c
 // picture, the Cb / Cr plane (plane 1 / 2: same geometry as luma, the chroma modes / flags / bit depth, no boundary filters).
 // DUAL = true: the 4:2:0 Cb (lanes 0..31) and Cr (lanes 32..63) side by side — h / l below are a lane's half and its index inside
 // the half, LW the lanes one component has.
+// INTER = false is also the build that reads the reconstruction plan (PLAN): intra pictures with 4:0:0 / 4:2:0 sampling only; its front end is the plan's
+// record list of the CTB instead of the staged unit words, the walk over them and the availability bitmap.
 template <typename Pix, bool DUAL, bool INTER>
-__device__ __forceinline__ void recon_rows(const ReconArgs& A, const ReconWave& wd, ReconLds<Pix>& L, int lane, int plane)
+__device__ __forceinline__ void recon_rows(const ReconArgs& A, const ReconWave& wd, ReconLds<Pix, !INTER>& L, int lane, int plane)
 {
+  constexpr bool PLAN = !INTER;
   constexpr int ES = (int)sizeof(Pix);
   constexpr int LW = DUAL ? 32 : 64;
   constexpr int PPW = 4 / ES;            // pixels per 32-bit word
@@ -775,7 +837,7 @@ __device__ __forceinline__ void recon_rows(const ReconArgs& A, const ReconWave& 
       top = (const Pix*)((const uint8_t*)(top_raw + 1) + (b0 - start));   // top[0] = above-left sample
     }
     // ---- stage the CTB's maps, one packed word per unit ----
-    {
+    if constexpr (!PLAN) {
       const size_t base = (size_t)ctb_rs * units;
       int inter_units = 0;
       for (int i = lane * 4; i < units; i += 256) {
@@ -843,6 +905,29 @@ __device__ __forceinline__ void recon_rows(const ReconArgs& A, const ReconWave& 
 
     // ---- the blocks of the CTB in z-scan order ----
     const int16_t* res_base = coeff + (size_t)ctb_rs * (ctb * ctb / (sub * suby));
+    if constexpr (PLAN) {
+      // the CTB's records of this plane group, in z-scan order; the next one is requested (a scalar load: the address is wave-uniform) before the block
+      // in hand is reconstructed
+      const PlanRecord* recs = (const PlanRecord*)(A.arena + P.off_plan) + (size_t)ctb_rs * (size_t)(units + (units >> 2)) + (DUAL ? units : 0);
+      const uint32_t counts = plan_load32((const uint32_t*)(A.arena + P.off_plan_cnt) + ctb_rs);
+      const int count = (int)(DUAL ? counts >> 16 : counts & 0xffffu);
+      uint2 nx = plan_load64(recs);    // (slot 0 always exists)
+      for (int i = 0; i < count; i++) {
+        const uint32_t w0 = nx.x, w1 = nx.y;
+        nx = plan_load64(recs + (i + 1 < count ? i + 1 : i));
+        const int xb = (int)(w0 & 15u) << 2, yb = (int)((w0 >> 4) & 15u) << 2, lg = (int)((w0 >> 8) & 7u), z = (int)(w0 >> 24);
+        const int mode = (int)(w1 & 255u), fl = (int)((w1 >> 8) & 255u);
+        PlanAvail V;
+        V.nl = (int)((w0 >> 12) & 31u); V.nt = (int)((w0 >> 17) & 31u); V.above = (int)((w0 >> 22) & 1u); V.corner = (int)((w0 >> 23) & 1u); V.smooth = (int)((w0 >> 11) & 1u);
+        if (!DUAL) {
+          if (lg == 2) reconstruct_block_reg<Pix, 2, PLAN>(L, C, top, xb, yb, mode, fl & (cbf_bit | UF_PCM), res_base + z * 16, V);
+          else if (lg == 3) reconstruct_block_reg<Pix, 3, PLAN>(L, C, top, xb, yb, mode, fl & (cbf_bit | UF_PCM), res_base + z * 16, V);
+          else reconstruct_block<Pix, PLAN>(L, C, top, xb, yb, lg, mode, fl & (cbf_bit | UF_PCM), res_base + z * 16, V);
+        } else if (lg == 2) reconstruct_chroma_pair_reg4<Pix, PLAN>(L, C, top, xb, yb, mode, fl & (cbf_bit | UF_PCM), res_base + z * 4, V);
+        else reconstruct_chroma_pair<Pix, PLAN>(L, C, top, xb, yb, lg, mode, fl & (cbf_bit | UF_PCM), res_base + z * 4, V);
+      }
+    } else {
+    const PlanAvail V{0, 0, 0, 0, 0};
     int z = 0;
     while (z < units) {
       const uint32_t w = L.m_unit[z];
@@ -882,26 +967,27 @@ __device__ __forceinline__ void recon_rows(const ReconArgs& A, const ReconWave& 
           }
         }
       } else if (!DUAL) {
-        if (tb == 2) reconstruct_block_reg<Pix, 2>(L, C, top, ux * 4, uy * 4, mode, fl & (cbf_bit | UF_PCM), res_base + z * 16);
-        else if (tb == 3) reconstruct_block_reg<Pix, 3>(L, C, top, ux * 4, uy * 4, mode, fl & (cbf_bit | UF_PCM), res_base + z * 16);
-        else reconstruct_block<Pix>(L, C, top, ux * 4, uy * 4, tb, mode, fl & (cbf_bit | UF_PCM), res_base + z * 16);
+        if (tb == 2) reconstruct_block_reg<Pix, 2, PLAN>(L, C, top, ux * 4, uy * 4, mode, fl & (cbf_bit | UF_PCM), res_base + z * 16, V);
+        else if (tb == 3) reconstruct_block_reg<Pix, 3, PLAN>(L, C, top, ux * 4, uy * 4, mode, fl & (cbf_bit | UF_PCM), res_base + z * 16, V);
+        else reconstruct_block<Pix, PLAN>(L, C, top, ux * 4, uy * 4, tb, mode, fl & (cbf_bit | UF_PCM), res_base + z * 16, V);
       } else if (tb > 2 || (z & 3) == 3) {
         // the 4x4 chroma blocks of four 4x4 luma TUs hang off the 4th unit (their flags are there); they sit at the quad's origin
         const int quad = tb == 2;
         const int zc = quad ? (z & ~3) : z, cux = quad ? (ux & ~1) : ux, cuy = quad ? (uy & ~1) : uy;
         const int lgc = quad ? 2 : tb - 1;
-        if (suby == 2 && lgc == 2) reconstruct_chroma_pair_reg4<Pix>(L, C, top, cux * 2, cuy * 2, mode, fl & (cbf_bit | UF_PCM), res_base + zc * 4);
-        else if (suby == 2) reconstruct_chroma_pair<Pix>(L, C, top, cux * 2, cuy * 2, lgc, mode, fl & (cbf_bit | UF_PCM), res_base + zc * 4);
+        if (suby == 2 && lgc == 2) reconstruct_chroma_pair_reg4<Pix, PLAN>(L, C, top, cux * 2, cuy * 2, mode, fl & (cbf_bit | UF_PCM), res_base + zc * 4, V);
+        else if (suby == 2) reconstruct_chroma_pair<Pix, PLAN>(L, C, top, cux * 2, cuy * 2, lgc, mode, fl & (cbf_bit | UF_PCM), res_base + zc * 4, V);
         else {
           // 4:2:2: two blocks one above the other, the upper one first (the lower one predicts from it); the lower one's flags sit in unit z ^ 1
           const int fl2 = (int)((L.m_unit[z ^ 1] >> 8) & 255u);
 #pragma nounroll
           for (int lower = 0; lower < 2; lower++)
-            reconstruct_chroma_pair<Pix>(L, C, top, cux * 2, cuy * 4 + (lower << lgc), lgc, mode, (lower ? fl2 : fl) & (cbf_bit | UF_PCM),
-                                         res_base + zc * 8 + (lower << (2 * lgc)));
+            reconstruct_chroma_pair<Pix, PLAN>(L, C, top, cux * 2, cuy * 4 + (lower << lgc), lgc, mode, (lower ? fl2 : fl) & (cbf_bit | UF_PCM),
+                                               res_base + zc * 8 + (lower << (2 * lgc)), V);
         }
       }
       z += 1 << (2 * (tb - 2));
+    }
     }
     lds_sync();
 
@@ -933,7 +1019,7 @@ __device__ __forceinline__ void recon_rows(const ReconArgs& A, const ReconWave& 
 template <typename Pix, bool INTER>
 __device__ __forceinline__ void recon_wave(const ReconArgs& A)
 {
-  __shared__ ReconLds<Pix> L;
+  __shared__ ReconLds<Pix, !INTER> L;
   const int lane = threadIdx.x;
   uint32_t t = 0;
   if (lane == 0) t = atomicAdd(A.ticket, 1u);
@@ -942,11 +1028,143 @@ __device__ __forceinline__ void recon_wave(const ReconArgs& A)
   if (__hip_atomic_load(A.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;   // failed parse: maps are garbage
   const ReconWave wd = A.waves[ticket];
   const int cfi = A.pics[wd.pic].chroma_format_idc;
+  if (!INTER && (cfi >= 2 || A.pics[wd.pic].is_inter)) {   // the plan covers neither (launch_recon sends such batches to the other build): not decoded, reported
+    if (lane == 0) atomicCAS((int*)A.status, 0, DEV_ERR_SYNTAX | (int)(0x40000000u));
+    return;
+  }
   if (wd.comp == 0 || cfi == 3) { if (wd.comp == 0 || cfi) recon_rows<Pix, false, INTER>(A, wd, L, lane, (int)wd.comp); }   // luma; 4:4:4: one wave per plane
   else if (cfi) recon_rows<Pix, true, INTER>(A, wd, L, lane, 1);                            // 4:2:0: comp 1 = Cb and Cr together
 }
 
-// 8-bit pictures: 7 waves per SIMD by registers (<= 72 VGPRs), 26 per CU by LDS (6072 B per wave, handed out in 512 B granules).  What was measured
+// ---- the reconstruction plan ----
+// Which blocks a wave reconstructs, where, and which of their neighbouring samples are available depends on the unit maps, the CTB's availability
+// bits and the picture size only - not on samples - so it is worked out here for all CTBs at once, one lane per 4x4 unit, instead of block by block
+// on the wavefront's scalar pipe.  One wave per luma wave of the wavefront's table walks that wave's CTBs (the launcher knows the wave count, not the
+// CTB count) and writes both lists of every CTB: luma, and the 4:2:0 chroma pair at the granularity of 8x8 luma areas.
+// Availability (6.4.1 with constrained intra prediction off) in closed form: a neighbour inside the CTB is available when it precedes the block in
+// z-scan order and lies inside the picture - for the below-left and above-right regions that is decided by the aligned square of the block's own size
+// there, which precedes or follows the block as a whole; a neighbour in another CTB by that CTB's bit in CtbInfo::avail (the CTBs below and to the right
+// inside the same row are never decoded yet).  What is available of a region is then a run that starts at the block and ends at the picture edge.
+namespace {
+// One record.  (gx, gy): the block inside the CTB, gk its size (a power of two), gside the CTB's, gz the z index of its first unit - all in grid units (4x4
+// luma units for the luma list, 8x8 luma areas for the chroma list); rem_x / rem_y: grid units from the CTB's origin to the right / bottom picture edge.
+// z indices of the neighbouring squares by arithmetic on the interleaved form: x lives in the even bits, y in the odd ones; a subtraction borrows across
+// the other coordinate's (masked-off) bits, an addition carries across them once they are filled with ones.
+__device__ __forceinline__ PlanRecord plan_record(int gx, int gy, int gk, int gside, uint32_t gz, int rem_x, int rem_y, uint32_t avail, int lg, uint32_t z,
+                                                  uint32_t mode, uint32_t flags, int smooth)
+{
+  constexpr uint32_t MX = 0x55555555u, MY = 0xaaaaaaaau;
+  const uint32_t zx = gz & MX, zy = gz & MY, dx = (uint32_t)(gk * gk), dy = 2u * dx;   // gk in interleaved form, as an x / a y step
+  const int left = gx > 0 || (avail & AV_LEFT), above = gy > 0 || (avail & AV_UP);
+  const int corner = gx > 0 ? (gy > 0 || (avail & AV_UP)) : (gy > 0 ? (avail & AV_LEFT) != 0 : (avail & AV_UPLEFT) != 0);
+  // below-left: rows gy + gk ... of the column left of the block - the square at (gx - gk, gy + gk)
+  int bl = 0;
+  if (gy + gk < gside && (gx > 0 ? (((zx - dx) & MX) | (((zy | MX) + dy) & MY)) < gz : (avail & AV_LEFT) != 0)) {
+    bl = rem_y - (gy + gk);
+    bl = bl < 0 ? 0 : (bl > gk ? gk : bl);
+  }
+  // above-right: columns gx + gk ... of the row above the block - the square at (gx + gk, gy - gk)
+  int ar = 0;
+  const int in_ctb = gx + gk < gside;
+  if (gy > 0 ? (in_ctb && ((((zx | MY) + dx) & MX) | ((zy - dy) & MY)) < gz) : (avail & (in_ctb ? AV_UP : AV_UPRIGHT)) != 0) {
+    ar = rem_x - (gx + gk);
+    ar = ar < 0 ? 0 : (ar > gk ? gk : ar);
+  }
+  const int nl = left ? gk + bl : 0, nt = above ? gk + ar : ar;
+  PlanRecord r;
+  r.w0 = (uint32_t)gx | ((uint32_t)gy << 4) | ((uint32_t)lg << 8) | ((uint32_t)(smooth ? 1 : 0) << 11) | ((uint32_t)nl << 12) | ((uint32_t)nt << 17) |
+         ((uint32_t)(above ? 1 : 0) << 22) | ((uint32_t)(corner ? 1 : 0) << 23) | (z << 24);
+  r.w1 = mode | (flags << 8);
+  return r;
+}
+}  // namespace
+
+// One wave per luma wave of the wavefront's table; a lane holds the four units of a quad (z = 4 lane + k: one 32-bit load per map, as the parser stored
+// them), so a 64x64 CTB is one pass.  No LDS, no barriers: the slot of a record is a prefix count over the ballots of the four unit positions; the map
+// words of the next CTB are requested before the records of the one in hand are worked out.
+__global__ __launch_bounds__(64) void k_recon_plan(ReconArgs A)
+{
+  const int lane = (int)threadIdx.x;
+  if (blockIdx.x >= A.num_waves) return;
+  if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(A.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0) return;   // failed parse: the maps are garbage
+  const ReconWave wd = A.waves[blockIdx.x];
+  const PicParams& P = A.pics[wd.pic];
+  if (wd.comp != 0 || P.is_inter || P.chroma_format_idc >= 2 || !P.off_plan_cnt) return;
+  const bool with_chroma = P.chroma_format_idc == 1;
+  const int log2_ctb = P.log2_ctb, ctb_w = P.ctb_w, ctb_h = P.ctb_h, pic_w = P.width, pic_h = P.height;
+  const int units = 1 << P.units_per_ctb_log2, side = 1 << (log2_ctb - 2);
+  const CtbInfo* ctb_info = (const CtbInfo*)(A.arena + P.off_ctb_info);
+  PlanRecord* plan = (PlanRecord*)(A.arena + P.off_plan);
+  uint16_t* plan_cnt = (uint16_t*)(A.arena + P.off_plan_cnt);
+  const uint8_t *u_size = A.arena + P.off_u_size, *u_flags = A.arena + P.off_u_flags, *u_ipm = A.arena + P.off_u_ipm, *u_ipmc = A.arena + P.off_u_ipmc;
+  const uint32_t z0 = (uint32_t)lane * 4u;
+  const bool active = (int)z0 < units;                                   // (a 16x16 CTB is four lanes, a 32x32 one sixteen)
+  const int ux0 = (int)compact1by1(z0), uy0 = (int)compact1by1(z0 >> 1);   // the quad's origin: both even
+  const uint64_t below = (1ull << lane) - 1ull;
+  uint32_t n_sz = 0, n_fl = 0, n_md = 0, n_mc = 0;                        // the next CTB's map words
+  auto request = [&](int rs) {
+    if (active) {
+      const size_t o = (size_t)rs * units + z0;
+      n_sz = *(const uint32_t*)(u_size + o); n_fl = *(const uint32_t*)(u_flags + o); n_md = *(const uint32_t*)(u_ipm + o); n_mc = *(const uint32_t*)(u_ipmc + o);
+    }
+  };
+  int cy = (int)wd.first_row, cx = 0;
+  if (cy < ctb_h && ctb_w > 0) request(cy * ctb_w);
+  while (cy < ctb_h) {
+    const int ctb_rs = cy * ctb_w + cx;
+    const uint32_t sz = n_sz, fl = n_fl, md = n_md, mc = n_mc;
+    int ncx = cx + 1, ncy = cy;
+    if (ncx == ctb_w) { ncx = 0; ncy += (int)wd.stride; }
+    if (ncy < ctb_h) request(ncy * ctb_w + ncx);
+    const uint32_t avail = ctb_info[ctb_rs].avail;
+    const int x_ctb = cx << log2_ctb, y_ctb = cy << log2_ctb;
+    const int rem_x = (pic_w - x_ctb + 3) >> 2, rem_y = (pic_h - y_ctb + 3) >> 2;     // 4x4 units to the picture's edges
+    uint32_t emit_l = 0, emit_c = 0;   // bit k: unit z0 + k starts a luma block / carries a block of the chroma pair
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t tb = (sz >> (8 * k)) & 15u, z = z0 + (uint32_t)k;
+      const bool inside = active && ux0 + (k & 1) < rem_x && uy0 + (k >> 1) < rem_y;
+      // a transform size outside 4 .. 32 (or beyond the CTB) is a broken map: reported, and the unit emits nothing
+      const bool wrong = inside && ((tb - 2u) > 3u || (int)tb > log2_ctb);
+      bad = bad || wrong;
+      const bool first = inside && !wrong && (z & ((1u << (2 * (tb - 2u))) - 1u)) == 0;   // the unit starts its transform block
+      if (first) emit_l |= 1u << k;
+      // the chroma pair: one block per luma block from 8x8 up, and one per quad of 4x4 luma blocks (the quad's fourth unit holds its flags and mode)
+      if (with_chroma && inside && !wrong && (tb > 2u ? first : k == 3)) emit_c |= 1u << k;
+    }
+    if (bad) atomicCAS((int*)A.status, 0, DEV_ERR_SYNTAX | (int)(0x40000000u) | (int)((wd.base_row + (uint32_t)cy) << 8));
+    uint32_t slot_l = 0, slot_c = 0, n_l = 0, n_c = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint64_t bl = __ballot((emit_l >> k) & 1u), bc = __ballot((emit_c >> k) & 1u);
+      slot_l += (uint32_t)__popcll(bl & below); slot_c += (uint32_t)__popcll(bc & below);
+      n_l += (uint32_t)__popcll(bl); n_c += (uint32_t)__popcll(bc);
+    }
+    PlanRecord* recs = plan + (size_t)ctb_rs * (size_t)(units + (units >> 2));
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t tb = (sz >> (8 * k)) & 15u, z = z0 + (uint32_t)k, f = (fl >> (8 * k)) & 255u;
+      const int ux = ux0 + (k & 1), uy = uy0 + (k >> 1), n = 1 << ((tb - 2u) & 3u);    // (emitting units: 1 .. 8 units per side)
+      if ((emit_l >> k) & 1u) {
+        constexpr uint64_t k8 = smooth_mode_mask(8), k16 = smooth_mode_mask(16), k32 = smooth_mode_mask(32);
+        const uint32_t m = (md >> (8 * k)) & 63u;
+        const uint64_t filtered_modes = tb == 3u ? k8 : (tb == 4u ? k16 : k32);
+        recs[slot_l++] = plan_record(ux, uy, n, side, z, rem_x, rem_y, avail, (int)tb, z, m, f, tb > 2u && ((filtered_modes >> m) & 1ull));
+      }
+      if ((k == 0 || k == 3) && ((emit_c >> k) & 1u)) {
+        const int quad = tb == 2u;
+        recs[units + slot_c++] = plan_record(ux >> 1, uy >> 1, quad ? 1 : n >> 1, side >> 1, z >> 2, (rem_x + 1) >> 1, (rem_y + 1) >> 1, avail,
+                                             quad ? 2 : (int)tb - 1, quad ? (z & ~3u) : z, (mc >> (8 * k)) & 255u, f, 0);
+      }
+    }
+    if (lane == 0) { plan_cnt[2 * ctb_rs] = (uint16_t)n_l; plan_cnt[2 * ctb_rs + 1] = (uint16_t)n_c; }
+    cx = ncx; cy = ncy;
+  }
+}
+
+// 8-bit pictures: 7 waves per SIMD by registers (<= 72 VGPRs); by LDS 32 per CU (4800 B per wave with the plan, handed out in 512 B granules; 26 with the
+// 6072 B of the builds that keep the unit words and the bitmap).  What was measured
 // on the way here (1024 4K stills, profiles/r04_recon_variants.txt): the kernel is bound by instruction issue, not by latency hiding - a compact unit
 // map that allowed 28 waves per CU bought nothing, 6 / 5 waves per SIMD with fewer spills cost 1 % / 10 %; fewer scalar instructions per block did
 // pay (78.0 -> 72.8 ms: mode tables, DS atomics on the availability map, units classified at staging, the chroma pair skipping to a quad's 4th
@@ -964,14 +1182,35 @@ __global__ __launch_bounds__(64) void k_recon16(ReconArgs A) { recon_wave<uint16
 __global__ __launch_bounds__(64) void k_recon8_inter(ReconArgs A) { recon_wave<uint8_t, true>(A); }
 __global__ __launch_bounds__(64) void k_recon16_inter(ReconArgs A) { recon_wave<uint16_t, true>(A); }
 
-void launch_recon(const ReconArgs& a, bool wide, hipStream_t s, bool inter)
+static thread_local int g_plan_launches_last = 0;   // did this thread's last launch_recon run the plan kernel (recon_plan_launched(): tests)
+
+void launch_recon(const ReconArgs& a, bool wide, hipStream_t s, bool inter, int general_chroma)
 {
   if (!a.num_waves) return;
-  if (inter) {
+  if (general_chroma < 0) {
+#ifdef HIPDEC_HOST_EMU
+    // (the CPU-test emulation's "device memory" is host memory: a caller that does not say is answered from the parameter blocks)
+    general_chroma = 0;
+    for (uint32_t i = 0; i < a.num_waves; i++) if (a.pics[a.waves[i].pic].chroma_format_idc >= 2) general_chroma = 1;
+#else
+    general_chroma = 1;
+#endif
+  }
+  g_plan_launches_last = 0;
+  // P pictures, 4:2:2 and 4:4:4 pictures: the builds that stage the unit maps and keep the availability bitmap; everything else reads the plan
+  if (inter || general_chroma) {
     if (wide) hipLaunchKernelGGL(k_recon16_inter, dim3(a.num_waves), dim3(64), 0, s, a);
     else hipLaunchKernelGGL(k_recon8_inter, dim3(a.num_waves), dim3(64), 0, s, a);
-  } else if (wide) hipLaunchKernelGGL(k_recon16, dim3(a.num_waves), dim3(64), 0, s, a);
+    return;
+  }
+  g_plan_launches_last = 1;
+  hipLaunchKernelGGL(k_recon_plan, dim3(a.num_waves), dim3(64), 0, s, a);
+  if (wide) hipLaunchKernelGGL(k_recon16, dim3(a.num_waves), dim3(64), 0, s, a);
   else hipLaunchKernelGGL(k_recon8, dim3(a.num_waves), dim3(64), 0, s, a);
 }
+int recon_plan_launched() { return g_plan_launches_last; }
 
 }  // namespace hipdec
+
+// (tests: did the calling thread's last reconstruction launch run the plan kernel)
+extern "C" __attribute__((visibility("default"))) int hipdec_debug_recon_plan_launched(void) { return hipdec::recon_plan_launched(); }

@@ -2,7 +2,8 @@
 count per line from a gcov run of the host emulation (tests/emu built with --coverage).  Lines inside the emulated-lane
 loops of parse_core.h (PC_VEC_BEGIN..PC_VEC_END) run 64x per wave step on the host and are scaled back.  Dev tool.
 usage: dyn_profile.py <kernel.hip> <kernel-symbol-substring> <source-with-gcov> <file.gcov> [pixels]
-env: SALU=1 / VS=1 / SPILL=1 add the top lines of that class, BY_ELEMENT=1 the parser's table by syntax element, TOPN=<lines>"""
+env: SALU=1 / VS=1 / SPILL=1 add the top lines of that class, BY_ELEMENT=1 the parser's table by syntax element, TOPN=<lines>,
+SKIP_LINES=<a-b,c,...> source lines left out of every total (a spin wait whose count is the host's thread scheduling, not the kernel's work)"""
 import collections, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 kern, sym, srcname, gcovf = sys.argv[1:5]
@@ -57,7 +58,12 @@ for ln in sorted(text):
     if "PC_VEC_BEGIN" in t and "define" not in t: on = True
     if on: invec.add(ln)
     if "PC_VEC_END" in t and "define" not in t: on = False
+skip = set()
+for part in filter(None, os.environ.get("SKIP_LINES", "").split(",")):
+    lo, _, hi = part.partition("-")
+    skip.update(range(int(lo), int(hi or lo) + 1))
 def count(ln):
+    if ln in skip: return 0
     # nearest executed line at or before ln (declarations / continuation lines carry no count)
     for k in range(ln, max(ln - 6, 0), -1):
         if k in dyn:

@@ -32,6 +32,9 @@ PY
 python runcov.py
 case $what in
   parse) gcov -o . libparse_emu_cov.so-parse_emu.gcda > /dev/null 2>&1; python $ROOT/tools/dyn_profile.py $C/parse_kernel_tp.hip k_parse_occ8 parse_core.h $B/parse_core.h.gcov 2073600;;
-  recon) gcov -o . libparse_emu_cov.so-recon_kernel.gcda > /dev/null 2>&1; python $ROOT/tools/dyn_profile.py $C/recon_kernel.hip k_recon8 recon_kernel.hip $B/recon_kernel.hip.gcov 2073600;;
+  # (gcov counts a line once per emulated lane: divide the per-pixel figures of these two by 64 for wave-instructions.  SKIP_LINES=<the spin wait on the row
+  #  above> takes the host's thread scheduling out of the totals.)  The plan kernel in front of the wavefront is weighted the same way, apart.
+  recon) gcov -o . libparse_emu_cov.so-recon_kernel.gcda > /dev/null 2>&1; python $ROOT/tools/dyn_profile.py $C/recon_kernel.hip k_recon8 recon_kernel.hip $B/recon_kernel.hip.gcov 2073600
+         echo "==== k_recon_plan"; TOPN=8 python $ROOT/tools/dyn_profile.py $C/recon_kernel.hip k_recon_plan recon_kernel.hip $B/recon_kernel.hip.gcov 2073600;;
   residual) gcov -o . libparse_emu_cov.so-residual_kernel.gcda > /dev/null 2>&1; python $ROOT/tools/dyn_profile.py $C/residual_kernel.hip k_residual residual_kernel.hip $B/residual_kernel.hip.gcov 2073600;;
 esac
