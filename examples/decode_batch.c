@@ -15,6 +15,9 @@
  *                                                     last among the --thumb options
  *   ./decode_batch --thumb 256 --filter bicubic ...   the previews with another filter: box (the default) | nearest | bilinear | bicubic - the last two are
  *                                                     PIL.Image.resize bit for bit (HIPDEC_SCALE_BILINEAR / HIPDEC_SCALE_BICUBIC); after --orient where both are given
+ *   ./decode_batch --thumb 256 --warp 15 item0.hevc   the previews rotated by 15 degrees counter-clockwise about their centre, exactly as PIL.Image.rotate(15,
+ *                                                     BILINEAR) turns the resized 8-bit preview (hipdec_batch_to_tensor_warped with hipdec_rotate_map): per
+ *                                                     preview one resize launch and one warp launch, black outside; after --orient / --filter, not with --patches
  *   ./decode_batch --tensor 224 item0.hevc ...        ends in ONE launch that writes a float16 N x 3 x 224 x 224 tensor: the centred square of every item,
  *                                                     area-averaged, (V / 255 - mean) / std with the usual ImageNet constants
  *   ./decode_batch --album 16 6x8 tile0.hevc ...      the items are TILES: 16 grid photos of 6 x 8 tiles (tile t of photo k is item (k * 48 + t) mod n; the
@@ -111,8 +114,16 @@ int main(int argc, char** argv)
     if (k == 4) argc = 0;                                          /* no or an unknown name: usage */
     else { filter = filters[k].value; argv += 2; argc -= 2; }
   }
+  int warp = 0;
+  double warp_angle = 0.0;
+  if (thumb && argc >= 2 && !strcmp(argv[1], "--warp")) {
+    char* end = NULL;
+    warp_angle = argc >= 3 ? strtod(argv[2], &end) : 0.0;
+    if (argc < 3 || end == argv[2] || *end || warp_angle < -36000.0 || warp_angle > 36000.0) argc = 0;   /* no or a bad ANGLE: usage */
+    else { warp = 1; argv += 2; argc -= 2; }
+  }
   int patch = 0, merge = 1;
-  if (thumb && argc >= 2 && !strcmp(argv[1], "--patches")) {
+  if (thumb && !warp && argc >= 2 && !strcmp(argv[1], "--patches")) {
     char tail = 0;
     const int got = argc >= 3 ? sscanf(argv[2], "%d:%d%c", &patch, &merge, &tail) : 0;
     if ((got != 1 && got != 2) || patch < 1 || patch > 256 || merge < 1 || merge > 16) argc = 0;   /* no or a bad P[:M]: usage */
@@ -124,7 +135,7 @@ int main(int argc, char** argv)
     if (tensor < 1) argc = 0;
     else { argv += 2; argc -= 2; }
   }
-  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] [--patches P[:M]] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] [--warp ANGLE | --patches P[:M]] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
   const int n = argc - 1;
   const void** data = (const void**)calloc((size_t)n, sizeof(void*));
   size_t* sizes = (size_t*)calloc((size_t)n, sizeof(size_t));
@@ -217,8 +228,23 @@ int main(int argc, char** argv)
       hipdec_shutdown();
       return 0;
     }
-    const int rc = orient < 0 ? hipdec_batch_to_rgb_scaled_all(prev, 10, ws, hs, filter, (void* const*)outs, strides, NULL)
-                              : hipdec_batch_to_rgb_scaled_oriented_all(prev, 10, codes, ws, hs, filter, (void* const*)outs, strides, NULL);
+    int rc = 0;
+    if (warp) {                                                    /* every preview has its own size: one warped call per preview, U8 / NHWC = RGB24 rows */
+      for (int i = 0; i < n && !rc; i++) {
+        hipdec_tensor_desc d;
+        memset(&d, 0, sizeof d);
+        d.width = ws[i]; d.height = hs[i]; d.dtype = HIPDEC_TENSOR_U8; d.layout = HIPDEC_TENSOR_NHWC; d.filter = filter;
+        for (int c = 0; c < 3; c++) d.scale[c] = 1.0f;
+        const hipdec_tensor_entry e = {i, 0, 0, 0, 0, 0};
+        const hipdec_warp_desc wd = {ws[i], hs[i], HIPDEC_SCALE_BILINEAR, 0};
+        hipdec_tensor_map map;
+        rc = hipdec_rotate_map(warp_angle, ws[i], hs[i], &map);
+        if (!rc) rc = hipdec_batch_to_tensor_warped(prev, &d, &e, codes + i, &wd, &map, NULL, 1, outs[i], strides[i] * (size_t)hs[i], NULL);
+      }
+    } else {
+      rc = orient < 0 ? hipdec_batch_to_rgb_scaled_all(prev, 10, ws, hs, filter, (void* const*)outs, strides, NULL)
+                      : hipdec_batch_to_rgb_scaled_oriented_all(prev, 10, codes, ws, hs, filter, (void* const*)outs, strides, NULL);
+    }
     if (rc || hipdec_batch_status(prev)) {
       fprintf(stderr, "%s\n", hipdec_last_error());
       return 1;

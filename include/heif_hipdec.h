@@ -799,6 +799,71 @@ HIPDEC_API int hipdec_clips_to_tensor_packed(hipdec_clips* c, const hipdec_tenso
 HIPDEC_API int hipdec_clip_packed_layout(const hipdec_clip_desc* clip, const hipdec_tensor_patches* patches, const int* widths, const int* heights, int n,
                                          uint64_t* offsets, uint32_t* tokens, uint64_t* total_elements);
 
+/* ---- warped tensor output: Pillow-exact affine transforms of the resized 8-bit picture, normalised, in one call ------------------------------------------
+ * RandomRotation, RandomAffine, the geometric operations of RandAugment / AutoAugment / TrivialAugment (Rotate, ShearX/Y, TranslateX/Y) and the scale and
+ * translate jitter of detection loaders are, in the libraries people train with, PIL.Image.transform(size, AFFINE, data, resample, fillcolor) applied to the
+ * already resized 8-bit picture.  The warp stage does exactly that to 8-bit interleaved RGB samples in device memory - per sample one map and one fill - and
+ * writes the normalised tensor the other tensor calls write.
+ *
+ * THE STAGE (hipdec_tensor_warp).  S is a source sample of sh x sw x 3 bytes (sw = src_width, sh = src_height), a = maps[e].m[0 .. 5] (PIL's AFFINE data:
+ * the centre of an output pixel to source coordinates).  All arithmetic is IEEE double, one rounding per written operation, no fused multiply-add, evaluated
+ * left to right.  FLOOR(v) = (int)floor(v) for v < 0, else (int)v.  COORD(v) = -1 for v < 0, else (int)v.  An output pixel that is "outside" holds the fill.
+ *  HIPDEC_SCALE_BILINEAR / HIPDEC_SCALE_BICUBIC, output pixel (x, y) of the desc->width x desc->height sample:
+ *    xin = a0 * (x + 0.5) + a1 * (y + 0.5) + a2,  yin = a3 * (x + 0.5) + a4 * (y + 0.5) + a5;  outside if xin < 0 || xin >= sw || yin < 0 || yin >= sh;
+ *    else xin -= 0.5, yin -= 0.5, ix = FLOOR(xin), iy = FLOOR(yin), dx = xin - ix, dy = yin - iy.  Columns are clamped to [0, sw - 1].
+ *    Bilinear: L(p, q, d) = p + (q - p) * d;  v1 = L over columns ix, ix + 1 of row clamp(iy);  v2 the same over row iy + 1 if 0 <= iy + 1 < sh, else v1;
+ *              V = (uint8)L(v1, v2, dy), truncating.
+ *    Bicubic:  B(v1, v2, v3, v4, d): p1 = v2, p2 = -v1 + v3, p3 = 2 * (v1 - v2) + v3 - v4, p4 = -v1 + v2 - v3 + v4, result p1 + d * (p2 + d * (p3 + d * p4)).
+ *              A row's value is B over columns ix - 1 .. ix + 2 with dx.  Row iy - 1 is clamped; rows iy, iy + 1, iy + 2 are each used only if inside
+ *              [0, sh), else they repeat the previous row's value.  v = B of the four row values with dy;  V = 0 if v <= 0, 255 if v >= 255, else (uint8)v.
+ *  HIPDEC_SCALE_NEAREST with a1 == 0 && a3 == 0 (Pillow's scale path): the host builds xt[x] = COORD(xo), xo starting at a2 + a0 * 0.5 and xo += a0 after
+ *    each x - a running sum -, and yt[y] likewise from a5, a4.  V = S[yt[y]][xt[x]]; outside if a table value is not inside the source.
+ *  HIPDEC_SCALE_NEAREST otherwise (Pillow's fixed-point path): FIX(v) = FLOOR(v * 65536.0 + 0.5);  A0 = FIX(a0), A1 = FIX(a1), A3 = FIX(a3), A4 = FIX(a4),
+ *    A2 = FIX(a2 + a0 * 0.5 + a1 * 0.5), A5 = FIX(a5 + a3 * 0.5 + a4 * 0.5);  column (A2 + y * A1 + x * A0) >> 16, row (A5 + y * A4 + x * A3) >> 16
+ *    (arithmetic shifts); outside if either is not inside the source.
+ *  HIPDEC_SCALE_BOX has no warp and is refused.
+ * Float stage, dtypes and layouts: those of hipdec_batch_to_tensor with V the 8-bit component value; desc->filter is not read by hipdec_tensor_warp.
+ * fill: hipdec_tensor_fill as in the placed call - HIPDEC_FILL_COMPONENT (an integer 0 .. 255) is normalised as a pixel is, HIPDEC_FILL_ELEMENT is stored
+ * as it is; NULL: component 0.  There is no mask output.
+ * src_dev: n dense samples back to back (NHWC), src_bytes at least n * sh * sw * 3.  n == 0 is allowed: nothing is launched, nothing is counted.
+ *
+ * THE DECODE-SIDE FORMS (hipdec_batch_to_tensor_warped, hipdec_album_to_tensor_warped).  Sample e of the intermediate is, byte for byte, what
+ * hipdec_batch_to_tensor_oriented writes for entry e (item, window, flip) and orientations[e] with dtype U8, layout NHWC, size src_width x src_height and
+ * desc->filter - the RESIZE filter, all four allowed; then the stage above with warp->filter.  The identity map with src_width x src_height equal to
+ * desc->width x height gives hipdec_batch_to_tensor_oriented's bytes.  A float dtype from a source above 8 bits is HIPDEC_ERR_UNSUPPORTED, as for the
+ * Pillow resize filters; U8 goes through to-SDR.  The intermediate of n * sh * sw * 3 bytes comes from the library's device pool; the handle keeps it for
+ * its next warped call and returns it to the pool when it is freed.  The inner resize counts in hipdec_tensor_stats and hipdec_oriented_stats as the
+ * oriented call does.
+ *
+ * Launches: the existing resize launch (decode-side forms), then ALL entries through ONE launch of k_warp, whatever their number; the maps may all differ.
+ * Asynchronous on `stream`.  Refused with HIPDEC_ERR_INVALID_ARGUMENT before anything is launched, `out_dev` untouched, the entry named: a non-finite
+ * coefficient; |m[i]| >= 32000; a corner of [0, width] x [0, height] whose mapped coordinate has magnitude >= 32000 (stricter than Pillow's own 32768, so
+ * that Pillow always takes the paths above and the fixed-point sums cannot wrap); and for the call: src_width or src_height < 1 or >= 32768, an unknown
+ * warp filter or BOX, a non-zero `reserved`, a fill the placed call refuses or a component fill above 255, src_bytes or out_bytes too small.  More than
+ * 2^31 - 1 output tiles (64 x 16 pixels) in a call: HIPDEC_ERR_LIMIT.
+ * Not part of it: perspective and quad transforms; expand (pass a larger size); the point-wise RandAugment operations; a mask; a clips entry point (repeat
+ * the map for the T frames of a clip and use hipdec_tensor_warp); Lanczos; warping straight from the full-size picture in one resampling. */
+typedef struct hipdec_tensor_map { double m[6]; } hipdec_tensor_map;
+typedef struct hipdec_warp_desc {
+  int src_width, src_height;   /* size of the intermediate picture the maps read */
+  int filter;                  /* HIPDEC_SCALE_NEAREST, _BILINEAR or _BICUBIC */
+  int reserved;                /* 0 */
+} hipdec_warp_desc;
+HIPDEC_API int hipdec_tensor_warp(const void* src_dev, size_t src_bytes, const hipdec_warp_desc* warp, const hipdec_tensor_map* maps,
+                                  const hipdec_tensor_fill* fill, const hipdec_tensor_desc* desc, int n, void* out_dev, size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_batch_to_tensor_warped(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                             const hipdec_warp_desc* warp, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill, int n_entries,
+                                             void* out_dev, size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_album_to_tensor_warped(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                             const hipdec_warp_desc* warp, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill, int n_entries,
+                                             void* out_dev, size_t out_bytes, void* stream);
+/* Host only.  The map PIL.Image.rotate(angle) - counter-clockwise degrees about the centre, no expand - hands to its AFFINE transform for a picture of
+ * width x height: the angle mod 360, cos and sin of -radians(angle) rounded to 15 decimal places, centre (width / 2, height / 2), the translation as
+ * Pillow computes it.  A non-finite angle, a non-positive size or out NULL: -1, hipdec_last_error says why. */
+HIPDEC_API int hipdec_rotate_map(double angle, int width, int height, hipdec_tensor_map* out);
+/* counters since load: launches of k_warp - one per call that wrote anything - and the entries they wrote */
+HIPDEC_API void hipdec_warp_stats(uint64_t* calls, uint64_t* entries);
+
 /* counters since load: images through hipdec_image_transform, grid canvases handed out by hipdec_grid_read_plane_tracked (hipdec_image_scale counts in
  * hipdec_image_scale_stats) */
 HIPDEC_API void hipdec_image_ops_stats(uint64_t* transforms, uint64_t* grid_canvases);

@@ -17,12 +17,15 @@
 // Float parity: compiled with -ffp-contract=off; the reference build (x86-64 baseline) has no FMA.
 #include "hipdec_internal.h"
 #include "color_device.h"
+#include "warp_host.h"
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 #include <atomic>
 #include <map>
+#include <mutex>
 #include <utility>
 
 namespace {
@@ -1196,6 +1199,9 @@ __global__ __launch_bounds__(256) void k_canvas_margin(const hipdec::CanvasMargi
     else canvas_margin_blocks<uint8_t, true, uint64_t>(m, (HIPDEC_GLOBAL uint8_t*)m.mask, 0u, 0u, 0u);
   }
 }
+
+// ---- warped tensor output (include/heif_hipdec.h hipdec_tensor_warp): k_warp_nearest / _bilinear / _bicubic
+#include "warp_kernels.h"
 
 // the plane scalers: blockIdx.z selects the plane (all planes of an image, or of all items of a batch, are ONE launch)
 // ---- Pillow's bilinear / bicubic resampling of 8-bit pictures (HIPDEC_SCALE_BILINEAR / _BICUBIC, include/heif_hipdec.h), bit for bit: two separable passes
@@ -2451,6 +2457,157 @@ int canvas_margin_launch(ColorBatchState& st, const CanvasMargin* blocks, int n,
   return 0;
 }
 
+// ---- warped tensor output: what the arguments alone decide, the per-entry table, ONE launch of k_warp_* for all entries of a call
+std::atomic<uint64_t> g_warp_calls{0}, g_warp_entries{0};
+
+int warp_check(const char* who, const hipdec_warp_desc* w, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill, const hipdec_tensor_desc* d, int n)
+{
+  if (!w || (!maps && n > 0)) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  if (w->src_width < 1 || w->src_height < 1 || w->src_width >= 32768 || w->src_height >= 32768)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: source size %d x %d (1 .. 32767 each way)", who, w->src_width, w->src_height);
+  if (w->filter != HIPDEC_SCALE_NEAREST && w->filter != HIPDEC_SCALE_BILINEAR && w->filter != HIPDEC_SCALE_BICUBIC)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: warp filter %d (nearest 0, bilinear 16, bicubic 17)", who, w->filter);
+  if (w->reserved) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: warp.reserved is %d, not 0", who, w->reserved);
+  if (fill) {
+    if (fill->domain != HIPDEC_FILL_COMPONENT && fill->domain != HIPDEC_FILL_ELEMENT) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown fill domain %d", who, fill->domain);
+    if (fill->reserved) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: fill.reserved is %d, not 0", who, fill->reserved);
+    for (int c = 0; c < 3; c++) {
+      const float v = fill->value[c];
+      if (!std::isfinite(v)) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: fill of channel %d is not finite", who, c);
+      const bool byte = v == std::floor(v) && v >= 0.0f && v <= 255.0f;
+      if (fill->domain == HIPDEC_FILL_COMPONENT && !byte)
+        return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: component fill %g of channel %d is not an integer a pixel can have", who, (double)v, c);
+      if (fill->domain == HIPDEC_FILL_ELEMENT && d->dtype == HIPDEC_TENSOR_U8 && !byte)
+        return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: element fill %g of channel %d is not an integer in 0 .. 255", who, (double)v, c);
+    }
+  }
+  for (int e = 0; e < n; e++) {
+    int which = 0;
+    switch (warp_map_check(maps[e].m, d->width, d->height, &which)) {
+      case 0: break;
+      case 1: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: map coefficient %d is not finite", who, e, which);
+      case 2: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: map coefficient %d is %g (magnitude 32000 or more)", who, e, which, maps[e].m[which]);
+      default:
+        return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: corner (%d, %d) of the output maps to a coordinate of magnitude 32000 or more", who, e,
+                         (which & 1) ? d->width : 0, (which & 2) ? d->height : 0);
+    }
+  }
+  const uint64_t tiles = (uint64_t)((d->width + kWarpTC - 1) / kWarpTC) * (uint64_t)((d->height + kWarpTR - 1) / kWarpTR);
+  if (tiles * (uint64_t)(n > 0 ? n : 1) > 0x7fffffffull) return set_error(HIPDEC_ERR_LIMIT, "%s: %d entries of %d x %d are more than 2^31 - 1 tiles", who, n, d->width, d->height);
+  return 0;
+}
+
+// the state's device memory is about to be rewritten or handed back: not before the last launch that read it has passed
+static int warp_state_order(WarpState& st, hipStream_t s, bool release)
+{
+  if (!st.done) return 0;
+  if (release) HIPDEC_CHECK_HIP(hipEventSynchronize(st.done));
+  else if (st.last != s) HIPDEC_CHECK_HIP(hipStreamWaitEvent(s, st.done, 0));
+  return 0;
+}
+
+int warp_scratch(WarpState& st, size_t bytes, hipStream_t s, void** out)
+{
+  if (st.scratch_bytes < bytes) {
+    if (int rc = warp_state_order(st, s, true)) return rc;
+    if (st.scratch) arena_release(st.scratch, st.scratch_bytes);
+    st.scratch = nullptr; st.scratch_bytes = 0;
+    HIPDEC_CHECK_HIP(arena_acquire(&st.scratch, bytes, &st.scratch_bytes));
+  } else if (int rc = warp_state_order(st, s, false)) {
+    return rc;
+  }
+  *out = st.scratch;
+  return 0;
+}
+
+void warp_state_free(WarpState& st)
+{
+  if (st.done) { (void)hipEventSynchronize(st.done); (void)hipEventDestroy(st.done); st.done = nullptr; }
+  if (st.scratch) arena_release(st.scratch, st.scratch_bytes);
+  st.scratch = nullptr; st.scratch_bytes = 0;
+  color_batch_state_free(st.table);
+}
+
+int warp_launch(WarpState& st, const void* src_dev, const hipdec_warp_desc* w, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill,
+                const hipdec_tensor_desc* d, int n, void* out_dev, hipStream_t s)
+{
+  if (n <= 0) return 0;
+  const int sw = w->src_width, sh = w->src_height, ow = d->width, oh = d->height;
+  const size_t src_entry = (size_t)sw * (size_t)sh * 3, out_entry = (size_t)ow * (size_t)oh * 3 * (d->dtype == TD_U8 ? 1 : (d->dtype == TD_F32 ? 4 : 2));
+  // the table: n records, then the index tables (ow + oh values) of the entries on Pillow's scale path
+  size_t n_tables = 0;
+  if (w->filter == HIPDEC_SCALE_NEAREST) for (int e = 0; e < n; e++) n_tables += warp_scale_only(maps[e].m) ? 1 : 0;
+  const size_t table_ints = (size_t)ow + (size_t)oh, bytes = (size_t)n * sizeof(WarpEntry) + n_tables * table_ints * sizeof(int32_t);
+  std::vector<uint8_t> host(bytes);
+  if (st.table.dev_bytes < bytes) {
+    if (int rc = warp_state_order(st, s, true)) return rc;
+    if (st.table.dev) arena_release(st.table.dev, st.table.dev_bytes);
+    st.table.dev = nullptr; st.table.dev_bytes = 0; st.table.host.clear();
+    HIPDEC_CHECK_HIP(arena_acquire(&st.table.dev, bytes, &st.table.dev_bytes));
+  } else if (int rc = warp_state_order(st, s, false)) {
+    return rc;
+  }
+  const uint8_t* dev_tables = (const uint8_t*)st.table.dev + (size_t)n * sizeof(WarpEntry);
+  int32_t* host_tables = (int32_t*)(host.data() + (size_t)n * sizeof(WarpEntry));
+  size_t t = 0;
+  for (int e = 0; e < n; e++) {
+    WarpEntry E;
+    memset(&E, 0, sizeof(E));
+    E.src = (const uint8_t*)src_dev + (size_t)e * src_entry;
+    E.o0 = (uint8_t*)out_dev + (size_t)e * out_entry;
+    const double* a = maps[e].m;
+    for (int i = 0; i < 6; i++) E.m[i] = a[i];
+    if (w->filter != HIPDEC_SCALE_NEAREST) {
+      E.path = WARP_PATH_DOUBLE;
+    } else if (warp_scale_only(a)) {
+      E.path = WARP_PATH_TABLE;
+      warp_scale_table(a[2], a[0], ow, host_tables + t * table_ints);
+      warp_scale_table(a[5], a[4], oh, host_tables + t * table_ints + (size_t)ow);
+      E.xt = (const int32_t*)dev_tables + t * table_ints;
+      E.yt = E.xt + ow;
+      t++;
+    } else {
+      E.path = WARP_PATH_FIXED;
+      warp_fixed_values(a, E.A);
+    }
+    E.domain = fill ? fill->domain : HIPDEC_FILL_COMPONENT;
+    for (int c = 0; c < 3; c++) E.value[c] = fill ? fill->value[c] : 0.0f;
+    memcpy(host.data() + (size_t)e * sizeof(WarpEntry), &E, sizeof(E));
+  }
+  if (st.table.host != host) {   // steady state (the same maps, fill, source and output): nothing to upload
+    st.table.prev.swap(st.table.host);
+    st.table.host.swap(host);
+    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.table.dev, st.table.host.data(), bytes, hipMemcpyHostToDevice, s));
+  }
+  WarpCall c;
+  memset(&c, 0, sizeof(c));
+  c.sw = sw; c.sh = sh; c.ow = ow; c.oh = oh; c.nhwc = d->layout == HIPDEC_TENSOR_NHWC;
+  c.tiles_x = (uint32_t)((ow + kWarpTC - 1) / kWarpTC);
+  c.tiles = c.tiles_x * (uint32_t)((oh + kWarpTR - 1) / kWarpTR);
+  for (int k = 0; k < 3; k++) { c.scale[k] = d->scale[k]; c.bias[k] = d->bias[k]; }
+  const WarpEntry* dev = (const WarpEntry*)st.table.dev;
+  dim3 block(256), grid((unsigned)((uint64_t)c.tiles * (uint64_t)n));   // (warp_check: below 2^31)
+#define HIPDEC_WARP_LAUNCH(K)                                                                      \
+  switch (d->dtype) {                                                                              \
+    case TD_U8: hipLaunchKernelGGL((K<TD_U8>), grid, block, 0, s, dev, c); break;                  \
+    case TD_F32: hipLaunchKernelGGL((K<TD_F32>), grid, block, 0, s, dev, c); break;                \
+    case TD_F16: hipLaunchKernelGGL((K<TD_F16>), grid, block, 0, s, dev, c); break;                \
+    case TD_BF16: hipLaunchKernelGGL((K<TD_BF16>), grid, block, 0, s, dev, c); break;              \
+    default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_warp: unknown dtype %d", d->dtype); \
+  }
+  if (w->filter == HIPDEC_SCALE_NEAREST) { HIPDEC_WARP_LAUNCH(k_warp_nearest) }
+  else if (w->filter == HIPDEC_SCALE_BILINEAR) { HIPDEC_WARP_LAUNCH(k_warp_bilinear) }
+  else { HIPDEC_WARP_LAUNCH(k_warp_bicubic) }
+#undef HIPDEC_WARP_LAUNCH
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "warp kernel launch: %s", hipGetErrorString(e));
+  if (!st.done) HIPDEC_CHECK_HIP(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+  HIPDEC_CHECK_HIP(hipEventRecord(st.done, s));
+  st.last = s;
+  g_warp_calls++; g_warp_entries += (uint64_t)n;
+  return 0;
+}
+
 // debug inspection of the blocks last handed to the tensor kernels: plane `plane` of entry `entry` as the kernel receives it - the pointer and stride of the
 // PLANE, and the window of it that is scaled
 int color_tensor_inspect(const ColorBatchState& st, int entry, int plane, const void** plane_dev, size_t* stride, int* x, int* y, int* w, int* h)
@@ -2540,6 +2697,64 @@ void hipdec_placed_stats(uint64_t* calls, uint64_t* entries, uint64_t* margin_la
   if (calls) *calls = g_placed_calls.load();
   if (entries) *entries = g_placed_entries.load();
   if (margin_launches) *margin_launches = g_placed_margin_launches.load();
+}
+
+void hipdec_warp_stats(uint64_t* calls, uint64_t* entries)
+{
+  if (calls) *calls = g_warp_calls.load();
+  if (entries) *entries = g_warp_entries.load();
+}
+
+// Pillow's Image.rotate matrix without expand (Image.py rotate): cos and sin of -radians(angle mod 360) rounded to 15 decimal places - printed with 15
+// places and read back, which is what Python's round(x, 15) does -, the centre (width / 2, height / 2), the translation as Pillow computes it
+int hipdec_rotate_map(double angle, int width, int height, hipdec_tensor_map* out)
+{
+  if (!out || !std::isfinite(angle) || width < 1 || height < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "rotate_map: angle %g, size %d x %d", angle, width, height), -1;
+  angle = std::fmod(angle, 360.0);
+  if (angle < 0.0) angle += 360.0;                                   // (Python's %: the result has the divisor's sign)
+  if (angle == 0.0) angle = 0.0;                                     // (... and a zero result is +0)
+  const double rad = -(angle * (3.14159265358979323846 / 180.0));   // math.radians
+  auto round15 = [](double v) { char buf[64]; snprintf(buf, sizeof buf, "%.15f", v); return strtod(buf, nullptr); };
+  const double c = round15(std::cos(rad)), s = round15(std::sin(rad)), ms = round15(-std::sin(rad));
+  const double cx = (double)width / 2.0, cy = (double)height / 2.0;
+  double* m = out->m;
+  m[0] = c; m[1] = s; m[2] = 0.0; m[3] = ms; m[4] = c; m[5] = 0.0;
+  const double tx = m[0] * -cx + m[1] * -cy + m[2], ty = m[3] * -cx + m[4] * -cy + m[5];
+  m[2] = tx + cx; m[5] = ty + cy;
+  return 0;
+}
+
+// the stage alone; its table lives in a state the process keeps per device (calls on different streams are ordered against each other by the state's event)
+int hipdec_tensor_warp(const void* src_dev, size_t src_bytes, const hipdec_warp_desc* warp, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill,
+                       const hipdec_tensor_desc* desc, int n, void* out_dev, size_t out_bytes, void* stream)
+{
+  static std::mutex mu;
+  static std::map<int, WarpState> states;   // by device: the table is device memory
+  if (!desc || n < 0) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_warp: bad arguments");
+  if (desc->width < 1 || desc->height < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_warp: output size %d x %d", desc->width, desc->height);
+  if (desc->dtype < HIPDEC_TENSOR_U8 || desc->dtype > HIPDEC_TENSOR_BF16) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_warp: unknown dtype %d", desc->dtype);
+  if (desc->layout != HIPDEC_TENSOR_NCHW && desc->layout != HIPDEC_TENSOR_NHWC) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_warp: unknown layout %d", desc->layout);
+  if (desc->dtype != HIPDEC_TENSOR_U8)
+    for (int c = 0; c < 3; c++)
+      if (!std::isfinite(desc->scale[c]) || !std::isfinite(desc->bias[c])) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_warp: scale / bias of channel %d is not finite", c);
+  if (int rc = warp_check("tensor_warp", warp, maps, fill, desc, n)) return rc;
+  const uint64_t es = desc->dtype == HIPDEC_TENSOR_U8 ? 1 : (desc->dtype == HIPDEC_TENSOR_F32 ? 4 : 2);
+  const uint64_t need_src = 3ull * (uint64_t)warp->src_width * (uint64_t)warp->src_height * (uint64_t)n;   // (below 2^63: sizes below 2^15, n below 2^31)
+  const uint64_t per_out = 3ull * (uint64_t)desc->width * (uint64_t)desc->height * es;
+  if ((uint64_t)desc->width * (uint64_t)desc->height > (1ull << 40) || (n > 0 && per_out > (~0ull) / (uint64_t)n))
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_warp: tensor too large");
+  if (src_bytes < need_src) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_warp: src_bytes %zu is smaller than the %d samples of %llu bytes", src_bytes, n, (unsigned long long)need_src);
+  if (out_bytes < per_out * (uint64_t)n) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_warp: out_bytes %zu is smaller than the tensor of %llu bytes", out_bytes, (unsigned long long)(per_out * (uint64_t)n));
+  if (n == 0) return 0;
+  if (!src_dev || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_warp: bad arguments");
+  // (everything above is decided without a device)
+  if (int rc = ensure_init()) return rc;
+  return guarded("tensor_warp", [&]() -> int {
+    std::lock_guard<std::mutex> lock(mu);
+    int dev = 0;
+    HIPDEC_CHECK_HIP(hipGetDevice(&dev));
+    return warp_launch(states[dev], src_dev, warp, maps, fill, desc, n, out_dev, stream ? (hipStream_t)stream : default_stream());
+  });
 }
 
 void hipdec_color_coefficients(const hipdec_nclx* nclx, float out[4]) { if (out) coefficients(nclx, out); }   // (nclx NULL: the reference's defaults)

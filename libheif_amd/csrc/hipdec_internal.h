@@ -130,6 +130,22 @@ void placed_note_call(uint64_t entries);   // hipdec_placed_stats
 void packed_note_call(uint64_t entries, bool patches);   // hipdec_packed_stats
 uint64_t clip_box_entries();   // entries that have gone through k_clip_box (hipdec_clips_stats)
 
+// Warped tensor output (color.hip k_warp, include/heif_hipdec.h hipdec_tensor_warp): n dense U8 / NHWC samples through one affine map each, ONE launch.
+// What the arguments alone decide (warp_check) is host-only; warp_launch builds the per-entry table - the six doubles, or Pillow's fixed-point values,
+// or the running-sum index tables of its scale path - uploads it with one copy and launches.
+struct WarpState {             // the device memory a handle (or, for hipdec_tensor_warp, the process) keeps for its warped calls
+  ColorBatchState table;       // the per-entry table last uploaded
+  void* scratch = nullptr;     // the U8 / NHWC intermediate of the decode-side forms
+  size_t scratch_bytes = 0;
+  hipEvent_t done = nullptr;   // behind the last launch that read either
+  hipStream_t last = nullptr;
+};
+int warp_check(const char* who, const hipdec_warp_desc* w, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill, const hipdec_tensor_desc* d, int n);
+int warp_scratch(WarpState& st, size_t bytes, hipStream_t s, void** out);   // the handle's intermediate, at least `bytes` long
+int warp_launch(WarpState& st, const void* src_dev, const hipdec_warp_desc* w, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill,
+                const hipdec_tensor_desc* d, int n, void* out_dev, hipStream_t s);
+void warp_state_free(WarpState& st);
+
 // The paste of an album of grid photos (transform.hip k_album_paste): one job per (tile, plane), already clipped to the photo's output size by the host
 // (a job clipped to nothing is not emitted); the job table lives in device memory and all jobs go out as ONE launch.
 struct PasteJob {

@@ -93,6 +93,14 @@ def _bind(lib):
                                                 C.POINTER(C.c_uint64)]
     lib.hipdec_packed_stats.restype = None
     lib.hipdec_packed_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
+    if hasattr(lib, "hipdec_tensor_warp"):     # (as for the clips below: an older branch's library has no warp stage, and the warped calls say so)
+        lib.hipdec_tensor_warp.argtypes = [vp, sz, C.POINTER(WarpDesc), C.POINTER(TensorMap), C.POINTER(TensorFill), C.POINTER(TensorDesc), ci, vp, sz, vp]
+        warped = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), C.POINTER(ci), C.POINTER(WarpDesc), C.POINTER(TensorMap), C.POINTER(TensorFill), ci, vp, sz, vp]
+        lib.hipdec_batch_to_tensor_warped.argtypes = warped
+        lib.hipdec_album_to_tensor_warped.argtypes = warped
+        lib.hipdec_rotate_map.argtypes = [C.c_double, ci, ci, C.POINTER(TensorMap)]
+        lib.hipdec_warp_stats.restype = None
+        lib.hipdec_warp_stats.argtypes = [C.POINTER(C.c_uint64)] * 2
     if hasattr(lib, "hipdec_clips_create"):   # (tools/ab_bench.sh loads an older branch's library through this module: it has no clips, and Clips() says so)
         lib.hipdec_clips_create.argtypes = [C.POINTER(vp), ci, C.POINTER(ci), C.POINTER(C.c_char_p), C.POINTER(sz), C.c_uint64]
         lib.hipdec_clips_free.argtypes = [vp]
@@ -151,6 +159,16 @@ class TensorSample(C.Structure):
 class TensorPatches(C.Structure):
     """hipdec_tensor_patches"""
     _fields_ = [("patch", C.c_int), ("merge", C.c_int), ("reserved", C.c_int * 2)]
+
+
+class TensorMap(C.Structure):
+    """hipdec_tensor_map: PIL's AFFINE data, the centre of an output pixel to source coordinates"""
+    _fields_ = [("m", C.c_double * 6)]
+
+
+class WarpDesc(C.Structure):
+    """hipdec_warp_desc"""
+    _fields_ = [("src_width", C.c_int), ("src_height", C.c_int), ("filter", C.c_int), ("reserved", C.c_int)]
 
 
 class ClipFrame(C.Structure):
@@ -532,6 +550,101 @@ def _tensor_packed_to_host(self):
     return flat, view
 
 
+def tensor_maps(maps, n=None):
+    """a ctypes array of hipdec_tensor_map from sequences of six numbers (PIL's AFFINE data) or TensorMap objects"""
+    maps = list(maps)
+    if n is not None and len(maps) != n:
+        raise ValueError("%d maps for %d entries" % (len(maps), n))
+    arr = (TensorMap * max(len(maps), 1))()
+    for k, m in enumerate(maps):
+        if isinstance(m, TensorMap):
+            arr[k] = m
+        else:
+            m = [float(v) for v in m]
+            if len(m) != 6:
+                raise ValueError("a map has six coefficients, not %d" % len(m))
+            arr[k] = TensorMap((C.c_double * 6)(*m))
+    return arr
+
+
+def warp_desc(src_size, warp_filter=SCALE_BILINEAR):
+    """hipdec_warp_desc for src_size = (width, height) of the intermediate picture"""
+    return WarpDesc(int(src_size[0]), int(src_size[1]), int(warp_filter), 0)
+
+
+def warp_stats():
+    """(launches of the warp kernel - one per warped call that wrote anything -, the entries they wrote) since load"""
+    lib = _bind(load_library())
+    a, b = C.c_uint64(), C.c_uint64()
+    lib.hipdec_warp_stats(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def rotate_matrix(angle, size):
+    """The six coefficients PIL.Image.rotate(angle) - counter-clockwise degrees about the centre, without expand or translate - hands to its AFFINE
+    transform for a picture of size = (width, height), computed as Pillow computes them: the angle taken mod 360, cos and sin of -radians(angle) rounded with
+    round(., 15), the centre (width / 2, height / 2), and the translation as the matrix applied to minus the centre, plus the centre.  (Image.rotate
+    short-cuts multiples of 90 degrees on square pictures to transposes; the map given here produces the same pixels.)"""
+    import math
+    w, h = size
+    angle = angle % 360.0
+    cx, cy = w / 2.0, h / 2.0
+    a = -math.radians(angle)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+
+    def transform(x, y):
+        return m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+
+    m[2], m[5] = transform(-cx, -cy)
+    m[2] += cx
+    m[5] += cy
+    return tuple(m)
+
+
+def affine_matrix(center, angle=0.0, translate=(0.0, 0.0), scale=1.0, shear=(0.0, 0.0)):
+    """The six coefficients of the INVERSE, in float64, of  T(center + translate) . R(angle) . scale . Shear(shear) . T(-center)  - the map from output to
+    source coordinates that a forward transform "rotate by `angle` degrees (counter-clockwise on the screen), scale, shear by (sx, sy) degrees about `center`,
+    then move by `translate`" needs, for RandomAffine-style parameters.  R(angle) = [[cos, sin], [-sin, cos]] of radians(angle) in image coordinates (y down);
+    Shear = [[1, -tan(sx)], [0, 1]] applied after [[1, 0], [-tan(sy), 1]].  The 2 x 2 part is inverted in closed form.
+    NOT pinned to torchvision's _get_inverse_affine_matrix: torchvision is not installed where this library is tested, so the conventions above are this
+    function's own; with shear (0, 0) the result for `angle` is rotate_matrix(angle) up to the rounding Pillow applies to cos and sin."""
+    import math
+    cx, cy = float(center[0]), float(center[1])
+    tx, ty = float(translate[0]), float(translate[1])
+    sx, sy = math.radians(float(shear[0])), math.radians(float(shear[1]))
+    r = math.radians(float(angle))
+    c, s_ = math.cos(r), math.sin(r)
+    # Shear = [[1, -tan sx], [0, 1]] . [[1, 0], [-tan sy, 1]]
+    h00, h01, h10, h11 = 1.0 + math.tan(sx) * math.tan(sy), -math.tan(sx), -math.tan(sy), 1.0
+    k = float(scale)
+    f00, f01 = k * (c * h00 + s_ * h10), k * (c * h01 + s_ * h11)
+    f10, f11 = k * (-s_ * h00 + c * h10), k * (-s_ * h01 + c * h11)
+    det = f00 * f11 - f01 * f10
+    if det == 0.0 or not math.isfinite(det):
+        raise ValueError("affine_matrix: the transform is singular")
+    i00, i01, i10, i11 = f11 / det, -f01 / det, -f10 / det, f00 / det
+    # forward: p' = F (p - center) + center + translate;  inverse: p = I (p' - center - translate) + center
+    ox, oy = cx + tx, cy + ty
+    return (i00, i01, cx - (i00 * ox + i01 * oy), i10, i11, cy - (i10 * ox + i11 * oy))
+
+
+def _warped_call(lib_call, n, size, src_size, maps, warp_filter, fill, fill_domain, orientations):
+    """the argument adapter of the warped entry points for _to_tensor"""
+    wd = warp_desc(size if src_size is None else src_size, warp_filter)
+    marr = tensor_maps(maps, n)
+    f = None if fill is None else tensor_fill(fill, fill_domain)
+    codes = None if orientations is None else _orientation_array(orientations, n)
+    keep = (wd, marr, f, codes)
+    return lambda h, desc, arr, n_, ptr, room, stream: lib_call(h, desc, arr, codes, C.byref(wd), marr, f, n_, ptr, room, stream), keep
+
+
+def _to_tensor_warped(self, lib_call, size, maps, entries, src_size, warp_filter, fill, fill_domain, orientations, filter, dtype, layout, mean, std, scale,
+                      bias, out, stream):
+    n = self.n if entries is None else len(entries)
+    call, _keep = _warped_call(lib_call, n, size, src_size, maps, warp_filter, fill, fill_domain, orientations)
+    return _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
+
+
 def fit_within(width, height, size):
     """The thumbnail size examples/heif_thumbnailer.cc:172-186 computes: the image as it is when both sides fit into `size`, else the longer
     side becomes `size` and the other one follows with integer division (which may give 0: the thumbnailer refuses that, and so does
@@ -856,6 +969,17 @@ class Batch:
             return _to_tensor(self, self._lib.hipdec_batch_to_tensor_oriented, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations)
         return _to_tensor(self, self._lib.hipdec_batch_to_tensor, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
 
+    def to_tensor_warped(self, size, maps, entries=None, src_size=None, warp_filter=SCALE_BILINEAR, fill=0, fill_domain="component", orientations=None,
+                         filter=SCALE_BILINEAR, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, out=None, stream=None):
+        """asynchronous: to_tensor with one affine warp per entry, Pillow-exact (hipdec_batch_to_tensor_warped).  Entry e is first resized as
+        to_tensor(src_size, entries, dtype="uint8", layout="NHWC", filter=filter, orientations=orientations) resizes it - src_size defaults to `size` -
+        and that 8-bit picture then goes through PIL.Image.transform(size, AFFINE, maps[e], warp_filter, fillcolor=fill) bit for bit, normalised as
+        to_tensor normalises.  maps: six numbers per entry (rotate_matrix(), affine_matrix(), or any AFFINE data); warp_filter: SCALE_NEAREST,
+        SCALE_BILINEAR or SCALE_BICUBIC; fill / fill_domain as in to_tensor(places=).  Sources above 8 bits: dtype "uint8" only.  `out`, `stream` and
+        tensor_to_host() as in to_tensor.  One resize launch and one warp launch per call."""
+        return _to_tensor_warped(self, self._lib.hipdec_batch_to_tensor_warped, size, maps, entries, src_size, warp_filter, fill, fill_domain, orientations,
+                                 filter, dtype, layout, mean, std, scale, bias, out, stream)
+
     def to_tensor_packed(self, sizes, entries=None, patch=0, merge=1, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None,
                          filter=SCALE_BOX, orientations=None, offsets=None, out=None, stream=None):
         """asynchronous: every entry at its OWN displayed size sizes[e] = (width, height), all entries in one launch into one 1-D output
@@ -1078,6 +1202,12 @@ class Album:
     tensor_to_host = Batch.tensor_to_host
     tensor_mask_to_host = Batch.tensor_mask_to_host
 
+    def to_tensor_warped(self, size, maps, entries=None, src_size=None, warp_filter=SCALE_BILINEAR, fill=0, fill_domain="component", orientations=None,
+                         filter=SCALE_BILINEAR, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, out=None, stream=None):
+        """Batch.to_tensor_warped over the composed photos"""
+        return _to_tensor_warped(self, self._lib.hipdec_album_to_tensor_warped, size, maps, entries, src_size, warp_filter, fill, fill_domain, orientations,
+                                 filter, dtype, layout, mean, std, scale, bias, out, stream)
+
     def to_tensor_packed(self, sizes, entries=None, patch=0, merge=1, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None,
                          filter=SCALE_BOX, orientations=None, offsets=None, out=None, stream=None):
         """Batch.to_tensor_packed over the composed photos"""
@@ -1105,6 +1235,52 @@ class Album:
 
 
 # ---- clips (video loaders): include/heif_hipdec.h hipdec_clips_* ------------------------------------------------------------------------------------------
+class _WarpStage:
+    """what _to_tensor needs of a handle, for decoder.tensor_warp: n samples of 8 bits, no handle"""
+
+    def __init__(self, lib, n):
+        self._lib, self._h, self.n = lib, None, n
+
+    def info(self, i):
+        return {"bit_depth_luma": 8}
+
+    tensor_to_host = Batch.tensor_to_host
+
+
+def tensor_warp(src, size, maps, src_size=None, warp_filter=SCALE_BILINEAR, fill=0, fill_domain="component", dtype="float16", layout="NCHW", mean=None,
+                std=None, scale=None, bias=None, out=None, stream=None, to_host=False):
+    """asynchronous: the warp stage alone (hipdec_tensor_warp) over n = len(maps) dense 8-bit RGB samples in device memory: a uint8 torch.Tensor of shape
+    (n, src_height, src_width, 3), or a DeviceBuffer of n * src_height * src_width * 3 bytes with src_size = (src_width, src_height).  Sample e goes through
+    PIL.Image.transform(size, AFFINE, maps[e], warp_filter, fillcolor=fill) bit for bit and is normalised as to_tensor normalises; everything else as in
+    Batch.to_tensor_warped.  A clip's T frames share one map by repeating it T times.  Returns `out` (to_host=True: the NumPy array, after waiting)."""
+    lib = _bind(load_library())
+    maps = list(maps)
+    n = len(maps)
+    if isinstance(src, DeviceBuffer):
+        if src_size is None:
+            raise ValueError("a DeviceBuffer source needs src_size = (width, height)")
+        sptr, sbytes = src.ptr, src.nbytes
+    else:
+        import torch
+        if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype != torch.uint8:
+            raise TypeError("src must be a DeviceBuffer or a CUDA / HIP torch.Tensor of uint8")
+        if src.dim() != 4 or src.shape[0] != n or src.shape[3] != 3 or not src.is_contiguous():
+            raise ValueError("src must be contiguous with shape (%d, src_height, src_width, 3)" % n)
+        if src_size is not None and (int(src_size[0]), int(src_size[1])) != (int(src.shape[2]), int(src.shape[1])):
+            raise ValueError("src_size %r does not match src of shape %s" % (tuple(src_size), tuple(src.shape)))
+        src_size = (int(src.shape[2]), int(src.shape[1]))
+        sptr, sbytes = src.data_ptr(), src.numel()
+        if out is None and stream is None and n > 0:
+            out = torch.empty(tensor_shape(n, size, layout), dtype=getattr(torch, dtype), device=src.device)   # (written on torch's current stream, as src was)
+    wd = warp_desc(src_size, warp_filter)
+    marr = tensor_maps(maps, n)
+    f = None if fill is None else tensor_fill(fill, fill_domain)
+    stage = _WarpStage(lib, n)
+    call = lambda h, desc, arr, n_, ptr, room, stream_: lib.hipdec_tensor_warp(sptr, sbytes, C.byref(wd), marr, f, desc, n_, ptr, room, stream_)
+    out = _to_tensor(stage, call, size, None, dtype, layout, mean, std, scale, bias, 0, out, stream)
+    return stage.tensor_to_host() if to_host else out
+
+
 def clips_stats():
     """(launch sets built, their tracks, their frames, clip tensor calls, frames through the strided box kernel) since load"""
     lib = _bind(load_library())
