@@ -18,6 +18,10 @@
  *   ./decode_batch --thumb 256 --warp 15 item0.hevc   the previews rotated by 15 degrees counter-clockwise about their centre, exactly as PIL.Image.rotate(15,
  *                                                     BILINEAR) turns the resized 8-bit preview (hipdec_batch_to_tensor_warped with hipdec_rotate_map): per
  *                                                     preview one resize launch and one warp launch, black outside; after --orient / --filter, not with --patches
+ *   ./decode_batch --thumb 256 --photo contrast 1.3 item0.hevc   the previews through one photometric operation, exactly as PIL.ImageEnhance / ImageOps
+ *                                                     change the resized 8-bit preview (hipdec_batch_to_tensor_photo): OP is brightness | color | contrast |
+ *                                                     sharpness | posterize | solarize | invert | autocontrast | equalize, VALUE its factor, bits or
+ *                                                     threshold (0 for the last three); after --orient / --filter, not with --warp or --patches
  *   ./decode_batch --tensor 224 item0.hevc ...        ends in ONE launch that writes a float16 N x 3 x 224 x 224 tensor: the centred square of every item,
  *                                                     area-averaged, (V / 255 - mean) / std with the usual ImageNet constants
  *   ./decode_batch --album 16 6x8 tile0.hevc ...      the items are TILES: 16 grid photos of 6 x 8 tiles (tile t of photo k is item (k * 48 + t) mod n; the
@@ -122,8 +126,18 @@ int main(int argc, char** argv)
     if (argc < 3 || end == argv[2] || *end || warp_angle < -36000.0 || warp_angle > 36000.0) argc = 0;   /* no or a bad ANGLE: usage */
     else { warp = 1; argv += 2; argc -= 2; }
   }
+  int photo = 0;
+  double photo_value = 0.0;
+  if (thumb && !warp && argc >= 2 && !strcmp(argv[1], "--photo")) {
+    static const char* const ops[] = {"brightness", "color", "contrast", "sharpness", "posterize", "solarize", "invert", "autocontrast", "equalize"};
+    char* end = NULL;
+    for (int k = 0; argc >= 3 && k < 9; k++) if (!strcmp(argv[2], ops[k])) photo = HIPDEC_PHOTO_BRIGHTNESS + k;
+    photo_value = argc >= 4 ? strtod(argv[3], &end) : 0.0;
+    if (!photo || argc < 4 || end == argv[3] || *end) argc = 0;    /* no or an unknown OP, no or a bad VALUE: usage (the library checks the value's range) */
+    else { argv += 3; argc -= 3; }
+  }
   int patch = 0, merge = 1;
-  if (thumb && !warp && argc >= 2 && !strcmp(argv[1], "--patches")) {
+  if (thumb && !warp && !photo && argc >= 2 && !strcmp(argv[1], "--patches")) {
     char tail = 0;
     const int got = argc >= 3 ? sscanf(argv[2], "%d:%d%c", &patch, &merge, &tail) : 0;
     if ((got != 1 && got != 2) || patch < 1 || patch > 256 || merge < 1 || merge > 16) argc = 0;   /* no or a bad P[:M]: usage */
@@ -135,7 +149,7 @@ int main(int argc, char** argv)
     if (tensor < 1) argc = 0;
     else { argv += 2; argc -= 2; }
   }
-  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] [--warp ANGLE | --patches P[:M]] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] [--warp ANGLE | --photo OP VALUE | --patches P[:M]] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
   const int n = argc - 1;
   const void** data = (const void**)calloc((size_t)n, sizeof(void*));
   size_t* sizes = (size_t*)calloc((size_t)n, sizeof(size_t));
@@ -240,6 +254,19 @@ int main(int argc, char** argv)
         hipdec_tensor_map map;
         rc = hipdec_rotate_map(warp_angle, ws[i], hs[i], &map);
         if (!rc) rc = hipdec_batch_to_tensor_warped(prev, &d, &e, codes + i, &wd, &map, NULL, 1, outs[i], strides[i] * (size_t)hs[i], NULL);
+      }
+    } else if (photo) {                                            /* likewise one photo call per preview: a resize launch, then the stage's launches */
+      for (int i = 0; i < n && !rc; i++) {
+        hipdec_tensor_desc d;
+        memset(&d, 0, sizeof d);
+        d.width = ws[i]; d.height = hs[i]; d.dtype = HIPDEC_TENSOR_U8; d.layout = HIPDEC_TENSOR_NHWC; d.filter = filter;
+        for (int c = 0; c < 3; c++) d.scale[c] = 1.0f;
+        const hipdec_tensor_entry e = {i, 0, 0, 0, 0, 0};
+        const hipdec_photo_desc pd = {ws[i], hs[i], {0, 0}};
+        hipdec_photo_chain chain;
+        memset(&chain, 0, sizeof chain);
+        chain.n_ops = 1; chain.ops[0].op = photo; chain.ops[0].value = photo_value;
+        rc = hipdec_batch_to_tensor_photo(prev, &d, &e, codes + i, &pd, &chain, 1, outs[i], strides[i] * (size_t)hs[i], NULL);
       }
     } else {
       rc = orient < 0 ? hipdec_batch_to_rgb_scaled_all(prev, 10, ws, hs, filter, (void* const*)outs, strides, NULL)

@@ -841,7 +841,8 @@ HIPDEC_API int hipdec_clip_packed_layout(const hipdec_clip_desc* clip, const hip
  * that Pillow always takes the paths above and the fixed-point sums cannot wrap); and for the call: src_width or src_height < 1 or >= 32768, an unknown
  * warp filter or BOX, a non-zero `reserved`, a fill the placed call refuses or a component fill above 255, src_bytes or out_bytes too small.  More than
  * 2^31 - 1 output tiles (64 x 16 pixels) in a call: HIPDEC_ERR_LIMIT.
- * Not part of it: perspective and quad transforms; expand (pass a larger size); the point-wise RandAugment operations; a mask; a clips entry point (repeat
+ * Not part of it: perspective and quad transforms; expand (pass a larger size); a mask (the point-wise RandAugment operations are the photo stage below,
+ * hipdec_tensor_photo: chain the two through a U8 / NHWC buffer); a clips entry point (repeat
  * the map for the T frames of a clip and use hipdec_tensor_warp); Lanczos; warping straight from the full-size picture in one resampling. */
 typedef struct hipdec_tensor_map { double m[6]; } hipdec_tensor_map;
 typedef struct hipdec_warp_desc {
@@ -863,6 +864,88 @@ HIPDEC_API int hipdec_album_to_tensor_warped(hipdec_album* a, const hipdec_tenso
 HIPDEC_API int hipdec_rotate_map(double angle, int width, int height, hipdec_tensor_map* out);
 /* counters since load: launches of k_warp - one per call that wrote anything - and the entries they wrote */
 HIPDEC_API void hipdec_warp_stats(uint64_t* calls, uint64_t* entries);
+
+/* ---- photometric tensor output: Pillow-exact ColorJitter / RandAugment colour operations on the resized 8-bit picture, normalised --------------------------
+ * ColorJitter (brightness, contrast, saturation), RandomGrayscale, the colour half of RandAugment / AutoAugment / TrivialAugment (Brightness, Color,
+ * Contrast, Sharpness, Posterize, Solarize, AutoContrast, Equalize, Invert) and RandomAdjustSharpness / RandomAutocontrast / RandomEqualize /
+ * RandomPosterize / RandomSolarize / RandomInvert are, in the libraries people train with, PIL.ImageEnhance.* and PIL.ImageOps.* calls on the already resized
+ * 8-bit picture.  The photo stage does exactly that to 8-bit interleaved RGB samples in device memory - per sample a chain of up to HIPDEC_PHOTO_MAX_OPS
+ * operations - and writes the normalised tensor the other tensor calls write.  Bit-equal to Pillow, no tolerance.
+ *
+ * THE STAGE (hipdec_tensor_photo).  S is a sample of h x w x 3 bytes (w = src_width, h = src_height), V one of its components.  The operations of
+ * chains[e] are applied in order, each to the 8-bit result of the one before it; an empty chain is the identity.
+ *  BLEND(D, V, f) - PIL.Image.blend(degenerate, image, f) per component: alpha = (float)f;  t = (float)D + alpha * (float)(V - D) in IEEE single precision,
+ *    the product rounded, then the sum (no fused multiply-add: the library is built with -ffp-contract=off, and this definition depends on it).
+ *    If 0 <= alpha <= 1 the result is (uint8)t, truncating; otherwise 0 if t <= 0, 255 if t >= 255, else (uint8)t.
+ *  LUM(R, G, B) = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16 - convert("L").
+ *  HIPDEC_PHOTO_BRIGHTNESS (value f)  BLEND(0, V, f)                                                          ImageEnhance.Brightness
+ *  HIPDEC_PHOTO_COLOR (f)             BLEND(LUM of the pixel, V, f); f = 0 is RandomGrayscale / convert("L") exactly   ImageEnhance.Color
+ *  HIPDEC_PHOTO_CONTRAST (f)          BLEND(m, V, f), m = (int)((double)(sum of LUM over the sample) / (double)(w * h) + 0.5)   ImageEnhance.Contrast
+ *  HIPDEC_PHOTO_SHARPNESS (f)         BLEND(SM, V, f), SM the sample through ImageFilter.SMOOTH:                ImageEnhance.Sharpness
+ *      interior pixels (uint8)clip(((0.5f + row(y - 1)) + row(y)) + row(y + 1)) in single precision - the top row first -, clip(s) = 0 if s <= 0, 255 if
+ *      s >= 255;  row(r) = (S[r][x - 1] * k + S[r][x] * c) + S[r][x + 1] * k with k = (float)(1.0 / 13) and c = (float)(5.0 / 13) for r = y, c = k for the
+ *      rows above and below (the kernel 1 1 1 / 1 5 1 / 1 1 1 over 13).  Border pixels - the first and last row and column, every pixel when w < 3 or
+ *      h < 3 - are S.
+ *  HIPDEC_PHOTO_POSTERIZE (value an integer 0 .. 8)   V & ((0xFF << (8 - bits)) & 0xFF)                        ImageOps.posterize
+ *  HIPDEC_PHOTO_SOLARIZE (threshold t, a double)      V if (double)V < t, else 255 - V                          ImageOps.solarize
+ *  HIPDEC_PHOTO_INVERT                                255 - V                                                   ImageOps.invert
+ *  HIPDEC_PHOTO_AUTOCONTRAST   per channel: lo, hi the least and greatest value present; hi <= lo: identity; else scale = 255.0 / (hi - lo),
+ *      offset = -lo * scale in double and V' = clamp((int)(V * scale + offset), 0, 255): one rounding per operation, no contraction, truncation toward
+ *      zero.                                                                                                    ImageOps.autocontrast, cutoff 0
+ *  HIPDEC_PHOTO_EQUALIZE       per channel with histogram H: fewer than two non-zero bins: identity; step = (w * h - H[last non-zero bin]) / 255 (integer);
+ *      step == 0: identity; else V' = min(255, (step / 2 + H[0] + .. + H[V - 1]) / step) (integer).            ImageOps.equalize
+ * The value of an operation that takes none is not read beyond the checks below (pass 0).
+ * Float stage, dtypes and layouts: those of hipdec_batch_to_tensor with V the 8-bit component value.  desc->width x height must equal the source size - the
+ * stage does not resize - and desc->filter is not read.  HIPDEC_TENSOR_U8 with HIPDEC_TENSOR_NHWC writes samples of the stage's own input format, so the
+ * stage chains with hipdec_tensor_warp in either order through such a buffer.
+ * src_dev: n dense samples back to back (NHWC), src_bytes at least n * h * w * 3; it is not written.  n == 0 is allowed: nothing is launched or counted.
+ * A clip's frames share a chain by repeating it; CONTRAST's mean is then per frame, as in the host recipes.
+ *
+ * THE DECODE-SIDE FORMS (hipdec_batch_to_tensor_photo, hipdec_album_to_tensor_photo).  Sample e of the intermediate is, byte for byte, what
+ * hipdec_batch_to_tensor_oriented writes for entry e and orientations[e] with dtype U8, layout NHWC, size src_width x src_height and desc->filter (all four
+ * resize filters, windows, flips, codes); then the stage above.  An empty chain for every entry gives hipdec_batch_to_tensor_oriented's bytes.  A float
+ * dtype from a source above 8 bits is HIPDEC_ERR_UNSUPPORTED, as for the warp; U8 goes through to-SDR.  The intermediate, the stage's ping-pong buffers
+ * and histograms come from the library's device pool; the handle keeps them for its next photo call and returns them when it is freed.  The inner resize
+ * counts in hipdec_tensor_stats and hipdec_oriented_stats as the oriented call does.
+ *
+ * Launches: the existing resize launch (decode-side forms); then per chain step at most ONE launch of k_photo_hist - only if an entry's operation at that
+ * step is CONTRAST, AUTOCONTRAST or EQUALIZE - and ONE of k_photo_apply, whatever the number of entries: at most 2 * HIPDEC_PHOTO_MAX_OPS.  Chains of
+ * different lengths and operations share the launches; they are aligned at their first operation.  The statistics never leave the device.
+ * Asynchronous on `stream`.  Refused with HIPDEC_ERR_INVALID_ARGUMENT before anything is launched, `out_dev` untouched, the entry and the operation
+ * named: n_ops outside 0 .. HIPDEC_PHOTO_MAX_OPS; an unknown op; a non-zero `reserved`; a value that is not finite or has |value| > 65536; POSTERIZE with a
+ * value that is not an integer 0 .. 8; and for the call: src_width or src_height < 1 or >= 32768, a desc size that is not the source size, an unknown dtype
+ * or layout, a non-finite scale or bias, src_bytes or out_bytes too small, more than 2^31 - 1 tiles (64 x 16 pixels).
+ * Not part of it: hue (Pillow's HSV round trip); gamma; Gaussian blur; autocontrast cutoffs and masks; a photometric and a warp step inside one call;
+ * parameter samplers; a clips entry point. */
+#define HIPDEC_PHOTO_MAX_OPS 4
+typedef enum hipdec_photo_opcode {
+  HIPDEC_PHOTO_BRIGHTNESS = 1, HIPDEC_PHOTO_COLOR = 2, HIPDEC_PHOTO_CONTRAST = 3, HIPDEC_PHOTO_SHARPNESS = 4, HIPDEC_PHOTO_POSTERIZE = 5,
+  HIPDEC_PHOTO_SOLARIZE = 6, HIPDEC_PHOTO_INVERT = 7, HIPDEC_PHOTO_AUTOCONTRAST = 8, HIPDEC_PHOTO_EQUALIZE = 9
+} hipdec_photo_opcode;
+typedef struct hipdec_photo_op {
+  int op;                      /* hipdec_photo_opcode */
+  int reserved;                /* 0 */
+  double value;                /* the factor f, the bits, the threshold; 0 for INVERT, AUTOCONTRAST, EQUALIZE */
+} hipdec_photo_op;
+typedef struct hipdec_photo_chain {
+  int n_ops;                   /* 0 .. HIPDEC_PHOTO_MAX_OPS */
+  int reserved;                /* 0 */
+  hipdec_photo_op ops[HIPDEC_PHOTO_MAX_OPS];
+} hipdec_photo_chain;
+typedef struct hipdec_photo_desc {
+  int src_width, src_height;   /* size of the samples: the intermediate picture of the decode-side forms */
+  int reserved[2];             /* 0 */
+} hipdec_photo_desc;
+HIPDEC_API int hipdec_tensor_photo(const void* src_dev, size_t src_bytes, const hipdec_photo_desc* photo, const hipdec_photo_chain* chains,
+                                   const hipdec_tensor_desc* desc, int n, void* out_dev, size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_batch_to_tensor_photo(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                            const hipdec_photo_desc* photo, const hipdec_photo_chain* chains, int n_entries, void* out_dev, size_t out_bytes,
+                                            void* stream);
+HIPDEC_API int hipdec_album_to_tensor_photo(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                            const hipdec_photo_desc* photo, const hipdec_photo_chain* chains, int n_entries, void* out_dev, size_t out_bytes,
+                                            void* stream);
+/* counters since load: photo calls that wrote anything, the entries they wrote, and the launches of k_photo_hist and k_photo_apply together */
+HIPDEC_API void hipdec_photo_stats(uint64_t* calls, uint64_t* entries, uint64_t* launches);
 
 /* counters since load: images through hipdec_image_transform, grid canvases handed out by hipdec_grid_read_plane_tracked (hipdec_image_scale counts in
  * hipdec_image_scale_stats) */

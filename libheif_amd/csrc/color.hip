@@ -18,6 +18,8 @@
 #include "hipdec_internal.h"
 #include "color_device.h"
 #include "warp_host.h"
+#define PHOTO_FN __host__ __device__ inline
+#include "photo_lut.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -1202,6 +1204,9 @@ __global__ __launch_bounds__(256) void k_canvas_margin(const hipdec::CanvasMargi
 
 // ---- warped tensor output (include/heif_hipdec.h hipdec_tensor_warp): k_warp_nearest / _bilinear / _bicubic
 #include "warp_kernels.h"
+
+// ---- photometric tensor output (include/heif_hipdec.h hipdec_tensor_photo): k_photo_hist, k_photo_apply
+#include "photo_kernels.h"
 
 // the plane scalers: blockIdx.z selects the plane (all planes of an image, or of all items of a batch, are ONE launch)
 // ---- Pillow's bilinear / bicubic resampling of 8-bit pictures (HIPDEC_SCALE_BILINEAR / _BICUBIC, include/heif_hipdec.h), bit for bit: two separable passes
@@ -2608,6 +2613,159 @@ int warp_launch(WarpState& st, const void* src_dev, const hipdec_warp_desc* w, c
   return 0;
 }
 
+// ---- photometric tensor output: what the arguments alone decide, the per-step tables, at most one k_photo_hist and one k_photo_apply launch per chain step
+#define HIPDEC_PHOTO_SAME(NAME) ((int)HIPDEC_PHOTO_##NAME == (int)PHOTO_##NAME)
+static_assert(HIPDEC_PHOTO_SAME(BRIGHTNESS) && HIPDEC_PHOTO_SAME(COLOR) && HIPDEC_PHOTO_SAME(CONTRAST) && HIPDEC_PHOTO_SAME(SHARPNESS) &&
+              HIPDEC_PHOTO_SAME(POSTERIZE) && HIPDEC_PHOTO_SAME(SOLARIZE) && HIPDEC_PHOTO_SAME(INVERT) && HIPDEC_PHOTO_SAME(AUTOCONTRAST) &&
+              HIPDEC_PHOTO_SAME(EQUALIZE), "photo_lut.h restates hipdec_photo_opcode");
+#undef HIPDEC_PHOTO_SAME
+std::atomic<uint64_t> g_photo_calls{0}, g_photo_entries{0}, g_photo_launches{0};
+
+int photo_check(const char* who, const hipdec_photo_desc* p, const hipdec_photo_chain* chains, const hipdec_tensor_desc* d, int n)
+{
+  static const char* const names[] = {"none", "BRIGHTNESS", "COLOR", "CONTRAST", "SHARPNESS", "POSTERIZE", "SOLARIZE", "INVERT", "AUTOCONTRAST", "EQUALIZE"};
+  if (!p || (!chains && n > 0)) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  if (p->src_width < 1 || p->src_height < 1 || p->src_width >= 32768 || p->src_height >= 32768)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: source size %d x %d (1 .. 32767 each way)", who, p->src_width, p->src_height);
+  if (p->reserved[0] || p->reserved[1]) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: photo.reserved is not 0", who);
+  if (d->width != p->src_width || d->height != p->src_height)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: the tensor's size %d x %d is not the source size %d x %d (the stage does not resize)", who, d->width, d->height,
+                     p->src_width, p->src_height);
+  for (int e = 0; e < n; e++) {
+    const hipdec_photo_chain& ch = chains[e];
+    if (ch.n_ops < 0 || ch.n_ops > HIPDEC_PHOTO_MAX_OPS) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: n_ops is %d (0 .. %d)", who, e, ch.n_ops, HIPDEC_PHOTO_MAX_OPS);
+    if (ch.reserved) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: chain.reserved is %d, not 0", who, e, ch.reserved);
+    for (int k = 0; k < ch.n_ops; k++) {
+      const hipdec_photo_op& o = ch.ops[k];
+      const char* name = o.op >= PHOTO_BRIGHTNESS && o.op <= PHOTO_EQUALIZE ? names[o.op] : "unknown";
+      switch (photo_op_check(o.op, o.reserved, o.value)) {
+        case 0: break;
+        case 1: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d: unknown op %d", who, e, k, o.op);
+        case 2: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (%s): reserved is %d, not 0", who, e, k, name, o.reserved);
+        case 3: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (%s): the value is not finite", who, e, k, name);
+        case 4: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (%s): the value %g has a magnitude above 65536", who, e, k, name, o.value);
+        default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (%s): %g bits (an integer 0 .. 8)", who, e, k, name, o.value);
+      }
+    }
+  }
+  const uint64_t tiles = (uint64_t)((d->width + kWarpTC - 1) / kWarpTC) * (uint64_t)((d->height + kWarpTR - 1) / kWarpTR);
+  if (tiles * (uint64_t)(n > 0 ? n : 1) > 0x7fffffffull)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: %d entries of %d x %d are more than 2^31 - 1 tiles", who, n, d->width, d->height);
+  return 0;
+}
+
+int photo_scratch(PhotoState& st, size_t bytes, hipStream_t s, void** out) { return warp_scratch(st.base, bytes, s, out); }
+
+void photo_state_free(PhotoState& st)
+{
+  warp_state_free(st.base);   // (waits for the last launch)
+  if (st.work) arena_release(st.work, st.work_bytes);
+  st.work = nullptr; st.work_bytes = 0;
+}
+
+int photo_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p, const hipdec_photo_chain* chains, const hipdec_tensor_desc* d, int n,
+                 void* out_dev, hipStream_t s)
+{
+  if (n <= 0) return 0;
+  const int w = p->src_width, h = p->src_height;
+  const size_t sample = (size_t)w * (size_t)h * 3, out_entry = sample * (d->dtype == TD_U8 ? 1 : (d->dtype == TD_F32 ? 4 : 2));
+  // Chains are aligned at their first step: entry e takes part in steps 0 .. max(n_ops, 1) - 1, and its last step writes the tensor (an empty chain is
+  // one identity step).  Step t of the call is the launches of all entries that have a step t.
+  int steps = 1;
+  for (int e = 0; e < n; e++) steps = std::max(steps, chains[e].n_ops);
+  std::vector<int> n_apply((size_t)steps, 0), n_hist((size_t)steps, 0);
+  for (int e = 0; e < n; e++)
+    for (int t = 0; t < std::max(chains[e].n_ops, 1); t++) {
+      n_apply[(size_t)t]++;
+      if (chains[e].n_ops && photo_needs_statistics(chains[e].ops[t].op)) n_hist[(size_t)t]++;
+    }
+  size_t records = 0;
+  int max_hist = 0;
+  for (int t = 0; t < steps; t++) { records += (size_t)n_apply[(size_t)t] + (size_t)n_hist[(size_t)t]; max_hist = std::max(max_hist, n_hist[(size_t)t]); }
+  // the work memory: up to two ping-pong buffers of n samples, then the histograms of the step with the most of them
+  const int n_pp = std::min(steps - 1, 2);
+  const size_t pp_bytes = ((size_t)n * sample + 255) & ~(size_t)255, hist_bytes = (size_t)max_hist * 4 * 256 * sizeof(uint32_t);
+  const size_t work_bytes = (size_t)n_pp * pp_bytes + hist_bytes, bytes = records * sizeof(PhotoEntry);
+  const bool grow_work = st.work_bytes < work_bytes, grow_table = st.base.table.dev_bytes < bytes;
+  if (int rc = warp_state_order(st.base, s, grow_work || grow_table)) return rc;
+  if (grow_work) {
+    if (st.work) arena_release(st.work, st.work_bytes);
+    st.work = nullptr; st.work_bytes = 0;
+    HIPDEC_CHECK_HIP(arena_acquire(&st.work, work_bytes, &st.work_bytes));
+  }
+  if (grow_table) {
+    if (st.base.table.dev) arena_release(st.base.table.dev, st.base.table.dev_bytes);
+    st.base.table.dev = nullptr; st.base.table.dev_bytes = 0; st.base.table.host.clear();
+    HIPDEC_CHECK_HIP(arena_acquire(&st.base.table.dev, bytes, &st.base.table.dev_bytes));
+  }
+  uint8_t* pp[2] = {(uint8_t*)st.work, (uint8_t*)st.work + pp_bytes};
+  uint32_t* hist = (uint32_t*)((uint8_t*)st.work + (size_t)n_pp * pp_bytes);
+  std::vector<uint8_t> host(bytes);
+  std::vector<size_t> first((size_t)steps);   // the step's first record: its apply records, then its histogram records
+  size_t at = 0;
+  for (int t = 0; t < steps; t++) {
+    first[(size_t)t] = at;
+    PhotoEntry* apply = (PhotoEntry*)host.data() + at;
+    PhotoEntry* stat = apply + n_apply[(size_t)t];
+    int ia = 0, ih = 0;
+    for (int e = 0; e < n; e++) {
+      const int len = std::max(chains[e].n_ops, 1);
+      if (t >= len) continue;
+      PhotoEntry E;
+      memset(&E, 0, sizeof(E));
+      E.src = t == 0 ? (const uint8_t*)src_dev + (size_t)e * sample : pp[(t - 1) & 1] + (size_t)e * sample;
+      E.last = t == len - 1;
+      E.dst = E.last ? (uint8_t*)out_dev + (size_t)e * out_entry : pp[t & 1] + (size_t)e * sample;
+      E.op = chains[e].n_ops ? chains[e].ops[t].op : PHOTO_NONE;
+      E.value = chains[e].n_ops ? chains[e].ops[t].value : 0.0;
+      if (photo_needs_statistics(E.op)) {
+        E.hist = hist + (size_t)ih * 4 * 256;
+        stat[ih++] = E;
+      }
+      apply[ia++] = E;
+    }
+    at += (size_t)n_apply[(size_t)t] + (size_t)n_hist[(size_t)t];
+  }
+  if (st.base.table.host != host) {   // steady state (the same chains, source and output): nothing to upload
+    st.base.table.prev.swap(st.base.table.host);
+    st.base.table.host.swap(host);
+    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.base.table.dev, st.base.table.host.data(), bytes, hipMemcpyHostToDevice, s));
+  }
+  PhotoCall c;
+  memset(&c, 0, sizeof(c));
+  c.w = w; c.h = h; c.nhwc = d->layout == HIPDEC_TENSOR_NHWC;
+  c.tiles_x = (uint32_t)((w + kWarpTC - 1) / kWarpTC);
+  c.tiles = c.tiles_x * (uint32_t)((h + kWarpTR - 1) / kWarpTR);
+  c.slices = (uint32_t)((h + kPhotoHistRows - 1) / kPhotoHistRows);
+  for (int k = 0; k < 3; k++) { c.scale[k] = d->scale[k]; c.bias[k] = d->bias[k]; }
+  const PhotoEntry* dev = (const PhotoEntry*)st.base.table.dev;
+  uint64_t launches = 0;
+  for (int t = 0; t < steps; t++) {
+    const PhotoEntry* tab = dev + first[(size_t)t];
+    if (n_hist[(size_t)t]) {
+      HIPDEC_CHECK_HIP(hipMemsetAsync(hist, 0, (size_t)n_hist[(size_t)t] * 4 * 256 * sizeof(uint32_t), s));
+      hipLaunchKernelGGL(k_photo_hist, dim3((unsigned)((uint64_t)c.slices * (uint64_t)n_hist[(size_t)t])), dim3(256), 0, s, tab + n_apply[(size_t)t], c);
+      launches++;
+    }
+    dim3 block(256), grid((unsigned)((uint64_t)c.tiles * (uint64_t)n_apply[(size_t)t]));   // (photo_check: below 2^31)
+    switch (d->dtype) {
+      case TD_U8: hipLaunchKernelGGL((k_photo_apply<TD_U8>), grid, block, 0, s, tab, c); break;
+      case TD_F32: hipLaunchKernelGGL((k_photo_apply<TD_F32>), grid, block, 0, s, tab, c); break;
+      case TD_F16: hipLaunchKernelGGL((k_photo_apply<TD_F16>), grid, block, 0, s, tab, c); break;
+      case TD_BF16: hipLaunchKernelGGL((k_photo_apply<TD_BF16>), grid, block, 0, s, tab, c); break;
+      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: unknown dtype %d", d->dtype);
+    }
+    launches++;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "photo kernel launch: %s", hipGetErrorString(e));
+  if (!st.base.done) HIPDEC_CHECK_HIP(hipEventCreateWithFlags(&st.base.done, hipEventDisableTiming));
+  HIPDEC_CHECK_HIP(hipEventRecord(st.base.done, s));
+  st.base.last = s;
+  g_photo_calls++; g_photo_entries += (uint64_t)n; g_photo_launches += launches;
+  return 0;
+}
+
 // debug inspection of the blocks last handed to the tensor kernels: plane `plane` of entry `entry` as the kernel receives it - the pointer and stride of the
 // PLANE, and the window of it that is scaled
 int color_tensor_inspect(const ColorBatchState& st, int entry, int plane, const void** plane_dev, size_t* stride, int* x, int* y, int* w, int* h)
@@ -2703,6 +2861,42 @@ void hipdec_warp_stats(uint64_t* calls, uint64_t* entries)
 {
   if (calls) *calls = g_warp_calls.load();
   if (entries) *entries = g_warp_entries.load();
+}
+
+void hipdec_photo_stats(uint64_t* calls, uint64_t* entries, uint64_t* launches)
+{
+  if (calls) *calls = g_photo_calls.load();
+  if (entries) *entries = g_photo_entries.load();
+  if (launches) *launches = g_photo_launches.load();
+}
+
+// the stage alone; its tables and work memory live in a state the process keeps per device, as hipdec_tensor_warp's do
+int hipdec_tensor_photo(const void* src_dev, size_t src_bytes, const hipdec_photo_desc* photo, const hipdec_photo_chain* chains, const hipdec_tensor_desc* desc,
+                        int n, void* out_dev, size_t out_bytes, void* stream)
+{
+  static std::mutex mu;
+  static std::map<int, PhotoState> states;   // by device
+  if (!desc || n < 0) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: bad arguments");
+  if (desc->dtype < HIPDEC_TENSOR_U8 || desc->dtype > HIPDEC_TENSOR_BF16) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: unknown dtype %d", desc->dtype);
+  if (desc->layout != HIPDEC_TENSOR_NCHW && desc->layout != HIPDEC_TENSOR_NHWC) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: unknown layout %d", desc->layout);
+  if (desc->dtype != HIPDEC_TENSOR_U8)
+    for (int c = 0; c < 3; c++)
+      if (!std::isfinite(desc->scale[c]) || !std::isfinite(desc->bias[c])) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: scale / bias of channel %d is not finite", c);
+  if (int rc = photo_check("tensor_photo", photo, chains, desc, n)) return rc;
+  const uint64_t es = desc->dtype == HIPDEC_TENSOR_U8 ? 1 : (desc->dtype == HIPDEC_TENSOR_F32 ? 4 : 2);
+  const uint64_t per_src = 3ull * (uint64_t)photo->src_width * (uint64_t)photo->src_height;   // (below 2^32: sizes below 2^15; times n below 2^31, times 4: below 2^63)
+  if (src_bytes < per_src * (uint64_t)n) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: src_bytes %zu is smaller than the %d samples of %llu bytes", src_bytes, n, (unsigned long long)per_src);
+  if (out_bytes < per_src * es * (uint64_t)n) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: out_bytes %zu is smaller than the tensor of %llu bytes", out_bytes, (unsigned long long)(per_src * es * (uint64_t)n));
+  if (n == 0) return 0;
+  if (!src_dev || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: bad arguments");
+  // (everything above is decided without a device)
+  if (int rc = ensure_init()) return rc;
+  return guarded("tensor_photo", [&]() -> int {
+    std::lock_guard<std::mutex> lock(mu);
+    int dev = 0;
+    HIPDEC_CHECK_HIP(hipGetDevice(&dev));
+    return photo_launch(states[dev], src_dev, photo, chains, desc, n, out_dev, stream ? (hipStream_t)stream : default_stream());
+  });
 }
 
 // Pillow's Image.rotate matrix without expand (Image.py rotate): cos and sin of -radians(angle mod 360) rounded to 15 decimal places - printed with 15

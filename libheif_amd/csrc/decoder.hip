@@ -68,6 +68,7 @@ struct hipdec_batch : BatchLayout {
   ColorBatchState color_margin;   // ... and the margin blocks of hipdec_batch_to_tensor_placed
   ColorBatchState color_packed;   // ... and of hipdec_batch_to_tensor_packed
   WarpState warp;                 // the table and the U8 intermediate of hipdec_batch_to_tensor_warped
+  PhotoState photo;               // the tables, the U8 intermediate and the work memory of hipdec_batch_to_tensor_photo
   uint64_t max_pixels = 0;      // the limit given at creation (0: none): scaled outputs are held against it as well
   // decoder path (plugin): the output planes of every item staged in pinned host memory by ONE set of asynchronous copies behind the
   // kernels, so that N decoder instances sharing the batch do not queue N x 3 pageable device-to-host copies (stage_planes_to_host)
@@ -133,6 +134,7 @@ struct hipdec_batch : BatchLayout {
     color_batch_state_free(color_margin);
     color_batch_state_free(color_packed);
     warp_state_free(warp);
+    photo_state_free(photo);
     if (arena) arena_release(arena, arena_capacity);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : chain_events) if (e) (void)hipEventDestroy(e);
@@ -1169,6 +1171,60 @@ int batch_to_tensor_warped_impl(hipdec_batch* b, const hipdec_tensor_desc* desc,
   });
 }
 
+// ---- photometric tensor output (hipdec_batch_to_tensor_photo / hipdec_album_to_tensor_photo): what the two forms share.
+// What the arguments alone decide; *mid: the description of the U8 / NHWC intermediate, *mid_bytes its size
+int photo_form_check(const char* who, const hipdec_tensor_desc* desc, const int* orientations, const hipdec_photo_desc* photo, const hipdec_photo_chain* chains,
+                     int n_entries, const void* out_dev, size_t out_bytes, hipdec_tensor_desc* mid, size_t* mid_bytes)
+{
+  if (!out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  size_t bytes = 0;
+  if (int rc = tensor_check_desc(who, desc, n_entries, &bytes)) return rc;
+  if (int rc = check_orientations(who, "entry", orientations, n_entries)) return rc;
+  if (int rc = photo_check(who, photo, chains, desc, n_entries)) return rc;
+  if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: out_bytes %zu is smaller than the tensor of %zu bytes", who, out_bytes, bytes);
+  memset(mid, 0, sizeof(*mid));
+  mid->width = photo->src_width; mid->height = photo->src_height; mid->dtype = HIPDEC_TENSOR_U8; mid->layout = HIPDEC_TENSOR_NHWC; mid->filter = desc->filter;
+  for (int c = 0; c < 3; c++) mid->scale[c] = 1.0f;
+  return tensor_check_desc(who, mid, n_entries, mid_bytes);
+}
+
+// the stage is defined on the 8-bit picture: a float dtype from a source above 8 bits is refused, as for the warp
+int photo_check_depth(const char* who, const hipdec_tensor_desc* d, int e, int bits)
+{
+  if (bits > 8 && d->dtype != HIPDEC_TENSOR_U8)
+    return set_error(HIPDEC_ERR_UNSUPPORTED, "%s: entry %d: the photometric operations on a %d-bit source are defined for HIPDEC_TENSOR_U8 only (they work on the 8-bit picture)", who, e, bits);
+  return 0;
+}
+
+int batch_to_tensor_photo_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                               const hipdec_photo_desc* photo, const hipdec_photo_chain* chains, int n_entries, void* out_dev, size_t out_bytes, void* stream)
+{
+  const char* who = "to_tensor_photo";
+  if (!b) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  hipdec_tensor_desc mid;
+  size_t mid_bytes = 0;
+  if (int rc = photo_form_check(who, desc, orientations, photo, chains, n_entries, out_dev, out_bytes, &mid, &mid_bytes)) return rc;
+  // (everything above is decided without reading the handle)
+  for (int e = 0; e < n_entries; e++) {
+    const int i = entries ? entries[e].item : e;
+    if (i < 0 || i >= (int)b->pics.size()) continue;   // (the resize stage refuses it)
+    if (int rc = photo_check_depth(who, desc, e, b->wide ? b->pics[i].info.bit_depth_luma : 8)) return rc;
+  }
+  DeviceScope scope(b->device);
+  if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: the batch's arena was handed to another batch", who);
+  if (b->max_pixels && (uint64_t)desc->width * (uint64_t)desc->height > b->max_pixels)
+    return set_error(HIPDEC_ERR_LIMIT, "%s: output of %d x %d pixels exceeds max_image_size_pixels", who, desc->width, desc->height);
+  void* scratch = nullptr;
+  if (int rc = guarded(who, [&]() -> int { return photo_scratch(b->photo, mid_bytes, follow_stream(b, stream), &scratch); })) return rc;
+  if (int rc = batch_to_tensor_impl(b, &mid, entries, orientations, true, n_entries, scratch, mid_bytes, stream)) return rc;   // the existing resize launch
+  return guarded(who, [&]() -> int {
+    hipStream_t s = follow_stream(b, stream);
+    const int rc = photo_launch(b->photo, scratch, photo, chains, desc, n_entries, out_dev, s);
+    b->mark_done(s);
+    return rc;
+  });
+}
+
 // what the RGB forms of the oriented output decide for one picture from the arguments alone (before a device is touched)
 int rgb_oriented_check_item(const char* who, int i, int out_chroma, int code, int ow, int oh, int filter, size_t stride)
 {
@@ -1275,6 +1331,12 @@ int hipdec_batch_to_tensor_warped(hipdec_batch* b, const hipdec_tensor_desc* des
                                   size_t out_bytes, void* stream)
 {
   return batch_to_tensor_warped_impl(b, desc, entries, orientations, warp, maps, fill, n_entries, out_dev, out_bytes, stream);
+}
+
+int hipdec_batch_to_tensor_photo(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                 const hipdec_photo_desc* photo, const hipdec_photo_chain* chains, int n_entries, void* out_dev, size_t out_bytes, void* stream)
+{
+  return batch_to_tensor_photo_impl(b, desc, entries, orientations, photo, chains, n_entries, out_dev, out_bytes, stream);
 }
 
 int hipdec_batch_to_tensor_packed(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,

@@ -146,6 +146,20 @@ int warp_launch(WarpState& st, const void* src_dev, const hipdec_warp_desc* w, c
                 const hipdec_tensor_desc* d, int n, void* out_dev, hipStream_t s);
 void warp_state_free(WarpState& st);
 
+// Photometric tensor output (color.hip k_photo_hist / k_photo_apply, include/heif_hipdec.h hipdec_tensor_photo): n dense U8 / NHWC samples through a chain
+// of up to four operations each.  What the arguments alone decide (photo_check) is host-only; photo_launch builds one table of records per chain step,
+// uploads them with one copy and launches at most one histogram and one apply kernel per step.
+struct PhotoState {            // the device memory a handle (or, for hipdec_tensor_photo, the process) keeps for its photo calls
+  WarpState base;              // the tables last uploaded, the U8 / NHWC intermediate of the decode-side forms, the event behind the last launch
+  void* work = nullptr;        // up to two ping-pong buffers of n samples, then the histograms of one step
+  size_t work_bytes = 0;
+};
+int photo_check(const char* who, const hipdec_photo_desc* p, const hipdec_photo_chain* chains, const hipdec_tensor_desc* d, int n);
+int photo_scratch(PhotoState& st, size_t bytes, hipStream_t s, void** out);   // the handle's intermediate, at least `bytes` long
+int photo_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p, const hipdec_photo_chain* chains, const hipdec_tensor_desc* d, int n,
+                 void* out_dev, hipStream_t s);
+void photo_state_free(PhotoState& st);
+
 // The paste of an album of grid photos (transform.hip k_album_paste): one job per (tile, plane), already clipped to the photo's output size by the host
 // (a job clipped to nothing is not emitted); the job table lives in device memory and all jobs go out as ONE launch.
 struct PasteJob {

@@ -101,6 +101,13 @@ def _bind(lib):
         lib.hipdec_rotate_map.argtypes = [C.c_double, ci, ci, C.POINTER(TensorMap)]
         lib.hipdec_warp_stats.restype = None
         lib.hipdec_warp_stats.argtypes = [C.POINTER(C.c_uint64)] * 2
+    if hasattr(lib, "hipdec_tensor_photo"):    # (likewise: an older branch's library has no photo stage)
+        lib.hipdec_tensor_photo.argtypes = [vp, sz, C.POINTER(PhotoDesc), C.POINTER(PhotoChain), C.POINTER(TensorDesc), ci, vp, sz, vp]
+        photo = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), C.POINTER(ci), C.POINTER(PhotoDesc), C.POINTER(PhotoChain), ci, vp, sz, vp]
+        lib.hipdec_batch_to_tensor_photo.argtypes = photo
+        lib.hipdec_album_to_tensor_photo.argtypes = photo
+        lib.hipdec_photo_stats.restype = None
+        lib.hipdec_photo_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
     if hasattr(lib, "hipdec_clips_create"):   # (tools/ab_bench.sh loads an older branch's library through this module: it has no clips, and Clips() says so)
         lib.hipdec_clips_create.argtypes = [C.POINTER(vp), ci, C.POINTER(ci), C.POINTER(C.c_char_p), C.POINTER(sz), C.c_uint64]
         lib.hipdec_clips_free.argtypes = [vp]
@@ -169,6 +176,21 @@ class TensorMap(C.Structure):
 class WarpDesc(C.Structure):
     """hipdec_warp_desc"""
     _fields_ = [("src_width", C.c_int), ("src_height", C.c_int), ("filter", C.c_int), ("reserved", C.c_int)]
+
+
+class PhotoOp(C.Structure):
+    """hipdec_photo_op"""
+    _fields_ = [("op", C.c_int), ("reserved", C.c_int), ("value", C.c_double)]
+
+
+class PhotoChain(C.Structure):
+    """hipdec_photo_chain: up to PHOTO_MAX_OPS operations, applied in order"""
+    _fields_ = [("n_ops", C.c_int), ("reserved", C.c_int), ("ops", PhotoOp * 4)]
+
+
+class PhotoDesc(C.Structure):
+    """hipdec_photo_desc"""
+    _fields_ = [("src_width", C.c_int), ("src_height", C.c_int), ("reserved", C.c_int * 2)]
 
 
 class ClipFrame(C.Structure):
@@ -645,6 +667,64 @@ def _to_tensor_warped(self, lib_call, size, maps, entries, src_size, warp_filter
     return _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
 
 
+# hipdec_photo_opcode: the photometric operations (PIL.ImageEnhance.* / PIL.ImageOps.* on the 8-bit picture, bit for bit)
+PHOTO_BRIGHTNESS, PHOTO_COLOR, PHOTO_CONTRAST, PHOTO_SHARPNESS, PHOTO_POSTERIZE, PHOTO_SOLARIZE, PHOTO_INVERT, PHOTO_AUTOCONTRAST, PHOTO_EQUALIZE = range(1, 10)
+PHOTO_MAX_OPS = 4
+PHOTO_OPS = {"brightness": PHOTO_BRIGHTNESS, "color": PHOTO_COLOR, "contrast": PHOTO_CONTRAST, "sharpness": PHOTO_SHARPNESS, "posterize": PHOTO_POSTERIZE,
+             "solarize": PHOTO_SOLARIZE, "invert": PHOTO_INVERT, "autocontrast": PHOTO_AUTOCONTRAST, "equalize": PHOTO_EQUALIZE}
+
+
+def photo_chain(*ops):
+    """hipdec_photo_chain from up to PHOTO_MAX_OPS operations, applied in order: ("contrast", 1.3), ("posterize", 4), "equalize", (PHOTO_INVERT,) - a name of
+    PHOTO_OPS or a PHOTO_* constant, with its value where it takes one (the factor, the bits, the threshold)"""
+    if len(ops) > PHOTO_MAX_OPS:
+        raise ValueError("a chain has at most %d operations, not %d" % (PHOTO_MAX_OPS, len(ops)))
+    ch = PhotoChain()
+    ch.n_ops = len(ops)
+    for k, o in enumerate(ops):
+        o = (o,) if isinstance(o, (str, int)) else tuple(o)
+        if not 1 <= len(o) <= 2:
+            raise ValueError("an operation is a name or (name, value), not %r" % (o,))
+        if isinstance(o[0], str) and o[0].lower() not in PHOTO_OPS:
+            raise ValueError("unknown photometric operation %r" % (o[0],))
+        ch.ops[k].op = PHOTO_OPS[o[0].lower()] if isinstance(o[0], str) else int(o[0])
+        ch.ops[k].value = float(o[1]) if len(o) == 2 else 0.0
+    return ch
+
+
+def photo_chains(chains, n=None):
+    """a ctypes array of hipdec_photo_chain from PhotoChain objects or sequences of operations (photo_chain's arguments)"""
+    chains = list(chains)
+    if n is not None and len(chains) != n:
+        raise ValueError("%d chains for %d entries" % (len(chains), n))
+    arr = (PhotoChain * max(len(chains), 1))()
+    for k, ch in enumerate(chains):
+        arr[k] = ch if isinstance(ch, PhotoChain) else photo_chain(*ch)
+    return arr
+
+
+def photo_desc(src_size):
+    """hipdec_photo_desc for src_size = (width, height) of the samples"""
+    return PhotoDesc(int(src_size[0]), int(src_size[1]), (C.c_int * 2)(0, 0))
+
+
+def photo_stats():
+    """(photo calls that wrote anything, the entries they wrote, launches of k_photo_hist and k_photo_apply together) since load"""
+    lib = _bind(load_library())
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    lib.hipdec_photo_stats(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def _to_tensor_photo(self, lib_call, size, chains, entries, orientations, filter, dtype, layout, mean, std, scale, bias, out, stream):
+    n = self.n if entries is None else len(entries)
+    pd = photo_desc(size)
+    carr = photo_chains(chains, n)
+    codes = None if orientations is None else _orientation_array(orientations, n)
+    call = lambda h, desc, arr, n_, ptr, room, stream_: lib_call(h, desc, arr, codes, C.byref(pd), carr, n_, ptr, room, stream_)
+    return _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
+
+
 def fit_within(width, height, size):
     """The thumbnail size examples/heif_thumbnailer.cc:172-186 computes: the image as it is when both sides fit into `size`, else the longer
     side becomes `size` and the other one follows with integer division (which may give 0: the thumbnailer refuses that, and so does
@@ -980,6 +1060,17 @@ class Batch:
         return _to_tensor_warped(self, self._lib.hipdec_batch_to_tensor_warped, size, maps, entries, src_size, warp_filter, fill, fill_domain, orientations,
                                  filter, dtype, layout, mean, std, scale, bias, out, stream)
 
+    def to_tensor_photo(self, size, chains, entries=None, filter=SCALE_BILINEAR, orientations=None, dtype="float16", layout="NCHW", mean=None, std=None,
+                        scale=None, bias=None, out=None, stream=None):
+        """asynchronous: to_tensor with one chain of photometric operations per entry, Pillow-exact (hipdec_batch_to_tensor_photo).  Entry e is first
+        resized as to_tensor(size, entries, dtype="uint8", layout="NHWC", filter=filter, orientations=orientations) resizes it, and that 8-bit picture then
+        goes through chains[e] - a PhotoChain or a sequence of operations as photo_chain takes them: ImageEnhance.Brightness / Color / Contrast /
+        Sharpness, ImageOps.posterize / solarize / invert / autocontrast / equalize, bit for bit, each on the 8-bit result of the one before - and is
+        normalised as to_tensor normalises.  The statistics contrast, autocontrast and equalize need are taken on the device.  Sources above 8 bits:
+        dtype "uint8" only.  `out`, `stream` and tensor_to_host() as in to_tensor.  One resize launch, then at most two launches per chain step."""
+        return _to_tensor_photo(self, self._lib.hipdec_batch_to_tensor_photo, size, chains, entries, orientations, filter, dtype, layout, mean, std, scale,
+                                bias, out, stream)
+
     def to_tensor_packed(self, sizes, entries=None, patch=0, merge=1, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None,
                          filter=SCALE_BOX, orientations=None, offsets=None, out=None, stream=None):
         """asynchronous: every entry at its OWN displayed size sizes[e] = (width, height), all entries in one launch into one 1-D output
@@ -1208,6 +1299,12 @@ class Album:
         return _to_tensor_warped(self, self._lib.hipdec_album_to_tensor_warped, size, maps, entries, src_size, warp_filter, fill, fill_domain, orientations,
                                  filter, dtype, layout, mean, std, scale, bias, out, stream)
 
+    def to_tensor_photo(self, size, chains, entries=None, filter=SCALE_BILINEAR, orientations=None, dtype="float16", layout="NCHW", mean=None, std=None,
+                        scale=None, bias=None, out=None, stream=None):
+        """Batch.to_tensor_photo over the composed photos"""
+        return _to_tensor_photo(self, self._lib.hipdec_album_to_tensor_photo, size, chains, entries, orientations, filter, dtype, layout, mean, std, scale,
+                                bias, out, stream)
+
     def to_tensor_packed(self, sizes, entries=None, patch=0, merge=1, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None,
                          filter=SCALE_BOX, orientations=None, offsets=None, out=None, stream=None):
         """Batch.to_tensor_packed over the composed photos"""
@@ -1277,6 +1374,41 @@ def tensor_warp(src, size, maps, src_size=None, warp_filter=SCALE_BILINEAR, fill
     f = None if fill is None else tensor_fill(fill, fill_domain)
     stage = _WarpStage(lib, n)
     call = lambda h, desc, arr, n_, ptr, room, stream_: lib.hipdec_tensor_warp(sptr, sbytes, C.byref(wd), marr, f, desc, n_, ptr, room, stream_)
+    out = _to_tensor(stage, call, size, None, dtype, layout, mean, std, scale, bias, 0, out, stream)
+    return stage.tensor_to_host() if to_host else out
+
+
+def tensor_photo(src, chains, src_size=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, out=None, stream=None,
+                 to_host=False):
+    """asynchronous: the photometric stage alone (hipdec_tensor_photo) over n = len(chains) dense 8-bit RGB samples in device memory: a uint8 torch.Tensor
+    of shape (n, height, width, 3), or a DeviceBuffer of n * height * width * 3 bytes with src_size = (width, height).  Sample e goes through chains[e] as
+    in Batch.to_tensor_photo and is normalised as to_tensor normalises; the tensor has the samples' size.  dtype "uint8" with layout "NHWC" gives samples
+    that tensor_warp and tensor_photo take again.  A clip's T frames share one chain by repeating it T times.  `out`: a DeviceBuffer, or a torch tensor on
+    the current stream.  Returns `out` (to_host=True: the NumPy array, after waiting)."""
+    lib = _bind(load_library())
+    chains = list(chains)
+    n = len(chains)
+    if isinstance(src, DeviceBuffer):
+        if src_size is None:
+            raise ValueError("a DeviceBuffer source needs src_size = (width, height)")
+        sptr, sbytes = src.ptr, src.nbytes
+    else:
+        import torch
+        if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype != torch.uint8:
+            raise TypeError("src must be a DeviceBuffer or a CUDA / HIP torch.Tensor of uint8")
+        if src.dim() != 4 or src.shape[0] != n or src.shape[3] != 3 or not src.is_contiguous():
+            raise ValueError("src must be contiguous with shape (%d, height, width, 3)" % n)
+        if src_size is not None and (int(src_size[0]), int(src_size[1])) != (int(src.shape[2]), int(src.shape[1])):
+            raise ValueError("src_size %r does not match src of shape %s" % (tuple(src_size), tuple(src.shape)))
+        src_size = (int(src.shape[2]), int(src.shape[1]))
+        sptr, sbytes = src.data_ptr(), src.numel()
+        if out is None and stream is None and n > 0:
+            out = torch.empty(tensor_shape(n, src_size, layout), dtype=getattr(torch, dtype), device=src.device)   # (written on torch's current stream, as src was)
+    size = (int(src_size[0]), int(src_size[1]))
+    pd = photo_desc(size)
+    carr = photo_chains(chains, n)
+    stage = _WarpStage(lib, n)
+    call = lambda h, desc, arr, n_, ptr, room, stream_: lib.hipdec_tensor_photo(sptr, sbytes, C.byref(pd), carr, desc, n_, ptr, room, stream_)
     out = _to_tensor(stage, call, size, None, dtype, layout, mean, std, scale, bias, 0, out, stream)
     return stage.tensor_to_host() if to_host else out
 
