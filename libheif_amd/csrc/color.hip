@@ -28,6 +28,7 @@
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 
 namespace {
@@ -1750,7 +1751,18 @@ thread_local std::vector<CapturedScaled> t_captured_scaled;
 // the recorded blocks go out as one launch (hipdec::color_tensor_launch).  Taken and checked like a scale request.
 struct TensorReq { bool on = false; hipdec::TensorRequest r; };
 thread_local TensorReq t_tensor;
-struct CapturedTensor { TensorParams p; int wide; int oriented, code; uint64_t pitch; int plane_rows; int resample; int patch, merge; /* patch > 0: a patch sequence, for the k_patch_* kernels */ int tpatch, strided; /* clips: frames per token; the entry goes to k_clip_box */ };   // oriented: for the k_oriented_* kernels, with a code, a row pitch and the rows of a channel plane; resample: the filter, for k_resample (code and pitch are set for every entry)
+struct CapturedTensor {
+  TensorParams p;
+  int wide;          // the source planes hold uint16_t samples
+  int oriented;      // for the k_oriented_* kernels, with a code, a row pitch and the rows of a channel plane
+  int code;          // (set for every resampled entry too)
+  uint64_t pitch;
+  int plane_rows;
+  int resample;      // the filter, for k_resample
+  int patch, merge;  // patch > 0: a patch sequence, for the k_patch_* kernels
+  int tpatch;        // clips: frames per token
+  int strided;       // clips: the entry goes to k_clip_box
+};
 thread_local std::vector<CapturedTensor> t_captured_tensor;
 
 // ---- the coefficient tables of HIPDEC_SCALE_BILINEAR / _BICUBIC: Pillow's precompute_coeffs + normalize_coeffs_8bpc (src/libImaging/Resample.c), statement
@@ -1845,19 +1857,86 @@ int box_tile_of(int pw, int qw)
   return (int)t;
 }
 
-template <typename Pix, int LAYOUT>
-void launch_scaled_grid(const ScaledParams* one, const ScaledParams* dev, int n, int filter, int max_ow, int max_oh, int max_tiles, hipStream_t s)
+// ---- the launch kit: what the batched launches of every output form share
+// A launch's block array lives in st.dev, the bytes last sent to it in st.host.  blocks_reserve makes room (from the arena pool: hipFree() would synchronise
+// the device every time a batch is retired) and forgets st.host when the memory is new, so that the next compare cannot match stale bytes; blocks_upload
+// sends `host` unless the device already holds these bytes - the steady state of a training loop.  A form that writes addresses inside st.dev into its
+// blocks fills them between the two.
+int blocks_reserve(hipdec::ColorBatchState& st, size_t bytes)
 {
-  if (filter == HIPDEC_SCALE_BOX) {
-    dim3 block(256), grid(max_tiles, max_oh < 65535 ? max_oh : 65535, n);
-    if (one) hipLaunchKernelGGL((k_scale_rgb_box<Pix, LAYOUT>), grid, block, 0, s, *one);
-    else hipLaunchKernelGGL((k_scale_rgb_box_batch<Pix, LAYOUT>), grid, block, 0, s, dev);
-  } else {
-    const int gy = (max_oh + 3) / 4;
-    dim3 block(64, 4), grid(((max_ow + 3) / 4 + 63) / 64, gy < 16384 ? gy : 16384, n);
-    if (one) hipLaunchKernelGGL((k_scale_rgb_nearest<Pix, LAYOUT>), grid, block, 0, s, *one);
-    else hipLaunchKernelGGL((k_scale_rgb_nearest_batch<Pix, LAYOUT>), grid, block, 0, s, dev);
+  if (st.dev_bytes >= bytes) return 0;
+  if (st.dev) hipdec::arena_release(st.dev, st.dev_bytes);
+  st.dev = nullptr; st.dev_bytes = 0; st.host.clear();
+  HIPDEC_CHECK_HIP(hipdec::arena_acquire(&st.dev, bytes, &st.dev_bytes));
+  return 0;
+}
+int blocks_upload(hipdec::ColorBatchState& st, std::vector<uint8_t>& host, hipStream_t s)
+{
+  if (st.host == host) return 0;
+  st.prev.swap(st.host);   // (not freed while its copy may be pending)
+  st.host.swap(host);
+  HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), st.host.size(), hipMemcpyHostToDevice, s));
+  return 0;
+}
+// the parameter blocks `p` of recorded entries, in recording order, as the block array of st
+template <typename Cap>
+int blocks_of_captured(const std::vector<Cap>& caps, hipdec::ColorBatchState& st, hipStream_t s)
+{
+  const size_t each = sizeof(caps[0].p);
+  std::vector<uint8_t> host(caps.size() * each);
+  for (size_t i = 0; i < caps.size(); i++) memcpy(host.data() + i * each, &caps[i].p, each);
+  if (int rc = blocks_reserve(st, host.size())) return rc;
+  return blocks_upload(st, host, s);
+}
+
+// f(DtypeTag) for a hipdec_tensor_dtype, f(PixTag, DtypeTag) for a source width and a dtype: the kernel's template arguments as the types of a generic
+// lambda's parameters.  false: no such dtype (the caller refuses it in its own words)
+template <int DT> using DtypeTag = std::integral_constant<int, DT>;
+template <typename Pix> struct PixTag { typedef Pix type; };
+template <typename F>
+bool dispatch_dtype(int dtype, F&& f)
+{
+  switch (dtype) {
+    case TD_U8: f(DtypeTag<TD_U8>()); return true;
+    case TD_F32: f(DtypeTag<TD_F32>()); return true;
+    case TD_F16: f(DtypeTag<TD_F16>()); return true;
+    case TD_BF16: f(DtypeTag<TD_BF16>()); return true;
+    default: return false;
   }
+}
+template <typename F>
+bool dispatch_pix_dtype(int wide, int dtype, F&& f)
+{
+  if (wide) return dispatch_dtype(dtype, [&](auto dt) { f(PixTag<uint16_t>(), dt); });
+  return dispatch_dtype(dtype, [&](auto dt) { f(PixTag<uint8_t>(), dt); });
+}
+
+// the two grid shapes of the scaling kernels over n entries.  Box (and the resampling filters): a workgroup per column tile and row (the kernels stride over
+// rows beyond the grid's y extent); nearest: a lane per 4 x 4 pixels of the largest output
+struct LaunchShape { dim3 block, grid; };
+LaunchShape box_grid(int tiles, int rows, size_t n) { return {dim3(256), dim3(tiles, std::min(rows, 65535), (unsigned)n)}; }
+LaunchShape nearest_grid(int ow, int oh, size_t n) { return {dim3(64, 4), dim3(((ow + 3) / 4 + 63) / 64, std::min((oh + 3) / 4, 16384), (unsigned)n)}; }
+// HIPDEC_SCALE_BOX: `box` over box_grid(tiles, rows, n); otherwise `nearest` over nearest_grid(ow, oh, n)
+template <typename Box, typename Nearest, typename Arg>
+void launch_box_or_nearest(int filter, Box box, Nearest nearest, int tiles, int rows, int ow, int oh, size_t n, hipStream_t s, const Arg& arg)
+{
+  const LaunchShape g = filter == HIPDEC_SCALE_BOX ? box_grid(tiles, rows, n) : nearest_grid(ow, oh, n);
+  if (filter == HIPDEC_SCALE_BOX) hipLaunchKernelGGL(box, g.grid, g.block, 0, s, arg);
+  else hipLaunchKernelGGL(nearest, g.grid, g.block, 0, s, arg);
+}
+
+// A grid's z extent is 65535: entries [first, end) go out in as few launches as that allows.  launch(first, n) issues one (non-zero: its refusal ends the
+// loop); a launch that fails is reported as "<what>: <error>", one that went out is counted in *launches
+template <typename F>
+int launch_z_chunks(size_t first, size_t end, const char* what, std::atomic<uint64_t>* launches, F&& launch)
+{
+  for (; first < end; first += 65535) {
+    if (int rc = launch(first, end - first < 65535 ? end - first : (size_t)65535)) return rc;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hipdec::set_error(HIPDEC_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+    if (launches) ++*launches;
+  }
+  return 0;
 }
 
 template <typename Pix, int LAYOUT>
@@ -1873,7 +1952,7 @@ int launch_rgb_scaled(const ColorParams& p, hipStream_t s)
   const int filter = t_scale.filter;
   t_scale.on = false;   // taken
   if (t_capture) { t_captured_scaled.push_back(CapturedScaled{sp, (int)sizeof(Pix) * 16 + LAYOUT, filter}); return 0; }
-  launch_scaled_grid<Pix, LAYOUT>(&sp, nullptr, 1, filter, sp.ow, sp.oh, (sp.ow + sp.tile - 1) / sp.tile, s);
+  launch_box_or_nearest(filter, k_scale_rgb_box<Pix, LAYOUT>, k_scale_rgb_nearest<Pix, LAYOUT>, (sp.ow + sp.tile - 1) / sp.tile, sp.oh, sp.ow, sp.oh, 1, s, sp);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hipdec::set_error(HIPDEC_ERR_DEVICE, "scaled colour kernel launch: %s", hipGetErrorString(e));
   return 0;
@@ -2003,19 +2082,7 @@ int color_capture_take(ColorBatchState& st, hipStream_t s, const void** dev, int
   if (caps.empty()) return 0;
   bool same = true;
   for (const auto& c : caps) same = same && c.variant == caps[0].variant;
-  const size_t bytes = caps.size() * sizeof(ColorParams);
-  std::vector<uint8_t> host(bytes);
-  for (size_t i = 0; i < caps.size(); i++) memcpy(host.data() + i * sizeof(ColorParams), &caps[i].p, sizeof(ColorParams));
-  if (st.dev_bytes < bytes) {
-    if (st.dev) arena_release(st.dev, st.dev_bytes);
-    st.dev = nullptr; st.dev_bytes = 0; st.host.clear();
-    HIPDEC_CHECK_HIP(arena_acquire(&st.dev, bytes, &st.dev_bytes));
-  }
-  if (st.host != host) {
-    st.prev.swap(st.host);   // (not freed while its copy may be pending)
-    st.host.swap(host);
-    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), bytes, hipMemcpyHostToDevice, s));
-  }
+  if (int rc = blocks_of_captured(caps, st, s)) return rc;
   *dev = st.dev;
   if (same) *uniform_variant = caps[0].variant;
   return 0;
@@ -2044,19 +2111,7 @@ int color_capture_launch(ColorBatchState& st, hipStream_t s)
     }
     return 0;
   }
-  const size_t bytes = caps.size() * sizeof(ColorParams);
-  std::vector<uint8_t> host(bytes);
-  for (size_t i = 0; i < caps.size(); i++) memcpy(host.data() + i * sizeof(ColorParams), &caps[i].p, sizeof(ColorParams));
-  if (st.dev_bytes < bytes) {   // from the arena pool: hipFree() would synchronise the device every time a batch is retired
-    if (st.dev) arena_release(st.dev, st.dev_bytes);
-    st.dev = nullptr; st.dev_bytes = 0; st.host.clear();
-    HIPDEC_CHECK_HIP(arena_acquire(&st.dev, bytes, &st.dev_bytes));
-  }
-  if (st.host != host) {   // steady state (same planes, same outputs): nothing to upload
-    st.prev.swap(st.host);   // (not freed while its copy may be pending)
-    st.host.swap(host);
-    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), bytes, hipMemcpyHostToDevice, s));
-  }
+  if (int rc = blocks_of_captured(caps, st, s)) return rc;
   const ColorParams* dev = (const ColorParams*)st.dev;
   switch (caps[0].variant) {
 #define X(id, Pix, LO) case id: launch_rgb_batch<Pix, LO>(dev, (int)caps.size(), max_w, max_h, s); break;
@@ -2090,22 +2145,11 @@ int color_capture_launch_scaled(ColorBatchState& st, int filter, hipStream_t s)
     const int tiles = (c.p.ow + c.p.tile - 1) / c.p.tile;
     max_tiles = tiles > max_tiles ? tiles : max_tiles;
   }
-  const size_t bytes = caps.size() * sizeof(ScaledParams);
-  std::vector<uint8_t> host(bytes);
-  for (size_t i = 0; i < caps.size(); i++) memcpy(host.data() + i * sizeof(ScaledParams), &caps[i].p, sizeof(ScaledParams));
-  if (st.dev_bytes < bytes) {
-    if (st.dev) arena_release(st.dev, st.dev_bytes);
-    st.dev = nullptr; st.dev_bytes = 0; st.host.clear();
-    HIPDEC_CHECK_HIP(arena_acquire(&st.dev, bytes, &st.dev_bytes));
-  }
-  if (st.host != host) {   // steady state (same planes, sizes and outputs): nothing to upload
-    st.prev.swap(st.host);
-    st.host.swap(host);
-    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), bytes, hipMemcpyHostToDevice, s));
-  }
+  if (int rc = blocks_of_captured(caps, st, s)) return rc;
   const ScaledParams* dev = (const ScaledParams*)st.dev;
   switch (caps[0].variant) {
-#define X(id, Pix, LO) case id: launch_scaled_grid<Pix, LO>(nullptr, dev, (int)caps.size(), filter, max_ow, max_oh, max_tiles, s); break;
+#define X(id, Pix, LO) \
+  case id: launch_box_or_nearest(filter, k_scale_rgb_box_batch<Pix, LO>, k_scale_rgb_nearest_batch<Pix, LO>, max_tiles, max_oh, max_ow, max_oh, caps.size(), s, dev); break;
     HIPDEC_RGB_SCALED_VARIANTS(X)
 #undef X
     default: return set_error(HIPDEC_ERR_UNSUPPORTED, "scaled colour batch: unknown kernel variant");
@@ -2122,34 +2166,7 @@ void color_tensor_begin() { t_captured_tensor.clear(); }
 void color_tensor_abort() { t_captured_tensor.clear(); t_tensor.on = false; }
 
 namespace {
-template <typename Pix, int DT>
-void launch_tensor_grid(const TensorParams* dev, int n, int filter, int ow, int oh, int tiles, hipStream_t s)
-{
-  if (filter == HIPDEC_SCALE_BOX) {
-    dim3 block(256), grid(tiles, oh < 65535 ? oh : 65535, n);
-    hipLaunchKernelGGL((k_tensor_box<Pix, DT>), grid, block, 0, s, dev);
-  } else {
-    const int gy = (oh + 3) / 4;
-    dim3 block(64, 4), grid(((ow + 3) / 4 + 63) / 64, gy < 16384 ? gy : 16384, n);
-    hipLaunchKernelGGL((k_tensor_nearest<Pix, DT>), grid, block, 0, s, dev);
-  }
-}
-
 std::atomic<uint64_t> g_oriented_launches{0}, g_oriented_entries{0}, g_oriented_quarter{0};
-
-// ow x oh: the largest DISPLAYED size among the entries (nearest); gy_box / tiles: the most row blocks and column tiles an entry has (box)
-template <typename Pix, int DT>
-void launch_oriented_grid(const OrientedParams* dev, int n, int filter, int ow, int oh, int gy_box, int tiles, hipStream_t s)
-{
-  if (filter == HIPDEC_SCALE_BOX) {
-    dim3 block(256), grid(tiles, gy_box < 65535 ? gy_box : 65535, n);
-    hipLaunchKernelGGL((k_oriented_box<Pix, DT>), grid, block, 0, s, dev);
-  } else {
-    const int gy = (oh + 3) / 4;
-    dim3 block(64, 4), grid(((ow + 3) / 4 + 63) / 64, gy < 16384 ? gy : 16384, n);
-    hipLaunchKernelGGL((k_oriented_nearest<Pix, DT>), grid, block, 0, s, dev);
-  }
-}
 
 // the blocked store's constants of an entry (PatchInfo above): its displayed width is a multiple of patch * merge
 PatchInfo patch_info_of(const CapturedTensor& c)
@@ -2164,19 +2181,6 @@ PatchInfo patch_info_of(const CapturedTensor& c)
   b.pxs = c.p.nhwc ? 3u : 1u; b.chs = c.p.nhwc ? 1u : Tp * P * P; b.prow = P * b.pxs;
   b.rowtok = (uint64_t)(dw / P / m) * (uint64_t)b.tokm;
   return b;
-}
-
-template <typename Pix, int DT>
-void launch_patch_grid(const PatchParams* dev, int n, int filter, int ow, int oh, int gy_box, int tiles, hipStream_t s)
-{
-  if (filter == HIPDEC_SCALE_BOX) {
-    dim3 block(256), grid(tiles, gy_box < 65535 ? gy_box : 65535, n);
-    hipLaunchKernelGGL((k_patch_box<Pix, DT>), grid, block, 0, s, dev);
-  } else {
-    const int gy = (oh + 3) / 4;
-    dim3 block(64, 4), grid(((ow + 3) / 4 + 63) / 64, gy < 16384 ? gy : 16384, n);
-    hipLaunchKernelGGL((k_patch_nearest<Pix, DT>), grid, block, 0, s, dev);
-  }
 }
 
 std::atomic<uint64_t> g_packed_calls{0}, g_packed_entries{0}, g_packed_patch_entries{0};
@@ -2222,53 +2226,30 @@ int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
       memcpy(host.data() + i * block_bytes + offsetof(PatchParams, b), &b, sizeof(b));
     }
   }
-  if (st.dev_bytes < bytes) {
-    if (st.dev) arena_release(st.dev, st.dev_bytes);
-    st.dev = nullptr; st.dev_bytes = 0; st.host.clear();
-    HIPDEC_CHECK_HIP(arena_acquire(&st.dev, bytes, &st.dev_bytes));
-  }
-  if (st.host != host) {   // steady state (same windows, codes and output): nothing to upload
-    st.prev.swap(st.host);
-    st.host.swap(host);
-    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), bytes, hipMemcpyHostToDevice, s));
-  }
-  for (size_t first = 0; first < n_clip; first += 65535) {
+  if (int rc = blocks_reserve(st, bytes)) return rc;
+  if (int rc = blocks_upload(st, host, s)) return rc;
+  const int wide = caps[0].wide;
+  int rc = launch_z_chunks(0, n_clip, "clip kernel launch", &g_oriented_launches, [&](size_t first, size_t n) {
     const OrientedParams* dev = (const OrientedParams*)st.dev + first;
-    dim3 block(256), grid(clip_tiles, clip_oh < 65535 ? clip_oh : 65535, (unsigned)(n_clip - first < 65535 ? n_clip - first : 65535));
-    switch (caps[0].wide * 4 + dtype) {
-#define X(DT) case DT: hipLaunchKernelGGL((k_clip_box<uint8_t, DT>), grid, block, 0, s, dev); break; \
-              case 4 + DT: hipLaunchKernelGGL((k_clip_box<uint16_t, DT>), grid, block, 0, s, dev); break;
-      X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
-#undef X
-      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "clip output: unknown dtype %d", dtype);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "clip kernel launch: %s", hipGetErrorString(e));
-    g_oriented_launches++;
-  }
+    const LaunchShape g = box_grid(clip_tiles, clip_oh, n);
+    if (dispatch_pix_dtype(wide, dtype, [&](auto pix, auto dt) {
+          hipLaunchKernelGGL((k_clip_box<typename decltype(pix)::type, decltype(dt)::value>), g.grid, g.block, 0, s, dev);
+        })) return 0;
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "clip output: unknown dtype %d", dtype);
+  });
+  if (rc) return rc;
   g_clip_box_entries += (uint64_t)n_clip;
-  for (size_t first = n_clip; first < caps.size(); first += 65535) {
-    const OrientedParams* dev = (const OrientedParams*)st.dev + first;
-    const PatchParams* pdev = (const PatchParams*)st.dev + first;
-    const int n = (int)(caps.size() - first < 65535 ? caps.size() - first : 65535);
-    if (blocked) switch (caps[0].wide * 4 + dtype) {
-#define X(DT) case DT: launch_patch_grid<uint8_t, DT>(pdev, n, filter, max_dw, max_dh, max_blocks, max_tiles, s); break; \
-              case 4 + DT: launch_patch_grid<uint16_t, DT>(pdev, n, filter, max_dw, max_dh, max_blocks, max_tiles, s); break;
-      X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
-#undef X
-      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "oriented output: unknown dtype %d", dtype);
-    }
-    else switch (caps[0].wide * 4 + dtype) {
-#define X(DT) case DT: launch_oriented_grid<uint8_t, DT>(dev, n, filter, max_dw, max_dh, max_blocks, max_tiles, s); break; \
-              case 4 + DT: launch_oriented_grid<uint16_t, DT>(dev, n, filter, max_dw, max_dh, max_blocks, max_tiles, s); break;
-      X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
-#undef X
-      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "oriented output: unknown dtype %d", dtype);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "oriented kernel launch: %s", hipGetErrorString(e));
-    g_oriented_launches++;
-  }
+  // box: the most column tiles and row blocks an entry has; nearest: the largest DISPLAYED size among the entries
+  rc = launch_z_chunks(n_clip, caps.size(), "oriented kernel launch", &g_oriented_launches, [&](size_t first, size_t n) {
+    if (dispatch_pix_dtype(wide, dtype, [&](auto pix, auto dt) {
+          typedef typename decltype(pix)::type Pix;
+          constexpr int DT = decltype(dt)::value;
+          if (blocked) launch_box_or_nearest(filter, k_patch_box<Pix, DT>, k_patch_nearest<Pix, DT>, max_tiles, max_blocks, max_dw, max_dh, n, s, (const PatchParams*)st.dev + first);
+          else launch_box_or_nearest(filter, k_oriented_box<Pix, DT>, k_oriented_nearest<Pix, DT>, max_tiles, max_blocks, max_dw, max_dh, n, s, (const OrientedParams*)st.dev + first);
+        })) return 0;
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "oriented output: unknown dtype %d", dtype);
+  });
+  if (rc) return rc;
   g_oriented_entries += (uint64_t)caps.size(); g_oriented_quarter += quarter;
   return 0;
 }
@@ -2276,19 +2257,6 @@ int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
 // HIPDEC_SCALE_BILINEAR / _BICUBIC: the recorded blocks with their coefficient tables as ONE launch of k_resample.  The tables of a call are deduplicated by
 // (input samples, output samples) - the filter is the call's - and travel behind the parameter blocks in the same buffer, so ONE asynchronous copy brings
 // both to the device and the staging memory is kept as the other launches keep theirs (st.host, st.prev).
-template <typename Pix, int DT>
-void launch_resample_grid(const ResampleParams* dev, int n, int tiles, int bands, hipStream_t s)
-{
-  dim3 block(256), grid(tiles, bands < 65535 ? bands : 65535, n);
-  hipLaunchKernelGGL((k_resample<Pix, DT>), grid, block, 0, s, dev);
-}
-template <typename Pix, int DT>
-void launch_patch_resample_grid(const PatchResampleParams* dev, int n, int tiles, int bands, hipStream_t s)
-{
-  dim3 block(256), grid(tiles, bands < 65535 ? bands : 65535, n);
-  hipLaunchKernelGGL((k_patch_resample<Pix, DT>), grid, block, 0, s, dev);
-}
-
 int resample_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int filter, int dtype, hipStream_t s)
 {
   std::map<std::pair<int, int>, uint64_t> where;   // axis -> the table's first int
@@ -2315,11 +2283,7 @@ int resample_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
   const size_t bytes = params_bytes + (size_t)ints * sizeof(int32_t);
   std::vector<uint8_t> host(bytes);
   for (const auto& w : where) resample_table_fill(w.first.first, w.first.second, filter, (int32_t*)(host.data() + params_bytes) + w.second);
-  if (st.dev_bytes < bytes) {
-    if (st.dev) arena_release(st.dev, st.dev_bytes);
-    st.dev = nullptr; st.dev_bytes = 0; st.host.clear();
-    HIPDEC_CHECK_HIP(arena_acquire(&st.dev, bytes, &st.dev_bytes));
-  }
+  if (int rc = blocks_reserve(st, bytes)) return rc;   // (the blocks below hold addresses inside it)
   const int32_t* tables_dev = (const int32_t*)((const uint8_t*)st.dev + params_bytes);
   for (size_t i = 0; i < caps.size(); i++) {
     const CapturedTensor& c = caps[i];
@@ -2334,33 +2298,19 @@ int resample_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
       memcpy(host.data() + i * block_bytes + offsetof(PatchResampleParams, b), &b, sizeof(b));
     }
   }
-  if (st.host != host) {   // steady state (same windows, sizes, codes and output): nothing to upload
-    st.prev.swap(st.host);
-    st.host.swap(host);
-    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), bytes, hipMemcpyHostToDevice, s));
-  }
-  for (size_t first = 0; first < caps.size(); first += 65535) {
-    const ResampleParams* dev = (const ResampleParams*)st.dev + first;
-    const PatchResampleParams* pdev = (const PatchResampleParams*)st.dev + first;
-    const int n = (int)(caps.size() - first < 65535 ? caps.size() - first : 65535);
-    if (blocked) switch (caps[0].wide * 4 + dtype) {
-#define X(DT) case DT: launch_patch_resample_grid<uint8_t, DT>(pdev, n, max_tiles, max_bands, s); break; \
-              case 4 + DT: launch_patch_resample_grid<uint16_t, DT>(pdev, n, max_tiles, max_bands, s); break;
-      X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
-#undef X
-      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "resampled output: unknown dtype %d", dtype);
-    }
-    else switch (caps[0].wide * 4 + dtype) {
-#define X(DT) case DT: launch_resample_grid<uint8_t, DT>(dev, n, max_tiles, max_bands, s); break; \
-              case 4 + DT: launch_resample_grid<uint16_t, DT>(dev, n, max_tiles, max_bands, s); break;
-      X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
-#undef X
-      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "resampled output: unknown dtype %d", dtype);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "resample kernel launch: %s", hipGetErrorString(e));
-    if (caps[0].oriented) g_oriented_launches++;
-  }
+  if (int rc = blocks_upload(st, host, s)) return rc;
+  const int wide = caps[0].wide;
+  const int rc = launch_z_chunks(0, caps.size(), "resample kernel launch", caps[0].oriented ? &g_oriented_launches : nullptr, [&](size_t first, size_t n) {
+    const LaunchShape g = box_grid(max_tiles, max_bands, n);
+    if (dispatch_pix_dtype(wide, dtype, [&](auto pix, auto dt) {
+          typedef typename decltype(pix)::type Pix;
+          constexpr int DT = decltype(dt)::value;
+          if (blocked) hipLaunchKernelGGL((k_patch_resample<Pix, DT>), g.grid, g.block, 0, s, (const PatchResampleParams*)st.dev + first);
+          else hipLaunchKernelGGL((k_resample<Pix, DT>), g.grid, g.block, 0, s, (const ResampleParams*)st.dev + first);
+        })) return 0;
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "resampled output: unknown dtype %d", dtype);
+  });
+  if (rc) return rc;
   if (caps[0].oriented) { g_oriented_entries += (uint64_t)caps.size(); g_oriented_quarter += quarter; }
   return 0;
 }
@@ -2380,34 +2330,17 @@ int color_tensor_launch(ColorBatchState& st, int filter, int dtype, hipStream_t 
     const int tiles = (c.p.ow + c.p.tile - 1) / c.p.tile;
     max_tiles = tiles > max_tiles ? tiles : max_tiles;
   }
-  const size_t bytes = caps.size() * sizeof(TensorParams);
-  std::vector<uint8_t> host(bytes);
-  for (size_t i = 0; i < caps.size(); i++) memcpy(host.data() + i * sizeof(TensorParams), &caps[i].p, sizeof(TensorParams));
-  if (st.dev_bytes < bytes) {
-    if (st.dev) arena_release(st.dev, st.dev_bytes);
-    st.dev = nullptr; st.dev_bytes = 0; st.host.clear();
-    HIPDEC_CHECK_HIP(arena_acquire(&st.dev, bytes, &st.dev_bytes));
-  }
-  if (st.host != host) {   // steady state (same windows, same output): nothing to upload
-    st.prev.swap(st.host);
-    st.host.swap(host);
-    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), bytes, hipMemcpyHostToDevice, s));
-  }
-  const int ow = caps[0].p.ow, oh = caps[0].p.oh;
-  for (size_t first = 0; first < caps.size(); first += 65535) {
+  if (int rc = blocks_of_captured(caps, st, s)) return rc;
+  const int ow = caps[0].p.ow, oh = caps[0].p.oh, wide = caps[0].wide;
+  return launch_z_chunks(0, caps.size(), "tensor kernel launch", nullptr, [&](size_t first, size_t n) {
     const TensorParams* dev = (const TensorParams*)st.dev + first;
-    const int n = (int)(caps.size() - first < 65535 ? caps.size() - first : 65535);
-    switch (caps[0].wide * 4 + dtype) {
-#define X(DT) case DT: launch_tensor_grid<uint8_t, DT>(dev, n, filter, ow, oh, max_tiles, s); break; \
-              case 4 + DT: launch_tensor_grid<uint16_t, DT>(dev, n, filter, ow, oh, max_tiles, s); break;
-      X(TD_U8) X(TD_F32) X(TD_F16) X(TD_BF16)
-#undef X
-      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor output: unknown dtype %d", dtype);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "tensor kernel launch: %s", hipGetErrorString(e));
-  }
-  return 0;
+    if (dispatch_pix_dtype(wide, dtype, [&](auto pix, auto dt) {
+          typedef typename decltype(pix)::type Pix;
+          constexpr int DT = decltype(dt)::value;
+          launch_box_or_nearest(filter, k_tensor_box<Pix, DT>, k_tensor_nearest<Pix, DT>, max_tiles, oh, ow, oh, n, s, dev);
+        })) return 0;
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor output: unknown dtype %d", dtype);
+  });
 }
 
 // ---- placed tensor output: the margins (and masks) of all entries of a call as ONE launch of k_canvas_margin; the blocks are kept and re-uploaded only
@@ -2431,35 +2364,18 @@ int canvas_margin_launch(ColorBatchState& st, const CanvasMargin* blocks, int n,
   const size_t bytes = (size_t)n * sizeof(CanvasMargin);
   std::vector<uint8_t> host(bytes);
   memcpy(host.data(), blocks, bytes);
-  if (st.dev_bytes < bytes) {
-    if (st.dev) arena_release(st.dev, st.dev_bytes);
-    st.dev = nullptr; st.dev_bytes = 0; st.host.clear();
-    HIPDEC_CHECK_HIP(arena_acquire(&st.dev, bytes, &st.dev_bytes));
-  }
-  if (st.host != host) {   // steady state (same rectangles, fill and output): nothing to upload
-    st.prev.swap(st.host);
-    st.host.swap(host);
-    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.dev, st.host.data(), bytes, hipMemcpyHostToDevice, s));
-  }
+  if (int rc = blocks_reserve(st, bytes)) return rc;
+  if (int rc = blocks_upload(st, host, s)) return rc;
   // a lane owns one 16-byte block at a time: an entry touches at most elements / (elements per block) + 2 of them (the kernel's loop strides over what the
   // grid leaves; a mask has fewer)
   const uint64_t per = dtype == TD_U8 ? 16 : (dtype == TD_F32 ? 4 : 8);
   const uint64_t gx = (max_elems / per + 2 + 255) / 256;
-  for (int first = 0; first < n; first += 65535) {
+  return launch_z_chunks(0, (size_t)n, "margin kernel launch", &g_placed_margin_launches, [&](size_t first, size_t count) {
     const CanvasMargin* dev = (const CanvasMargin*)st.dev + first;
-    dim3 block(256), grid((unsigned)(gx < 65536 ? gx : 65536), 1, (unsigned)(n - first < 65535 ? n - first : 65535));
-    switch (dtype) {
-      case TD_U8: hipLaunchKernelGGL((k_canvas_margin<TD_U8>), grid, block, 0, s, dev); break;
-      case TD_F32: hipLaunchKernelGGL((k_canvas_margin<TD_F32>), grid, block, 0, s, dev); break;
-      case TD_F16: hipLaunchKernelGGL((k_canvas_margin<TD_F16>), grid, block, 0, s, dev); break;
-      case TD_BF16: hipLaunchKernelGGL((k_canvas_margin<TD_BF16>), grid, block, 0, s, dev); break;
-      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "placed output: unknown dtype %d", dtype);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "margin kernel launch: %s", hipGetErrorString(e));
-    g_placed_margin_launches++;
-  }
-  return 0;
+    dim3 block(256), grid((unsigned)(gx < 65536 ? gx : 65536), 1, (unsigned)count);
+    if (dispatch_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((k_canvas_margin<decltype(dt)::value>), grid, block, 0, s, dev); })) return 0;
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "placed output: unknown dtype %d", dtype);
+  });
 }
 
 // ---- warped tensor output: what the arguments alone decide, the per-entry table, ONE launch of k_warp_* for all entries of a call
@@ -2544,14 +2460,8 @@ int warp_launch(WarpState& st, const void* src_dev, const hipdec_warp_desc* w, c
   if (w->filter == HIPDEC_SCALE_NEAREST) for (int e = 0; e < n; e++) n_tables += warp_scale_only(maps[e].m) ? 1 : 0;
   const size_t table_ints = (size_t)ow + (size_t)oh, bytes = (size_t)n * sizeof(WarpEntry) + n_tables * table_ints * sizeof(int32_t);
   std::vector<uint8_t> host(bytes);
-  if (st.table.dev_bytes < bytes) {
-    if (int rc = warp_state_order(st, s, true)) return rc;
-    if (st.table.dev) arena_release(st.table.dev, st.table.dev_bytes);
-    st.table.dev = nullptr; st.table.dev_bytes = 0; st.table.host.clear();
-    HIPDEC_CHECK_HIP(arena_acquire(&st.table.dev, bytes, &st.table.dev_bytes));
-  } else if (int rc = warp_state_order(st, s, false)) {
-    return rc;
-  }
+  if (int rc = warp_state_order(st, s, st.table.dev_bytes < bytes)) return rc;
+  if (int rc = blocks_reserve(st.table, bytes)) return rc;   // (the entries below hold addresses inside it)
   const uint8_t* dev_tables = (const uint8_t*)st.table.dev + (size_t)n * sizeof(WarpEntry);
   int32_t* host_tables = (int32_t*)(host.data() + (size_t)n * sizeof(WarpEntry));
   size_t t = 0;
@@ -2579,11 +2489,7 @@ int warp_launch(WarpState& st, const void* src_dev, const hipdec_warp_desc* w, c
     for (int c = 0; c < 3; c++) E.value[c] = fill ? fill->value[c] : 0.0f;
     memcpy(host.data() + (size_t)e * sizeof(WarpEntry), &E, sizeof(E));
   }
-  if (st.table.host != host) {   // steady state (the same maps, fill, source and output): nothing to upload
-    st.table.prev.swap(st.table.host);
-    st.table.host.swap(host);
-    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.table.dev, st.table.host.data(), bytes, hipMemcpyHostToDevice, s));
-  }
+  if (int rc = blocks_upload(st.table, host, s)) return rc;
   WarpCall c;
   memset(&c, 0, sizeof(c));
   c.sw = sw; c.sh = sh; c.ow = ow; c.oh = oh; c.nhwc = d->layout == HIPDEC_TENSOR_NHWC;
@@ -2592,18 +2498,12 @@ int warp_launch(WarpState& st, const void* src_dev, const hipdec_warp_desc* w, c
   for (int k = 0; k < 3; k++) { c.scale[k] = d->scale[k]; c.bias[k] = d->bias[k]; }
   const WarpEntry* dev = (const WarpEntry*)st.table.dev;
   dim3 block(256), grid((unsigned)((uint64_t)c.tiles * (uint64_t)n));   // (warp_check: below 2^31)
-#define HIPDEC_WARP_LAUNCH(K)                                                                      \
-  switch (d->dtype) {                                                                              \
-    case TD_U8: hipLaunchKernelGGL((K<TD_U8>), grid, block, 0, s, dev, c); break;                  \
-    case TD_F32: hipLaunchKernelGGL((K<TD_F32>), grid, block, 0, s, dev, c); break;                \
-    case TD_F16: hipLaunchKernelGGL((K<TD_F16>), grid, block, 0, s, dev, c); break;                \
-    case TD_BF16: hipLaunchKernelGGL((K<TD_BF16>), grid, block, 0, s, dev, c); break;              \
-    default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_warp: unknown dtype %d", d->dtype); \
-  }
-  if (w->filter == HIPDEC_SCALE_NEAREST) { HIPDEC_WARP_LAUNCH(k_warp_nearest) }
-  else if (w->filter == HIPDEC_SCALE_BILINEAR) { HIPDEC_WARP_LAUNCH(k_warp_bilinear) }
-  else { HIPDEC_WARP_LAUNCH(k_warp_bicubic) }
-#undef HIPDEC_WARP_LAUNCH
+  if (!dispatch_dtype(d->dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (w->filter == HIPDEC_SCALE_NEAREST) hipLaunchKernelGGL((k_warp_nearest<DT>), grid, block, 0, s, dev, c);
+        else if (w->filter == HIPDEC_SCALE_BILINEAR) hipLaunchKernelGGL((k_warp_bilinear<DT>), grid, block, 0, s, dev, c);
+        else hipLaunchKernelGGL((k_warp_bicubic<DT>), grid, block, 0, s, dev, c);
+      })) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_warp: unknown dtype %d", d->dtype);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "warp kernel launch: %s", hipGetErrorString(e));
   if (!st.done) HIPDEC_CHECK_HIP(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
@@ -2686,18 +2586,14 @@ int photo_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p
   const int n_pp = std::min(steps - 1, 2);
   const size_t pp_bytes = ((size_t)n * sample + 255) & ~(size_t)255, hist_bytes = (size_t)max_hist * 4 * 256 * sizeof(uint32_t);
   const size_t work_bytes = (size_t)n_pp * pp_bytes + hist_bytes, bytes = records * sizeof(PhotoEntry);
-  const bool grow_work = st.work_bytes < work_bytes, grow_table = st.base.table.dev_bytes < bytes;
-  if (int rc = warp_state_order(st.base, s, grow_work || grow_table)) return rc;
+  const bool grow_work = st.work_bytes < work_bytes;
+  if (int rc = warp_state_order(st.base, s, grow_work || st.base.table.dev_bytes < bytes)) return rc;
   if (grow_work) {
     if (st.work) arena_release(st.work, st.work_bytes);
     st.work = nullptr; st.work_bytes = 0;
     HIPDEC_CHECK_HIP(arena_acquire(&st.work, work_bytes, &st.work_bytes));
   }
-  if (grow_table) {
-    if (st.base.table.dev) arena_release(st.base.table.dev, st.base.table.dev_bytes);
-    st.base.table.dev = nullptr; st.base.table.dev_bytes = 0; st.base.table.host.clear();
-    HIPDEC_CHECK_HIP(arena_acquire(&st.base.table.dev, bytes, &st.base.table.dev_bytes));
-  }
+  if (int rc = blocks_reserve(st.base.table, bytes)) return rc;
   uint8_t* pp[2] = {(uint8_t*)st.work, (uint8_t*)st.work + pp_bytes};
   uint32_t* hist = (uint32_t*)((uint8_t*)st.work + (size_t)n_pp * pp_bytes);
   std::vector<uint8_t> host(bytes);
@@ -2726,11 +2622,7 @@ int photo_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p
     }
     at += (size_t)n_apply[(size_t)t] + (size_t)n_hist[(size_t)t];
   }
-  if (st.base.table.host != host) {   // steady state (the same chains, source and output): nothing to upload
-    st.base.table.prev.swap(st.base.table.host);
-    st.base.table.host.swap(host);
-    HIPDEC_CHECK_HIP(hipMemcpyAsync(st.base.table.dev, st.base.table.host.data(), bytes, hipMemcpyHostToDevice, s));
-  }
+  if (int rc = blocks_upload(st.base.table, host, s)) return rc;
   PhotoCall c;
   memset(&c, 0, sizeof(c));
   c.w = w; c.h = h; c.nhwc = d->layout == HIPDEC_TENSOR_NHWC;
@@ -2748,13 +2640,8 @@ int photo_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p
       launches++;
     }
     dim3 block(256), grid((unsigned)((uint64_t)c.tiles * (uint64_t)n_apply[(size_t)t]));   // (photo_check: below 2^31)
-    switch (d->dtype) {
-      case TD_U8: hipLaunchKernelGGL((k_photo_apply<TD_U8>), grid, block, 0, s, tab, c); break;
-      case TD_F32: hipLaunchKernelGGL((k_photo_apply<TD_F32>), grid, block, 0, s, tab, c); break;
-      case TD_F16: hipLaunchKernelGGL((k_photo_apply<TD_F16>), grid, block, 0, s, tab, c); break;
-      case TD_BF16: hipLaunchKernelGGL((k_photo_apply<TD_BF16>), grid, block, 0, s, tab, c); break;
-      default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: unknown dtype %d", d->dtype);
-    }
+    if (!dispatch_dtype(d->dtype, [&](auto dt) { hipLaunchKernelGGL((k_photo_apply<decltype(dt)::value>), grid, block, 0, s, tab, c); }))
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: unknown dtype %d", d->dtype);
     launches++;
   }
   hipError_t e = hipGetLastError();
@@ -2794,16 +2681,8 @@ int scale_planes_launch(PlaneScaleParams* jobs, int n, int bytes_per_sample, int
   }
   HIPDEC_CHECK_HIP(hipMemcpyAsync(dev_params, jobs, (size_t)n * sizeof(PlaneScaleParams), hipMemcpyHostToDevice, s));
   const PlaneScaleParams* dev = (const PlaneScaleParams*)dev_params;
-  if (filter == HIPDEC_SCALE_BOX) {
-    dim3 block(256), grid(max_tiles, max_qh < 65535 ? max_qh : 65535, n);
-    if (bytes_per_sample == 1) hipLaunchKernelGGL(k_scale_plane_box<uint8_t>, grid, block, 0, s, dev);
-    else hipLaunchKernelGGL(k_scale_plane_box<uint16_t>, grid, block, 0, s, dev);
-  } else {
-    const int gy = (max_qh + 3) / 4;
-    dim3 block(64, 4), grid(((max_qw + 3) / 4 + 63) / 64, gy < 16384 ? gy : 16384, n);
-    if (bytes_per_sample == 1) hipLaunchKernelGGL(k_scale_plane_nearest<uint8_t>, grid, block, 0, s, dev);
-    else hipLaunchKernelGGL(k_scale_plane_nearest<uint16_t>, grid, block, 0, s, dev);
-  }
+  if (bytes_per_sample == 1) launch_box_or_nearest(filter, k_scale_plane_box<uint8_t>, k_scale_plane_nearest<uint8_t>, max_tiles, max_qh, max_qw, max_qh, n, s, dev);
+  else launch_box_or_nearest(filter, k_scale_plane_box<uint16_t>, k_scale_plane_nearest<uint16_t>, max_tiles, max_qh, max_qw, max_qh, n, s, dev);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "plane scaler launch: %s", hipGetErrorString(e));
   return 0;

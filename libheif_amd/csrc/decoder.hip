@@ -1116,113 +1116,111 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
   });
 }
 
-// ---- warped tensor output (hipdec_batch_to_tensor_warped / hipdec_album_to_tensor_warped): what the two forms share.
+// ---- the two-stage tensor forms (hipdec_batch / hipdec_album _to_tensor_warped and _to_tensor_photo): the existing resize launch writes a U8 / NHWC
+// intermediate into the handle's scratch memory, a stage of color.hip reads it and writes the tensor.  A stage is what differs between the forms:
+//   src_width(), src_height()   the intermediate's size
+//   check(who, d, n)            what the stage's arguments alone decide
+//   depth(who, d, e, bits)      the stage is defined on the 8-bit picture: a float dtype from a source above 8 bits is refused
+//   scratch(b, bytes, s, out)   the intermediate, from the state the batch keeps for the stage
+//   launch(b, src, d, n, out, s)
+struct WarpStage {
+  const hipdec_warp_desc* warp; const hipdec_tensor_map* maps; const hipdec_tensor_fill* fill;
+  int src_width() const { return warp->src_width; }
+  int src_height() const { return warp->src_height; }
+  int check(const char* who, const hipdec_tensor_desc* d, int n) const { return warp_check(who, warp, maps, fill, d, n); }
+  int depth(const char* who, const hipdec_tensor_desc* d, int e, int bits) const
+  {
+    if (bits > 8 && d->dtype != HIPDEC_TENSOR_U8)
+      return set_error(HIPDEC_ERR_UNSUPPORTED, "%s: entry %d: a warp from a %d-bit source is defined for HIPDEC_TENSOR_U8 only (the 8-bit picture is what is warped)", who, e, bits);
+    return 0;
+  }
+  int scratch(hipdec_batch* b, size_t bytes, hipStream_t s, void** out) const { return warp_scratch(b->warp, bytes, s, out); }
+  int launch(hipdec_batch* b, const void* src, const hipdec_tensor_desc* d, int n, void* out_dev, hipStream_t s) const
+  {
+    return warp_launch(b->warp, src, warp, maps, fill, d, n, out_dev, s);
+  }
+};
+
+struct PhotoStage {
+  const hipdec_photo_desc* photo; const hipdec_photo_chain* chains;
+  int src_width() const { return photo->src_width; }
+  int src_height() const { return photo->src_height; }
+  int check(const char* who, const hipdec_tensor_desc* d, int n) const { return photo_check(who, photo, chains, d, n); }
+  int depth(const char* who, const hipdec_tensor_desc* d, int e, int bits) const
+  {
+    if (bits > 8 && d->dtype != HIPDEC_TENSOR_U8)
+      return set_error(HIPDEC_ERR_UNSUPPORTED, "%s: entry %d: the photometric operations on a %d-bit source are defined for HIPDEC_TENSOR_U8 only (they work on the 8-bit picture)", who, e, bits);
+    return 0;
+  }
+  int scratch(hipdec_batch* b, size_t bytes, hipStream_t s, void** out) const { return photo_scratch(b->photo, bytes, s, out); }
+  int launch(hipdec_batch* b, const void* src, const hipdec_tensor_desc* d, int n, void* out_dev, hipStream_t s) const
+  {
+    return photo_launch(b->photo, src, photo, chains, d, n, out_dev, s);
+  }
+};
+
 // What the arguments alone decide; *mid: the description of the U8 / NHWC intermediate, *mid_bytes its size
-int warped_check(const char* who, const hipdec_tensor_desc* desc, const int* orientations, const hipdec_warp_desc* warp, const hipdec_tensor_map* maps,
-                 const hipdec_tensor_fill* fill, int n_entries, const void* out_dev, size_t out_bytes, hipdec_tensor_desc* mid, size_t* mid_bytes)
+template <typename Stage>
+int two_stage_check(const char* who, const Stage& stage, const hipdec_tensor_desc* desc, const int* orientations, int n_entries, const void* out_dev, size_t out_bytes,
+                    hipdec_tensor_desc* mid, size_t* mid_bytes)
 {
   if (!out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
   size_t bytes = 0;
   if (int rc = tensor_check_desc(who, desc, n_entries, &bytes)) return rc;
   if (int rc = check_orientations(who, "entry", orientations, n_entries)) return rc;
-  if (int rc = warp_check(who, warp, maps, fill, desc, n_entries)) return rc;
+  if (int rc = stage.check(who, desc, n_entries)) return rc;
   if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: out_bytes %zu is smaller than the tensor of %zu bytes", who, out_bytes, bytes);
   memset(mid, 0, sizeof(*mid));
-  mid->width = warp->src_width; mid->height = warp->src_height; mid->dtype = HIPDEC_TENSOR_U8; mid->layout = HIPDEC_TENSOR_NHWC; mid->filter = desc->filter;
+  mid->width = stage.src_width(); mid->height = stage.src_height(); mid->dtype = HIPDEC_TENSOR_U8; mid->layout = HIPDEC_TENSOR_NHWC; mid->filter = desc->filter;
   for (int c = 0; c < 3; c++) mid->scale[c] = 1.0f;
   return tensor_check_desc(who, mid, n_entries, mid_bytes);
 }
 
-// the warp stage is defined on the 8-bit picture: a float dtype from a source above 8 bits is refused, as for the Pillow resize filters
-int warped_check_depth(const char* who, const hipdec_tensor_desc* d, int e, int bits)
-{
-  if (bits > 8 && d->dtype != HIPDEC_TENSOR_U8)
-    return set_error(HIPDEC_ERR_UNSUPPORTED, "%s: entry %d: a warp from a %d-bit source is defined for HIPDEC_TENSOR_U8 only (the 8-bit picture is what is warped)", who, e, bits);
-  return 0;
-}
+// what a two-stage form reads from its handle once the arguments alone have passed: the batch that owns the stage's state and whose stream is followed
+// (an album's: its own), the items an entry can name, and the limits
+struct TwoStageSource { hipdec_batch* b; int device, n_items; bool retired; uint64_t max_pixels; };
 
-int batch_to_tensor_warped_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
-                                const hipdec_warp_desc* warp, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill, int n_entries, void* out_dev,
-                                size_t out_bytes, void* stream)
+// source(): the TwoStageSource of the handle; bits(i): the bit depth of the samples item i hands to the colour stage; resize(mid, out, bytes, stream): the
+// handle's oriented tensor form
+template <typename Stage, typename Source, typename Bits, typename Resize>
+int to_tensor_two_stage(const char* who, const void* handle, const Stage& stage, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                        int n_entries, void* out_dev, size_t out_bytes, void* stream, Source source, Bits bits, Resize resize)
 {
-  const char* who = "to_tensor_warped";
-  if (!b) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  if (!handle) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
   hipdec_tensor_desc mid;
   size_t mid_bytes = 0;
-  if (int rc = warped_check(who, desc, orientations, warp, maps, fill, n_entries, out_dev, out_bytes, &mid, &mid_bytes)) return rc;
+  if (int rc = two_stage_check(who, stage, desc, orientations, n_entries, out_dev, out_bytes, &mid, &mid_bytes)) return rc;
   // (everything above is decided without reading the handle)
+  const TwoStageSource S = source();
   for (int e = 0; e < n_entries; e++) {
     const int i = entries ? entries[e].item : e;
-    if (i < 0 || i >= (int)b->pics.size()) continue;   // (the resize stage refuses it)
-    if (int rc = warped_check_depth(who, desc, e, b->wide ? b->pics[i].info.bit_depth_luma : 8)) return rc;
+    if (i < 0 || i >= S.n_items) continue;   // (the resize stage refuses it)
+    if (int rc = stage.depth(who, desc, e, bits(i))) return rc;
   }
-  DeviceScope scope(b->device);
-  if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: the batch's arena was handed to another batch", who);
-  if (b->max_pixels && (uint64_t)desc->width * (uint64_t)desc->height > b->max_pixels)
+  DeviceScope scope(S.device);
+  if (S.retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: the batch's arena was handed to another batch", who);
+  if (S.max_pixels && (uint64_t)desc->width * (uint64_t)desc->height > S.max_pixels)
     return set_error(HIPDEC_ERR_LIMIT, "%s: output of %d x %d pixels exceeds max_image_size_pixels", who, desc->width, desc->height);
   void* scratch = nullptr;
-  if (int rc = guarded(who, [&]() -> int { return warp_scratch(b->warp, mid_bytes, follow_stream(b, stream), &scratch); })) return rc;
-  if (int rc = batch_to_tensor_impl(b, &mid, entries, orientations, true, n_entries, scratch, mid_bytes, stream)) return rc;   // the existing resize launch
+  if (int rc = guarded(who, [&]() -> int { return stage.scratch(S.b, mid_bytes, follow_stream(S.b, stream), &scratch); })) return rc;
+  if (int rc = resize(&mid, scratch, mid_bytes, stream)) return rc;   // the existing resize launch
   return guarded(who, [&]() -> int {
-    hipStream_t s = follow_stream(b, stream);
-    const int rc = warp_launch(b->warp, scratch, warp, maps, fill, desc, n_entries, out_dev, s);
-    b->mark_done(s);
+    hipStream_t s = follow_stream(S.b, stream);
+    const int rc = stage.launch(S.b, scratch, desc, n_entries, out_dev, s);
+    S.b->mark_done(s);
     return rc;
   });
 }
 
-// ---- photometric tensor output (hipdec_batch_to_tensor_photo / hipdec_album_to_tensor_photo): what the two forms share.
-// What the arguments alone decide; *mid: the description of the U8 / NHWC intermediate, *mid_bytes its size
-int photo_form_check(const char* who, const hipdec_tensor_desc* desc, const int* orientations, const hipdec_photo_desc* photo, const hipdec_photo_chain* chains,
-                     int n_entries, const void* out_dev, size_t out_bytes, hipdec_tensor_desc* mid, size_t* mid_bytes)
+template <typename Stage>
+int batch_to_tensor_two_stage(const char* who, hipdec_batch* b, const Stage& stage, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                              int n_entries, void* out_dev, size_t out_bytes, void* stream)
 {
-  if (!out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
-  size_t bytes = 0;
-  if (int rc = tensor_check_desc(who, desc, n_entries, &bytes)) return rc;
-  if (int rc = check_orientations(who, "entry", orientations, n_entries)) return rc;
-  if (int rc = photo_check(who, photo, chains, desc, n_entries)) return rc;
-  if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: out_bytes %zu is smaller than the tensor of %zu bytes", who, out_bytes, bytes);
-  memset(mid, 0, sizeof(*mid));
-  mid->width = photo->src_width; mid->height = photo->src_height; mid->dtype = HIPDEC_TENSOR_U8; mid->layout = HIPDEC_TENSOR_NHWC; mid->filter = desc->filter;
-  for (int c = 0; c < 3; c++) mid->scale[c] = 1.0f;
-  return tensor_check_desc(who, mid, n_entries, mid_bytes);
-}
-
-// the stage is defined on the 8-bit picture: a float dtype from a source above 8 bits is refused, as for the warp
-int photo_check_depth(const char* who, const hipdec_tensor_desc* d, int e, int bits)
-{
-  if (bits > 8 && d->dtype != HIPDEC_TENSOR_U8)
-    return set_error(HIPDEC_ERR_UNSUPPORTED, "%s: entry %d: the photometric operations on a %d-bit source are defined for HIPDEC_TENSOR_U8 only (they work on the 8-bit picture)", who, e, bits);
-  return 0;
-}
-
-int batch_to_tensor_photo_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
-                               const hipdec_photo_desc* photo, const hipdec_photo_chain* chains, int n_entries, void* out_dev, size_t out_bytes, void* stream)
-{
-  const char* who = "to_tensor_photo";
-  if (!b) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
-  hipdec_tensor_desc mid;
-  size_t mid_bytes = 0;
-  if (int rc = photo_form_check(who, desc, orientations, photo, chains, n_entries, out_dev, out_bytes, &mid, &mid_bytes)) return rc;
-  // (everything above is decided without reading the handle)
-  for (int e = 0; e < n_entries; e++) {
-    const int i = entries ? entries[e].item : e;
-    if (i < 0 || i >= (int)b->pics.size()) continue;   // (the resize stage refuses it)
-    if (int rc = photo_check_depth(who, desc, e, b->wide ? b->pics[i].info.bit_depth_luma : 8)) return rc;
-  }
-  DeviceScope scope(b->device);
-  if (b->retired) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: the batch's arena was handed to another batch", who);
-  if (b->max_pixels && (uint64_t)desc->width * (uint64_t)desc->height > b->max_pixels)
-    return set_error(HIPDEC_ERR_LIMIT, "%s: output of %d x %d pixels exceeds max_image_size_pixels", who, desc->width, desc->height);
-  void* scratch = nullptr;
-  if (int rc = guarded(who, [&]() -> int { return photo_scratch(b->photo, mid_bytes, follow_stream(b, stream), &scratch); })) return rc;
-  if (int rc = batch_to_tensor_impl(b, &mid, entries, orientations, true, n_entries, scratch, mid_bytes, stream)) return rc;   // the existing resize launch
-  return guarded(who, [&]() -> int {
-    hipStream_t s = follow_stream(b, stream);
-    const int rc = photo_launch(b->photo, scratch, photo, chains, desc, n_entries, out_dev, s);
-    b->mark_done(s);
-    return rc;
-  });
+  return to_tensor_two_stage(
+      who, b, stage, desc, entries, orientations, n_entries, out_dev, out_bytes, stream,
+      [&]() { return TwoStageSource{b, b->device, (int)b->pics.size(), b->retired, b->max_pixels}; },
+      [&](int i) { return b->wide ? b->pics[i].info.bit_depth_luma : 8; },
+      [&](const hipdec_tensor_desc* mid, void* out, size_t bytes, void* st) { return batch_to_tensor_impl(b, mid, entries, orientations, true, n_entries, out, bytes, st); });
 }
 
 // what the RGB forms of the oriented output decide for one picture from the arguments alone (before a device is touched)
@@ -1330,13 +1328,13 @@ int hipdec_batch_to_tensor_warped(hipdec_batch* b, const hipdec_tensor_desc* des
                                   const hipdec_warp_desc* warp, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill, int n_entries, void* out_dev,
                                   size_t out_bytes, void* stream)
 {
-  return batch_to_tensor_warped_impl(b, desc, entries, orientations, warp, maps, fill, n_entries, out_dev, out_bytes, stream);
+  return batch_to_tensor_two_stage("to_tensor_warped", b, WarpStage{warp, maps, fill}, desc, entries, orientations, n_entries, out_dev, out_bytes, stream);
 }
 
 int hipdec_batch_to_tensor_photo(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
                                  const hipdec_photo_desc* photo, const hipdec_photo_chain* chains, int n_entries, void* out_dev, size_t out_bytes, void* stream)
 {
-  return batch_to_tensor_photo_impl(b, desc, entries, orientations, photo, chains, n_entries, out_dev, out_bytes, stream);
+  return batch_to_tensor_two_stage("to_tensor_photo", b, PhotoStage{photo, chains}, desc, entries, orientations, n_entries, out_dev, out_bytes, stream);
 }
 
 int hipdec_batch_to_tensor_packed(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,

@@ -376,6 +376,18 @@ int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const 
     return rc;
   });
 }
+
+// the album forms of batch_to_tensor_two_stage: the stage's tables, intermediate and work memory are those of the album's batch
+template <typename Stage>
+int album_to_tensor_two_stage(const char* who, hipdec_album* a, const Stage& stage, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                              int n_entries, void* out_dev, size_t out_bytes, void* stream)
+{
+  return to_tensor_two_stage(
+      who, a, stage, desc, entries, orientations, n_entries, out_dev, out_bytes, stream,
+      [&]() { return TwoStageSource{a->batch.get(), a->device, (int)a->photos.size(), false, a->max_pixels}; },
+      [&](int p) { const RgbSource S = album_source(a, p); return S.wide ? S.info->bit_depth_luma : 8; },
+      [&](const hipdec_tensor_desc* mid, void* out, size_t bytes, void* st) { return album_to_tensor_impl(a, mid, entries, orientations, true, n_entries, out, bytes, st); });
+}
 }  // namespace
 
 extern "C" {
@@ -407,69 +419,17 @@ int hipdec_album_to_tensor_packed(hipdec_album* a, const hipdec_tensor_desc* des
   return album_to_tensor_impl(a, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, nullptr, &ps);
 }
 
-// the album form of batch_to_tensor_warped_impl: the table and the intermediate are those of the album's batch
 int hipdec_album_to_tensor_warped(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
                                   const hipdec_warp_desc* warp, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill, int n_entries, void* out_dev,
                                   size_t out_bytes, void* stream)
 {
-  const char* who = "album_to_tensor_warped";
-  if (!a) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
-  hipdec_tensor_desc mid;
-  size_t mid_bytes = 0;
-  if (int rc = warped_check(who, desc, orientations, warp, maps, fill, n_entries, out_dev, out_bytes, &mid, &mid_bytes)) return rc;
-  // (everything above is decided without reading the handle)
-  const int n_photos = (int)a->photos.size();
-  for (int e = 0; e < n_entries; e++) {
-    const int p = entries ? entries[e].item : e;
-    if (p < 0 || p >= n_photos) continue;   // (the resize stage refuses it)
-    const RgbSource S = album_source(a, p);
-    if (int rc = warped_check_depth(who, desc, e, S.wide ? S.info->bit_depth_luma : 8)) return rc;
-  }
-  DeviceScope scope(a->device);
-  if (a->max_pixels && (uint64_t)desc->width * (uint64_t)desc->height > a->max_pixels)
-    return set_error(HIPDEC_ERR_LIMIT, "%s: output of %d x %d pixels exceeds max_image_size_pixels", who, desc->width, desc->height);
-  hipdec_batch* b = a->batch.get();
-  void* scratch = nullptr;
-  if (int rc = guarded(who, [&]() -> int { return warp_scratch(b->warp, mid_bytes, follow_stream(b, stream), &scratch); })) return rc;
-  if (int rc = album_to_tensor_impl(a, &mid, entries, orientations, true, n_entries, scratch, mid_bytes, stream)) return rc;   // the existing resize launch
-  return guarded(who, [&]() -> int {
-    hipStream_t s = follow_stream(b, stream);
-    const int rc = warp_launch(b->warp, scratch, warp, maps, fill, desc, n_entries, out_dev, s);
-    b->mark_done(s);
-    return rc;
-  });
+  return album_to_tensor_two_stage("album_to_tensor_warped", a, WarpStage{warp, maps, fill}, desc, entries, orientations, n_entries, out_dev, out_bytes, stream);
 }
 
-// the album form of batch_to_tensor_photo_impl: the tables, the intermediate and the work memory are those of the album's batch
 int hipdec_album_to_tensor_photo(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
                                  const hipdec_photo_desc* photo, const hipdec_photo_chain* chains, int n_entries, void* out_dev, size_t out_bytes, void* stream)
 {
-  const char* who = "album_to_tensor_photo";
-  if (!a) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
-  hipdec_tensor_desc mid;
-  size_t mid_bytes = 0;
-  if (int rc = photo_form_check(who, desc, orientations, photo, chains, n_entries, out_dev, out_bytes, &mid, &mid_bytes)) return rc;
-  // (everything above is decided without reading the handle)
-  const int n_photos = (int)a->photos.size();
-  for (int e = 0; e < n_entries; e++) {
-    const int p = entries ? entries[e].item : e;
-    if (p < 0 || p >= n_photos) continue;   // (the resize stage refuses it)
-    const RgbSource S = album_source(a, p);
-    if (int rc = photo_check_depth(who, desc, e, S.wide ? S.info->bit_depth_luma : 8)) return rc;
-  }
-  DeviceScope scope(a->device);
-  if (a->max_pixels && (uint64_t)desc->width * (uint64_t)desc->height > a->max_pixels)
-    return set_error(HIPDEC_ERR_LIMIT, "%s: output of %d x %d pixels exceeds max_image_size_pixels", who, desc->width, desc->height);
-  hipdec_batch* b = a->batch.get();
-  void* scratch = nullptr;
-  if (int rc = guarded(who, [&]() -> int { return photo_scratch(b->photo, mid_bytes, follow_stream(b, stream), &scratch); })) return rc;
-  if (int rc = album_to_tensor_impl(a, &mid, entries, orientations, true, n_entries, scratch, mid_bytes, stream)) return rc;   // the existing resize launch
-  return guarded(who, [&]() -> int {
-    hipStream_t s = follow_stream(b, stream);
-    const int rc = photo_launch(b->photo, scratch, photo, chains, desc, n_entries, out_dev, s);
-    b->mark_done(s);
-    return rc;
-  });
+  return album_to_tensor_two_stage("album_to_tensor_photo", a, PhotoStage{photo, chains}, desc, entries, orientations, n_entries, out_dev, out_bytes, stream);
 }
 
 int hipdec_album_to_rgb_scaled_oriented_all(hipdec_album* a, int out_chroma, const int* orientations, const int* out_widths, const int* out_heights, int filter,
