@@ -24,6 +24,8 @@
  *                                                     threshold (0 for the last three); after --orient / --filter, not with --warp or --patches
  *   ./decode_batch --tensor 224 item0.hevc ...        ends in ONE launch that writes a float16 N x 3 x 224 x 224 tensor: the centred square of every item,
  *                                                     area-averaged, (V / 255 - mean) / std with the usual ImageNet constants
+ *   ./decode_batch --thumb 256 --hue 43 --blur 1.5 item0.hevc    the previews through Pillow's hue shift (D of 0 .. 255 added to H of convert("HSV")) and / or
+ *                                                     PIL.ImageFilter.GaussianBlur(RADIUS), RADIUS 0 .. 8, bit for bit (hipdec_batch_to_tensor_augmented)
  *   ./decode_batch --album 16 6x8 tile0.hevc ...      the items are TILES: 16 grid photos of 6 x 8 tiles (tile t of photo k is item (k * 48 + t) mod n; the
  *                                                     output is the whole tiled area) composed by ONE launch set and ONE paste launch; prints Mpixel/s
  */
@@ -136,8 +138,17 @@ int main(int argc, char** argv)
     if (!photo || argc < 4 || end == argv[3] || *end) argc = 0;    /* no or an unknown OP, no or a bad VALUE: usage (the library checks the value's range) */
     else { argv += 3; argc -= 3; }
   }
+  int augment = 0;                                                /* --hue D and / or --blur RADIUS: a chain of the augment stage, in that order */
+  double hue = -1.0, blur = -1.0;
+  while (thumb && !warp && !photo && argc >= 2 && (!strcmp(argv[1], "--hue") || !strcmp(argv[1], "--blur"))) {
+    char* end = NULL;
+    const double v = argc >= 3 ? strtod(argv[2], &end) : 0.0;
+    if (argc < 3 || end == argv[2] || *end) { argc = 0; break; }  /* no or a bad value: usage (the library checks the range) */
+    if (!strcmp(argv[1], "--hue")) hue = v; else blur = v;
+    augment = 1; argv += 2; argc -= 2;
+  }
   int patch = 0, merge = 1;
-  if (thumb && !warp && !photo && argc >= 2 && !strcmp(argv[1], "--patches")) {
+  if (thumb && !warp && !photo && !augment && argc >= 2 && !strcmp(argv[1], "--patches")) {
     char tail = 0;
     const int got = argc >= 3 ? sscanf(argv[2], "%d:%d%c", &patch, &merge, &tail) : 0;
     if ((got != 1 && got != 2) || patch < 1 || patch > 256 || merge < 1 || merge > 16) argc = 0;   /* no or a bad P[:M]: usage */
@@ -149,7 +160,7 @@ int main(int argc, char** argv)
     if (tensor < 1) argc = 0;
     else { argv += 2; argc -= 2; }
   }
-  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] [--warp ANGLE | --photo OP VALUE | --patches P[:M]] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] [--warp ANGLE | --photo OP VALUE | [--hue D] [--blur RADIUS] | --patches P[:M]] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
   const int n = argc - 1;
   const void** data = (const void**)calloc((size_t)n, sizeof(void*));
   size_t* sizes = (size_t*)calloc((size_t)n, sizeof(size_t));
@@ -267,6 +278,20 @@ int main(int argc, char** argv)
         memset(&chain, 0, sizeof chain);
         chain.n_ops = 1; chain.ops[0].op = photo; chain.ops[0].value = photo_value;
         rc = hipdec_batch_to_tensor_photo(prev, &d, &e, codes + i, &pd, &chain, 1, outs[i], strides[i] * (size_t)hs[i], NULL);
+      }
+    } else if (augment) {                                          /* and one augmented call per preview: hue, then Gaussian blur, as Pillow does them */
+      for (int i = 0; i < n && !rc; i++) {
+        hipdec_tensor_desc d;
+        memset(&d, 0, sizeof d);
+        d.width = ws[i]; d.height = hs[i]; d.dtype = HIPDEC_TENSOR_U8; d.layout = HIPDEC_TENSOR_NHWC; d.filter = filter;
+        for (int c = 0; c < 3; c++) d.scale[c] = 1.0f;
+        const hipdec_tensor_entry e = {i, 0, 0, 0, 0, 0};
+        const hipdec_photo_desc pd = {ws[i], hs[i], {0, 0}};
+        hipdec_augment_chain chain;
+        memset(&chain, 0, sizeof chain);
+        if (hue >= 0.0) { chain.ops[chain.n_ops].op = HIPDEC_AUGMENT_HUE; chain.ops[chain.n_ops++].value = hue; }
+        if (blur >= 0.0) { chain.ops[chain.n_ops].op = HIPDEC_AUGMENT_GAUSSIAN_BLUR; chain.ops[chain.n_ops++].value = blur; }
+        rc = hipdec_batch_to_tensor_augmented(prev, &d, &e, codes + i, &pd, &chain, 1, outs[i], strides[i] * (size_t)hs[i], NULL);
       }
     } else {
       rc = orient < 0 ? hipdec_batch_to_rgb_scaled_all(prev, 10, ws, hs, filter, (void* const*)outs, strides, NULL)

@@ -915,8 +915,8 @@ HIPDEC_API void hipdec_warp_stats(uint64_t* calls, uint64_t* entries);
  * named: n_ops outside 0 .. HIPDEC_PHOTO_MAX_OPS; an unknown op; a non-zero `reserved`; a value that is not finite or has |value| > 65536; POSTERIZE with a
  * value that is not an integer 0 .. 8; and for the call: src_width or src_height < 1 or >= 32768, a desc size that is not the source size, an unknown dtype
  * or layout, a non-finite scale or bias, src_bytes or out_bytes too small, more than 2^31 - 1 tiles (64 x 16 pixels).
- * Not part of it: hue (Pillow's HSV round trip); gamma; Gaussian blur; autocontrast cutoffs and masks; a photometric and a warp step inside one call;
- * parameter samplers; a clips entry point. */
+ * Not part of it: gamma; autocontrast cutoffs and masks; a photometric and a warp step inside one call; parameter samplers; a clips entry point.  Hue,
+ * Gaussian blur and chains of more than four operations are the augment stage below (hipdec_tensor_augment). */
 #define HIPDEC_PHOTO_MAX_OPS 4
 typedef enum hipdec_photo_opcode {
   HIPDEC_PHOTO_BRIGHTNESS = 1, HIPDEC_PHOTO_COLOR = 2, HIPDEC_PHOTO_CONTRAST = 3, HIPDEC_PHOTO_SHARPNESS = 4, HIPDEC_PHOTO_POSTERIZE = 5,
@@ -946,6 +946,75 @@ HIPDEC_API int hipdec_album_to_tensor_photo(hipdec_album* a, const hipdec_tensor
                                             void* stream);
 /* counters since load: photo calls that wrote anything, the entries they wrote, and the launches of k_photo_hist and k_photo_apply together */
 HIPDEC_API void hipdec_photo_stats(uint64_t* calls, uint64_t* entries, uint64_t* launches);
+
+/* ---- augmented tensor output: the photo stage's operations plus Pillow-exact hue and Gaussian blur, chains of up to eight --------------------------------
+ * The self-supervised and contrastive recipes (SimCLR, MoCo v2 / v3, BYOL, SwAV, DINO / iBOT / DINOv2) are ColorJitter(brightness, contrast, saturation,
+ * hue) -> RandomGrayscale -> PIL.ImageFilter.GaussianBlur(radius) -> Solarize per crop: up to seven steps, two of which the photo stage does not have.  The
+ * augment stage is the photo stage with those two operations and chains of up to HIPDEC_AUGMENT_MAX_OPS.  Bit-equal to Pillow, no tolerance.
+ *
+ * THE STAGE (hipdec_tensor_augment).  As hipdec_tensor_photo, word for word: S is a sample of h x w x 3 bytes, the operations of chains[e] are applied in
+ * order, each to the 8-bit result of the one before it, an empty chain is the identity; the float stage, dtypes, layouts, src_dev / src_bytes, n == 0, and
+ * desc's size being the source size are the photo stage's; U8 / NHWC output chains with hipdec_tensor_warp, hipdec_tensor_photo and this call.  Opcodes
+ * 1 .. 9 are hipdec_photo_opcode with exactly the photo stage's definitions, value checks and refusals: a chain of at most HIPDEC_PHOTO_MAX_OPS of them
+ * gives hipdec_tensor_photo's bytes.  The two further operations:
+ *  HIPDEC_AUGMENT_HUE (value: the shift d, an integer 0 .. 255)   per pixel (H, S, V) = rgb2hsv(R, G, B); H' = (H + d) & 255; hsv2rgb(H', S, V) -
+ *    convert("HSV"), a uint8 wrap-around add on H, convert("RGB"): what torchvision's PIL adjust_hue does with d = (int)(hue_factor * 255) mod 256.
+ *    rgb2hsv: mx, mn the greatest and least component; V = mx.  mx == mn: H = S = 0.  Otherwise, in float unless a double constant is written:
+ *      cr = (float)(mx - mn); s = cr / (float)mx; rc = (float)(mx - R) / cr, gc and bc alike;
+ *      R == mx: h = bc - gc;  else G == mx: h = (float)(2.0 + (double)rc - (double)bc);  else h = (float)(4.0 + (double)gc - (double)rc);
+ *      h = (float)fmod((double)h / 6.0 + 1.0, 1.0);  H = clip8((int)((double)h * 255.0)), S = clip8((int)((double)s * 255.0)).
+ *    hsv2rgb: S == 0: R = G = B = V.  Otherwise hf = (double)(float)H * 6.0 / 255.0; i = (int)floor(hf); f = (float)(hf - (double)(float)i);
+ *      fs = (float)((double)S / 255.0); with round() half away from zero and every result clipped to 0 .. 255:
+ *      p = round(V * (1.0 - (double)fs)); q = round(V * (1.0 - (double)(fs * f))) - the product fs * f in float -;
+ *      t = round(V * (1.0 - (double)fs * (1.0 - (double)f))) - all in double -;
+ *      (R, G, B) by i % 6: 0 (V, t, p); 1 (q, V, p); 2 (p, V, t); 3 (p, q, V); 4 (t, p, V); 5 (V, p, q).  (H = 255 gives i = 6: case 0.)
+ *    Single-precision divisions are correctly rounded, one rounding per written operation (no fast-math, -ffp-contract=off).
+ *  HIPDEC_AUGMENT_GAUSSIAN_BLUR (value: Pillow's radius rho, 0 <= rho <= HIPDEC_AUGMENT_BLUR_MAX_RADIUS)   ImageFilter.GaussianBlur(rho): three extended box
+ *    blurs along rows, then three along columns, of all three channels, each pass on the 8-bit result of the one before.  The box (hipdec_gaussian_box), in
+ *    single precision with one rounding per operation: sigma2 = rho * rho / 3; L = (float)sqrt(12.0 * (double)sigma2 + 1.0);
+ *      l = (float)floor(((double)L - 1.0) / 2.0); a = (2 l + 1) * (l * (l + 1) - 3 * sigma2); a = a / (6 * (sigma2 - (l + 1) * (l + 1))); fr = l + a;
+ *      r = (int)fr; ww = (uint32)((float)(1 << 24) / (fr * 2 + 1)); fw = ((1 << 24) - (2 r + 1) * ww) / 2.
+ *    One pass over a line of n samples, c(i) = min(max(i, 0), n - 1), in 32-bit unsigned arithmetic:
+ *      out[x] = (ww * (in[c(x - r)] + .. + in[c(x + r)]) + fw * (in[c(x - r - 1)] + in[c(x + r + 1)]) + (1 << 23)) >> 24.
+ *    rho = 0 is the identity; the cap gives r <= 7.
+ *
+ * THE DECODE-SIDE FORMS (hipdec_batch_to_tensor_augmented, hipdec_album_to_tensor_augmented): as the _photo forms - sample e of the intermediate is what
+ * hipdec_batch_to_tensor_oriented writes for entry e as U8 / NHWC of size src_width x src_height with desc->filter; an empty chain for every entry gives
+ * that call's bytes; a float dtype from a source above 8 bits is HIPDEC_ERR_UNSUPPORTED; the intermediate and the work memory come from the library's
+ * device pool and stay with the handle.
+ *
+ * Launches: the existing resize launch (decode-side forms); then per chain step at most ONE launch each of k_photo_hist, k_photo_apply, k_augment_hue and
+ * k_augment_blur, each over the entries whose operation at that step is of its kind (an empty chain's identity step is k_photo_apply's): at most
+ * 4 * HIPDEC_AUGMENT_MAX_OPS, whatever the number of entries.  Chains are aligned at their first operation.  The blur's six passes are one launch: a
+ * workgroup stages its 64 x 32 tile and a halo of 3 (r + 1) pixels in LDS and no intermediate goes through memory; entries of one launch may have
+ * different radii.  Asynchronous on `stream`.  hipdec_photo_stats does not move for these calls.
+ * Refused with HIPDEC_ERR_INVALID_ARGUMENT before anything is launched and before a device is touched, `out_dev` untouched, the entry and the operation
+ * named: what hipdec_tensor_photo refuses (with HIPDEC_AUGMENT_MAX_OPS for the chain length); an op other than 1 .. 9, 16, 17 ("unknown op"); HUE with a
+ * value that is not an integer 0 .. 255; GAUSSIAN_BLUR with a radius that is not finite, negative or above the cap; more than 2^31 - 1 tiles.
+ * Not part of it: per-axis radii, BoxBlur, UnsharpMask; torchvision's tensor-path GaussianBlur(kernel_size, sigma), a different filter; gamma; parameter
+ * samplers and the random order of ColorJitter's steps (the caller orders the chain); a warp step inside the chain; a clips entry point. */
+#define HIPDEC_AUGMENT_MAX_OPS 8
+#define HIPDEC_AUGMENT_HUE 16            /* value: integer shift d, 0 .. 255 */
+#define HIPDEC_AUGMENT_GAUSSIAN_BLUR 17  /* value: Pillow's radius, 0 <= radius <= HIPDEC_AUGMENT_BLUR_MAX_RADIUS */
+#define HIPDEC_AUGMENT_BLUR_MAX_RADIUS 8.0
+typedef struct hipdec_augment_chain {
+  int n_ops;                   /* 0 .. HIPDEC_AUGMENT_MAX_OPS */
+  int reserved;                /* 0 */
+  hipdec_photo_op ops[HIPDEC_AUGMENT_MAX_OPS];   /* op: hipdec_photo_opcode, HIPDEC_AUGMENT_HUE or HIPDEC_AUGMENT_GAUSSIAN_BLUR */
+} hipdec_augment_chain;
+HIPDEC_API int hipdec_tensor_augment(const void* src_dev, size_t src_bytes, const hipdec_photo_desc* photo, const hipdec_augment_chain* chains,
+                                     const hipdec_tensor_desc* desc, int n, void* out_dev, size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_batch_to_tensor_augmented(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                                const hipdec_photo_desc* photo, const hipdec_augment_chain* chains, int n_entries, void* out_dev,
+                                                size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_album_to_tensor_augmented(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                                const hipdec_photo_desc* photo, const hipdec_augment_chain* chains, int n_entries, void* out_dev,
+                                                size_t out_bytes, void* stream);
+/* counters since load: augment calls that wrote anything, the entries they wrote, and all kernel launches of the stage */
+HIPDEC_API void hipdec_augment_stats(uint64_t* calls, uint64_t* entries, uint64_t* launches);
+/* host only: the box GAUSSIAN_BLUR runs three times along each axis for `radius` - what the blur kernel receives.  0, or -1 (radius not finite, negative
+ * or above the cap; a NULL output) */
+HIPDEC_API int hipdec_gaussian_box(double radius, int* r, uint32_t* ww, uint32_t* fw);
 
 /* counters since load: images through hipdec_image_transform, grid canvases handed out by hipdec_grid_read_plane_tracked (hipdec_image_scale counts in
  * hipdec_image_scale_stats) */

@@ -20,7 +20,9 @@
 #include "warp_host.h"
 #define PHOTO_FN __host__ __device__ inline
 #include "photo_lut.h"
+#include "augment_lut.h"
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -1208,6 +1210,8 @@ __global__ __launch_bounds__(256) void k_canvas_margin(const hipdec::CanvasMargi
 
 // ---- photometric tensor output (include/heif_hipdec.h hipdec_tensor_photo): k_photo_hist, k_photo_apply
 #include "photo_kernels.h"
+// ---- augment stage (include/heif_hipdec.h hipdec_tensor_augment): k_augment_hue, k_augment_blur beside the photo stage's kernels
+#include "augment_kernels.h"
 
 // the plane scalers: blockIdx.z selects the plane (all planes of an image, or of all items of a batch, are ONE launch)
 // ---- Pillow's bilinear / bicubic resampling of 8-bit pictures (HIPDEC_SCALE_BILINEAR / _BICUBIC, include/heif_hipdec.h), bit for bit: two separable passes
@@ -2519,12 +2523,16 @@ static_assert(HIPDEC_PHOTO_SAME(BRIGHTNESS) && HIPDEC_PHOTO_SAME(COLOR) && HIPDE
               HIPDEC_PHOTO_SAME(POSTERIZE) && HIPDEC_PHOTO_SAME(SOLARIZE) && HIPDEC_PHOTO_SAME(INVERT) && HIPDEC_PHOTO_SAME(AUTOCONTRAST) &&
               HIPDEC_PHOTO_SAME(EQUALIZE), "photo_lut.h restates hipdec_photo_opcode");
 #undef HIPDEC_PHOTO_SAME
+static_assert((int)HIPDEC_AUGMENT_HUE == (int)AUGMENT_HUE && (int)HIPDEC_AUGMENT_GAUSSIAN_BLUR == (int)AUGMENT_GAUSSIAN_BLUR &&
+              HIPDEC_AUGMENT_BLUR_MAX_RADIUS == kAugmentBlurMaxRadius, "augment_lut.h restates the augment opcodes and the cap");
 std::atomic<uint64_t> g_photo_calls{0}, g_photo_entries{0}, g_photo_launches{0};
+std::atomic<uint64_t> g_augment_calls{0}, g_augment_entries{0}, g_augment_launches{0};
 
-int photo_check(const char* who, const hipdec_photo_desc* p, const hipdec_photo_chain* chains, const hipdec_tensor_desc* d, int n)
+// the photo stage's checks, and the augment stage's: the chain length and the operations a view admits are what differs
+int chain_check(const char* who, const hipdec_photo_desc* p, const ChainView& chains, const hipdec_tensor_desc* d, int n)
 {
   static const char* const names[] = {"none", "BRIGHTNESS", "COLOR", "CONTRAST", "SHARPNESS", "POSTERIZE", "SOLARIZE", "INVERT", "AUTOCONTRAST", "EQUALIZE"};
-  if (!p || (!chains && n > 0)) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  if (!p || (!chains.base && n > 0)) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
   if (p->src_width < 1 || p->src_height < 1 || p->src_width >= 32768 || p->src_height >= 32768)
     return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: source size %d x %d (1 .. 32767 each way)", who, p->src_width, p->src_height);
   if (p->reserved[0] || p->reserved[1]) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: photo.reserved is not 0", who);
@@ -2532,18 +2540,21 @@ int photo_check(const char* who, const hipdec_photo_desc* p, const hipdec_photo_
     return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: the tensor's size %d x %d is not the source size %d x %d (the stage does not resize)", who, d->width, d->height,
                      p->src_width, p->src_height);
   for (int e = 0; e < n; e++) {
-    const hipdec_photo_chain& ch = chains[e];
-    if (ch.n_ops < 0 || ch.n_ops > HIPDEC_PHOTO_MAX_OPS) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: n_ops is %d (0 .. %d)", who, e, ch.n_ops, HIPDEC_PHOTO_MAX_OPS);
-    if (ch.reserved) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: chain.reserved is %d, not 0", who, e, ch.reserved);
-    for (int k = 0; k < ch.n_ops; k++) {
-      const hipdec_photo_op& o = ch.ops[k];
-      const char* name = o.op >= PHOTO_BRIGHTNESS && o.op <= PHOTO_EQUALIZE ? names[o.op] : "unknown";
-      switch (photo_op_check(o.op, o.reserved, o.value)) {
+    const int n_ops = chains.n_ops(e);
+    if (n_ops < 0 || n_ops > chains.max_ops) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: n_ops is %d (0 .. %d)", who, e, n_ops, chains.max_ops);
+    if (chains.reserved(e)) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: chain.reserved is %d, not 0", who, e, chains.reserved(e));
+    for (int k = 0; k < n_ops; k++) {
+      const hipdec_photo_op& o = chains.op(e, k);
+      const char* name = o.op >= PHOTO_BRIGHTNESS && o.op <= PHOTO_EQUALIZE ? names[o.op]
+                         : (chains.augment && o.op == AUGMENT_HUE ? "HUE" : (chains.augment && o.op == AUGMENT_GAUSSIAN_BLUR ? "GAUSSIAN_BLUR" : "unknown"));
+      switch (chains.augment ? augment_op_check(o.op, o.reserved, o.value) : photo_op_check(o.op, o.reserved, o.value)) {
         case 0: break;
         case 1: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d: unknown op %d", who, e, k, o.op);
         case 2: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (%s): reserved is %d, not 0", who, e, k, name, o.reserved);
         case 3: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (%s): the value is not finite", who, e, k, name);
         case 4: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (%s): the value %g has a magnitude above 65536", who, e, k, name, o.value);
+        case 6: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (%s): the shift %g is not an integer 0 .. 255", who, e, k, name, o.value);
+        case 7: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (%s): the radius %g is not 0 .. %g", who, e, k, name, o.value, kAugmentBlurMaxRadius);
         default: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (%s): %g bits (an integer 0 .. 8)", who, e, k, name, o.value);
       }
     }
@@ -2563,28 +2574,40 @@ void photo_state_free(PhotoState& st)
   st.work = nullptr; st.work_bytes = 0;
 }
 
-int photo_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p, const hipdec_photo_chain* chains, const hipdec_tensor_desc* d, int n,
-                 void* out_dev, hipStream_t s)
+namespace {
+enum ChainKind { KIND_APPLY = 0, KIND_HIST = 1, KIND_HUE = 2, KIND_BLUR = 3, KIND_COUNT = 4 };   // a step's records, in this order
+inline int chain_kind(int op) { return op == AUGMENT_HUE ? KIND_HUE : (op == AUGMENT_GAUSSIAN_BLUR ? KIND_BLUR : KIND_APPLY); }
+}
+
+int chain_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p, const ChainView& chains, const hipdec_tensor_desc* d, int n, void* out_dev,
+                 hipStream_t s)
 {
   if (n <= 0) return 0;
   const int w = p->src_width, h = p->src_height;
   const size_t sample = (size_t)w * (size_t)h * 3, out_entry = sample * (d->dtype == TD_U8 ? 1 : (d->dtype == TD_F32 ? 4 : 2));
   // Chains are aligned at their first step: entry e takes part in steps 0 .. max(n_ops, 1) - 1, and its last step writes the tensor (an empty chain is
-  // one identity step).  Step t of the call is the launches of all entries that have a step t.
+  // one identity step).  Step t of the call is the launches of all entries that have a step t: per kind - apply, histogram, hue, blur - one launch over
+  // the compacted records of the entries whose operation at t is of that kind (a histogram record goes with the apply record of the same entry).
   int steps = 1;
-  for (int e = 0; e < n; e++) steps = std::max(steps, chains[e].n_ops);
-  std::vector<int> n_apply((size_t)steps, 0), n_hist((size_t)steps, 0);
+  for (int e = 0; e < n; e++) steps = std::max(steps, chains.n_ops(e));
+  std::vector<std::array<int, KIND_COUNT>> count((size_t)steps, std::array<int, KIND_COUNT>{0, 0, 0, 0});
+  std::vector<int> blur_r((size_t)steps, 0);   // the step's largest box radius
   for (int e = 0; e < n; e++)
-    for (int t = 0; t < std::max(chains[e].n_ops, 1); t++) {
-      n_apply[(size_t)t]++;
-      if (chains[e].n_ops && photo_needs_statistics(chains[e].ops[t].op)) n_hist[(size_t)t]++;
+    for (int t = 0; t < std::max(chains.n_ops(e), 1); t++) {
+      const int op = chains.n_ops(e) ? chains.op(e, t).op : PHOTO_NONE;
+      count[(size_t)t][chain_kind(op)]++;
+      if (photo_needs_statistics(op)) count[(size_t)t][KIND_HIST]++;
     }
   size_t records = 0;
   int max_hist = 0;
-  for (int t = 0; t < steps; t++) { records += (size_t)n_apply[(size_t)t] + (size_t)n_hist[(size_t)t]; max_hist = std::max(max_hist, n_hist[(size_t)t]); }
+  for (int t = 0; t < steps; t++) {
+    for (int k = 0; k < KIND_COUNT; k++) records += (size_t)count[(size_t)t][k];
+    max_hist = std::max(max_hist, count[(size_t)t][KIND_HIST]);
+  }
   // the work memory: up to two ping-pong buffers of n samples, then the histograms of the step with the most of them
   const int n_pp = std::min(steps - 1, 2);
   const size_t pp_bytes = ((size_t)n * sample + 255) & ~(size_t)255, hist_bytes = (size_t)max_hist * 4 * 256 * sizeof(uint32_t);
+  static_assert(sizeof(PhotoEntry) == sizeof(AugmentEntry), "a step's records share one table");
   const size_t work_bytes = (size_t)n_pp * pp_bytes + hist_bytes, bytes = records * sizeof(PhotoEntry);
   const bool grow_work = st.work_bytes < work_bytes;
   if (int rc = warp_state_order(st.base, s, grow_work || st.base.table.dev_bytes < bytes)) return rc;
@@ -2597,30 +2620,48 @@ int photo_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p
   uint8_t* pp[2] = {(uint8_t*)st.work, (uint8_t*)st.work + pp_bytes};
   uint32_t* hist = (uint32_t*)((uint8_t*)st.work + (size_t)n_pp * pp_bytes);
   std::vector<uint8_t> host(bytes);
-  std::vector<size_t> first((size_t)steps);   // the step's first record: its apply records, then its histogram records
+  std::vector<size_t> first((size_t)steps);   // the step's first record: its apply records, then its histogram, hue and blur records
   size_t at = 0;
   for (int t = 0; t < steps; t++) {
     first[(size_t)t] = at;
+    const std::array<int, KIND_COUNT>& cnt = count[(size_t)t];
     PhotoEntry* apply = (PhotoEntry*)host.data() + at;
-    PhotoEntry* stat = apply + n_apply[(size_t)t];
-    int ia = 0, ih = 0;
+    PhotoEntry* stat = apply + cnt[KIND_APPLY];
+    AugmentEntry* hue = (AugmentEntry*)(stat + cnt[KIND_HIST]);
+    AugmentEntry* blur = hue + cnt[KIND_HUE];
+    int ia = 0, ih = 0, iu = 0, ib = 0;
     for (int e = 0; e < n; e++) {
-      const int len = std::max(chains[e].n_ops, 1);
+      const int len = std::max(chains.n_ops(e), 1);
       if (t >= len) continue;
-      PhotoEntry E;
-      memset(&E, 0, sizeof(E));
-      E.src = t == 0 ? (const uint8_t*)src_dev + (size_t)e * sample : pp[(t - 1) & 1] + (size_t)e * sample;
-      E.last = t == len - 1;
-      E.dst = E.last ? (uint8_t*)out_dev + (size_t)e * out_entry : pp[t & 1] + (size_t)e * sample;
-      E.op = chains[e].n_ops ? chains[e].ops[t].op : PHOTO_NONE;
-      E.value = chains[e].n_ops ? chains[e].ops[t].value : 0.0;
-      if (photo_needs_statistics(E.op)) {
-        E.hist = hist + (size_t)ih * 4 * 256;
-        stat[ih++] = E;
+      const uint8_t* src = t == 0 ? (const uint8_t*)src_dev + (size_t)e * sample : pp[(t - 1) & 1] + (size_t)e * sample;
+      const int last = t == len - 1;
+      uint8_t* dst = last ? (uint8_t*)out_dev + (size_t)e * out_entry : pp[t & 1] + (size_t)e * sample;
+      const int op = chains.n_ops(e) ? chains.op(e, t).op : PHOTO_NONE;
+      const double value = chains.n_ops(e) ? chains.op(e, t).value : 0.0;
+      if (chain_kind(op) == KIND_APPLY) {
+        PhotoEntry E;
+        memset(&E, 0, sizeof(E));
+        E.src = src; E.dst = dst; E.last = last; E.op = op; E.value = value;
+        if (photo_needs_statistics(E.op)) {
+          E.hist = hist + (size_t)ih * 4 * 256;
+          stat[ih++] = E;
+        }
+        apply[ia++] = E;
+      } else {
+        AugmentEntry E;
+        memset(&E, 0, sizeof(E));
+        E.src = src; E.dst = dst; E.last = last; E.op = op;
+        if (op == AUGMENT_HUE) {
+          E.shift = (int32_t)value;
+          hue[iu++] = E;
+        } else {
+          augment_gaussian_box(value, &E.r, &E.ww, &E.fw);
+          blur_r[(size_t)t] = std::max(blur_r[(size_t)t], (int)E.r);
+          blur[ib++] = E;
+        }
       }
-      apply[ia++] = E;
     }
-    at += (size_t)n_apply[(size_t)t] + (size_t)n_hist[(size_t)t];
+    for (int k = 0; k < KIND_COUNT; k++) at += (size_t)cnt[k];
   }
   if (int rc = blocks_upload(st.base.table, host, s)) return rc;
   PhotoCall c;
@@ -2630,26 +2671,55 @@ int photo_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p
   c.tiles = c.tiles_x * (uint32_t)((h + kWarpTR - 1) / kWarpTR);
   c.slices = (uint32_t)((h + kPhotoHistRows - 1) / kPhotoHistRows);
   for (int k = 0; k < 3; k++) { c.scale[k] = d->scale[k]; c.bias[k] = d->bias[k]; }
+  BlurCall bc;
+  memset(&bc, 0, sizeof(bc));
+  bc.p = c;
+  bc.tiles_x = (uint32_t)((w + kBlurTC - 1) / kBlurTC);
+  bc.tiles = bc.tiles_x * (uint32_t)((h + kBlurTR - 1) / kBlurTR);
   const PhotoEntry* dev = (const PhotoEntry*)st.base.table.dev;
   uint64_t launches = 0;
-  for (int t = 0; t < steps; t++) {
+  bool known = true;
+  for (int t = 0; t < steps && known; t++) {
+    const std::array<int, KIND_COUNT>& cnt = count[(size_t)t];
     const PhotoEntry* tab = dev + first[(size_t)t];
-    if (n_hist[(size_t)t]) {
-      HIPDEC_CHECK_HIP(hipMemsetAsync(hist, 0, (size_t)n_hist[(size_t)t] * 4 * 256 * sizeof(uint32_t), s));
-      hipLaunchKernelGGL(k_photo_hist, dim3((unsigned)((uint64_t)c.slices * (uint64_t)n_hist[(size_t)t])), dim3(256), 0, s, tab + n_apply[(size_t)t], c);
+    const AugmentEntry* hue = (const AugmentEntry*)(tab + cnt[KIND_APPLY] + cnt[KIND_HIST]);
+    const AugmentEntry* blur = hue + cnt[KIND_HUE];
+    dim3 block(256);
+    if (cnt[KIND_HIST]) {
+      HIPDEC_CHECK_HIP(hipMemsetAsync(hist, 0, (size_t)cnt[KIND_HIST] * 4 * 256 * sizeof(uint32_t), s));
+      hipLaunchKernelGGL(k_photo_hist, dim3((unsigned)((uint64_t)c.slices * (uint64_t)cnt[KIND_HIST])), block, 0, s, tab + cnt[KIND_APPLY], c);
       launches++;
     }
-    dim3 block(256), grid((unsigned)((uint64_t)c.tiles * (uint64_t)n_apply[(size_t)t]));   // (photo_check: below 2^31)
-    if (!dispatch_dtype(d->dtype, [&](auto dt) { hipLaunchKernelGGL((k_photo_apply<decltype(dt)::value>), grid, block, 0, s, tab, c); }))
-      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: unknown dtype %d", d->dtype);
-    launches++;
+    if (cnt[KIND_APPLY]) {
+      dim3 grid((unsigned)((uint64_t)c.tiles * (uint64_t)cnt[KIND_APPLY]));   // (chain_check: below 2^31)
+      known = dispatch_dtype(d->dtype, [&](auto dt) { hipLaunchKernelGGL((k_photo_apply<decltype(dt)::value>), grid, block, 0, s, tab, c); });
+      launches++;
+    }
+    if (known && cnt[KIND_HUE]) {
+      dim3 grid((unsigned)((uint64_t)c.tiles * (uint64_t)cnt[KIND_HUE]));
+      known = dispatch_dtype(d->dtype, [&](auto dt) { hipLaunchKernelGGL((k_augment_hue<decltype(dt)::value>), grid, block, 0, s, hue, c); });
+      launches++;
+    }
+    if (known && cnt[KIND_BLUR]) {
+      dim3 grid((unsigned)((uint64_t)bc.tiles * (uint64_t)cnt[KIND_BLUR]));   // (fewer than the 64 x 16 tiles chain_check bounds)
+      const int rmax = blur_r[(size_t)t];
+      known = dispatch_dtype(d->dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (rmax <= 1) hipLaunchKernelGGL((k_augment_blur<DT, 1>), grid, block, 0, s, blur, bc);
+        else if (rmax <= 3) hipLaunchKernelGGL((k_augment_blur<DT, 3>), grid, block, 0, s, blur, bc);
+        else hipLaunchKernelGGL((k_augment_blur<DT, kAugmentBlurMaxR>), grid, block, 0, s, blur, bc);
+      });
+      launches++;
+    }
   }
+  if (!known) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown dtype %d", chains.augment ? "tensor_augment" : "tensor_photo", d->dtype);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "photo kernel launch: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "%s kernel launch: %s", chains.augment ? "augment" : "photo", hipGetErrorString(e));
   if (!st.base.done) HIPDEC_CHECK_HIP(hipEventCreateWithFlags(&st.base.done, hipEventDisableTiming));
   HIPDEC_CHECK_HIP(hipEventRecord(st.base.done, s));
   st.base.last = s;
-  g_photo_calls++; g_photo_entries += (uint64_t)n; g_photo_launches += launches;
+  if (chains.augment) { g_augment_calls++; g_augment_entries += (uint64_t)n; g_augment_launches += launches; }
+  else { g_photo_calls++; g_photo_entries += (uint64_t)n; g_photo_launches += launches; }
   return 0;
 }
 
@@ -2749,33 +2819,62 @@ void hipdec_photo_stats(uint64_t* calls, uint64_t* entries, uint64_t* launches)
   if (launches) *launches = g_photo_launches.load();
 }
 
-// the stage alone; its tables and work memory live in a state the process keeps per device, as hipdec_tensor_warp's do
-int hipdec_tensor_photo(const void* src_dev, size_t src_bytes, const hipdec_photo_desc* photo, const hipdec_photo_chain* chains, const hipdec_tensor_desc* desc,
-                        int n, void* out_dev, size_t out_bytes, void* stream)
+// the stage alone (hipdec_tensor_photo, hipdec_tensor_augment); its tables and work memory live in a state the process keeps per device, as
+// hipdec_tensor_warp's do
+static int tensor_chain_stage(const char* who, const void* src_dev, size_t src_bytes, const hipdec_photo_desc* photo, const ChainView& chains,
+                              const hipdec_tensor_desc* desc, int n, void* out_dev, size_t out_bytes, void* stream)
 {
   static std::mutex mu;
   static std::map<int, PhotoState> states;   // by device
-  if (!desc || n < 0) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: bad arguments");
-  if (desc->dtype < HIPDEC_TENSOR_U8 || desc->dtype > HIPDEC_TENSOR_BF16) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: unknown dtype %d", desc->dtype);
-  if (desc->layout != HIPDEC_TENSOR_NCHW && desc->layout != HIPDEC_TENSOR_NHWC) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: unknown layout %d", desc->layout);
+  if (!desc || n < 0) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  if (desc->dtype < HIPDEC_TENSOR_U8 || desc->dtype > HIPDEC_TENSOR_BF16) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown dtype %d", who, desc->dtype);
+  if (desc->layout != HIPDEC_TENSOR_NCHW && desc->layout != HIPDEC_TENSOR_NHWC) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown layout %d", who, desc->layout);
   if (desc->dtype != HIPDEC_TENSOR_U8)
     for (int c = 0; c < 3; c++)
-      if (!std::isfinite(desc->scale[c]) || !std::isfinite(desc->bias[c])) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: scale / bias of channel %d is not finite", c);
-  if (int rc = photo_check("tensor_photo", photo, chains, desc, n)) return rc;
+      if (!std::isfinite(desc->scale[c]) || !std::isfinite(desc->bias[c])) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: scale / bias of channel %d is not finite", who, c);
+  if (int rc = chain_check(who, photo, chains, desc, n)) return rc;
   const uint64_t es = desc->dtype == HIPDEC_TENSOR_U8 ? 1 : (desc->dtype == HIPDEC_TENSOR_F32 ? 4 : 2);
   const uint64_t per_src = 3ull * (uint64_t)photo->src_width * (uint64_t)photo->src_height;   // (below 2^32: sizes below 2^15; times n below 2^31, times 4: below 2^63)
-  if (src_bytes < per_src * (uint64_t)n) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: src_bytes %zu is smaller than the %d samples of %llu bytes", src_bytes, n, (unsigned long long)per_src);
-  if (out_bytes < per_src * es * (uint64_t)n) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: out_bytes %zu is smaller than the tensor of %llu bytes", out_bytes, (unsigned long long)(per_src * es * (uint64_t)n));
+  if (src_bytes < per_src * (uint64_t)n) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: src_bytes %zu is smaller than the %d samples of %llu bytes", who, src_bytes, n, (unsigned long long)per_src);
+  if (out_bytes < per_src * es * (uint64_t)n) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: out_bytes %zu is smaller than the tensor of %llu bytes", who, out_bytes, (unsigned long long)(per_src * es * (uint64_t)n));
   if (n == 0) return 0;
-  if (!src_dev || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_photo: bad arguments");
+  if (!src_dev || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
   // (everything above is decided without a device)
   if (int rc = ensure_init()) return rc;
-  return guarded("tensor_photo", [&]() -> int {
+  return guarded(who, [&]() -> int {
     std::lock_guard<std::mutex> lock(mu);
     int dev = 0;
     HIPDEC_CHECK_HIP(hipGetDevice(&dev));
-    return photo_launch(states[dev], src_dev, photo, chains, desc, n, out_dev, stream ? (hipStream_t)stream : default_stream());
+    return chain_launch(states[dev], src_dev, photo, chains, desc, n, out_dev, stream ? (hipStream_t)stream : default_stream());
   });
+}
+
+int hipdec_tensor_photo(const void* src_dev, size_t src_bytes, const hipdec_photo_desc* photo, const hipdec_photo_chain* chains, const hipdec_tensor_desc* desc,
+                        int n, void* out_dev, size_t out_bytes, void* stream)
+{
+  return tensor_chain_stage("tensor_photo", src_dev, src_bytes, photo, chain_view(chains), desc, n, out_dev, out_bytes, stream);
+}
+
+int hipdec_tensor_augment(const void* src_dev, size_t src_bytes, const hipdec_photo_desc* photo, const hipdec_augment_chain* chains,
+                          const hipdec_tensor_desc* desc, int n, void* out_dev, size_t out_bytes, void* stream)
+{
+  return tensor_chain_stage("tensor_augment", src_dev, src_bytes, photo, chain_view(chains), desc, n, out_dev, out_bytes, stream);
+}
+
+void hipdec_augment_stats(uint64_t* calls, uint64_t* entries, uint64_t* launches)
+{
+  if (calls) *calls = g_augment_calls.load();
+  if (entries) *entries = g_augment_entries.load();
+  if (launches) *launches = g_augment_launches.load();
+}
+
+int hipdec_gaussian_box(double radius, int* r, uint32_t* ww, uint32_t* fw)
+{
+  if (!r || !ww || !fw) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "gaussian_box: bad arguments"), -1;
+  if (!std::isfinite(radius) || radius < 0.0 || radius > kAugmentBlurMaxRadius)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "gaussian_box: the radius %g is not 0 .. %g", radius, kAugmentBlurMaxRadius), -1;
+  augment_gaussian_box(radius, r, ww, fw);
+  return 0;
 }
 
 // Pillow's Image.rotate matrix without expand (Image.py rotate): cos and sin of -radians(angle mod 360) rounded to 15 decimal places - printed with 15

@@ -1141,11 +1141,11 @@ struct WarpStage {
   }
 };
 
-struct PhotoStage {
-  const hipdec_photo_desc* photo; const hipdec_photo_chain* chains;
+struct PhotoStage {   // the photo stage and the augment stage: what the ChainView admits is what differs
+  const hipdec_photo_desc* photo; ChainView chains;
   int src_width() const { return photo->src_width; }
   int src_height() const { return photo->src_height; }
-  int check(const char* who, const hipdec_tensor_desc* d, int n) const { return photo_check(who, photo, chains, d, n); }
+  int check(const char* who, const hipdec_tensor_desc* d, int n) const { return chain_check(who, photo, chains, d, n); }
   int depth(const char* who, const hipdec_tensor_desc* d, int e, int bits) const
   {
     if (bits > 8 && d->dtype != HIPDEC_TENSOR_U8)
@@ -1155,7 +1155,7 @@ struct PhotoStage {
   int scratch(hipdec_batch* b, size_t bytes, hipStream_t s, void** out) const { return photo_scratch(b->photo, bytes, s, out); }
   int launch(hipdec_batch* b, const void* src, const hipdec_tensor_desc* d, int n, void* out_dev, hipStream_t s) const
   {
-    return photo_launch(b->photo, src, photo, chains, d, n, out_dev, s);
+    return chain_launch(b->photo, src, photo, chains, d, n, out_dev, s);
   }
 };
 
@@ -1334,7 +1334,13 @@ int hipdec_batch_to_tensor_warped(hipdec_batch* b, const hipdec_tensor_desc* des
 int hipdec_batch_to_tensor_photo(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
                                  const hipdec_photo_desc* photo, const hipdec_photo_chain* chains, int n_entries, void* out_dev, size_t out_bytes, void* stream)
 {
-  return batch_to_tensor_two_stage("to_tensor_photo", b, PhotoStage{photo, chains}, desc, entries, orientations, n_entries, out_dev, out_bytes, stream);
+  return batch_to_tensor_two_stage("to_tensor_photo", b, PhotoStage{photo, chain_view(chains)}, desc, entries, orientations, n_entries, out_dev, out_bytes, stream);
+}
+
+int hipdec_batch_to_tensor_augmented(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                     const hipdec_photo_desc* photo, const hipdec_augment_chain* chains, int n_entries, void* out_dev, size_t out_bytes, void* stream)
+{
+  return batch_to_tensor_two_stage("to_tensor_augmented", b, PhotoStage{photo, chain_view(chains)}, desc, entries, orientations, n_entries, out_dev, out_bytes, stream);
 }
 
 int hipdec_batch_to_tensor_packed(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <vector>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <string>
 #include <new>
@@ -147,18 +148,34 @@ int warp_launch(WarpState& st, const void* src_dev, const hipdec_warp_desc* w, c
 void warp_state_free(WarpState& st);
 
 // Photometric tensor output (color.hip k_photo_hist / k_photo_apply, include/heif_hipdec.h hipdec_tensor_photo): n dense U8 / NHWC samples through a chain
-// of up to four operations each.  What the arguments alone decide (photo_check) is host-only; photo_launch builds one table of records per chain step,
+// of up to four operations each.  What the arguments alone decide (chain_check) is host-only; chain_launch builds one table of records per chain step,
 // uploads them with one copy and launches at most one histogram and one apply kernel per step.
 struct PhotoState {            // the device memory a handle (or, for hipdec_tensor_photo, the process) keeps for its photo calls
   WarpState base;              // the tables last uploaded, the U8 / NHWC intermediate of the decode-side forms, the event behind the last launch
   void* work = nullptr;        // up to two ping-pong buffers of n samples, then the histograms of one step
   size_t work_bytes = 0;
 };
-int photo_check(const char* who, const hipdec_photo_desc* p, const hipdec_photo_chain* chains, const hipdec_tensor_desc* d, int n);
 int photo_scratch(PhotoState& st, size_t bytes, hipStream_t s, void** out);   // the handle's intermediate, at least `bytes` long
-int photo_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p, const hipdec_photo_chain* chains, const hipdec_tensor_desc* d, int n,
-                 void* out_dev, hipStream_t s);
 void photo_state_free(PhotoState& st);
+
+// Augmented tensor output (color.hip k_augment_hue / k_augment_blur beside the photo kernels, include/heif_hipdec.h hipdec_tensor_augment): the photo stage
+// with hue, Gaussian blur and chains of up to eight.  The same host code serves both: a ChainView reads either chain array, and per step the records are
+// compacted per kind - apply, histogram, hue, blur - with at most one launch each.  The state, the scratch and the work memory are a PhotoState.
+struct ChainView {             // hipdec_photo_chain and hipdec_augment_chain share their head: n_ops, reserved, ops[]
+  const void* base; size_t stride; int max_ops; bool augment;
+  const uint8_t* at(int e) const { return (const uint8_t*)base + (size_t)e * stride; }
+  int n_ops(int e) const { return ((const int*)at(e))[0]; }
+  int reserved(int e) const { return ((const int*)at(e))[1]; }
+  const hipdec_photo_op& op(int e, int k) const { return ((const hipdec_photo_op*)(at(e) + offsetof(hipdec_photo_chain, ops)))[k]; }   // (k below max_ops)
+};
+static_assert(offsetof(hipdec_photo_chain, ops) == offsetof(hipdec_augment_chain, ops) && offsetof(hipdec_photo_chain, n_ops) == 0 &&
+              offsetof(hipdec_augment_chain, n_ops) == 0 && offsetof(hipdec_photo_chain, reserved) == 4 && offsetof(hipdec_augment_chain, reserved) == 4,
+              "ChainView reads both chain types through their common head");
+inline ChainView chain_view(const hipdec_photo_chain* c) { return ChainView{c, sizeof(hipdec_photo_chain), HIPDEC_PHOTO_MAX_OPS, false}; }
+inline ChainView chain_view(const hipdec_augment_chain* c) { return ChainView{c, sizeof(hipdec_augment_chain), HIPDEC_AUGMENT_MAX_OPS, true}; }
+int chain_check(const char* who, const hipdec_photo_desc* p, const ChainView& chains, const hipdec_tensor_desc* d, int n);
+int chain_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p, const ChainView& chains, const hipdec_tensor_desc* d, int n, void* out_dev,
+                 hipStream_t s);
 
 // The paste of an album of grid photos (transform.hip k_album_paste): one job per (tile, plane), already clipped to the photo's output size by the host
 // (a job clipped to nothing is not emitted); the job table lives in device memory and all jobs go out as ONE launch.

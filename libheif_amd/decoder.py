@@ -108,6 +108,14 @@ def _bind(lib):
         lib.hipdec_album_to_tensor_photo.argtypes = photo
         lib.hipdec_photo_stats.restype = None
         lib.hipdec_photo_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
+    if hasattr(lib, "hipdec_tensor_augment"):  # (likewise: the augment stage)
+        lib.hipdec_tensor_augment.argtypes = [vp, sz, C.POINTER(PhotoDesc), C.POINTER(AugmentChain), C.POINTER(TensorDesc), ci, vp, sz, vp]
+        augmented = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), C.POINTER(ci), C.POINTER(PhotoDesc), C.POINTER(AugmentChain), ci, vp, sz, vp]
+        lib.hipdec_batch_to_tensor_augmented.argtypes = augmented
+        lib.hipdec_album_to_tensor_augmented.argtypes = augmented
+        lib.hipdec_augment_stats.restype = None
+        lib.hipdec_augment_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
+        lib.hipdec_gaussian_box.argtypes = [C.c_double, C.POINTER(ci), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     if hasattr(lib, "hipdec_clips_create"):   # (tools/ab_bench.sh loads an older branch's library through this module: it has no clips, and Clips() says so)
         lib.hipdec_clips_create.argtypes = [C.POINTER(vp), ci, C.POINTER(ci), C.POINTER(C.c_char_p), C.POINTER(sz), C.c_uint64]
         lib.hipdec_clips_free.argtypes = [vp]
@@ -191,6 +199,11 @@ class PhotoChain(C.Structure):
 class PhotoDesc(C.Structure):
     """hipdec_photo_desc"""
     _fields_ = [("src_width", C.c_int), ("src_height", C.c_int), ("reserved", C.c_int * 2)]
+
+
+class AugmentChain(C.Structure):
+    """hipdec_augment_chain: up to AUGMENT_MAX_OPS operations, applied in order"""
+    _fields_ = [("n_ops", C.c_int), ("reserved", C.c_int), ("ops", PhotoOp * 8)]
 
 
 class ClipFrame(C.Structure):
@@ -725,6 +738,75 @@ def _to_tensor_photo(self, lib_call, size, chains, entries, orientations, filter
     return _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
 
 
+# the augment stage (hipdec_tensor_augment): the photo stage's operations, Pillow's hue shift and ImageFilter.GaussianBlur, chains of up to eight
+AUGMENT_HUE, AUGMENT_GAUSSIAN_BLUR = 16, 17
+AUGMENT_MAX_OPS = 8
+AUGMENT_BLUR_MAX_RADIUS = 8.0
+AUGMENT_OPS = dict(PHOTO_OPS, hue=AUGMENT_HUE, gaussian_blur=AUGMENT_GAUSSIAN_BLUR)
+
+
+def augment_chain(*ops):
+    """hipdec_augment_chain from up to AUGMENT_MAX_OPS operations, applied in order: photo_chain's operations, ("hue", d) with the integer shift d of
+    0 .. 255 (hue_shift(hue_factor) for torchvision's factor) and ("gaussian_blur", radius) with Pillow's radius, 0 .. AUGMENT_BLUR_MAX_RADIUS"""
+    if len(ops) > AUGMENT_MAX_OPS:
+        raise ValueError("a chain has at most %d operations, not %d" % (AUGMENT_MAX_OPS, len(ops)))
+    ch = AugmentChain()
+    ch.n_ops = len(ops)
+    for k, o in enumerate(ops):
+        o = (o,) if isinstance(o, (str, int)) else tuple(o)
+        if not 1 <= len(o) <= 2:
+            raise ValueError("an operation is a name or (name, value), not %r" % (o,))
+        if isinstance(o[0], str) and o[0].lower() not in AUGMENT_OPS:
+            raise ValueError("unknown augment operation %r" % (o[0],))
+        ch.ops[k].op = AUGMENT_OPS[o[0].lower()] if isinstance(o[0], str) else int(o[0])
+        ch.ops[k].value = float(o[1]) if len(o) == 2 else 0.0
+    return ch
+
+
+def augment_chains(chains, n=None):
+    """a ctypes array of hipdec_augment_chain from AugmentChain objects or sequences of operations (augment_chain's arguments)"""
+    chains = list(chains)
+    if n is not None and len(chains) != n:
+        raise ValueError("%d chains for %d entries" % (len(chains), n))
+    arr = (AugmentChain * max(len(chains), 1))()
+    for k, ch in enumerate(chains):
+        arr[k] = ch if isinstance(ch, AugmentChain) else augment_chain(*ch)
+    return arr
+
+
+def hue_shift(hue_factor):
+    """the integer shift of ("hue", d) for the hue_factor of torchvision's adjust_hue on PIL images, -0.5 .. 0.5: int(hue_factor * 255), truncated
+    toward zero, then mod 256 (the library's own statement of that convention; the operation itself is pinned to Pillow)"""
+    if not -0.5 <= float(hue_factor) <= 0.5:
+        raise ValueError("hue_factor %r is not in [-0.5, 0.5]" % (hue_factor,))
+    return int(float(hue_factor) * 255) % 256
+
+
+def gaussian_box(radius):
+    """(r, ww, fw) of hipdec_gaussian_box: the extended box ImageFilter.GaussianBlur(radius) runs three times along each axis (host only)"""
+    lib = _bind(load_library())
+    r, ww, fw = C.c_int(), C.c_uint32(), C.c_uint32()
+    check(lib.hipdec_gaussian_box(float(radius), C.byref(r), C.byref(ww), C.byref(fw)))
+    return r.value, ww.value, fw.value
+
+
+def augment_stats():
+    """(augment calls that wrote anything, the entries they wrote, all kernel launches of the stage) since load"""
+    lib = _bind(load_library())
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    lib.hipdec_augment_stats(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def _to_tensor_augmented(self, lib_call, size, chains, entries, orientations, filter, dtype, layout, mean, std, scale, bias, out, stream):
+    n = self.n if entries is None else len(entries)
+    pd = photo_desc(size)
+    carr = augment_chains(chains, n)
+    codes = None if orientations is None else _orientation_array(orientations, n)
+    call = lambda h, desc, arr, n_, ptr, room, stream_: lib_call(h, desc, arr, codes, C.byref(pd), carr, n_, ptr, room, stream_)
+    return _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
+
+
 def fit_within(width, height, size):
     """The thumbnail size examples/heif_thumbnailer.cc:172-186 computes: the image as it is when both sides fit into `size`, else the longer
     side becomes `size` and the other one follows with integer division (which may give 0: the thumbnailer refuses that, and so does
@@ -1071,6 +1153,15 @@ class Batch:
         return _to_tensor_photo(self, self._lib.hipdec_batch_to_tensor_photo, size, chains, entries, orientations, filter, dtype, layout, mean, std, scale,
                                 bias, out, stream)
 
+    def to_tensor_augmented(self, size, chains, entries=None, filter=SCALE_BILINEAR, orientations=None, dtype="float16", layout="NCHW", mean=None, std=None,
+                            scale=None, bias=None, out=None, stream=None):
+        """asynchronous: to_tensor_photo with the augment stage's chains (hipdec_batch_to_tensor_augmented): up to AUGMENT_MAX_OPS operations per entry,
+        the photometric ones plus ("hue", d) - Pillow's HSV round trip with a wrap-around shift of H, hue_shift(hue_factor) gives d - and
+        ("gaussian_blur", radius) - PIL.ImageFilter.GaussianBlur(radius), radius 0 .. AUGMENT_BLUR_MAX_RADIUS -, bit for bit.  chains[e]: an AugmentChain or
+        a sequence of operations as augment_chain takes them.  One resize launch, then at most four launches per chain step."""
+        return _to_tensor_augmented(self, self._lib.hipdec_batch_to_tensor_augmented, size, chains, entries, orientations, filter, dtype, layout, mean, std,
+                                    scale, bias, out, stream)
+
     def to_tensor_packed(self, sizes, entries=None, patch=0, merge=1, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None,
                          filter=SCALE_BOX, orientations=None, offsets=None, out=None, stream=None):
         """asynchronous: every entry at its OWN displayed size sizes[e] = (width, height), all entries in one launch into one 1-D output
@@ -1305,6 +1396,12 @@ class Album:
         return _to_tensor_photo(self, self._lib.hipdec_album_to_tensor_photo, size, chains, entries, orientations, filter, dtype, layout, mean, std, scale,
                                 bias, out, stream)
 
+    def to_tensor_augmented(self, size, chains, entries=None, filter=SCALE_BILINEAR, orientations=None, dtype="float16", layout="NCHW", mean=None, std=None,
+                            scale=None, bias=None, out=None, stream=None):
+        """Batch.to_tensor_augmented over the composed photos"""
+        return _to_tensor_augmented(self, self._lib.hipdec_album_to_tensor_augmented, size, chains, entries, orientations, filter, dtype, layout, mean, std,
+                                    scale, bias, out, stream)
+
     def to_tensor_packed(self, sizes, entries=None, patch=0, merge=1, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None,
                          filter=SCALE_BOX, orientations=None, offsets=None, out=None, stream=None):
         """Batch.to_tensor_packed over the composed photos"""
@@ -1378,13 +1475,8 @@ def tensor_warp(src, size, maps, src_size=None, warp_filter=SCALE_BILINEAR, fill
     return stage.tensor_to_host() if to_host else out
 
 
-def tensor_photo(src, chains, src_size=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, out=None, stream=None,
-                 to_host=False):
-    """asynchronous: the photometric stage alone (hipdec_tensor_photo) over n = len(chains) dense 8-bit RGB samples in device memory: a uint8 torch.Tensor
-    of shape (n, height, width, 3), or a DeviceBuffer of n * height * width * 3 bytes with src_size = (width, height).  Sample e goes through chains[e] as
-    in Batch.to_tensor_photo and is normalised as to_tensor normalises; the tensor has the samples' size.  dtype "uint8" with layout "NHWC" gives samples
-    that tensor_warp and tensor_photo take again.  A clip's T frames share one chain by repeating it T times.  `out`: a DeviceBuffer, or a torch tensor on
-    the current stream.  Returns `out` (to_host=True: the NumPy array, after waiting)."""
+def _tensor_chain_stage(lib_call, make_chains, src, chains, src_size, dtype, layout, mean, std, scale, bias, out, stream, to_host):
+    """tensor_photo and tensor_augment: the source, the chains, then the stage's call"""
     lib = _bind(load_library())
     chains = list(chains)
     n = len(chains)
@@ -1406,11 +1498,29 @@ def tensor_photo(src, chains, src_size=None, dtype="float16", layout="NCHW", mea
             out = torch.empty(tensor_shape(n, src_size, layout), dtype=getattr(torch, dtype), device=src.device)   # (written on torch's current stream, as src was)
     size = (int(src_size[0]), int(src_size[1]))
     pd = photo_desc(size)
-    carr = photo_chains(chains, n)
+    carr = make_chains(chains, n)
     stage = _WarpStage(lib, n)
-    call = lambda h, desc, arr, n_, ptr, room, stream_: lib.hipdec_tensor_photo(sptr, sbytes, C.byref(pd), carr, desc, n_, ptr, room, stream_)
+    call = lambda h, desc, arr, n_, ptr, room, stream_: getattr(lib, lib_call)(sptr, sbytes, C.byref(pd), carr, desc, n_, ptr, room, stream_)
     out = _to_tensor(stage, call, size, None, dtype, layout, mean, std, scale, bias, 0, out, stream)
     return stage.tensor_to_host() if to_host else out
+
+
+def tensor_photo(src, chains, src_size=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, out=None, stream=None,
+                 to_host=False):
+    """asynchronous: the photometric stage alone (hipdec_tensor_photo) over n = len(chains) dense 8-bit RGB samples in device memory: a uint8 torch.Tensor
+    of shape (n, height, width, 3), or a DeviceBuffer of n * height * width * 3 bytes with src_size = (width, height).  Sample e goes through chains[e] as
+    in Batch.to_tensor_photo and is normalised as to_tensor normalises; the tensor has the samples' size.  dtype "uint8" with layout "NHWC" gives samples
+    that tensor_warp and tensor_photo take again.  A clip's T frames share one chain by repeating it T times.  `out`: a DeviceBuffer, or a torch tensor on
+    the current stream.  Returns `out` (to_host=True: the NumPy array, after waiting)."""
+    return _tensor_chain_stage("hipdec_tensor_photo", photo_chains, src, chains, src_size, dtype, layout, mean, std, scale, bias, out, stream, to_host)
+
+
+def tensor_augment(src, chains, src_size=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, out=None, stream=None,
+                   to_host=False):
+    """asynchronous: the augment stage alone (hipdec_tensor_augment): tensor_photo with chains as Batch.to_tensor_augmented takes them - up to
+    AUGMENT_MAX_OPS operations, hue and Gaussian blur among them.  Everything else as tensor_photo; dtype "uint8" with layout "NHWC" gives samples that
+    tensor_warp, tensor_photo and tensor_augment take again."""
+    return _tensor_chain_stage("hipdec_tensor_augment", augment_chains, src, chains, src_size, dtype, layout, mean, std, scale, bias, out, stream, to_host)
 
 
 def clips_stats():
