@@ -26,6 +26,9 @@
  *                                                     area-averaged, (V / 255 - mean) / std with the usual ImageNet constants
  *   ./decode_batch --thumb 256 --hue 43 --blur 1.5 item0.hevc    the previews through Pillow's hue shift (D of 0 .. 255 added to H of convert("HSV")) and / or
  *                                                     PIL.ImageFilter.GaussianBlur(RADIUS), RADIUS 0 .. 8, bit for bit (hipdec_batch_to_tensor_augmented)
+ *   ./decode_batch --thumb 256 --recipe 15 color 1.4 item0.hevc   the previews rotated by ANGLE degrees (BILINEAR, black outside) and then through one photometric
+ *                                                     operation, both steps in ONE chain, as RandAugment draws them (hipdec_batch_to_tensor_recipe): OP and
+ *                                                     VALUE as for --photo; a statistics operation (contrast, autocontrast, equalize) sees the fill pixels
  *   ./decode_batch --album 16 6x8 tile0.hevc ...      the items are TILES: 16 grid photos of 6 x 8 tiles (tile t of photo k is item (k * 48 + t) mod n; the
  *                                                     output is the whole tiled area) composed by ONE launch set and ONE paste launch; prints Mpixel/s
  */
@@ -138,9 +141,20 @@ int main(int argc, char** argv)
     if (!photo || argc < 4 || end == argv[3] || *end) argc = 0;    /* no or an unknown OP, no or a bad VALUE: usage (the library checks the value's range) */
     else { argv += 3; argc -= 3; }
   }
+  int recipe = 0;                                                 /* --recipe ANGLE OP VALUE: rotate, then one photometric operation, one chain */
+  double recipe_angle = 0.0, recipe_value = 0.0;
+  if (thumb && !warp && !photo && argc >= 2 && !strcmp(argv[1], "--recipe")) {
+    static const char* const ops[] = {"brightness", "color", "contrast", "sharpness", "posterize", "solarize", "invert", "autocontrast", "equalize"};
+    char *end_a = NULL, *end_v = NULL;
+    recipe_angle = argc >= 3 ? strtod(argv[2], &end_a) : 0.0;
+    for (int k = 0; argc >= 4 && k < 9; k++) if (!strcmp(argv[3], ops[k])) recipe = HIPDEC_PHOTO_BRIGHTNESS + k;
+    recipe_value = argc >= 5 ? strtod(argv[4], &end_v) : 0.0;
+    if (!recipe || argc < 5 || end_a == argv[2] || *end_a || recipe_angle < -36000.0 || recipe_angle > 36000.0 || end_v == argv[4] || *end_v) argc = 0;
+    else { argv += 4; argc -= 4; }
+  }
   int augment = 0;                                                /* --hue D and / or --blur RADIUS: a chain of the augment stage, in that order */
   double hue = -1.0, blur = -1.0;
-  while (thumb && !warp && !photo && argc >= 2 && (!strcmp(argv[1], "--hue") || !strcmp(argv[1], "--blur"))) {
+  while (thumb && !warp && !photo && !recipe && argc >= 2 && (!strcmp(argv[1], "--hue") || !strcmp(argv[1], "--blur"))) {
     char* end = NULL;
     const double v = argc >= 3 ? strtod(argv[2], &end) : 0.0;
     if (argc < 3 || end == argv[2] || *end) { argc = 0; break; }  /* no or a bad value: usage (the library checks the range) */
@@ -148,7 +162,7 @@ int main(int argc, char** argv)
     augment = 1; argv += 2; argc -= 2;
   }
   int patch = 0, merge = 1;
-  if (thumb && !warp && !photo && !augment && argc >= 2 && !strcmp(argv[1], "--patches")) {
+  if (thumb && !warp && !photo && !recipe && !augment && argc >= 2 && !strcmp(argv[1], "--patches")) {
     char tail = 0;
     const int got = argc >= 3 ? sscanf(argv[2], "%d:%d%c", &patch, &merge, &tail) : 0;
     if ((got != 1 && got != 2) || patch < 1 || patch > 256 || merge < 1 || merge > 16) argc = 0;   /* no or a bad P[:M]: usage */
@@ -160,7 +174,7 @@ int main(int argc, char** argv)
     if (tensor < 1) argc = 0;
     else { argv += 2; argc -= 2; }
   }
-  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] [--warp ANGLE | --photo OP VALUE | [--hue D] [--blur RADIUS] | --patches P[:M]] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] [--warp ANGLE | --photo OP VALUE | --recipe ANGLE OP VALUE | [--hue D] [--blur RADIUS] | --patches P[:M]] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
   const int n = argc - 1;
   const void** data = (const void**)calloc((size_t)n, sizeof(void*));
   size_t* sizes = (size_t*)calloc((size_t)n, sizeof(size_t));
@@ -278,6 +292,25 @@ int main(int argc, char** argv)
         memset(&chain, 0, sizeof chain);
         chain.n_ops = 1; chain.ops[0].op = photo; chain.ops[0].value = photo_value;
         rc = hipdec_batch_to_tensor_photo(prev, &d, &e, codes + i, &pd, &chain, 1, outs[i], strides[i] * (size_t)hs[i], NULL);
+      }
+    } else if (recipe) {                                           /* one recipe call per preview: the rotation and the operation are steps of ONE chain */
+      for (int i = 0; i < n && !rc; i++) {
+        hipdec_tensor_desc d;
+        memset(&d, 0, sizeof d);
+        d.width = ws[i]; d.height = hs[i]; d.dtype = HIPDEC_TENSOR_U8; d.layout = HIPDEC_TENSOR_NHWC; d.filter = filter;
+        for (int c = 0; c < 3; c++) d.scale[c] = 1.0f;
+        const hipdec_tensor_entry e = {i, 0, 0, 0, 0, 0};
+        const hipdec_photo_desc pd = {ws[i], hs[i], {0, 0}};
+        hipdec_recipe_affine affine;
+        memset(&affine, 0, sizeof affine);                         /* fill 0, 0, 0 */
+        affine.filter = HIPDEC_SCALE_BILINEAR;
+        rc = hipdec_rotate_map(recipe_angle, ws[i], hs[i], &affine.map);
+        hipdec_augment_chain chain;
+        memset(&chain, 0, sizeof chain);
+        chain.n_ops = 2;
+        chain.ops[0].op = HIPDEC_RECIPE_AFFINE; chain.ops[0].value = 0.0;   /* the index of `affine` among the call's records */
+        chain.ops[1].op = recipe; chain.ops[1].value = recipe_value;
+        if (!rc) rc = hipdec_batch_to_tensor_recipe(prev, &d, &e, codes + i, &pd, &chain, &affine, 1, 1, outs[i], strides[i] * (size_t)hs[i], NULL);
       }
     } else if (augment) {                                          /* and one augmented call per preview: hue, then Gaussian blur, as Pillow does them */
       for (int i = 0; i < n && !rc; i++) {

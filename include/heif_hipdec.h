@@ -915,8 +915,9 @@ HIPDEC_API void hipdec_warp_stats(uint64_t* calls, uint64_t* entries);
  * named: n_ops outside 0 .. HIPDEC_PHOTO_MAX_OPS; an unknown op; a non-zero `reserved`; a value that is not finite or has |value| > 65536; POSTERIZE with a
  * value that is not an integer 0 .. 8; and for the call: src_width or src_height < 1 or >= 32768, a desc size that is not the source size, an unknown dtype
  * or layout, a non-finite scale or bias, src_bytes or out_bytes too small, more than 2^31 - 1 tiles (64 x 16 pixels).
- * Not part of it: gamma; autocontrast cutoffs and masks; a photometric and a warp step inside one call; parameter samplers; a clips entry point.  Hue,
- * Gaussian blur and chains of more than four operations are the augment stage below (hipdec_tensor_augment). */
+ * Not part of it: gamma; autocontrast cutoffs and masks; parameter samplers; a clips entry point.  Hue, Gaussian blur and chains of more than four
+ * operations are the augment stage below (hipdec_tensor_augment); a photometric and a warp step inside one call is the recipe stage
+ * (hipdec_tensor_recipe). */
 #define HIPDEC_PHOTO_MAX_OPS 4
 typedef enum hipdec_photo_opcode {
   HIPDEC_PHOTO_BRIGHTNESS = 1, HIPDEC_PHOTO_COLOR = 2, HIPDEC_PHOTO_CONTRAST = 3, HIPDEC_PHOTO_SHARPNESS = 4, HIPDEC_PHOTO_POSTERIZE = 5,
@@ -992,7 +993,8 @@ HIPDEC_API void hipdec_photo_stats(uint64_t* calls, uint64_t* entries, uint64_t*
  * named: what hipdec_tensor_photo refuses (with HIPDEC_AUGMENT_MAX_OPS for the chain length); an op other than 1 .. 9, 16, 17 ("unknown op"); HUE with a
  * value that is not an integer 0 .. 255; GAUSSIAN_BLUR with a radius that is not finite, negative or above the cap; more than 2^31 - 1 tiles.
  * Not part of it: per-axis radii, BoxBlur, UnsharpMask; torchvision's tensor-path GaussianBlur(kernel_size, sigma), a different filter; gamma; parameter
- * samplers and the random order of ColorJitter's steps (the caller orders the chain); a warp step inside the chain; a clips entry point. */
+ * samplers and the random order of ColorJitter's steps (the caller orders the chain); a clips entry point.  A warp step inside the chain is the recipe stage below
+ * (hipdec_tensor_recipe). */
 #define HIPDEC_AUGMENT_MAX_OPS 8
 #define HIPDEC_AUGMENT_HUE 16            /* value: integer shift d, 0 .. 255 */
 #define HIPDEC_AUGMENT_GAUSSIAN_BLUR 17  /* value: Pillow's radius, 0 <= radius <= HIPDEC_AUGMENT_BLUR_MAX_RADIUS */
@@ -1015,6 +1017,62 @@ HIPDEC_API void hipdec_augment_stats(uint64_t* calls, uint64_t* entries, uint64_
 /* host only: the box GAUSSIAN_BLUR runs three times along each axis for `radius` - what the blur kernel receives.  0, or -1 (radius not finite, negative
  * or above the cap; a NULL output) */
 HIPDEC_API int hipdec_gaussian_box(double radius, int* r, uint32_t* ww, uint32_t* fw);
+
+/* ---- recipe tensor output: affine steps inside augment chains - RandAugment / TrivialAugment / AutoAugment per sample, in one call ------------------------
+ * RandAugment, TrivialAugment and AutoAugment draw, per sample, a few operations from ONE list of geometric (Rotate, ShearX/Y, TranslateX/Y) and colour
+ * operations, in the sample's own order: one sample is [Rotate, Color], the next [Posterize, ShearX].  timm draws the warp filter per operation and fills
+ * with the dataset mean.  The order changes the bytes - CONTRAST after a rotation takes its mean over the fill pixels, a blur after a shear smears the fill
+ * edge - so the recipe stage is the augment stage with one more kind of step, not two stages in a row.  Bit-equal to Pillow, no tolerance.
+ *
+ * THE STAGE (hipdec_tensor_recipe).  As hipdec_tensor_augment, word for word - chains are hipdec_augment_chain, up to HIPDEC_AUGMENT_MAX_OPS steps, each on
+ * the 8-bit result of the step before - with affines[0 .. n_affines - 1], the affine records of the call.  A step is one of:
+ *  opcodes 1 .. 9       exactly the photo stage's definitions (hipdec_tensor_photo);
+ *  opcodes 16, 17       exactly the augment stage's definitions (hipdec_tensor_augment);
+ *  HIPDEC_RECIPE_AFFINE (value: an integer index i into affines)   PIL.Image.transform((w, h), AFFINE, affines[i].map, affines[i].filter,
+ *    fillcolor = affines[i].fill) of the 8-bit result of the step before: exactly the arithmetic hipdec_tensor_warp states - BILINEAR, BICUBIC, and NEAREST on
+ *    its table path (a1 == 0 && a3 == 0) or its fixed-point path - with src_width x src_height the sample's size (the stage does not resize) and an
+ *    "outside" pixel holding the fill.  Several steps, of one entry or of many, may name the same record.
+ * The last step of a chain writes the normalised tensor; if it is an affine step its fill is normalised as a pixel is (HIPDEC_FILL_COMPONENT).  There is
+ * no element-domain fill inside a chain: an 8-bit intermediate cannot hold one.
+ * Equalities: an empty chain gives hipdec_batch_to_tensor_oriented's bytes (decode-side forms); a chain without HIPDEC_RECIPE_AFFINE gives
+ * hipdec_tensor_augment's bytes; a chain of one affine step gives hipdec_tensor_warp's bytes for that map, filter and a component fill; with a U8 / NHWC
+ * output the stage chains with hipdec_tensor_warp, hipdec_tensor_photo, hipdec_tensor_augment and itself.
+ *
+ * THE DECODE-SIDE FORMS (hipdec_batch_to_tensor_recipe, hipdec_album_to_tensor_recipe): as the _augmented forms - sample e of the intermediate is what
+ * hipdec_batch_to_tensor_oriented writes for entry e as U8 / NHWC of size src_width x src_height with desc->filter; a float dtype from a source above 8
+ * bits is HIPDEC_ERR_UNSUPPORTED; the intermediate and the work memory come from the library's device pool and stay with the handle.
+ *
+ * Launches: the existing resize launch (decode-side forms); then per chain step at most ONE launch each of k_photo_hist, k_photo_apply, k_augment_hue,
+ * k_augment_blur, k_recipe_affine_nearest, _bilinear and _bicubic, each over the compacted records of the entries whose operation at that step is of its
+ * kind: at most 7 per step and 7 * HIPDEC_AUGMENT_MAX_OPS per call, whatever the number of entries.  The index tables of NEAREST scale-only maps (w + h
+ * int32 each) travel behind the records in the same upload.  A step never reads the buffer it writes: the first step reads src_dev, the last writes
+ * out_dev, the others alternate between two 8-bit intermediates.  Asynchronous on `stream`.  A recipe call counts in hipdec_recipe_stats only:
+ * hipdec_warp_stats, hipdec_photo_stats and hipdec_augment_stats do not move.
+ * Refused with HIPDEC_ERR_INVALID_ARGUMENT before anything is launched and before a device is touched, `out_dev` untouched, the entry and the operation
+ * named: everything hipdec_tensor_augment refuses; n_affines < 0; and for HIPDEC_RECIPE_AFFINE a value that is not an integer 0 .. n_affines - 1, `affines`
+ * NULL, a non-zero op.reserved, and of the record: a non-finite coefficient, |m[i]| >= 32000, a corner of [0, w] x [0, h] whose mapped coordinate has
+ * magnitude >= 32000 (hipdec_tensor_warp's bounds), a filter other than NEAREST, BILINEAR, BICUBIC, a fill component outside 0 .. 255.  hipdec_tensor_photo
+ * and hipdec_tensor_augment keep refusing opcode 32 as an unknown op.
+ * Not part of it: perspective and quad maps; a step that changes the size; a mask; element-domain fills; timm's SolarizeAdd and the *Increasing magnitude
+ * schedules; samplers and magnitude tables (drawing stays with the caller); a clips entry point; staging source tiles in LDS. */
+#define HIPDEC_RECIPE_AFFINE 32          /* value: integer index into the call's affines, 0 .. n_affines - 1 */
+typedef struct hipdec_recipe_affine {
+  hipdec_tensor_map map;       /* PIL's AFFINE data, as for hipdec_tensor_warp */
+  int filter;                  /* HIPDEC_SCALE_NEAREST, _BILINEAR or _BICUBIC: per operation */
+  int fill[3];                 /* Pillow's fillcolor: component values 0 .. 255 */
+} hipdec_recipe_affine;        /* 64 bytes, no padding (the library asserts it) */
+HIPDEC_API int hipdec_tensor_recipe(const void* src_dev, size_t src_bytes, const hipdec_photo_desc* photo, const hipdec_augment_chain* chains,
+                                    const hipdec_recipe_affine* affines, int n_affines, const hipdec_tensor_desc* desc, int n, void* out_dev,
+                                    size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_batch_to_tensor_recipe(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                             const hipdec_photo_desc* photo, const hipdec_augment_chain* chains, const hipdec_recipe_affine* affines,
+                                             int n_affines, int n_entries, void* out_dev, size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_album_to_tensor_recipe(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                             const hipdec_photo_desc* photo, const hipdec_augment_chain* chains, const hipdec_recipe_affine* affines,
+                                             int n_affines, int n_entries, void* out_dev, size_t out_bytes, void* stream);
+/* counters since load: recipe calls that wrote anything, the entries they wrote, all kernel launches of the stage, and the affine steps among the
+ * entries' steps (any may be NULL) */
+HIPDEC_API void hipdec_recipe_stats(uint64_t* calls, uint64_t* entries, uint64_t* launches, uint64_t* affine_steps);
 
 /* counters since load: images through hipdec_image_transform, grid canvases handed out by hipdec_grid_read_plane_tracked (hipdec_image_scale counts in
  * hipdec_image_scale_stats) */

@@ -1212,6 +1212,8 @@ __global__ __launch_bounds__(256) void k_canvas_margin(const hipdec::CanvasMargi
 #include "photo_kernels.h"
 // ---- augment stage (include/heif_hipdec.h hipdec_tensor_augment): k_augment_hue, k_augment_blur beside the photo stage's kernels
 #include "augment_kernels.h"
+// ---- recipe stage (include/heif_hipdec.h hipdec_tensor_recipe): k_recipe_affine_nearest / _bilinear / _bicubic, an affine step inside a chain
+#include "recipe_kernels.h"
 
 // the plane scalers: blockIdx.z selects the plane (all planes of an image, or of all items of a batch, are ONE launch)
 // ---- Pillow's bilinear / bicubic resampling of 8-bit pictures (HIPDEC_SCALE_BILINEAR / _BICUBIC, include/heif_hipdec.h), bit for bit: two separable passes
@@ -2527,12 +2529,46 @@ static_assert((int)HIPDEC_AUGMENT_HUE == (int)AUGMENT_HUE && (int)HIPDEC_AUGMENT
               HIPDEC_AUGMENT_BLUR_MAX_RADIUS == kAugmentBlurMaxRadius, "augment_lut.h restates the augment opcodes and the cap");
 std::atomic<uint64_t> g_photo_calls{0}, g_photo_entries{0}, g_photo_launches{0};
 std::atomic<uint64_t> g_augment_calls{0}, g_augment_entries{0}, g_augment_launches{0};
+std::atomic<uint64_t> g_recipe_calls{0}, g_recipe_entries{0}, g_recipe_launches{0}, g_recipe_affine_steps{0};
 
-// the photo stage's checks, and the augment stage's: the chain length and the operations a view admits are what differs
+// what an affine step of a recipe chain alone decides: its index, and of the record it names what warp_check refuses of a map for an output of the
+// sample's size, the filter and the fill
+static int recipe_affine_check(const char* who, const ChainView& chains, const hipdec_tensor_desc* d, int e, int k, const hipdec_photo_op& o)
+{
+  if (o.reserved) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (AFFINE): reserved is %d, not 0", who, e, k, o.reserved);
+  if (!std::isfinite(o.value)) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (AFFINE): the value is not finite", who, e, k);
+  if (o.value != std::floor(o.value) || o.value < 0.0 || o.value >= (double)chains.n_affines)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (AFFINE): the value %g is not an index into the %d affine records", who, e, k, o.value,
+                     chains.n_affines);
+  if (!chains.affines) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (AFFINE): affines is NULL", who, e, k);
+  const int i = (int)o.value;
+  const hipdec_recipe_affine& a = chains.affines[i];
+  int which = 0;
+  switch (warp_map_check(a.map.m, d->width, d->height, &which)) {
+    case 0: break;
+    case 1: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (AFFINE): map coefficient %d of record %d is not finite", who, e, k, which, i);
+    case 2:
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (AFFINE): map coefficient %d of record %d is %g (magnitude 32000 or more)", who, e, k,
+                       which, i, a.map.m[which]);
+    default:
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (AFFINE): record %d maps corner (%d, %d) of the output to a coordinate of magnitude 32000 or more",
+                       who, e, k, i, (which & 1) ? d->width : 0, (which & 2) ? d->height : 0);
+  }
+  if (a.filter != HIPDEC_SCALE_NEAREST && a.filter != HIPDEC_SCALE_BILINEAR && a.filter != HIPDEC_SCALE_BICUBIC)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (AFFINE): warp filter %d of record %d (nearest 0, bilinear 16, bicubic 17)", who, e, k,
+                     a.filter, i);
+  for (int c = 0; c < 3; c++)
+    if (a.fill[c] < 0 || a.fill[c] > 255)
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: operation %d (AFFINE): fill %d of channel %d of record %d is not 0 .. 255", who, e, k, a.fill[c], c, i);
+  return 0;
+}
+
+// the photo stage's checks, the augment stage's and the recipe stage's: the chain length and the operations a view admits are what differs
 int chain_check(const char* who, const hipdec_photo_desc* p, const ChainView& chains, const hipdec_tensor_desc* d, int n)
 {
   static const char* const names[] = {"none", "BRIGHTNESS", "COLOR", "CONTRAST", "SHARPNESS", "POSTERIZE", "SOLARIZE", "INVERT", "AUTOCONTRAST", "EQUALIZE"};
   if (!p || (!chains.base && n > 0)) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  if (chains.recipe && chains.n_affines < 0) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: n_affines is %d", who, chains.n_affines);
   if (p->src_width < 1 || p->src_height < 1 || p->src_width >= 32768 || p->src_height >= 32768)
     return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: source size %d x %d (1 .. 32767 each way)", who, p->src_width, p->src_height);
   if (p->reserved[0] || p->reserved[1]) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: photo.reserved is not 0", who);
@@ -2545,6 +2581,10 @@ int chain_check(const char* who, const hipdec_photo_desc* p, const ChainView& ch
     if (chains.reserved(e)) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: chain.reserved is %d, not 0", who, e, chains.reserved(e));
     for (int k = 0; k < n_ops; k++) {
       const hipdec_photo_op& o = chains.op(e, k);
+      if (chains.recipe && o.op == HIPDEC_RECIPE_AFFINE) {
+        if (int rc = recipe_affine_check(who, chains, d, e, k, o)) return rc;
+        continue;
+      }
       const char* name = o.op >= PHOTO_BRIGHTNESS && o.op <= PHOTO_EQUALIZE ? names[o.op]
                          : (chains.augment && o.op == AUGMENT_HUE ? "HUE" : (chains.augment && o.op == AUGMENT_GAUSSIAN_BLUR ? "GAUSSIAN_BLUR" : "unknown"));
       switch (chains.augment ? augment_op_check(o.op, o.reserved, o.value) : photo_op_check(o.op, o.reserved, o.value)) {
@@ -2575,8 +2615,23 @@ void photo_state_free(PhotoState& st)
 }
 
 namespace {
-enum ChainKind { KIND_APPLY = 0, KIND_HIST = 1, KIND_HUE = 2, KIND_BLUR = 3, KIND_COUNT = 4 };   // a step's records, in this order
+enum ChainKind { KIND_APPLY = 0, KIND_HIST = 1, KIND_HUE = 2, KIND_BLUR = 3,
+                 KIND_AFFINE_NEAREST = 4, KIND_AFFINE_BILINEAR = 5, KIND_AFFINE_BICUBIC = 6, KIND_COUNT = 7 };   // a step's records, in this order
 inline int chain_kind(int op) { return op == AUGMENT_HUE ? KIND_HUE : (op == AUGMENT_GAUSSIAN_BLUR ? KIND_BLUR : KIND_APPLY); }
+// the table is counted in units of a PhotoEntry: an affine record (a WarpEntry) takes two
+static_assert(sizeof(WarpEntry) == 2 * sizeof(PhotoEntry), "an affine record is two units of a step's table");
+inline size_t kind_units(int kind) { return kind >= KIND_AFFINE_NEAREST ? 2 : 1; }
+// the affine record of step t of entry e, or NULL (a checked chain: the index is in range)
+inline const hipdec_recipe_affine* step_affine(const ChainView& chains, int e, int t)
+{
+  if (!chains.recipe || !chains.n_ops(e) || chains.op(e, t).op != HIPDEC_RECIPE_AFFINE) return nullptr;
+  return chains.affines + (int)chains.op(e, t).value;
+}
+inline int affine_kind(const hipdec_recipe_affine* a)
+{
+  return a->filter == HIPDEC_SCALE_NEAREST ? KIND_AFFINE_NEAREST : (a->filter == HIPDEC_SCALE_BILINEAR ? KIND_AFFINE_BILINEAR : KIND_AFFINE_BICUBIC);
+}
+inline const char* chain_stage_name(const ChainView& chains) { return chains.recipe ? "tensor_recipe" : (chains.augment ? "tensor_augment" : "tensor_photo"); }
 }
 
 int chain_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p, const ChainView& chains, const hipdec_tensor_desc* d, int n, void* out_dev,
@@ -2590,25 +2645,35 @@ int chain_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p
   // the compacted records of the entries whose operation at t is of that kind (a histogram record goes with the apply record of the same entry).
   int steps = 1;
   for (int e = 0; e < n; e++) steps = std::max(steps, chains.n_ops(e));
-  std::vector<std::array<int, KIND_COUNT>> count((size_t)steps, std::array<int, KIND_COUNT>{0, 0, 0, 0});
+  // (the recipe surface: an affine step is three more kinds, one per warp filter, with records of their own behind the step's others)
+  std::vector<std::array<int, KIND_COUNT>> count((size_t)steps, std::array<int, KIND_COUNT>{});
   std::vector<int> blur_r((size_t)steps, 0);   // the step's largest box radius
+  size_t n_tables = 0;                         // affine steps on Pillow's NEAREST scale path: w + h indices each, behind all records
+  uint64_t affine_steps = 0;
   for (int e = 0; e < n; e++)
     for (int t = 0; t < std::max(chains.n_ops(e), 1); t++) {
+      if (const hipdec_recipe_affine* a = step_affine(chains, e, t)) {
+        count[(size_t)t][affine_kind(a)]++;
+        affine_steps++;
+        if (a->filter == HIPDEC_SCALE_NEAREST && warp_scale_only(a->map.m)) n_tables++;
+        continue;
+      }
       const int op = chains.n_ops(e) ? chains.op(e, t).op : PHOTO_NONE;
       count[(size_t)t][chain_kind(op)]++;
       if (photo_needs_statistics(op)) count[(size_t)t][KIND_HIST]++;
     }
-  size_t records = 0;
+  size_t records = 0;   // in units of a PhotoEntry
   int max_hist = 0;
   for (int t = 0; t < steps; t++) {
-    for (int k = 0; k < KIND_COUNT; k++) records += (size_t)count[(size_t)t][k];
+    for (int k = 0; k < KIND_COUNT; k++) records += (size_t)count[(size_t)t][k] * kind_units(k);
     max_hist = std::max(max_hist, count[(size_t)t][KIND_HIST]);
   }
+  const size_t table_ints = (size_t)w + (size_t)h;
   // the work memory: up to two ping-pong buffers of n samples, then the histograms of the step with the most of them
   const int n_pp = std::min(steps - 1, 2);
   const size_t pp_bytes = ((size_t)n * sample + 255) & ~(size_t)255, hist_bytes = (size_t)max_hist * 4 * 256 * sizeof(uint32_t);
   static_assert(sizeof(PhotoEntry) == sizeof(AugmentEntry), "a step's records share one table");
-  const size_t work_bytes = (size_t)n_pp * pp_bytes + hist_bytes, bytes = records * sizeof(PhotoEntry);
+  const size_t work_bytes = (size_t)n_pp * pp_bytes + hist_bytes, bytes = records * sizeof(PhotoEntry) + n_tables * table_ints * sizeof(int32_t);
   const bool grow_work = st.work_bytes < work_bytes;
   if (int rc = warp_state_order(st.base, s, grow_work || st.base.table.dev_bytes < bytes)) return rc;
   if (grow_work) {
@@ -2620,8 +2685,10 @@ int chain_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p
   uint8_t* pp[2] = {(uint8_t*)st.work, (uint8_t*)st.work + pp_bytes};
   uint32_t* hist = (uint32_t*)((uint8_t*)st.work + (size_t)n_pp * pp_bytes);
   std::vector<uint8_t> host(bytes);
-  std::vector<size_t> first((size_t)steps);   // the step's first record: its apply records, then its histogram, hue and blur records
-  size_t at = 0;
+  std::vector<size_t> first((size_t)steps);   // the step's first record: its apply records, then its histogram, hue, blur and affine records
+  int32_t* host_tables = (int32_t*)(host.data() + records * sizeof(PhotoEntry));
+  const int32_t* dev_tables = (const int32_t*)((const uint8_t*)st.base.table.dev + records * sizeof(PhotoEntry));
+  size_t at = 0, tables_at = 0;
   for (int t = 0; t < steps; t++) {
     first[(size_t)t] = at;
     const std::array<int, KIND_COUNT>& cnt = count[(size_t)t];
@@ -2629,13 +2696,43 @@ int chain_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p
     PhotoEntry* stat = apply + cnt[KIND_APPLY];
     AugmentEntry* hue = (AugmentEntry*)(stat + cnt[KIND_HIST]);
     AugmentEntry* blur = hue + cnt[KIND_HUE];
-    int ia = 0, ih = 0, iu = 0, ib = 0;
+    WarpEntry* affine[3];   // by kind: nearest, bilinear, bicubic
+    affine[0] = (WarpEntry*)(blur + cnt[KIND_BLUR]);
+    affine[1] = affine[0] + cnt[KIND_AFFINE_NEAREST];
+    affine[2] = affine[1] + cnt[KIND_AFFINE_BILINEAR];
+    int ia = 0, ih = 0, iu = 0, ib = 0, iw[3] = {0, 0, 0};
     for (int e = 0; e < n; e++) {
       const int len = std::max(chains.n_ops(e), 1);
       if (t >= len) continue;
       const uint8_t* src = t == 0 ? (const uint8_t*)src_dev + (size_t)e * sample : pp[(t - 1) & 1] + (size_t)e * sample;
       const int last = t == len - 1;
       uint8_t* dst = last ? (uint8_t*)out_dev + (size_t)e * out_entry : pp[t & 1] + (size_t)e * sample;
+      if (const hipdec_recipe_affine* a = step_affine(chains, e, t)) {   // warp_launch's record, the sample's size both ways, `last` in the reserved word
+        WarpEntry E;
+        memset(&E, 0, sizeof(E));
+        E.src = src; E.o0 = dst;
+        const double* m = a->map.m;
+        for (int i = 0; i < 6; i++) E.m[i] = m[i];
+        if (a->filter != HIPDEC_SCALE_NEAREST) {
+          E.path = WARP_PATH_DOUBLE;
+        } else if (warp_scale_only(m)) {
+          E.path = WARP_PATH_TABLE;
+          warp_scale_table(m[2], m[0], w, host_tables + tables_at * table_ints);
+          warp_scale_table(m[5], m[4], h, host_tables + tables_at * table_ints + (size_t)w);
+          E.xt = dev_tables + tables_at * table_ints;
+          E.yt = E.xt + w;
+          tables_at++;
+        } else {
+          E.path = WARP_PATH_FIXED;
+          warp_fixed_values(m, E.A);
+        }
+        E.domain = HIPDEC_FILL_COMPONENT;
+        for (int c = 0; c < 3; c++) E.value[c] = (float)a->fill[c];
+        E.reserved = last;
+        const int f = affine_kind(a) - KIND_AFFINE_NEAREST;
+        affine[f][iw[f]++] = E;
+        continue;
+      }
       const int op = chains.n_ops(e) ? chains.op(e, t).op : PHOTO_NONE;
       const double value = chains.n_ops(e) ? chains.op(e, t).value : 0.0;
       if (chain_kind(op) == KIND_APPLY) {
@@ -2661,7 +2758,7 @@ int chain_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p
         }
       }
     }
-    for (int k = 0; k < KIND_COUNT; k++) at += (size_t)cnt[k];
+    for (int k = 0; k < KIND_COUNT; k++) at += (size_t)cnt[k] * kind_units(k);
   }
   if (int rc = blocks_upload(st.base.table, host, s)) return rc;
   PhotoCall c;
@@ -2676,6 +2773,10 @@ int chain_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p
   bc.p = c;
   bc.tiles_x = (uint32_t)((w + kBlurTC - 1) / kBlurTC);
   bc.tiles = bc.tiles_x * (uint32_t)((h + kBlurTR - 1) / kBlurTR);
+  WarpCall wc;   // the affine steps': the source and the output are the sample's size
+  memset(&wc, 0, sizeof(wc));
+  wc.sw = w; wc.sh = h; wc.ow = w; wc.oh = h; wc.nhwc = c.nhwc; wc.tiles_x = c.tiles_x; wc.tiles = c.tiles;
+  for (int k = 0; k < 3; k++) { wc.scale[k] = d->scale[k]; wc.bias[k] = d->bias[k]; }
   const PhotoEntry* dev = (const PhotoEntry*)st.base.table.dev;
   uint64_t launches = 0;
   bool known = true;
@@ -2711,14 +2812,29 @@ int chain_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p
       });
       launches++;
     }
+    const WarpEntry* affine = (const WarpEntry*)(blur + cnt[KIND_BLUR]);
+    for (int f = 0; f < 3 && known; f++) {   // nearest, bilinear, bicubic: the step's affine records of that filter
+      const int na = cnt[KIND_AFFINE_NEAREST + f];
+      if (!na) continue;
+      dim3 grid((unsigned)((uint64_t)wc.tiles * (uint64_t)na));   // (chain_check: below 2^31)
+      known = dispatch_dtype(d->dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (f == 0) hipLaunchKernelGGL((k_recipe_affine_nearest<DT>), grid, block, 0, s, affine, wc);
+        else if (f == 1) hipLaunchKernelGGL((k_recipe_affine_bilinear<DT>), grid, block, 0, s, affine, wc);
+        else hipLaunchKernelGGL((k_recipe_affine_bicubic<DT>), grid, block, 0, s, affine, wc);
+      });
+      launches++;
+      affine += na;
+    }
   }
-  if (!known) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown dtype %d", chains.augment ? "tensor_augment" : "tensor_photo", d->dtype);
+  if (!known) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: unknown dtype %d", chain_stage_name(chains), d->dtype);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "%s kernel launch: %s", chains.augment ? "augment" : "photo", hipGetErrorString(e));
+  if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "%s kernel launch: %s", chains.recipe ? "recipe" : (chains.augment ? "augment" : "photo"), hipGetErrorString(e));
   if (!st.base.done) HIPDEC_CHECK_HIP(hipEventCreateWithFlags(&st.base.done, hipEventDisableTiming));
   HIPDEC_CHECK_HIP(hipEventRecord(st.base.done, s));
   st.base.last = s;
-  if (chains.augment) { g_augment_calls++; g_augment_entries += (uint64_t)n; g_augment_launches += launches; }
+  if (chains.recipe) { g_recipe_calls++; g_recipe_entries += (uint64_t)n; g_recipe_launches += launches; g_recipe_affine_steps += affine_steps; }
+  else if (chains.augment) { g_augment_calls++; g_augment_entries += (uint64_t)n; g_augment_launches += launches; }
   else { g_photo_calls++; g_photo_entries += (uint64_t)n; g_photo_launches += launches; }
   return 0;
 }
@@ -2866,6 +2982,20 @@ void hipdec_augment_stats(uint64_t* calls, uint64_t* entries, uint64_t* launches
   if (calls) *calls = g_augment_calls.load();
   if (entries) *entries = g_augment_entries.load();
   if (launches) *launches = g_augment_launches.load();
+}
+
+int hipdec_tensor_recipe(const void* src_dev, size_t src_bytes, const hipdec_photo_desc* photo, const hipdec_augment_chain* chains,
+                         const hipdec_recipe_affine* affines, int n_affines, const hipdec_tensor_desc* desc, int n, void* out_dev, size_t out_bytes, void* stream)
+{
+  return tensor_chain_stage("tensor_recipe", src_dev, src_bytes, photo, recipe_view(chains, affines, n_affines), desc, n, out_dev, out_bytes, stream);
+}
+
+void hipdec_recipe_stats(uint64_t* calls, uint64_t* entries, uint64_t* launches, uint64_t* affine_steps)
+{
+  if (calls) *calls = g_recipe_calls.load();
+  if (entries) *entries = g_recipe_entries.load();
+  if (launches) *launches = g_recipe_launches.load();
+  if (affine_steps) *affine_steps = g_recipe_affine_steps.load();
 }
 
 int hipdec_gaussian_box(double radius, int* r, uint32_t* ww, uint32_t* fw)

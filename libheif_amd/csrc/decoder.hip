@@ -1343,6 +1343,14 @@ int hipdec_batch_to_tensor_augmented(hipdec_batch* b, const hipdec_tensor_desc* 
   return batch_to_tensor_two_stage("to_tensor_augmented", b, PhotoStage{photo, chain_view(chains)}, desc, entries, orientations, n_entries, out_dev, out_bytes, stream);
 }
 
+int hipdec_batch_to_tensor_recipe(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                  const hipdec_photo_desc* photo, const hipdec_augment_chain* chains, const hipdec_recipe_affine* affines, int n_affines,
+                                  int n_entries, void* out_dev, size_t out_bytes, void* stream)
+{
+  return batch_to_tensor_two_stage("to_tensor_recipe", b, PhotoStage{photo, recipe_view(chains, affines, n_affines)}, desc, entries, orientations, n_entries, out_dev,
+                                   out_bytes, stream);
+}
+
 int hipdec_batch_to_tensor_packed(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
                                   const hipdec_tensor_sample* samples, const hipdec_tensor_patches* patches, int n_entries, void* out_dev, size_t out_bytes, void* stream)
 {

@@ -438,6 +438,14 @@ int hipdec_album_to_tensor_augmented(hipdec_album* a, const hipdec_tensor_desc* 
   return album_to_tensor_two_stage("album_to_tensor_augmented", a, PhotoStage{photo, chain_view(chains)}, desc, entries, orientations, n_entries, out_dev, out_bytes, stream);
 }
 
+int hipdec_album_to_tensor_recipe(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                  const hipdec_photo_desc* photo, const hipdec_augment_chain* chains, const hipdec_recipe_affine* affines, int n_affines,
+                                  int n_entries, void* out_dev, size_t out_bytes, void* stream)
+{
+  return album_to_tensor_two_stage("album_to_tensor_recipe", a, PhotoStage{photo, recipe_view(chains, affines, n_affines)}, desc, entries, orientations, n_entries,
+                                   out_dev, out_bytes, stream);
+}
+
 int hipdec_album_to_rgb_scaled_oriented_all(hipdec_album* a, int out_chroma, const int* orientations, const int* out_widths, const int* out_heights, int filter,
                                             void* const* outs_dev, const size_t* out_strides, void* stream)
 {

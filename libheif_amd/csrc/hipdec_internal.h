@@ -163,6 +163,8 @@ void photo_state_free(PhotoState& st);
 // compacted per kind - apply, histogram, hue, blur - with at most one launch each.  The state, the scratch and the work memory are a PhotoState.
 struct ChainView {             // hipdec_photo_chain and hipdec_augment_chain share their head: n_ops, reserved, ops[]
   const void* base; size_t stride; int max_ops; bool augment;
+  bool recipe = false;         // the recipe surface (hipdec_tensor_recipe): the augment view plus HIPDEC_RECIPE_AFFINE steps into affines[0 .. n_affines)
+  const hipdec_recipe_affine* affines = nullptr; int n_affines = 0;
   const uint8_t* at(int e) const { return (const uint8_t*)base + (size_t)e * stride; }
   int n_ops(int e) const { return ((const int*)at(e))[0]; }
   int reserved(int e) const { return ((const int*)at(e))[1]; }
@@ -173,6 +175,14 @@ static_assert(offsetof(hipdec_photo_chain, ops) == offsetof(hipdec_augment_chain
               "ChainView reads both chain types through their common head");
 inline ChainView chain_view(const hipdec_photo_chain* c) { return ChainView{c, sizeof(hipdec_photo_chain), HIPDEC_PHOTO_MAX_OPS, false}; }
 inline ChainView chain_view(const hipdec_augment_chain* c) { return ChainView{c, sizeof(hipdec_augment_chain), HIPDEC_AUGMENT_MAX_OPS, true}; }
+// Recipe tensor output (color.hip k_recipe_affine_* beside the photo and augment kernels, include/heif_hipdec.h hipdec_tensor_recipe): the augment stage
+// with affine steps - three more kinds of record per step, one per warp filter, each a WarpEntry whose `reserved` word is the `last` flag.
+static_assert(sizeof(hipdec_recipe_affine) == 64 && offsetof(hipdec_recipe_affine, filter) == 48 && offsetof(hipdec_recipe_affine, fill) == 52,
+              "hipdec_recipe_affine has no padding");
+inline ChainView recipe_view(const hipdec_augment_chain* c, const hipdec_recipe_affine* affines, int n_affines)
+{
+  return ChainView{c, sizeof(hipdec_augment_chain), HIPDEC_AUGMENT_MAX_OPS, true, true, affines, n_affines};
+}
 int chain_check(const char* who, const hipdec_photo_desc* p, const ChainView& chains, const hipdec_tensor_desc* d, int n);
 int chain_launch(PhotoState& st, const void* src_dev, const hipdec_photo_desc* p, const ChainView& chains, const hipdec_tensor_desc* d, int n, void* out_dev,
                  hipStream_t s);

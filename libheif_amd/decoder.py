@@ -116,6 +116,14 @@ def _bind(lib):
         lib.hipdec_augment_stats.restype = None
         lib.hipdec_augment_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
         lib.hipdec_gaussian_box.argtypes = [C.c_double, C.POINTER(ci), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    if hasattr(lib, "hipdec_tensor_recipe"):   # (likewise: the recipe stage)
+        lib.hipdec_tensor_recipe.argtypes = [vp, sz, C.POINTER(PhotoDesc), C.POINTER(AugmentChain), C.POINTER(RecipeAffine), ci, C.POINTER(TensorDesc), ci, vp, sz, vp]
+        recipe = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), C.POINTER(ci), C.POINTER(PhotoDesc), C.POINTER(AugmentChain), C.POINTER(RecipeAffine), ci, ci,
+                  vp, sz, vp]
+        lib.hipdec_batch_to_tensor_recipe.argtypes = recipe
+        lib.hipdec_album_to_tensor_recipe.argtypes = recipe
+        lib.hipdec_recipe_stats.restype = None
+        lib.hipdec_recipe_stats.argtypes = [C.POINTER(C.c_uint64)] * 4
     if hasattr(lib, "hipdec_clips_create"):   # (tools/ab_bench.sh loads an older branch's library through this module: it has no clips, and Clips() says so)
         lib.hipdec_clips_create.argtypes = [C.POINTER(vp), ci, C.POINTER(ci), C.POINTER(C.c_char_p), C.POINTER(sz), C.c_uint64]
         lib.hipdec_clips_free.argtypes = [vp]
@@ -204,6 +212,11 @@ class PhotoDesc(C.Structure):
 class AugmentChain(C.Structure):
     """hipdec_augment_chain: up to AUGMENT_MAX_OPS operations, applied in order"""
     _fields_ = [("n_ops", C.c_int), ("reserved", C.c_int), ("ops", PhotoOp * 8)]
+
+
+class RecipeAffine(C.Structure):
+    """hipdec_recipe_affine: the map, the warp filter and Pillow's fillcolor of one affine step of a recipe chain"""
+    _fields_ = [("map", TensorMap), ("filter", C.c_int), ("fill", C.c_int * 3)]
 
 
 class ClipFrame(C.Structure):
@@ -807,6 +820,91 @@ def _to_tensor_augmented(self, lib_call, size, chains, entries, orientations, fi
     return _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
 
 
+# the recipe stage (hipdec_tensor_recipe): augment chains with affine steps - RandAugment / TrivialAugment / AutoAugment per sample in one call
+RECIPE_AFFINE = 32
+RECIPE_OPS = dict(AUGMENT_OPS, affine=RECIPE_AFFINE)
+
+
+def shear_matrix(sx, sy=0.0):
+    """(1, sx, 0, sy, 1, 0): PIL's AFFINE data of timm's and torchvision's PIL-path ShearX (sy = 0) and ShearY (sx = 0), exact - the literal tuple they hand
+    to Image.transform.  (The library's own statement of that convention: neither timm nor torchvision is installed where this library is tested; the
+    transform itself is pinned to Pillow.)"""
+    return (1.0, float(sx), 0.0, float(sy), 1.0, 0.0)
+
+
+def translate_matrix(tx, ty=0.0):
+    """(1, 0, tx, 0, 1, ty): PIL's AFFINE data of timm's and torchvision's PIL-path TranslateX / TranslateY by tx / ty pixels, exact (the library's own
+    statement of that convention, as shear_matrix)"""
+    return (1.0, 0.0, float(tx), 0.0, 1.0, float(ty))
+
+
+def recipe_affine(map, filter=SCALE_BILINEAR, fill=0):
+    """hipdec_recipe_affine: PIL's AFFINE data (six numbers or a TensorMap), the warp filter of this operation (SCALE_NEAREST, SCALE_BILINEAR or
+    SCALE_BICUBIC) and Pillow's fillcolor - one integer 0 .. 255 for all channels, or three"""
+    fill = [int(fill)] * 3 if isinstance(fill, (int, np.integer)) else [int(v) for v in fill]
+    if len(fill) != 3:
+        raise ValueError("a fill is one integer or three, not %r" % (fill,))
+    return RecipeAffine(tensor_maps([map])[0], int(filter), (C.c_int * 3)(*fill))
+
+
+def recipe_chain(*ops, affines=None):
+    """(chain, affines): a hipdec_augment_chain for the recipe stage from up to AUGMENT_MAX_OPS operations, applied in order - augment_chain's operations
+    and ("affine", map, filter, fill) as recipe_affine takes them (filter and fill may be left out) -, and the list of RecipeAffine records its affine
+    steps index.  Pass the list of an earlier chain as `affines` to collect the records of all chains of a call in one list."""
+    if len(ops) > AUGMENT_MAX_OPS:
+        raise ValueError("a chain has at most %d operations, not %d" % (AUGMENT_MAX_OPS, len(ops)))
+    affines = [] if affines is None else affines
+    ch = AugmentChain()
+    ch.n_ops = len(ops)
+    for k, o in enumerate(ops):
+        o = (o,) if isinstance(o, (str, int)) else tuple(o)
+        if isinstance(o[0], str) and o[0].lower() not in RECIPE_OPS:
+            raise ValueError("unknown recipe operation %r" % (o[0],))
+        op = RECIPE_OPS[o[0].lower()] if isinstance(o[0], str) else int(o[0])
+        if op == RECIPE_AFFINE:
+            if not 2 <= len(o) <= 4:
+                raise ValueError("an affine operation is (\"affine\", map[, filter[, fill]]), not %r" % (o,))
+            affines.append(o[1] if isinstance(o[1], RecipeAffine) and len(o) == 2 else recipe_affine(*o[1:]))
+            ch.ops[k].op, ch.ops[k].value = op, float(len(affines) - 1)
+            continue
+        if not 1 <= len(o) <= 2:
+            raise ValueError("an operation is a name or (name, value), not %r" % (o,))
+        ch.ops[k].op = op
+        ch.ops[k].value = float(o[1]) if len(o) == 2 else 0.0
+    return ch, affines
+
+
+def recipe_chains(chains, n=None):
+    """(a ctypes array of hipdec_augment_chain, a ctypes array of hipdec_recipe_affine, n_affines) from sequences of operations (recipe_chain's
+    arguments): what the recipe entry points take"""
+    chains = list(chains)
+    if n is not None and len(chains) != n:
+        raise ValueError("%d chains for %d entries" % (len(chains), n))
+    arr = (AugmentChain * max(len(chains), 1))()
+    affines = []
+    for k, ch in enumerate(chains):
+        arr[k] = recipe_chain(*ch, affines=affines)[0]
+    aarr = (RecipeAffine * max(len(affines), 1))(*affines)
+    return arr, aarr, len(affines)
+
+
+def recipe_stats():
+    """(recipe calls that wrote anything, the entries they wrote, all kernel launches of the stage, the affine steps among the entries' steps) since load"""
+    lib = _bind(load_library())
+    v = [C.c_uint64() for _ in range(4)]
+    lib.hipdec_recipe_stats(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def _to_tensor_recipe(self, lib_call, size, chains, entries, orientations, filter, dtype, layout, mean, std, scale, bias, out, stream):
+    n = self.n if entries is None else len(entries)
+    pd = photo_desc(size)
+    carr, aarr, n_aff = recipe_chains(chains, n)
+    codes = None if orientations is None else _orientation_array(orientations, n)
+    call = lambda h, desc, arr, n_, ptr, room, stream_: lib_call(h, desc, arr, codes, C.byref(pd), carr, aarr, n_aff, n_, ptr, room, stream_)
+    return _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
+
+
 def fit_within(width, height, size):
     """The thumbnail size examples/heif_thumbnailer.cc:172-186 computes: the image as it is when both sides fit into `size`, else the longer
     side becomes `size` and the other one follows with integer division (which may give 0: the thumbnailer refuses that, and so does
@@ -1162,6 +1260,15 @@ class Batch:
         return _to_tensor_augmented(self, self._lib.hipdec_batch_to_tensor_augmented, size, chains, entries, orientations, filter, dtype, layout, mean, std,
                                     scale, bias, out, stream)
 
+    def to_tensor_recipe(self, size, chains, entries=None, filter=SCALE_BILINEAR, orientations=None, dtype="float16", layout="NCHW", mean=None, std=None,
+                         scale=None, bias=None, out=None, stream=None):
+        """asynchronous: to_tensor_augmented with affine steps inside the chains (hipdec_batch_to_tensor_recipe) - what RandAugment, TrivialAugment and
+        AutoAugment draw per sample: chains[e] is a sequence of operations as recipe_chain takes them, augment_chain's plus ("affine", map, filter, fill) -
+        PIL.Image.transform(size, AFFINE, map, filter, fillcolor=fill) of the 8-bit result of the step before, bit for bit, with the warp filter and the fill
+        per operation (rotate_matrix, shear_matrix, translate_matrix give the maps).  One resize launch, then at most seven launches per chain step."""
+        return _to_tensor_recipe(self, self._lib.hipdec_batch_to_tensor_recipe, size, chains, entries, orientations, filter, dtype, layout, mean, std, scale,
+                                 bias, out, stream)
+
     def to_tensor_packed(self, sizes, entries=None, patch=0, merge=1, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None,
                          filter=SCALE_BOX, orientations=None, offsets=None, out=None, stream=None):
         """asynchronous: every entry at its OWN displayed size sizes[e] = (width, height), all entries in one launch into one 1-D output
@@ -1402,6 +1509,12 @@ class Album:
         return _to_tensor_augmented(self, self._lib.hipdec_album_to_tensor_augmented, size, chains, entries, orientations, filter, dtype, layout, mean, std,
                                     scale, bias, out, stream)
 
+    def to_tensor_recipe(self, size, chains, entries=None, filter=SCALE_BILINEAR, orientations=None, dtype="float16", layout="NCHW", mean=None, std=None,
+                         scale=None, bias=None, out=None, stream=None):
+        """Batch.to_tensor_recipe over the composed photos"""
+        return _to_tensor_recipe(self, self._lib.hipdec_album_to_tensor_recipe, size, chains, entries, orientations, filter, dtype, layout, mean, std, scale,
+                                 bias, out, stream)
+
     def to_tensor_packed(self, sizes, entries=None, patch=0, merge=1, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None,
                          filter=SCALE_BOX, orientations=None, offsets=None, out=None, stream=None):
         """Batch.to_tensor_packed over the composed photos"""
@@ -1499,8 +1612,9 @@ def _tensor_chain_stage(lib_call, make_chains, src, chains, src_size, dtype, lay
     size = (int(src_size[0]), int(src_size[1]))
     pd = photo_desc(size)
     carr = make_chains(chains, n)
+    carr = carr if isinstance(carr, tuple) else (carr,)   # (the recipe stage: the chains, the affine records, their number)
     stage = _WarpStage(lib, n)
-    call = lambda h, desc, arr, n_, ptr, room, stream_: getattr(lib, lib_call)(sptr, sbytes, C.byref(pd), carr, desc, n_, ptr, room, stream_)
+    call = lambda h, desc, arr, n_, ptr, room, stream_: getattr(lib, lib_call)(sptr, sbytes, C.byref(pd), *carr, desc, n_, ptr, room, stream_)
     out = _to_tensor(stage, call, size, None, dtype, layout, mean, std, scale, bias, 0, out, stream)
     return stage.tensor_to_host() if to_host else out
 
@@ -1521,6 +1635,14 @@ def tensor_augment(src, chains, src_size=None, dtype="float16", layout="NCHW", m
     AUGMENT_MAX_OPS operations, hue and Gaussian blur among them.  Everything else as tensor_photo; dtype "uint8" with layout "NHWC" gives samples that
     tensor_warp, tensor_photo and tensor_augment take again."""
     return _tensor_chain_stage("hipdec_tensor_augment", augment_chains, src, chains, src_size, dtype, layout, mean, std, scale, bias, out, stream, to_host)
+
+
+def tensor_recipe(src, chains, src_size=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, out=None, stream=None,
+                  to_host=False):
+    """asynchronous: the recipe stage alone (hipdec_tensor_recipe): tensor_augment with chains as Batch.to_tensor_recipe takes them - affine steps with
+    their own warp filter and fill among the operations.  Everything else as tensor_photo: `out` a DeviceBuffer, or a torch tensor on the current stream;
+    dtype "uint8" with layout "NHWC" gives samples that tensor_warp, tensor_photo, tensor_augment and tensor_recipe take again."""
+    return _tensor_chain_stage("hipdec_tensor_recipe", recipe_chains, src, chains, src_size, dtype, layout, mean, std, scale, bias, out, stream, to_host)
 
 
 def clips_stats():
