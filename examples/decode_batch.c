@@ -29,6 +29,11 @@
  *   ./decode_batch --thumb 256 --recipe 15 color 1.4 item0.hevc   the previews rotated by ANGLE degrees (BILINEAR, black outside) and then through one photometric
  *                                                     operation, both steps in ONE chain, as RandAugment draws them (hipdec_batch_to_tensor_recipe): OP and
  *                                                     VALUE as for --photo; a statistics operation (contrast, autocontrast, equalize) sees the fill pixels
+ *   ./decode_batch --thumb 256 --frame 256 224 item0.hevc   instead of previews, ONE launch writes the evaluation batch: every item resized so that its shorter
+ *                                                     side is RESIZE, then the centred CROP x CROP square of it - torchvision's Resize(RESIZE) -> CenterCrop(CROP),
+ *                                                     hipdec_resize_crop_place and hipdec_batch_to_tensor_framed - as a uint8 N x CROP x CROP x 3 tensor; only the
+ *                                                     square is computed, an item smaller than it is padded with black; RESIZE takes the place of --thumb's N;
+ *                                                     after --orient / --filter, not with the options above
  *   ./decode_batch --album 16 6x8 tile0.hevc ...      the items are TILES: 16 grid photos of 6 x 8 tiles (tile t of photo k is item (k * 48 + t) mod n; the
  *                                                     output is the whole tiled area) composed by ONE launch set and ONE paste launch; prints Mpixel/s
  */
@@ -168,13 +173,20 @@ int main(int argc, char** argv)
     if ((got != 1 && got != 2) || patch < 1 || patch > 256 || merge < 1 || merge > 16) argc = 0;   /* no or a bad P[:M]: usage */
     else { argv += 2; argc -= 2; }
   }
+  int frame_resize = 0, frame_crop = 0;
+  if (thumb && !warp && !photo && !recipe && !augment && !patch && argc >= 2 && !strcmp(argv[1], "--frame")) {
+    frame_resize = argc >= 3 ? atoi(argv[2]) : 0;
+    frame_crop = argc >= 4 ? atoi(argv[3]) : 0;
+    if (frame_resize < 1 || frame_crop < 1) argc = 0;             /* no or a bad RESIZE / CROP: usage */
+    else { argv += 3; argc -= 3; }
+  }
   int tensor = 0;
   if (!thumb && argc >= 2 && !strcmp(argv[1], "--tensor")) {
     tensor = argc >= 3 ? atoi(argv[2]) : 0;
     if (tensor < 1) argc = 0;
     else { argv += 2; argc -= 2; }
   }
-  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] [--warp ANGLE | --photo OP VALUE | --recipe ANGLE OP VALUE | [--hue D] [--blur RADIUS] | --patches P[:M]] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] [--warp ANGLE | --photo OP VALUE | --recipe ANGLE OP VALUE | [--hue D] [--blur RADIUS] | --patches P[:M] | --frame RESIZE CROP] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
   const int n = argc - 1;
   const void** data = (const void**)calloc((size_t)n, sizeof(void*));
   size_t* sizes = (size_t*)calloc((size_t)n, sizeof(size_t));
@@ -215,6 +227,44 @@ int main(int argc, char** argv)
     int* ws = (int*)calloc((size_t)n, sizeof(int));
     int* hs = (int*)calloc((size_t)n, sizeof(int));
     int* codes = (int*)calloc((size_t)n, sizeof(int));
+    if (frame_resize) {                                            /* Resize -> CenterCrop of the whole batch: one framed call, one tensor */
+      hipdec_tensor_desc d;
+      memset(&d, 0, sizeof d);
+      d.width = d.height = frame_crop; d.dtype = HIPDEC_TENSOR_U8; d.layout = HIPDEC_TENSOR_NHWC; d.filter = filter;
+      for (int c = 0; c < 3; c++) d.scale[c] = 1.0f;
+      hipdec_tensor_place* pl = (hipdec_tensor_place*)calloc((size_t)n, sizeof(hipdec_tensor_place));
+      for (int i = 0; i < n; i++) {
+        hipdec_image_info info;
+        hipdec_batch_info(prev, i, &info);
+        const int turned = orient > 0 && (orient & 1);             /* the rule sees the DISPLAYED picture */
+        codes[i] = orient > 0 ? orient : 0;
+        if (hipdec_resize_crop_place(turned ? info.height : info.width, turned ? info.width : info.height, frame_resize, frame_crop, frame_crop, pl + i)) {
+          fprintf(stderr, "%s\n", hipdec_last_error());
+          return 1;
+        }
+      }
+      const size_t bytes = hipdec_tensor_bytes(&d, n), each = bytes / (size_t)n;
+      void* t = bytes ? hipdec_malloc(bytes) : NULL;
+      uint8_t* host = (uint8_t*)malloc(bytes ? bytes : 1);
+      if (!t || !host || hipdec_batch_to_tensor_framed(prev, &d, NULL, codes, pl, NULL, NULL, n, t, bytes, NULL) || hipdec_batch_status(prev) ||
+          hipdec_memcpy_d2h(host, t, bytes)) {
+        fprintf(stderr, "%s\n", hipdec_last_error());
+        return 1;
+      }
+      for (int i = 0; i < n; i++) {
+        unsigned long long sum = 0;
+        for (size_t k = 0; k < each; k++) sum += host[(size_t)i * each + k];
+        printf("%s: %dx%d of the sample resized to %dx%d, at (%d, %d), byte sum %llu\n", argv[1 + i], frame_crop, frame_crop, pl[i].width, pl[i].height, -pl[i].x, -pl[i].y, sum);
+      }
+      uint64_t tiles = 0, skipped = 0;
+      hipdec_framed_stats(NULL, NULL, &tiles, &skipped);
+      printf("framed tensor %dx%dx%dx3 uint8: %llu tiles computed, %llu skipped\n", n, frame_crop, frame_crop, (unsigned long long)tiles, (unsigned long long)skipped);
+      free(host); hipdec_free(t); free(pl);
+      free(ws); free(hs); free(codes);
+      hipdec_batch_free(prev);
+      hipdec_shutdown();
+      return 0;
+    }
     void** outs = (void**)calloc((size_t)n, sizeof(void*));
     size_t* strides = (size_t*)calloc((size_t)n, sizeof(size_t));
     for (int i = 0; i < n; i++) {

@@ -669,6 +669,52 @@ HIPDEC_API int hipdec_letterbox_place(int src_width, int src_height, int canvas_
 /* counters since load: placed calls, their entries, launches of the margin kernel */
 HIPDEC_API void hipdec_placed_stats(uint64_t* calls, uint64_t* entries, uint64_t* margin_launches);
 
+/* ---- framed tensor output: resize-then-crop and crop-with-padding in one launch ------------------------------------------------------------------------
+ * Resize(256) -> CenterCrop(224) (the evaluation pipeline of ImageNet models, CLIP / SigLIP preprocessing), RandomCrop(size, padding, pad_if_needed) and
+ * detection-style jitter all RESIZE the picture and then cut a canvas out of it - or out of it and the padding around it.  An entry's window is a crop of
+ * the stored picture taken BEFORE the resize, which is another operation: the crop rectangle of a resized picture maps back to a non-integer window, and
+ * Pillow clamps the filter support at the edge of what it resizes, so border pixels differ.  The placed calls refuse a rectangle that leaves the canvas.
+ * These calls take it: the rectangle of the resized sample may leave the canvas on any side, and only its visible part is computed and written.
+ *
+ * THE DEFINITION OF THE RESULT.  desc->width x height is the CANVAS of every entry - the crop size.  pl = places[e] is the rectangle of the resized,
+ * DISPLAYED sample in canvas coordinates: pl.x and pl.y may be negative, pl.x + pl.width and pl.y + pl.height may exceed the canvas.  The VISIBLE PART is
+ * the intersection of pl with the canvas.
+ *  - Inside the visible part, canvas element (c, pl.y + Y, pl.x + X) is element (c, Y, X) of what hipdec_batch_to_tensor_oriented writes for the same entry
+ *    (item, window, flip), orientation code, filter, dtype, scale and bias with desc->width / height replaced by pl.width / pl.height.  All four filters, all
+ *    eight codes, all four dtypes and both layouts are taken; windows, flips and the size swap of quarter turns are that call's; whatever it refuses for a
+ *    sample of pl.width x pl.height is refused here with the same status.
+ *  - Everywhere else the canvas holds the fill element of its channel, with both fill domains exactly as in hipdec_batch_to_tensor_placed (fill NULL:
+ *    component 0).  mask_dev (may be NULL): n_entries x height x width uint8, 1 outside the visible part and 0 inside it; every byte of it is written.
+ *  - Every canvas element is written exactly once, and nothing outside out_dev's tensor and the mask is written.
+ * A rectangle inside the canvas gives the bytes of hipdec_batch_to_tensor_placed.  places NULL: every rectangle is the whole canvas and the call is the
+ * placed call with places NULL - with mask_dev NULL as well hipdec_batch_to_tensor_oriented, byte for byte and launch for launch.
+ * Refused before a device is touched, HIPDEC_ERR_INVALID_ARGUMENT naming the entry: a non-positive side; an empty visible part; |x|, |y| or a side above
+ * 2^24 (64-bit host arithmetic cannot overflow below it); a sample of pl.width x pl.height the oriented call's description check refuses.  Fills, domains,
+ * `reserved`, out_bytes and codes are refused as the placed call refuses them.  pl.width * pl.height, or the canvas, above max_image_size_pixels:
+ * HIPDEC_ERR_LIMIT.
+ * Launches: ONE launch of the k_frame_* kernels - the oriented / resampling kernels with a clipping store - for all entries, and the margins and the mask in
+ * ONE launch of k_canvas_margin over the visible rectangles (counted by hipdec_placed_stats' margin_launches); none when every visible part is its whole
+ * canvas and no mask is asked for.  Work follows the visible part: the grid covers the pieces of work - a column tile of P x a block of rows (box: up to 96
+ * columns for 8-bit and 64 for wider samples x 16 rows, or 64 / 32 rows for a quarter turn), a column tile x a band (bilinear / bicubic: up to 64 columns
+ * x 16 rows of P), 256 x 4 displayed pixels (nearest) - from the first to the last one with a visible pixel along either axis; a piece with none loads no
+ * source sample, and inside a piece the box filter accumulates the visible rows of P only.  No scratch memory, no intermediate.
+ * CLIPS.  A frame of a clip is framed through the borrowed batch (hipdec_clips_batch, below) with no further code. */
+HIPDEC_API int hipdec_batch_to_tensor_framed(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                             const hipdec_tensor_place* places, const hipdec_tensor_fill* fill, void* mask_dev, int n_entries, void* out_dev,
+                                             size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_album_to_tensor_framed(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                             const hipdec_tensor_place* places, const hipdec_tensor_fill* fill, void* mask_dev, int n_entries, void* out_dev,
+                                             size_t out_bytes, void* stream);
+/* Host only, 64-bit integer arithmetic: the library's statement of torchvision's Resize(resize) -> CenterCrop((crop_height, crop_width)) on a DISPLAYED
+ * sample of src_width x src_height, as the rectangle of a framed call whose canvas is the crop.  The shorter side becomes `resize`, the longer
+ * floor(resize * long / short).  Per axis, with side the resized side and crop the crop's: side >= crop: offset = -roundhalfeven((side - crop) / 2) (Python's
+ * round()); side < crop: offset = (crop - side) / 2 rounding down (the picture is padded, the smaller half in front).  A non-positive argument, or a side
+ * above 2^24: -1, hipdec_last_error says why. */
+HIPDEC_API int hipdec_resize_crop_place(int src_width, int src_height, int resize, int crop_width, int crop_height, hipdec_tensor_place* out);
+/* counters since load: framed calls, their entries, and from the host's geometry the pieces of work (above) of entries with rectangles that held a visible
+ * pixel and those that held none; tiles + tiles_skipped is the count of the unclipped samples */
+HIPDEC_API void hipdec_framed_stats(uint64_t* calls, uint64_t* entries, uint64_t* tiles, uint64_t* tiles_skipped);
+
 /* ---- packed tensor output: per-sample sizes and patch sequences in one launch ---------------------------------------------------------------------------
  * Native-resolution vision encoders (Qwen2-VL / 2.5-VL, SigLIP2 NaFlex, Pixtral, NaViT-style packing) take no common size: each photo keeps its aspect
  * ratio, is resized to its own w x h - a multiple of the patch size - and the batch is ONE packed sequence of patch tokens, [sum of tokens, 3 * P * P].

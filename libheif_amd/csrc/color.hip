@@ -797,7 +797,18 @@ __device__ __forceinline__ void store_patch4(const OrientedParams& op, const Pat
 // The store policies of the nearest and resampling kernel bodies: the dense one is the store the kernels have had (rows of `pitch` elements), the blocked
 // one writes token order.  A policy is an argument of the body the way LAYOUT is one of rgb_block.
 // Block: the parameter block the kernel reads (the body loads it, as the kernels did); inner(): the block the body works on.
-template <typename Blk> struct DenseStore {
+// shown_*(): does a piece of the sample hold a pixel the policy stores?  Constant true for the dense and the blocked store (their kernels' code does not
+// know the question was asked); the clipping store of the framed output (FrameStore below) answers from the entry's window, and a body skips the loads of
+// a piece that is not shown.  _p: columns / rows of P (the resampler's tiles and bands), _d: of the displayed sample (the nearest kernel's groups and rows).
+struct ShowsEverything {
+  static __device__ __forceinline__ constexpr bool shown_cols_p(int, int) { return true; }
+  static __device__ __forceinline__ constexpr bool shown_rows_p(int, int) { return true; }
+  static __device__ __forceinline__ constexpr bool shown_cols_d(int, int) { return true; }
+  static __device__ __forceinline__ constexpr bool shown_row_d(int) { return true; }
+  static __device__ __forceinline__ constexpr int origin_x() { return 0; }   // what a workgroup adds to blockIdx.x / .y (the framed grid starts at the window)
+  static __device__ __forceinline__ constexpr int origin_y() { return 0; }
+};
+template <typename Blk> struct DenseStore : ShowsEverything {
   typedef Blk Block;
   __device__ __forceinline__ explicit DenseStore(const Blk&) {}
   static __device__ __forceinline__ const Blk& inner(const Blk& k) { return k; }
@@ -808,7 +819,7 @@ template <typename Blk> struct DenseStore {
     store_oriented4<DT>(op, dw, dh, rev, x0, row, npx, R, G, B);
   }
 };
-template <typename Blk> struct PatchStore {   // Blk: PatchParams, or PatchResampleParams - {the dense block `in`, PatchInfo b}
+template <typename Blk> struct PatchStore : ShowsEverything {   // Blk: PatchParams, or PatchResampleParams - {the dense block `in`, PatchInfo b}
   typedef Blk Block;
   const PatchInfo& b;
   __device__ __forceinline__ explicit PatchStore(const Blk& k) : b(k.b) {}
@@ -1057,12 +1068,14 @@ __device__ __forceinline__ void oriented_nearest_body(const typename Store::Bloc
   const ColorParams& p = tp.c;
   const int quarter = op.code & 1, fx = ((op.code >> 1) ^ (op.code >> 2)) & 1, fy = ((op.code >> 1) ^ op.code) & 1;
   const int dw = quarter ? tp.oh : tp.ow, dh = quarter ? tp.ow : tp.oh;   // the displayed size
-  const int X0 = (blockIdx.x * blockDim.x + tx) * 4;
+  const int X0 = ((blockIdx.x + st.origin_x()) * blockDim.x + tx) * 4;
   if (X0 >= dw) return;
   const int npx = min(4, dw - X0);
+  if (!st.shown_cols_d(X0, npx)) return;                  // (the framed store: a group outside the window reads nothing)
   const bool mono = p.arith == AR_MONO;
   const int ra = quarter ? tp.rh : tp.rw, rc = quarter ? tp.rw : tp.rh;   // the window's extent along a displayed row, and across the rows
-  for (int Yd = blockIdx.y * blockDim.y + ty; Yd < dh; Yd += gridDim.y * blockDim.y) {
+  for (int Yd = (blockIdx.y + st.origin_y()) * blockDim.y + ty; Yd < dh; Yd += gridDim.y * blockDim.y) {
+    if (!st.shown_row_d(Yd)) continue;
     const int c = fy ? dh - 1 - Yd : Yd;
     const int sc = (int)((uint64_t)c * (uint64_t)rc / (uint64_t)dh);
     int Y[4], CB[4], CR[4], R[4], G[4], B[4];
@@ -1105,6 +1118,180 @@ template <typename Pix, int DT>
 __global__ __launch_bounds__(256) void k_patch_nearest(const PatchParams* __restrict__ ps)
 {
   oriented_nearest_body<Pix, DT, PatchStore<PatchParams>>(ps, threadIdx.x, threadIdx.y);
+}
+
+// ---- framed tensor output (include/heif_hipdec.h hipdec_batch_to_tensor_framed): the entry's rectangle may leave its canvas, and only the part of the
+// sample on the canvas - the window, hipdec::FrameWindow - is computed and stored.  o0 is where the whole sample's first element would lie (in front of the
+// canvas for a negative offset), pitch and plane are the canvas', as for a placed entry; k_canvas_margin writes everything outside the window.
+// The kernels are siblings of the oriented ones with a clipping store, built as the k_patch_* kernels are: the nearest and resampling bodies take the store
+// as a policy, the box kernel is a sibling text of k_oriented_box.  The window is wave-uniform and comes from the entry's block through scalar loads.
+struct FrameParams { OrientedParams in; hipdec::FrameWindow b; };
+static_assert(sizeof(hipdec::FrameWindow) == 48, "the blocks behind it stay 16-byte multiples");
+
+// store_oriented4 inside the window: a group wholly outside it is neither converted nor stored, a whole group inside it is store_oriented4's (vector stores
+// behind the run-time alignment test), a group the window's edge cuts goes out as element stores - for a quarter turn the resampler's groups run along a
+// column of P, and reversed groups are cut from the other end: both are columns xs .. xs + npx - 1 of displayed row `row` here.
+template <int DT>
+__device__ __forceinline__ void store_frame4(const OrientedParams& op, const hipdec::FrameWindow& f, int dw_, int dh_, int rev, int x0, int row, int npx,
+                                             const int (&R)[4], const int (&G)[4], const int (&B)[4])
+{
+  typedef typename TensorElem<DT>::T E;
+  if (row < f.vy0 || row >= f.vy1) return;
+  const int xs = rev ? dw_ - npx - x0 : x0;   // the group's first column in memory
+  if (xs + npx <= f.vx0 || xs >= f.vx1) return;
+  if (xs >= f.vx0 && xs + npx <= f.vx1) { store_oriented4<DT>(op, dw_, dh_, rev, x0, row, npx, R, G, B); return; }
+  const TensorParams& tp = op.t;
+  const size_t pitch = (size_t)op.pitch, plane = (size_t)op.plane_rows * pitch;
+  HIPDEC_GLOBAL E* o = (HIPDEC_GLOBAL E*)tp.c.o0 + (size_t)row * pitch;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    if (i >= npx) break;
+    const int col = rev ? dw_ - 1 - (x0 + i) : x0 + i;
+    if (col < f.vx0 || col >= f.vx1) continue;
+    const uint32_t r = tensor_elem<DT>(R[i], tp.scale[0], tp.bias[0]), g = tensor_elem<DT>(G[i], tp.scale[1], tp.bias[1]), b = tensor_elem<DT>(B[i], tp.scale[2], tp.bias[2]);
+    if (tp.nhwc) {
+      HIPDEC_GLOBAL E* d = o + (size_t)col * 3;
+      d[0] = (E)r; d[1] = (E)g; d[2] = (E)b;
+    } else {
+      HIPDEC_GLOBAL E* d = o + (size_t)col;
+      d[0] = (E)r; d[plane] = (E)g; d[2 * plane] = (E)b;
+    }
+  }
+}
+
+template <typename Blk> struct FrameStore {   // Blk: FrameParams, or FrameResampleParams - {the dense block `in`, hipdec::FrameWindow b}
+  typedef Blk Block;
+  const hipdec::FrameWindow& f;
+  __device__ __forceinline__ explicit FrameStore(const Blk& k) : f(k.b) {}
+  static __device__ __forceinline__ auto inner(const Blk& k) -> decltype((k.in)) { return k.in; }
+  __device__ __forceinline__ bool shown_cols_p(int x0, int n) const { return x0 + n > f.px0 && x0 < f.px1; }
+  __device__ __forceinline__ bool shown_rows_p(int y0, int n) const { return y0 + n > f.py0 && y0 < f.py1; }
+  __device__ __forceinline__ bool shown_cols_d(int x0, int n) const { return x0 + n > f.vx0 && x0 < f.vx1; }
+  __device__ __forceinline__ bool shown_row_d(int y) const { return y >= f.vy0 && y < f.vy1; }
+  __device__ __forceinline__ int origin_x() const { return f.tx0; }
+  __device__ __forceinline__ int origin_y() const { return f.ty0; }
+  template <int DT>
+  __device__ __forceinline__ void group4(const OrientedParams& op, int dw, int dh, int rev, int x0, int row, int npx, const int (&R)[4], const int (&G)[4],
+                                         const int (&B)[4]) const
+  {
+    store_frame4<DT>(op, f, dw, dh, rev, x0, row, npx, R, G, B);
+  }
+};
+
+__device__ __forceinline__ hipdec::FrameWindow frame_window_late(const FrameParams* q)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(HIPDEC_HOST_EMU)
+  asm volatile("" : "+s"(q));   // (the loads stay behind this point, as patch_info_late's)
+#endif
+  return q->b;
+}
+
+// k_oriented_box with the clipping store.  Its integer stage is k_oriented_box's, statement for statement, over the rows and column tiles of P that hold a
+// visible pixel: a workgroup whose column tile lies outside the window returns before it loads a sample, a block of rows outside it is passed over, and
+// inside a block the rows of P outside the window are not accumulated (their stage rows are never read: the write-out below stores inside the window only).
+//   row-preserving codes:  4-pixel groups through store_frame4.
+//   quarter turns:         k_oriented_box's runs along displayed rows, element by element as there, each element behind the window test.
+// The displayed window is read where the store needs it, behind the box stage (k_patch_box's reason), the window in P in front of it.
+// (the occupancy step is stated as for k_patch_box and k_clip_box)
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(Pix) == 1 ? 4 : 3))) void k_frame_box(const FrameParams* __restrict__ ps)
+{
+  typedef OrientedTile<Pix, DT> T;
+  typedef OrientedStage<T::kNarrow> St;
+  typedef typename TensorElem<DT>::T E;
+  constexpr int RB = T::RB, TC = T::TC;
+  __shared__ typename BoxAcc<Pix>::T colsum[3][kBoxSpan];
+  __shared__ typename St::S stage[RB][TC + 1];
+  const OrientedParams op = ps[blockIdx.z].in;   // wave-uniform: scalar loads into SGPRs
+  const TensorParams& tp = op.t;
+  const ColorParams& p = tp.c;
+  const int tid = threadIdx.x;
+  const int oxA = ((int)blockIdx.x + ps[blockIdx.z].b.tx0) * tp.tile;   // (the grid starts at the first column tile and block of rows with a visible pixel)
+  if (oxA >= tp.ow) return;                               // (the whole workgroup)
+  const int nox = min(tp.tile, tp.ow - oxA);              // <= TC: the host caps the tile
+  const int px0 = ps[blockIdx.z].b.px0, px1 = ps[blockIdx.z].b.px1, py0 = ps[blockIdx.z].b.py0, py1 = ps[blockIdx.z].b.py1;
+  if (oxA + nox <= px0 || oxA >= px1) return;             // no visible pixel in this column tile: nothing is loaded
+  const bool mono = p.arith == AR_MONO;
+  const int quarter = op.code & 1, fx = ((op.code >> 1) ^ (op.code >> 2)) & 1, fy = ((op.code >> 1) ^ op.code) & 1;
+  const int cl = tp.left >> tp.sH, ct = tp.top >> tp.sV;
+  const int cw = ((tp.left + tp.rw - 1) >> tp.sH) - cl + 1, ch = ((tp.top + tp.rh - 1) >> tp.sV) - ct + 1;
+  const int fcw = (p.w + (1 << tp.sH) - 1) >> tp.sH;
+  const BoxPlane pl[3] = {{p.y, p.ys, tp.rw, tp.rh, p.w, tp.left, tp.top}, {p.cb, p.cbs, cw, ch, fcw, cl, ct}, {p.cr, p.crs, cw, ch, fcw, cl, ct}};
+  const int rb = max(1, min((int)op.rb, RB));                  // (the stage has RB rows whatever the block says)
+  for (int yb = ((int)blockIdx.y + ps[blockIdx.z].b.ty0) * rb; yb < tp.oh; yb += gridDim.y * rb) {
+    const int nrows = min(rb, tp.oh - yb);
+    if (yb >= py1) break;                                 // no visible pixel from this block of rows on (uniform over the workgroup)
+    if (yb + nrows <= py0) continue;
+    for (int r = 0; r < nrows; r++) {
+      if (yb + r < py0 || yb + r >= py1) continue;        // a row of P outside the window is not accumulated
+      uint32_t v[3];
+      box_tile<Pix, 3, true>(pl, mono ? 1 : 3, tp.ow, tp.oh, oxA, nox, yb + r, colsum, v);
+      if (tid < nox) {                                    // the owner of column oxA + tid converts its own pixel (four copies of it: one statement of the arithmetic)
+        const int Y[4] = {(int)v[0], (int)v[0], (int)v[0], (int)v[0]}, CB[4] = {(int)v[1], (int)v[1], (int)v[1], (int)v[1]}, CR[4] = {(int)v[2], (int)v[2], (int)v[2], (int)v[2]};
+        int R[4], G[4], B[4];
+        tensor_convert4<Pix>(p, Y, CB, CR, R, G, B);
+        stage[r][tid] = St::pack(R[0], G[0], B[0]);
+      }
+      __syncthreads();                                    // colsum is written again by the next row; after the last one the stage is complete
+    }
+    const hipdec::FrameWindow f = frame_window_late(ps + blockIdx.z);
+    if (!quarter) {
+      const uint32_t ng = ((uint32_t)nox + 3u) >> 2, total = ng * (uint32_t)nrows;
+#pragma unroll 1
+      for (uint32_t idx = (uint32_t)tid; idx < total; idx += 256u) {
+        const uint32_t r = idx / ng, g = idx - r * ng;
+        int R[4], G[4], B[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {                     // (past the tile's last pixel: inside the padded stage row, not stored)
+          const typename St::S s = stage[r][g * 4u + (uint32_t)i];
+          R[i] = St::get(s, 0); G[i] = St::get(s, 1); B[i] = St::get(s, 2);
+        }
+        const int oy = yb + (int)r;
+        store_frame4<DT>(op, f, tp.ow, tp.oh, fx, oxA + (int)g * 4, fy ? tp.oh - 1 - oy : oy, min(4, nox - (int)g * 4), R, G, B);
+      }
+      __syncthreads();                                    // the stage is written again by the next block of rows
+      continue;
+    }
+    // rows yb .. yb + nrows - 1 of P are displayed columns xrun .. xrun + nrows - 1 (in reverse order where fx), column x of P is displayed row Y
+    const uint32_t n = (uint32_t)nrows;
+    const int xrun = fx ? tp.oh - yb - nrows : yb;
+    const size_t pitch = (size_t)op.pitch;
+    HIPDEC_GLOBAL E* o = (HIPDEC_GLOBAL E*)p.o0;
+    if (tp.nhwc) {
+      const uint32_t per = 3u * n, total = per * (uint32_t)nox;
+#pragma unroll 1
+      for (uint32_t idx = (uint32_t)tid; idx < total; idx += 256u) {
+        const uint32_t c = idx / per, e = idx - c * per, j = e / 3u, k = e - 3u * j;
+        const int x = oxA + (int)c;
+        const int Yd = fy ? tp.ow - 1 - x : x, Xd = xrun + (int)j;
+        if (Yd < f.vy0 || Yd >= f.vy1 || Xd < f.vx0 || Xd >= f.vx1) continue;
+        const int val = St::get(stage[fx ? n - 1u - j : j][c], k);
+        o[(size_t)Yd * pitch + (size_t)xrun * 3 + e] = (E)tensor_elem<DT>(val, k == 0 ? tp.scale[0] : (k == 1 ? tp.scale[1] : tp.scale[2]), k == 0 ? tp.bias[0] : (k == 1 ? tp.bias[1] : tp.bias[2]));
+      }
+    } else {
+      const uint32_t total = n * (uint32_t)nox;
+      const size_t plane = (size_t)op.plane_rows * pitch;   // (the canvas' rows)
+#pragma unroll 1
+      for (uint32_t idx = (uint32_t)tid; idx < total; idx += 256u) {
+        const uint32_t c = idx / n, j = idx - c * n;
+        const int x = oxA + (int)c;
+        const int Yd = fy ? tp.ow - 1 - x : x, Xd = xrun + (int)j;
+        if (Yd < f.vy0 || Yd >= f.vy1 || Xd < f.vx0 || Xd >= f.vx1) continue;
+        const typename St::S s = stage[fx ? n - 1u - j : j][c];
+        HIPDEC_GLOBAL E* d = o + (size_t)Yd * pitch + (size_t)Xd;
+        d[0] = (E)tensor_elem<DT>(St::get(s, 0), tp.scale[0], tp.bias[0]);
+        d[plane] = (E)tensor_elem<DT>(St::get(s, 1), tp.scale[1], tp.bias[1]);
+        d[2 * plane] = (E)tensor_elem<DT>(St::get(s, 2), tp.scale[2], tp.bias[2]);
+      }
+    }
+    __syncthreads();                                      // the stage is written again by the next block of rows
+  }
+}
+
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) void k_frame_nearest(const FrameParams* __restrict__ ps)
+{
+  oriented_nearest_body<Pix, DT, FrameStore<FrameParams>>(ps, threadIdx.x, threadIdx.y);
 }
 
 // ---- placed tensor output (include/heif_hipdec.h hipdec_batch_to_tensor_placed): the oriented / resampling kernels write an entry's sample into its
@@ -1294,9 +1481,10 @@ __device__ __forceinline__ void resample_body(const typename Store::Block* ps, c
   const ColorParams& p = tp.c;
   const int c = tid & (kResTC - 1), rg = tid / kResTC;   // rg: the wave - source row of the chunk in H, row group of the band in V   // rg: the wave - source row of the chunk in H, row group of the band in V
   const int tile = max(1, min(tp.tile, kResTC));
-  const int ox0 = blockIdx.x * tile;
+  const int ox0 = (blockIdx.x + st.origin_x()) * tile;
   if (ox0 >= tp.ow) return;                               // (the whole workgroup)
   const int ncol = min(tile, tp.ow - ox0);
+  if (!st.shown_cols_p(ox0, ncol)) return;                // (the framed store: a column tile outside the window - the whole workgroup, before any load)
   const bool mono = p.arith == AR_MONO;
   const int quarter = op.code & 1, fx = ((op.code >> 1) ^ (op.code >> 2)) & 1, fy = ((op.code >> 1) ^ op.code) & 1;
   HIPDEC_GLOBAL const int32_t* xt = (HIPDEC_GLOBAL const int32_t*)rp.xt;
@@ -1311,8 +1499,9 @@ __device__ __forceinline__ void resample_body(const typename Store::Block* ps, c
   const int cx = ox0 + (hascol ? c : 0);
   const int xa = tp.left + xt[2 * cx], xn = hascol ? xt[2 * cx + 1] : 0;   // this thread's column: its first tap as a plane column, and its tap count
   HIPDEC_GLOBAL const int32_t* kx = xk + (size_t)cx * (size_t)rp.xstride;
-  for (int oy0 = blockIdx.y * kResTR; oy0 < tp.oh; oy0 += gridDim.y * kResTR) {
+  for (int oy0 = (blockIdx.y + st.origin_y()) * kResTR; oy0 < tp.oh; oy0 += gridDim.y * kResTR) {
     const int nrow = min(kResTR, tp.oh - oy0);
+    if (!st.shown_rows_p(oy0, nrow)) continue;            // (the framed store: a band outside the window is not staged; uniform over the workgroup)
     const int srow0 = yt[2 * oy0], srow1 = yt[2 * (oy0 + nrow - 1)] + yt[2 * (oy0 + nrow - 1) + 1];   // window rows [srow0, srow1) hold every tap of the band
     int ymin[4], yn[4], acc[4][3];
 #pragma unroll
@@ -1413,6 +1602,15 @@ template <typename Pix, int DT>
 __global__ __launch_bounds__(256) void k_patch_resample(const PatchResampleParams* __restrict__ ps)
 {
   resample_body<Pix, DT, PatchStore<PatchResampleParams>>(ps, threadIdx.x);
+}
+
+// the resampler of a framed entry: column tiles and bands of P with no visible pixel are not staged (the body asks the store), the write-out's groups go
+// through store_frame4
+struct FrameResampleParams { ResampleParams in; hipdec::FrameWindow b; };
+template <typename Pix, int DT>
+__global__ __launch_bounds__(256) void k_frame_resample(const FrameResampleParams* __restrict__ ps)
+{
+  resample_body<Pix, DT, FrameStore<FrameResampleParams>>(ps, threadIdx.x);
 }
 
 template <typename Pix>
@@ -1768,6 +1966,8 @@ struct CapturedTensor {
   int patch, merge;  // patch > 0: a patch sequence, for the k_patch_* kernels
   int tpatch;        // clips: frames per token
   int strided;       // clips: the entry goes to k_clip_box
+  int framed;        // for the k_frame_* kernels: vis is the window in displayed coordinates of the sample
+  int vis[4];
 };
 thread_local std::vector<CapturedTensor> t_captured_tensor;
 
@@ -1991,7 +2191,8 @@ int record_tensor(const ColorParams& p)
   }
   t_tensor.on = false;   // taken
   t_captured_tensor.push_back(CapturedTensor{tp, sizeof(Pix) == 2, r.oriented ? 1 : 0, r.code, (uint64_t)r.pitch, r.plane_rows, r.resample, r.patch, r.merge, r.tpatch > 1 ? r.tpatch : 1,
-                                             r.oriented && !r.resample && !r.patch && r.strided_box ? 1 : 0});
+                                             r.oriented && !r.resample && !r.patch && r.strided_box ? 1 : 0, r.oriented && !r.patch && r.framed ? 1 : 0,
+                                             {r.frame_vis[0], r.frame_vis[1], r.frame_vis[2], r.frame_vis[3]}});
   return 0;
   }
 }
@@ -2192,6 +2393,38 @@ PatchInfo patch_info_of(const CapturedTensor& c)
 std::atomic<uint64_t> g_packed_calls{0}, g_packed_entries{0}, g_packed_patch_entries{0};
 std::atomic<uint64_t> g_clip_box_entries{0};
 
+// the window of a framed entry (hipdec::FrameWindow): the displayed one as recorded, and the columns and rows of P it covers - with code = r + 4 * m
+// (OrientedParams above) a displayed axis is an axis of P, forward or reversed: X in [lo, hi) reversed over n is n - hi .. n - lo
+hipdec::FrameWindow frame_window_of(const CapturedTensor& c)
+{
+  hipdec::FrameWindow f;
+  memset(&f, 0, sizeof(f));
+  f.vx0 = c.vis[0]; f.vy0 = c.vis[1]; f.vx1 = c.vis[2]; f.vy1 = c.vis[3];
+  const int quarter = c.code & 1, fx = ((c.code >> 1) ^ (c.code >> 2)) & 1, fy = ((c.code >> 1) ^ c.code) & 1;
+  auto back = [](int lo, int hi, int n, int flip, int* a, int* b) { *a = flip ? n - hi : lo; *b = flip ? n - lo : hi; };
+  if (!quarter) { back(f.vx0, f.vx1, c.p.ow, fx, &f.px0, &f.px1); back(f.vy0, f.vy1, c.p.oh, fy, &f.py0, &f.py1); }
+  else { back(f.vx0, f.vx1, c.p.oh, fx, &f.py0, &f.py1); back(f.vy0, f.vy1, c.p.ow, fy, &f.px0, &f.px1); }
+  return f;
+}
+
+// hipdec_framed_stats: the pieces of work of the framed entries - a column tile x a block of rows (box), a column tile x a band (the resampling filters),
+// a workgroup's 256 x 4 displayed pixels (nearest) - that hold a visible pixel, and those that hold none: the host's geometry, counted per launch
+std::atomic<uint64_t> g_framed_calls{0}, g_framed_entries{0}, g_framed_tiles{0}, g_framed_skipped{0};
+struct FrameTileCount {
+  uint64_t tiles = 0, skipped = 0;
+  int max_x = 0, max_y = 0;   // the most pieces with a visible pixel an entry has along either axis: the grid
+  // nx x ny samples in pieces of ux x uy, of which [x0, x1) x [y0, y1) is visible; sets the entry's origin
+  void add(hipdec::FrameWindow* f, int nx, int ux, int x0, int x1, int ny, int uy, int y0, int y1)
+  {
+    f->tx0 = x0 / ux; f->ty0 = y0 / uy;
+    const int hx = (x1 - 1) / ux - f->tx0 + 1, hy = (y1 - 1) / uy - f->ty0 + 1;
+    const uint64_t all = (uint64_t)((nx + ux - 1) / ux) * (uint64_t)((ny + uy - 1) / uy), hit = (uint64_t)hx * (uint64_t)hy;
+    tiles += hit; skipped += all - hit;
+    max_x = hx > max_x ? hx : max_x; max_y = hy > max_y ? hy : max_y;
+  }
+  void commit() const { g_framed_tiles += tiles; g_framed_skipped += skipped; }
+};
+
 // the oriented form of color_tensor_launch: entries of all codes and (RGB form) sizes share the launch, so the grid covers the largest of each extent
 int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int filter, int dtype, hipStream_t s)
 {
@@ -2219,9 +2452,11 @@ int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
     quarter += (uint64_t)(c.code & 1);
   }
   const bool blocked = caps[0].patch > 0;   // (a call's entries are all patch sequences, or none is): PatchParams blocks for the k_patch_* kernels
-  const size_t block_bytes = blocked ? sizeof(PatchParams) : sizeof(OrientedParams);
+  const bool framed = !blocked && caps[0].framed;   // (... are all framed, or none is): FrameParams blocks for the k_frame_* kernels
+  const size_t block_bytes = blocked ? sizeof(PatchParams) : (framed ? sizeof(FrameParams) : sizeof(OrientedParams));
   const size_t bytes = caps.size() * block_bytes;
   std::vector<uint8_t> host(bytes);
+  FrameTileCount frame_tiles;
   for (size_t i = 0; i < caps.size(); i++) {
     OrientedParams op;
     memset(&op, 0, sizeof(op));
@@ -2231,6 +2466,17 @@ int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
       const PatchInfo b = patch_info_of(caps[i]);
       memcpy(host.data() + i * block_bytes + offsetof(PatchParams, b), &b, sizeof(b));
     }
+    if (framed) {
+      hipdec::FrameWindow f = frame_window_of(caps[i]);
+      const int dw = caps[i].code & 1 ? caps[i].p.oh : caps[i].p.ow, dh = caps[i].code & 1 ? caps[i].p.ow : caps[i].p.oh;
+      if (filter == HIPDEC_SCALE_BOX) frame_tiles.add(&f, caps[i].p.ow, caps[i].p.tile, f.px0, f.px1, caps[i].p.oh, block_rows(caps[i]), f.py0, f.py1);
+      else frame_tiles.add(&f, dw, 256, f.vx0, f.vx1, dh, 4, f.vy0, f.vy1);
+      memcpy(host.data() + i * block_bytes + offsetof(FrameParams, b), &f, sizeof(f));
+    }
+  }
+  if (framed) {   // the grid covers the pieces of work with a visible pixel (nearest: their 256 x 4 displayed pixels)
+    max_tiles = frame_tiles.max_x; max_blocks = frame_tiles.max_y;
+    max_dw = frame_tiles.max_x * 256; max_dh = frame_tiles.max_y * 4;
   }
   if (int rc = blocks_reserve(st, bytes)) return rc;
   if (int rc = blocks_upload(st, host, s)) return rc;
@@ -2251,12 +2497,14 @@ int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
           typedef typename decltype(pix)::type Pix;
           constexpr int DT = decltype(dt)::value;
           if (blocked) launch_box_or_nearest(filter, k_patch_box<Pix, DT>, k_patch_nearest<Pix, DT>, max_tiles, max_blocks, max_dw, max_dh, n, s, (const PatchParams*)st.dev + first);
+          else if (framed) launch_box_or_nearest(filter, k_frame_box<Pix, DT>, k_frame_nearest<Pix, DT>, max_tiles, max_blocks, max_dw, max_dh, n, s, (const FrameParams*)st.dev + first);
           else launch_box_or_nearest(filter, k_oriented_box<Pix, DT>, k_oriented_nearest<Pix, DT>, max_tiles, max_blocks, max_dw, max_dh, n, s, (const OrientedParams*)st.dev + first);
         })) return 0;
     return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "oriented output: unknown dtype %d", dtype);
   });
   if (rc) return rc;
   g_oriented_entries += (uint64_t)caps.size(); g_oriented_quarter += quarter;
+  frame_tiles.commit();
   return 0;
 }
 
@@ -2284,7 +2532,9 @@ int resample_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
     quarter += (uint64_t)(c.code & 1);
   }
   const bool blocked = caps[0].patch > 0;   // (as in oriented_launch): PatchResampleParams blocks for k_patch_resample
-  const size_t block_bytes = blocked ? sizeof(PatchResampleParams) : sizeof(ResampleParams);
+  const bool framed = !blocked && caps[0].framed;   // ... FrameResampleParams blocks for k_frame_resample
+  const size_t block_bytes = blocked ? sizeof(PatchResampleParams) : (framed ? sizeof(FrameResampleParams) : sizeof(ResampleParams));
+  FrameTileCount frame_tiles;
   const size_t params_bytes = (caps.size() * block_bytes + 15) & ~(size_t)15;
   const size_t bytes = params_bytes + (size_t)ints * sizeof(int32_t);
   std::vector<uint8_t> host(bytes);
@@ -2303,21 +2553,29 @@ int resample_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
       const PatchInfo b = patch_info_of(c);
       memcpy(host.data() + i * block_bytes + offsetof(PatchResampleParams, b), &b, sizeof(b));
     }
+    if (framed) {
+      hipdec::FrameWindow f = frame_window_of(c);
+      frame_tiles.add(&f, c.p.ow, c.p.tile < kResTC ? (c.p.tile > 0 ? c.p.tile : 1) : kResTC, f.px0, f.px1, c.p.oh, kResTR, f.py0, f.py1);
+      memcpy(host.data() + i * block_bytes + offsetof(FrameResampleParams, b), &f, sizeof(f));
+    }
   }
   if (int rc = blocks_upload(st, host, s)) return rc;
   const int wide = caps[0].wide;
+  if (framed) { max_tiles = frame_tiles.max_x; max_bands = frame_tiles.max_y; }   // the grid covers the tiles and bands with a visible pixel
   const int rc = launch_z_chunks(0, caps.size(), "resample kernel launch", caps[0].oriented ? &g_oriented_launches : nullptr, [&](size_t first, size_t n) {
     const LaunchShape g = box_grid(max_tiles, max_bands, n);
     if (dispatch_pix_dtype(wide, dtype, [&](auto pix, auto dt) {
           typedef typename decltype(pix)::type Pix;
           constexpr int DT = decltype(dt)::value;
           if (blocked) hipLaunchKernelGGL((k_patch_resample<Pix, DT>), g.grid, g.block, 0, s, (const PatchResampleParams*)st.dev + first);
+          else if (framed) hipLaunchKernelGGL((k_frame_resample<Pix, DT>), g.grid, g.block, 0, s, (const FrameResampleParams*)st.dev + first);
           else hipLaunchKernelGGL((k_resample<Pix, DT>), g.grid, g.block, 0, s, (const ResampleParams*)st.dev + first);
         })) return 0;
     return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "resampled output: unknown dtype %d", dtype);
   });
   if (rc) return rc;
   if (caps[0].oriented) { g_oriented_entries += (uint64_t)caps.size(); g_oriented_quarter += quarter; }
+  frame_tiles.commit();
   return 0;
 }
 }  // namespace
@@ -2353,6 +2611,7 @@ int color_tensor_launch(ColorBatchState& st, int filter, int dtype, hipStream_t 
 // when they change, as the picture blocks are
 std::atomic<uint64_t> g_placed_calls{0}, g_placed_entries{0}, g_placed_margin_launches{0};
 void placed_note_call(uint64_t entries) { g_placed_calls++; g_placed_entries += entries; }
+void framed_note_call(uint64_t entries) { g_framed_calls++; g_framed_entries += entries; }
 uint64_t clip_box_entries() { return g_clip_box_entries.load(); }
 void packed_note_call(uint64_t entries, bool patches) { g_packed_calls++; g_packed_entries += entries; if (patches) g_packed_patch_entries += entries; }
 
@@ -2913,6 +3172,14 @@ void hipdec_packed_stats(uint64_t* calls, uint64_t* entries, uint64_t* patch_ent
   if (calls) *calls = g_packed_calls.load();
   if (entries) *entries = g_packed_entries.load();
   if (patch_entries) *patch_entries = g_packed_patch_entries.load();
+}
+
+void hipdec_framed_stats(uint64_t* calls, uint64_t* entries, uint64_t* tiles, uint64_t* tiles_skipped)
+{
+  if (calls) *calls = g_framed_calls.load();
+  if (entries) *entries = g_framed_entries.load();
+  if (tiles) *tiles = g_framed_tiles.load();
+  if (tiles_skipped) *tiles_skipped = g_framed_skipped.load();
 }
 
 void hipdec_placed_stats(uint64_t* calls, uint64_t* entries, uint64_t* margin_launches)

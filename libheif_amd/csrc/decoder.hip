@@ -833,7 +833,8 @@ int tensor_window(const char* who, const hipdec_tensor_entry* e, int idx, int w,
 // presents the planes as the 4:4:4 image they are scaled to.  The entry point records the block (color.hip); elem0: the entry's first element.
 int tensor_record_entry(const char* who, const uint8_t* y, size_t ys, const uint8_t* cb, size_t cbs, const uint8_t* cr, size_t crs, int w, int h, int bits, int cf,
                         const hipdec_nclx* nclx, const hipdec_nclx* nclx_after_sdr, const hipdec_tensor_desc* d, int left, int top, int rw, int rh, int flip, void* elem0,
-                        int orientation = -1, size_t pitch = 0, int plane_rows = 0, int patch = 0, int merge = 1, int tpatch = 1, bool* strided_box = nullptr)
+                        int orientation = -1, size_t pitch = 0, int plane_rows = 0, int patch = 0, int merge = 1, int tpatch = 1, bool* strided_box = nullptr,
+                        const int* frame_vis = nullptr)   // frame_vis: a framed entry's visible part (placed_entry)
 {
   if (int rc = tensor_check_resample_depth(who, d, bits)) return rc;
   TensorRequest rq;
@@ -857,6 +858,7 @@ int tensor_record_entry(const char* who, const uint8_t* y, size_t ys, const uint
   rq.tpatch = tpatch;
   if (strided_box) *strided_box = *strided_box && rq.oriented && !rq.resample && !patch && d->filter == HIPDEC_SCALE_BOX && (rq.code == HIPDEC_ORIENT_0 || rq.code == HIPDEC_ORIENT_MIRROR);
   rq.strided_box = strided_box && *strided_box;
+  if (frame_vis) { rq.framed = 1; for (int k = 0; k < 4; k++) rq.frame_vis[k] = frame_vis[k]; }
   rq.plane_rows = plane_rows ? plane_rows : d->height;   // (d->height: the displayed rows)
   rq.sH = cf == 1 || cf == 2 ? 1 : 0; rq.sV = cf == 1 ? 1 : 0;
   rq.left = left; rq.top = top; rq.rw = rw; rq.rh = rh; rq.flip = flip; rq.nhwc = d->layout == HIPDEC_TENSOR_NHWC;
@@ -915,7 +917,9 @@ int check_orientations(const char* who, const char* what, const int* orientation
 }
 
 // ---- placed tensor output (hipdec_batch_to_tensor_placed / hipdec_album_to_tensor_placed): what the two forms share
-struct PlacedArgs { const hipdec_tensor_place* places; const hipdec_tensor_fill* fill; void* mask; };
+// framed (hipdec_batch_to_tensor_framed / hipdec_album_to_tensor_framed): a rectangle may leave the canvas, and the k_frame_* kernels store its visible part
+struct PlacedArgs { const hipdec_tensor_place* places; const hipdec_tensor_fill* fill; void* mask; bool framed = false; };
+constexpr int kFrameReach = 1 << 24;   // |x|, |y| and the sides of a framed rectangle: sums and products of two stay far inside 64 bits
 
 // what the arguments alone decide (the description has passed tensor_check_desc)
 int placed_check(const char* who, const hipdec_tensor_desc* d, const PlacedArgs& pa, int n_entries)
@@ -923,6 +927,19 @@ int placed_check(const char* who, const hipdec_tensor_desc* d, const PlacedArgs&
   for (int e = 0; pa.places && e < n_entries; e++) {
     const hipdec_tensor_place& pl = pa.places[e];
     if (pl.width < 1 || pl.height < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: rectangle size %d x %d", who, e, pl.width, pl.height);
+    if (pa.framed) {
+      if (pl.width > kFrameReach || pl.height > kFrameReach || pl.x > kFrameReach || pl.x < -kFrameReach || pl.y > kFrameReach || pl.y < -kFrameReach)
+        return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: rectangle %d x %d at (%d, %d): offsets and sides reach 2^24 at most", who, e, pl.width, pl.height, pl.x, pl.y);
+      if ((int64_t)pl.x + pl.width <= 0 || (int64_t)pl.y + pl.height <= 0 || pl.x >= d->width || pl.y >= d->height)
+        return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: rectangle %d x %d at (%d, %d) has no pixel on the canvas of %d x %d", who, e, pl.width, pl.height, pl.x,
+                         pl.y, d->width, d->height);
+      hipdec_tensor_desc sample = *d;   // what the oriented call refuses for a tensor of the rectangle's size
+      sample.width = pl.width; sample.height = pl.height;
+      size_t bytes = 0;
+      if (tensor_check_desc(who, &sample, 1, &bytes))
+        return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: rectangle size %d x %d: the sample is too large", who, e, pl.width, pl.height);
+      continue;
+    }
     if (pl.x < 0 || pl.y < 0 || (int64_t)pl.x + pl.width > d->width || (int64_t)pl.y + pl.height > d->height)
       return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: rectangle %d x %d at (%d, %d) leaves the canvas of %d x %d", who, e, pl.width, pl.height, pl.x, pl.y,
                        d->width, d->height);
@@ -958,7 +975,10 @@ int placed_check_component(const char* who, const hipdec_tensor_desc* d, const P
 }
 
 // entry e of a placed call: *sample is the description of the sample in its rectangle, *elem0 the rectangle's first element, *m the entry's margin block
-void placed_entry(const hipdec_tensor_desc* d, const PlacedArgs& pa, int e, void* out_dev, size_t entry_bytes, hipdec_tensor_desc* sample, void** elem0, CanvasMargin* m)
+// Framed: vis is the part of the rectangle on the canvas, in the sample's displayed coordinates (x0, y0, x1, y1); *elem0 - where the rectangle's first
+// element would lie, in front of the canvas for a negative offset - is dereferenced inside it only, and the margin block names the visible rectangle.
+void placed_entry(const hipdec_tensor_desc* d, const PlacedArgs& pa, int e, void* out_dev, size_t entry_bytes, hipdec_tensor_desc* sample, void** elem0, CanvasMargin* m,
+                  int* vis = nullptr)
 {
   const hipdec_tensor_place whole{0, 0, d->width, d->height};
   const hipdec_tensor_place& pl = pa.places ? pa.places[e] : whole;
@@ -966,14 +986,17 @@ void placed_entry(const hipdec_tensor_desc* d, const PlacedArgs& pa, int e, void
   uint8_t* canvas = (uint8_t*)out_dev + (size_t)e * entry_bytes;
   *sample = *d;
   sample->width = pl.width; sample->height = pl.height;
-  *elem0 = canvas + ((size_t)pl.y * (size_t)d->width + (size_t)pl.x) * k * tensor_elem_bytes(d->dtype);
+  *elem0 = canvas + ((int64_t)pl.y * (int64_t)d->width + (int64_t)pl.x) * (int64_t)(k * tensor_elem_bytes(d->dtype));
+  const int x0 = pl.x < 0 ? -pl.x : 0, y0 = pl.y < 0 ? -pl.y : 0;   // (a placed rectangle lies on the canvas: all of it is visible)
+  const int x1 = (int)std::min<int64_t>(pl.width, (int64_t)d->width - pl.x), y1 = (int)std::min<int64_t>(pl.height, (int64_t)d->height - pl.y);
+  if (vis) { vis[0] = x0; vis[1] = y0; vis[2] = x1; vis[3] = y1; }
   memset(m, 0, sizeof(*m));
   m->o0 = canvas;
   m->mask = pa.mask ? (uint8_t*)pa.mask + (size_t)e * (size_t)d->width * (size_t)d->height : nullptr;
-  m->W = d->width; m->H = d->height; m->x = pl.x; m->y = pl.y; m->w = pl.width; m->h = pl.height;
+  m->W = d->width; m->H = d->height; m->x = pl.x + x0; m->y = pl.y + y0; m->w = x1 - x0; m->h = y1 - y0;
   m->nhwc = d->layout == HIPDEC_TENSOR_NHWC;
   m->domain = pa.fill ? pa.fill->domain : HIPDEC_FILL_COMPONENT;
-  m->margin = pl.width != d->width || pl.height != d->height;
+  m->margin = m->w != d->width || m->h != d->height;
   for (int c = 0; c < 3; c++) { m->value[c] = pa.fill ? pa.fill->value[c] : 0.0f; m->scale[c] = d->scale[c]; m->bias[c] = d->bias[c]; }
 }
 
@@ -1058,7 +1081,8 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
   if (ps) if (int rc = packed_check_desc("to_tensor_packed", desc, &unit)) return rc;
   if (int rc = tensor_check_desc("to_tensor", ps ? &unit : desc, n_entries, &bytes)) return rc;
   if (oriented) if (int rc = check_orientations("to_tensor_oriented", "entry", orientations, n_entries)) return rc;
-  if (pa) if (int rc = placed_check("to_tensor_placed", desc, *pa, n_entries)) return rc;
+  const bool framed = pa && pa->framed && pa->places;   // (without rectangles every sample is its canvas: the oriented kernels)
+  if (pa) if (int rc = placed_check(pa->framed ? "to_tensor_framed" : "to_tensor_placed", desc, *pa, n_entries)) return rc;
   if (ps) { if (int rc = packed_check("to_tensor_packed", desc, ps->samples, ps->patches, n_entries, out_bytes, &pk)) return rc; }
   else if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
   // (everything above is decided without reading the handle)
@@ -1071,6 +1095,9 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
   for (int e = 0; ps && b->max_pixels && e < n_entries; e++)
     if ((uint64_t)pk.samples[e].width * (uint64_t)pk.samples[e].height > b->max_pixels)
       return set_error(HIPDEC_ERR_LIMIT, "to_tensor_packed: entry %d: sample of %d x %d pixels exceeds max_image_size_pixels", e, pk.samples[e].width, pk.samples[e].height);
+  for (int e = 0; framed && b->max_pixels && e < n_entries; e++)
+    if ((uint64_t)pa->places[e].width * (uint64_t)pa->places[e].height > b->max_pixels)
+      return set_error(HIPDEC_ERR_LIMIT, "to_tensor_framed: entry %d: rectangle of %d x %d pixels exceeds max_image_size_pixels", e, pa->places[e].width, pa->places[e].height);
   return guarded("to_tensor", [&]() -> int {
     hipStream_t s = follow_stream(b, stream);
     const size_t entry_bytes = bytes / (size_t)n_entries;
@@ -1089,15 +1116,17 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
       void* elem0 = (uint8_t*)out_dev + (size_t)e * entry_bytes;
       size_t pitch = 0;
       int plane_rows = 0;
+      int vis[4];
       if (pa) {
-        if (!rc) rc = placed_check_component("to_tensor_placed", desc, *pa, e, b->wide ? I.bit_depth_luma : 8);
-        placed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0, &margins[(size_t)e]);
+        if (!rc) rc = placed_check_component(pa->framed ? "to_tensor_framed" : "to_tensor_placed", desc, *pa, e, b->wide ? I.bit_depth_luma : 8);
+        placed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0, &margins[(size_t)e], vis);
         pitch = (size_t)desc->width * (desc->layout == HIPDEC_TENSOR_NHWC ? 3 : 1); plane_rows = desc->height;
       }
       if (ps) packed_entry(desc, pk, e, out_dev, &sample, &elem0);   // (its own size, dense pitch and plane: the defaults of the sample's description)
       if (!rc) rc = tensor_record_entry("to_tensor", b->arena + P.off_out[0], P.out_stride[0], b->arena + P.off_out[1], P.out_stride[1], b->arena + P.off_out[2], P.out_stride[2],
                                         P.out_width, P.out_height, b->wide ? I.bit_depth_luma : 8, P.chroma_format_idc, &nclx, &nclx, &sample, left, top, rw, rh,
-                                        entries ? entries[e].flip : 0, elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows, pk.patch, pk.merge);
+                                        entries ? entries[e].flip : 0, elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows, pk.patch, pk.merge, 1, nullptr,
+                                        framed ? vis : nullptr);
       if (rc) { color_tensor_abort(); return rc; }
     }
     const size_t slot = b->runs ? (b->runs - 1) % (b->ev.size() / kEv) : 0;
@@ -1110,7 +1139,8 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
     if (!rc && b->runs) b->colour_timed[slot] = 1;
     b->mark_done(s);
     if (!rc) { g_tensor_calls++; g_tensor_entries += (uint64_t)n_entries; }
-    if (!rc && pa) placed_note_call((uint64_t)n_entries);
+    if (!rc && pa && !pa->framed) placed_note_call((uint64_t)n_entries);
+    if (!rc && pa && pa->framed) framed_note_call((uint64_t)n_entries);
     if (!rc && ps) packed_note_call((uint64_t)n_entries, pk.patch > 0);
     return rc;
   });
@@ -1324,6 +1354,14 @@ int hipdec_batch_to_tensor_placed(hipdec_batch* b, const hipdec_tensor_desc* des
   return batch_to_tensor_impl(b, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, &pa);
 }
 
+int hipdec_batch_to_tensor_framed(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                  const hipdec_tensor_place* places, const hipdec_tensor_fill* fill, void* mask_dev, int n_entries, void* out_dev, size_t out_bytes,
+                                  void* stream)
+{
+  const PlacedArgs pa{places, fill, mask_dev, true};
+  return batch_to_tensor_impl(b, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, &pa);
+}
+
 int hipdec_batch_to_tensor_warped(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
                                   const hipdec_warp_desc* warp, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill, int n_entries, void* out_dev,
                                   size_t out_bytes, void* stream)
@@ -1391,6 +1429,27 @@ int hipdec_letterbox_place(int src_width, int src_height, int canvas_width, int 
   out->width = (int)w; out->height = (int)h;
   out->x = anchor ? (int)((cw - w) / 2) : 0;
   out->y = anchor ? (int)((ch - h) / 2) : 0;
+  return 0;
+}
+
+// torchvision's Resize(int) on the displayed size, then CenterCrop: Python's round() is round half to even, and a side shorter than the crop is padded
+// with floor(d / 2) in front
+int hipdec_resize_crop_place(int src_width, int src_height, int resize, int crop_width, int crop_height, hipdec_tensor_place* out)
+{
+  if (!out || src_width < 1 || src_height < 1 || resize < 1 || crop_width < 1 || crop_height < 1)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "resize_crop_place: source %d x %d, resize %d, crop %d x %d", src_width, src_height, resize, crop_width, crop_height), -1;
+  const int64_t sw = src_width, sh = src_height, r = resize;
+  const int64_t w = sw <= sh ? r : r * sw / sh, h = sw <= sh ? r * sh / sw : r;
+  if (w > kFrameReach || h > kFrameReach || crop_width > kFrameReach || crop_height > kFrameReach)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "resize_crop_place: resized sample %lld x %lld, crop %d x %d: sides reach 2^24 at most", (long long)w, (long long)h, crop_width,
+                     crop_height), -1;
+  auto offset = [](int64_t side, int64_t crop) -> int {
+    if (side < crop) return (int)((crop - side) / 2);
+    const int64_t d = side - crop, k = d / 2;
+    return (int)-(d & 1 ? k + (k & 1) : k);   // d / 2 = k + 1 / 2 goes to the even one of k and k + 1
+  };
+  out->x = offset(w, crop_width); out->y = offset(h, crop_height);
+  out->width = (int)w; out->height = (int)h;
   return 0;
 }
 

@@ -326,7 +326,8 @@ int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const 
   if (ps) if (int rc = packed_check_desc("album_to_tensor_packed", desc, &unit)) return rc;
   if (int rc = tensor_check_desc("album_to_tensor", ps ? &unit : desc, n_entries, &bytes)) return rc;
   if (oriented) if (int rc = check_orientations("album_to_tensor_oriented", "entry", orientations, n_entries)) return rc;
-  if (pa) if (int rc = placed_check("album_to_tensor_placed", desc, *pa, n_entries)) return rc;
+  const bool framed = pa && pa->framed && pa->places;
+  if (pa) if (int rc = placed_check(pa->framed ? "album_to_tensor_framed" : "album_to_tensor_placed", desc, *pa, n_entries)) return rc;
   if (ps) { if (int rc = packed_check("album_to_tensor_packed", desc, ps->samples, ps->patches, n_entries, out_bytes, &pk)) return rc; }
   else if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
   // (everything above is decided without reading the handle)
@@ -339,6 +340,9 @@ int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const 
   for (int e = 0; ps && a->max_pixels && e < n_entries; e++)
     if ((uint64_t)pk.samples[e].width * (uint64_t)pk.samples[e].height > a->max_pixels)
       return set_error(HIPDEC_ERR_LIMIT, "album_to_tensor_packed: entry %d: sample of %d x %d pixels exceeds max_image_size_pixels", e, pk.samples[e].width, pk.samples[e].height);
+  for (int e = 0; framed && a->max_pixels && e < n_entries; e++)
+    if ((uint64_t)pa->places[e].width * (uint64_t)pa->places[e].height > a->max_pixels)
+      return set_error(HIPDEC_ERR_LIMIT, "album_to_tensor_framed: entry %d: rectangle of %d x %d pixels exceeds max_image_size_pixels", e, pa->places[e].width, pa->places[e].height);
   return guarded("album_to_tensor", [&]() -> int {
     hipdec_batch* b = a->batch.get();
     hipStream_t s = follow_stream(b, stream);
@@ -357,21 +361,23 @@ int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const 
       void* elem0 = (uint8_t*)out_dev + (size_t)e * entry_bytes;
       size_t pitch = 0;
       int plane_rows = 0;
+      int vis[4];
       if (pa) {
-        if (!rc) rc = placed_check_component("album_to_tensor_placed", desc, *pa, e, S.wide ? I.bit_depth_luma : 8);
-        placed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0, &margins[(size_t)e]);
+        if (!rc) rc = placed_check_component(pa->framed ? "album_to_tensor_framed" : "album_to_tensor_placed", desc, *pa, e, S.wide ? I.bit_depth_luma : 8);
+        placed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0, &margins[(size_t)e], vis);
         pitch = (size_t)desc->width * (desc->layout == HIPDEC_TENSOR_NHWC ? 3 : 1); plane_rows = desc->height;
       }
       if (ps) packed_entry(desc, pk, e, out_dev, &sample, &elem0);
       if (!rc) rc = tensor_record_entry("album_to_tensor", S.plane[0], S.stride[0], S.plane[1], S.stride[1], S.plane[2], S.stride[2], S.width, S.height,
                                         S.wide ? I.bit_depth_luma : 8, S.chroma_format_idc, &nclx, &nclx, &sample, left, top, rw, rh, entries ? entries[e].flip : 0,
-                                        elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows, pk.patch, pk.merge);
+                                        elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows, pk.patch, pk.merge, 1, nullptr, framed ? vis : nullptr);
       if (rc) { color_tensor_abort(); return rc; }
     }
     int rc = color_tensor_launch(ps ? a->color_packed : (oriented || resample_filter(desc->filter) ? a->color_oriented : a->color_tensor), desc->filter, desc->dtype, s);
     if (!rc && pa) rc = canvas_margin_launch(a->color_margin, margins.data(), n_entries, desc->dtype, s);
     b->mark_done(s);
-    if (!rc && pa) placed_note_call((uint64_t)n_entries);
+    if (!rc && pa && !pa->framed) placed_note_call((uint64_t)n_entries);
+    if (!rc && pa && pa->framed) framed_note_call((uint64_t)n_entries);
     if (!rc && ps) packed_note_call((uint64_t)n_entries, pk.patch > 0);
     return rc;
   });
@@ -409,6 +415,14 @@ int hipdec_album_to_tensor_placed(hipdec_album* a, const hipdec_tensor_desc* des
                                   void* stream)
 {
   const PlacedArgs pa{places, fill, mask_dev};
+  return album_to_tensor_impl(a, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, &pa);
+}
+
+int hipdec_album_to_tensor_framed(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                  const hipdec_tensor_place* places, const hipdec_tensor_fill* fill, void* mask_dev, int n_entries, void* out_dev, size_t out_bytes,
+                                  void* stream)
+{
+  const PlacedArgs pa{places, fill, mask_dev, true};
   return album_to_tensor_impl(a, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, &pa);
 }
 

@@ -103,7 +103,22 @@ struct TensorRequest { int ow, oh, sH, sV, left, top, rw, rh, flip, nhwc; float 
                        int resample; /* HIPDEC_SCALE_BILINEAR / _BICUBIC: the block is recorded for k_resample, code and pitch set for every entry (0: no) */
                        int patch, merge;
                        int tpatch;        /* clips (hipdec_clips_to_tensor_packed): frames per token, a token is 3 * tpatch * patch * patch elements (0 / 1: a still's) */
-                       int strided_box;   /* clips: a box entry whose folded code is 0 or 4 goes to k_clip_box - k_tensor_box's stage, the oriented store - not k_oriented_box */ };
+                       int strided_box;   /* clips: a box entry whose folded code is 0 or 4 goes to k_clip_box - k_tensor_box's stage, the oriented store - not k_oriented_box */
+                       int framed;        /* the (oriented) block goes to the k_frame_* kernels, which store inside frame_vis only (FrameWindow below) */
+                       int frame_vis[4]; };
+// Framed tensor output (color.hip k_frame_*, include/heif_hipdec.h hipdec_batch_to_tensor_framed): the part of an entry's sample that lies on its canvas.
+// A request with `framed` set carries the window in displayed coordinates of the sample (frame_vis: x0, y0, x1, y1, half open, not empty); its `out` is
+// where element (0, 0, 0) of the whole sample WOULD lie - in front of the canvas where the rectangle starts above or left of it - and is dereferenced inside
+// the window only.  The block the kernels read holds the window twice: as displayed columns and rows (what a store is tested against) and as columns and
+// rows of the pre-orientation picture P (what a workgroup's tile, band and box rows are tested against); color.hip derives the second from the code,
+// and shrinks the grid to the pieces of work between the first and the last that hold a visible pixel.
+struct FrameWindow {
+  int vx0, vy0, vx1, vy1;   // displayed sample
+  int px0, py0, px1, py1;   // P
+  int tx0, ty0;             // the first piece of work along either axis that holds a visible pixel - a column tile and a block of rows / a band of P, or the
+                            // nearest kernel's 256 x 4 displayed pixels: the grid covers the pieces from there on, a workgroup adds the origin to its index
+  int reserved[2];
+};
 void color_tensor_request(const TensorRequest& r);
 void color_tensor_clear();
 bool color_tensor_pending();
@@ -128,6 +143,7 @@ struct CanvasMargin {
 // launches when an entry has a margin or a mask (nothing otherwise); dtype: hipdec_tensor_dtype
 int canvas_margin_launch(ColorBatchState& st, const CanvasMargin* blocks, int n, int dtype, hipStream_t s);
 void placed_note_call(uint64_t entries);   // hipdec_placed_stats
+void framed_note_call(uint64_t entries);   // hipdec_framed_stats (its tile counts: the launches of the k_frame_* kernels, color.hip)
 void packed_note_call(uint64_t entries, bool patches);   // hipdec_packed_stats
 uint64_t clip_box_entries();   // entries that have gone through k_clip_box (hipdec_clips_stats)
 

@@ -86,6 +86,11 @@ def _bind(lib):
     lib.hipdec_letterbox_place.argtypes = [ci, ci, ci, ci, ci, ci, C.POINTER(TensorPlace)]
     lib.hipdec_placed_stats.restype = None
     lib.hipdec_placed_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
+    lib.hipdec_batch_to_tensor_framed.argtypes = placed
+    lib.hipdec_album_to_tensor_framed.argtypes = placed
+    lib.hipdec_resize_crop_place.argtypes = [ci, ci, ci, ci, ci, C.POINTER(TensorPlace)]
+    lib.hipdec_framed_stats.restype = None
+    lib.hipdec_framed_stats.argtypes = [C.POINTER(C.c_uint64)] * 4
     packed = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), C.POINTER(ci), C.POINTER(TensorSample), C.POINTER(TensorPatches), ci, vp, sz, vp]
     lib.hipdec_batch_to_tensor_packed.argtypes = packed
     lib.hipdec_album_to_tensor_packed.argtypes = packed
@@ -500,6 +505,56 @@ def placed_stats():
     a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
     lib.hipdec_placed_stats(C.byref(a), C.byref(b), C.byref(c))
     return a.value, b.value, c.value
+
+
+def resize_crop_place(src_size, resize, crop):
+    """(x, y, width, height): torchvision's Resize(resize) -> CenterCrop(crop) on a DISPLAYED sample of src_size = (width, height), as the rectangle of a
+    to_tensor(frames=) call whose canvas is crop = (width, height) (hipdec_resize_crop_place; host only).  The shorter side becomes `resize`, the longer
+    floor(resize * long / short); the offsets are negative where the resized sample is larger than the crop."""
+    pl = TensorPlace()
+    if _bind(load_library()).hipdec_resize_crop_place(int(src_size[0]), int(src_size[1]), int(resize), int(crop[0]), int(crop[1]), C.byref(pl)) != 0:
+        raise ValueError("resize_crop_place(%r, %r, %r)" % (tuple(src_size), resize, tuple(crop)))
+    return pl.x, pl.y, pl.width, pl.height
+
+
+def resize_crop_places(sizes, resize, crop):
+    """resize_crop_place for a list of DISPLAYED sizes (oriented_size() of the stored ones): the `frames` of a to_tensor call"""
+    return [resize_crop_place(s, resize, crop) for s in sizes]
+
+
+def random_crop_places(rng, sizes, crop, padding=0, pad_if_needed=False):
+    """the `frames` of torchvision's RandomCrop(crop, padding, pad_if_needed) for samples of the DISPLAYED sizes (width, height), crop = (width, height): the
+    sample keeps its size, is padded by `padding` - a number, (left / right, top / bottom) or (left, top, right, bottom) - and, with pad_if_needed, by
+    crop - side on both sides of an axis that is still shorter than the crop; the crop's corner is drawn uniformly from the padded picture with
+    rng.integers (a numpy Generator), x before y, sample by sample.  A padded picture smaller than the crop raises ValueError."""
+    pad = (padding,) * 4 if np.isscalar(padding) else tuple(int(v) for v in padding)
+    if len(pad) == 2:
+        pad = (pad[0], pad[1], pad[0], pad[1])
+    if len(pad) != 4 or min(pad) < 0:
+        raise ValueError("padding must be a non-negative number, a pair or four of them")
+    cw, ch = int(crop[0]), int(crop[1])
+    out = []
+    for w, h in sizes:
+        w, h = int(w), int(h)
+        left, top, pw, ph = pad[0], pad[1], w + pad[0] + pad[2], h + pad[1] + pad[3]
+        if pad_if_needed and pw < cw:
+            left, pw = left + cw - pw, pw + 2 * (cw - pw)
+        if pad_if_needed and ph < ch:
+            top, ph = top + ch - ph, ph + 2 * (ch - ph)
+        if pw < cw or ph < ch:
+            raise ValueError("the padded sample of %d x %d is smaller than the crop of %d x %d" % (pw, ph, cw, ch))
+        i = int(rng.integers(0, pw - cw + 1))
+        j = int(rng.integers(0, ph - ch + 1))
+        out.append((left - i, top - j, w, h))
+    return out
+
+
+def framed_stats():
+    """(framed to_tensor calls, their entries, pieces of work that held a visible pixel, pieces skipped) since load (hipdec_framed_stats)"""
+    lib = _bind(load_library())
+    v = [C.c_uint64() for _ in range(4)]
+    lib.hipdec_framed_stats(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
 
 
 def packed_layout(sizes, patch=0, merge=1):
@@ -1195,7 +1250,7 @@ class Batch:
                                                        self._srgb_strides, stream))
 
     def to_tensor(self, size, entries=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, filter=SCALE_BOX, out=None,
-                  stream=None, orientations=None, places=None, fill=None, fill_domain="component", mask=None):
+                  stream=None, orientations=None, places=None, fill=None, fill_domain="component", mask=None, frames=None):
         """asynchronous: crop windows of the decoded pictures, scaled to size = (width, height), optionally flipped, as ONE dense tensor of shape
         (N, 3, height, width) ("NCHW") or (N, height, width, 3) ("NHWC") written by one fused kernel (hipdec_batch_to_tensor).
 
@@ -1221,7 +1276,15 @@ class Batch:
         rectangle (tensor_mask_to_host() reads the mask of the LAST call back; it raises when that call wrote none).  The mask is written on the stream the
         tensor is written on: `stream`, or - stream None - torch's current stream when `out` is a torch.Tensor and the library's own stream when `out`
         is a DeviceBuffer, whatever the mask is; a torch mask next to a DeviceBuffer `out` therefore needs `stream=` (or synchronize()) to be ordered
-        with torch's work."""
+        with torch's work.
+        frames (hipdec_batch_to_tensor_framed; instead of places): one (x, y, width, height) rectangle per entry that may leave the canvas on any side -
+        x and y may be negative - of which the part on the canvas is computed and written: resize-then-crop (resize_crop_places()), RandomCrop with
+        padding (random_crop_places()).  fill / fill_domain / mask as with places, the mask 0 on the visible part."""
+        if frames is not None:
+            if places is not None:
+                raise ValueError("places and frames are mutually exclusive")
+            return _to_tensor(self, self._lib.hipdec_batch_to_tensor_framed, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations,
+                              (frames, fill, fill_domain, mask))
         if places is not None or fill is not None or mask is not None:
             return _to_tensor(self, self._lib.hipdec_batch_to_tensor_placed, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations,
                               (places, fill, fill_domain, mask))
@@ -1479,8 +1542,13 @@ class Album:
         return buf.to_numpy((h, stride), np.uint8)
 
     def to_tensor(self, size, entries=None, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, filter=SCALE_BOX, out=None,
-                  stream=None, orientations=None, places=None, fill=None, fill_domain="component", mask=None):
+                  stream=None, orientations=None, places=None, fill=None, fill_domain="component", mask=None, frames=None):
         """Batch.to_tensor over the composed photos: an entry's item names a photo, its window lies in the photo's output size"""
+        if frames is not None:
+            if places is not None:
+                raise ValueError("places and frames are mutually exclusive")
+            return _to_tensor(self, self._lib.hipdec_album_to_tensor_framed, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations,
+                              (frames, fill, fill_domain, mask))
         if places is not None or fill is not None or mask is not None:
             return _to_tensor(self, self._lib.hipdec_album_to_tensor_placed, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations,
                               (places, fill, fill_domain, mask))
