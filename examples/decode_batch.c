@@ -34,6 +34,9 @@
  *                                                     hipdec_resize_crop_place and hipdec_batch_to_tensor_framed - as a uint8 N x CROP x CROP x 3 tensor; only the
  *                                                     square is computed, an item smaller than it is padded with black; RESIZE takes the place of --thumb's N;
  *                                                     after --orient / --filter, not with the options above
+ *   ./decode_batch --thumb 96 --sheet 4 3 item0.hevc ...   instead of previews, ONE launch set writes a contact sheet: COLS x ROWS cells of N x N with 2 pixels
+ *                                                     between them, item k letterboxed into cell k (hipdec_sheet_tiles, hipdec_batch_to_tensor_composed),
+ *                                                     white elsewhere, as ONE uint8 H x W x 3 picture; at most COLS * ROWS items; where --frame may stand
  *   ./decode_batch --album 16 6x8 tile0.hevc ...      the items are TILES: 16 grid photos of 6 x 8 tiles (tile t of photo k is item (k * 48 + t) mod n; the
  *                                                     output is the whole tiled area) composed by ONE launch set and ONE paste launch; prints Mpixel/s
  */
@@ -180,13 +183,20 @@ int main(int argc, char** argv)
     if (frame_resize < 1 || frame_crop < 1) argc = 0;             /* no or a bad RESIZE / CROP: usage */
     else { argv += 3; argc -= 3; }
   }
+  int sheet_cols = 0, sheet_rows = 0;
+  if (thumb && !warp && !photo && !recipe && !augment && !patch && !frame_resize && argc >= 2 && !strcmp(argv[1], "--sheet")) {
+    sheet_cols = argc >= 3 ? atoi(argv[2]) : 0;
+    sheet_rows = argc >= 4 ? atoi(argv[3]) : 0;
+    if (sheet_cols < 1 || sheet_rows < 1 || sheet_cols > 1024 || sheet_rows > 1024 || argc - 4 > sheet_cols * sheet_rows) argc = 0;   /* no or bad COLS / ROWS, too many items: usage */
+    else { argv += 3; argc -= 3; }
+  }
   int tensor = 0;
   if (!thumb && argc >= 2 && !strcmp(argv[1], "--tensor")) {
     tensor = argc >= 3 ? atoi(argv[2]) : 0;
     if (tensor < 1) argc = 0;
     else { argv += 2; argc -= 2; }
   }
-  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] [--warp ANGLE | --photo OP VALUE | --recipe ANGLE OP VALUE | [--hue D] [--blur RADIUS] | --patches P[:M] | --frame RESIZE CROP] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: %s [--thumb N [--orient CODE] [--filter box|nearest|bilinear|bicubic] [--warp ANGLE | --photo OP VALUE | --recipe ANGLE OP VALUE | [--hue D] [--blur RADIUS] | --patches P[:M] | --frame RESIZE CROP | --sheet COLS ROWS] | --tensor N | --album K ROWSxCOLS] item.hevc [item.hevc ...]\n", prog); return 2; }
   const int n = argc - 1;
   const void** data = (const void**)calloc((size_t)n, sizeof(void*));
   size_t* sizes = (size_t*)calloc((size_t)n, sizeof(size_t));
@@ -260,6 +270,47 @@ int main(int argc, char** argv)
       hipdec_framed_stats(NULL, NULL, &tiles, &skipped);
       printf("framed tensor %dx%dx%dx3 uint8: %llu tiles computed, %llu skipped\n", n, frame_crop, frame_crop, (unsigned long long)tiles, (unsigned long long)skipped);
       free(host); hipdec_free(t); free(pl);
+      free(ws); free(hs); free(codes);
+      hipdec_batch_free(prev);
+      hipdec_shutdown();
+      return 0;
+    }
+    if (sheet_cols) {                                              /* a contact sheet of the whole batch: one composed call, one picture */
+      const int gap = 2;
+      hipdec_tensor_desc d;
+      memset(&d, 0, sizeof d);
+      d.width = sheet_cols * thumb + (sheet_cols - 1) * gap; d.height = sheet_rows * thumb + (sheet_rows - 1) * gap;
+      d.dtype = HIPDEC_TENSOR_U8; d.layout = HIPDEC_TENSOR_NHWC; d.filter = filter;
+      for (int c = 0; c < 3; c++) d.scale[c] = 1.0f;
+      hipdec_tensor_tile* tiles = (hipdec_tensor_tile*)calloc((size_t)n, sizeof(hipdec_tensor_tile));
+      for (int i = 0; i < n; i++) {
+        hipdec_image_info info;
+        hipdec_batch_info(prev, i, &info);
+        const int turned = orient > 0 && (orient & 1);             /* a cell holds the DISPLAYED picture */
+        codes[i] = orient > 0 ? orient : 0;
+        ws[i] = turned ? info.height : info.width; hs[i] = turned ? info.width : info.height;
+      }
+      hipdec_tensor_fill white;
+      memset(&white, 0, sizeof white);
+      white.value[0] = white.value[1] = white.value[2] = 255.0f; white.domain = HIPDEC_FILL_COMPONENT;
+      const size_t bytes = hipdec_tensor_bytes(&d, 1);
+      void* t = bytes ? hipdec_malloc(bytes) : NULL;
+      uint8_t* host = (uint8_t*)malloc(bytes ? bytes : 1);
+      if (!t || !host || hipdec_sheet_tiles(sheet_cols, sheet_rows, thumb, thumb, gap, ws, hs, n, 1, 0, tiles) ||
+          hipdec_batch_to_tensor_composed(prev, &d, NULL, codes, tiles, &white, NULL, n, 1, t, bytes, NULL) || hipdec_batch_status(prev) ||
+          hipdec_memcpy_d2h(host, t, bytes)) {
+        fprintf(stderr, "%s\n", hipdec_last_error());
+        return 1;
+      }
+      for (int i = 0; i < n; i++)
+        printf("%s: cell %d, %dx%d at (%d, %d)\n", argv[1 + i], i, tiles[i].place.width, tiles[i].place.height, tiles[i].place.x, tiles[i].place.y);
+      unsigned long long sum = 0;
+      for (size_t k = 0; k < bytes; k++) sum += host[k];
+      uint64_t pieces = 0, launches = 0;
+      hipdec_composed_stats(NULL, NULL, &pieces, NULL, &launches);
+      printf("contact sheet %dx%dx3 uint8, %d x %d cells: %llu pieces, %llu cover launch(es), byte sum %llu\n", d.height, d.width, sheet_cols, sheet_rows,
+             (unsigned long long)pieces, (unsigned long long)launches, sum);
+      free(host); hipdec_free(t); free(tiles);
       free(ws); free(hs); free(codes);
       hipdec_batch_free(prev);
       hipdec_shutdown();

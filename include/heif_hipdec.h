@@ -715,6 +715,66 @@ HIPDEC_API int hipdec_resize_crop_place(int src_width, int src_height, int resiz
  * pixel and those that held none; tiles + tiles_skipped is the count of the unclipped samples */
 HIPDEC_API void hipdec_framed_stats(uint64_t* calls, uint64_t* entries, uint64_t* tiles, uint64_t* tiles_skipped);
 
+/* ---- composed tensor output: mosaic, CutMix and contact sheets - several samples in one canvas, one launch set ------------------------------------------
+ * Mosaic-4 (the default augmentation of YOLOv5 / v8 / 11: four resized photos around a random centre, grey 114 elsewhere), CutMix (timm / DeiT / ConvNeXt:
+ * a box of sample B pasted over sample A) and contact sheets / image grids (photo services, vision-language models that take an N x M sheet of letterboxed
+ * thumbnails) all put SEVERAL samples into one picture.  Every other tensor form writes one sample per canvas; a host composing from them pays a round
+ * trip or a pile of slice copies.  These calls map several entries to one canvas and decide who owns which pixel.
+ *
+ * THE DEFINITION OF THE RESULT.  The output is n_canvases x 3 x H x W (or NHWC) with desc->width x height the CANVAS; hipdec_tensor_bytes(desc, n_canvases)
+ * is its size, and the mask (may be NULL) is n_canvases x H x W uint8.  Entry e belongs to canvas tiles[e].canvas.  tiles[e].place is the rectangle of its
+ * resized, DISPLAYED sample in canvas coordinates and may leave the canvas on any side, as in the framed call.  tiles[e].clip is a rectangle of the canvas
+ * the entry may write: clip.width == 0 && clip.height == 0 means the whole canvas (clip.x and clip.y are then not read); otherwise both sides are positive,
+ * and it may leave the canvas too.  The entry's REGION is place n clip n canvas.  LATER ENTRIES LIE ON TOP: entry e OWNS the pixels of its region that lie
+ * in no region of an entry j > e of the same canvas.
+ *  - An owned canvas element (c, place.y + Y, place.x + X) is element (c, Y, X) of what hipdec_batch_to_tensor_oriented writes for that entry (item,
+ *    window, flip), orientation code, filter, dtype, scale and bias with desc->width / height replaced by place.width / place.height.  All four filters, all
+ *    eight codes, all four dtypes and both layouts are taken; whatever that call refuses for a sample of that size is refused here with the same status.
+ *  - Pixels nobody owns hold the fill element of their channel, with both fill domains exactly as in hipdec_batch_to_tensor_placed (fill NULL: component
+ *    0); the mask is 1 there and 0 on owned pixels.  A canvas without entries is all fill.
+ *  - Every element of the tensor and of the mask is written exactly once, and nothing outside them is touched.
+ * If every canvas has one entry with a whole-canvas clip and tiles[e].canvas == e, the bytes are those of hipdec_batch_to_tensor_framed.
+ * Refused before a device is touched, HIPDEC_ERR_INVALID_ARGUMENT naming the entry: tiles NULL; n_entries or n_canvases below 1; a canvas outside
+ * 0 .. n_canvases - 1; a non-positive side of place; a clip with one zero or a negative side; an empty region; |x|, |y| or a side above 2^24, of place or
+ * of clip; more than HIPDEC_COMPOSE_MAX_ENTRIES entries in one canvas; out_bytes below hipdec_tensor_bytes(desc, n_canvases); fills, domains, `reserved`
+ * and codes as the placed call refuses them.  HIPDEC_ERR_LIMIT: place.width * place.height, or the canvas, above max_image_size_pixels; the cover tables of
+ * the call (below) above HIPDEC_COMPOSE_TABLE_BYTES; more than HIPDEC_COMPOSE_MAX_PIECES pieces.
+ * An entry whose region later entries cover completely is legal: it records no work and counts in hidden_entries.
+ * How it is done.  Per canvas the regions of later entries are subtracted from each entry's region, which leaves disjoint rectangles - PIECES (the rows
+ * above the subtracted rectangle, those below it, and what lies left and right of it in between; the bytes do not depend on the decomposition).  Each piece
+ * is one block of the k_frame_* kernels of the framed call: the sample's first element where it would lie in its canvas, the piece as the window.  ONE
+ * launch of those kernels for all pieces of a call (a grid's z extent is 65535: more pieces take as few launches as that allows).  The fill and the mask
+ * go out in ONE launch of k_compose_cover for all canvases: per canvas the union of all regions as a COVER TABLE - the ascending distinct row edges and, per
+ * band of rows between two edges, the sorted, merged, disjoint covered column intervals; 2 * (bands + 1) + 2 * intervals 32-bit words - uploaded with the
+ * per-canvas blocks in one copy.  No cover launch when no canvas has an unowned pixel and no mask is asked for.  No scratch memory, no intermediate.
+ * CLIPS.  A clip's frame is composed through the borrowed batch (hipdec_clips_batch, below) with no further code. */
+#define HIPDEC_COMPOSE_MAX_ENTRIES 256           /* entries of one canvas */
+#define HIPDEC_COMPOSE_MAX_PIECES 65536          /* pieces of one call */
+#define HIPDEC_COMPOSE_TABLE_BYTES (1u << 20)    /* cover tables of one call */
+typedef struct hipdec_tensor_tile { int canvas; hipdec_tensor_place place; hipdec_tensor_place clip; } hipdec_tensor_tile;
+HIPDEC_API int hipdec_batch_to_tensor_composed(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                               const hipdec_tensor_tile* tiles, const hipdec_tensor_fill* fill, void* mask_dev, int n_entries, int n_canvases,
+                                               void* out_dev, size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_album_to_tensor_composed(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                               const hipdec_tensor_tile* tiles, const hipdec_tensor_fill* fill, void* mask_dev, int n_entries, int n_canvases,
+                                               void* out_dev, size_t out_bytes, void* stream);
+/* The helpers below are host only, work in 64-bit integer arithmetic and return -1 with hipdec_last_error on bad arguments.
+ * area[e]: the pixels entry e owns on a canvas of width x height, by the rules above (tiles are refused as the composed call refuses them).  CutMix's
+ * lambda - the share of the base sample that stays visible - is exactly area[base] / (width * height). */
+HIPDEC_API int hipdec_compose_visible_area(int width, int height, const hipdec_tensor_tile* tiles, int n_entries, int n_canvases, uint64_t* area);
+/* The library's statement of YOLOv5's mosaic-4 rule: four DISPLAYED samples of widths[k] x heights[k], already resized, around the centre (xc, yc),
+ * 0 < xc < canvas_w and 0 < yc < canvas_h, on canvas `canvas`.  Sample 0 has its bottom-right corner at the centre, sample 1 its bottom-left, sample 2 its
+ * top-right, sample 3 its top-left; each is clipped to its quadrant (0: x < xc, y < yc; 1: x >= xc, y < yc; 2: x < xc, y >= yc; 3: x >= xc, y >= yc).
+ * Sizes above 2^24 are refused. */
+HIPDEC_API int hipdec_mosaic_tiles(int canvas_w, int canvas_h, int xc, int yc, const int* widths, const int* heights, int canvas, hipdec_tensor_tile* out);
+/* A contact sheet of cols x rows cells of cell_w x cell_h with `gap` (>= 0) pixels between them, row-major: cell (r, c) is at (c * (cell_w + gap),
+ * r * (cell_h + gap)) - the sheet is cols * cell_w + (cols - 1) * gap wide.  Entry k < n <= cols * rows, a DISPLAYED sample of widths[k] x heights[k], goes
+ * into cell k through hipdec_letterbox_place(widths[k], heights[k], cell_w, cell_h, upscale, 1 (centre)), moved to the cell; its clip is the cell. */
+HIPDEC_API int hipdec_sheet_tiles(int cols, int rows, int cell_w, int cell_h, int gap, const int* widths, const int* heights, int n, int upscale, int canvas,
+                                  hipdec_tensor_tile* out);
+/* counters since load: composed calls, their entries, the pieces recorded, the entries that were fully hidden, launches of k_compose_cover */
+HIPDEC_API void hipdec_composed_stats(uint64_t* calls, uint64_t* entries, uint64_t* pieces, uint64_t* hidden_entries, uint64_t* cover_launches);
+
 /* ---- packed tensor output: per-sample sizes and patch sequences in one launch ---------------------------------------------------------------------------
  * Native-resolution vision encoders (Qwen2-VL / 2.5-VL, SigLIP2 NaFlex, Pixtral, NaViT-style packing) take no common size: each photo keeps its aspect
  * ratio, is resized to its own w x h - a multiple of the patch size - and the batch is ONE packed sequence of patch tokens, [sum of tokens, 3 * P * P].

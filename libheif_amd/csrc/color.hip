@@ -1392,6 +1392,112 @@ __global__ __launch_bounds__(256) void k_canvas_margin(const hipdec::CanvasMargi
   }
 }
 
+// ---- composed tensor output (include/heif_hipdec.h hipdec_batch_to_tensor_composed): several entries share a canvas - the k_frame_* kernels write each
+// entry's pieces, and k_compose_cover writes everything NO entry's region covers: the fill element of each channel and, where asked for, the whole mask (1
+// uncovered, 0 covered).  ONE launch for all canvases of a call, blockIdx.z the canvas.  k_canvas_margin's shape - a canvas is one run of 3 * W * H elements
+// cut into the 16-byte blocks of memory it touches, a lane owns one block at a time, consecutive lanes own consecutive blocks, the canvas' block is
+// wave-uniform - with a cover table (hipdec::CanvasCover) in place of the one rectangle: a lane finds (channel, row, column) of its first element with two
+// divisions, the band of its row by binary search over the canvas' edges and, in the band, the first interval that ends right of its column; from there it
+// walks its 16 / 8 / 4 elements with compares only - the interval cursor moves on when the column reaches the interval's end, the band is looked up again
+// when a row ends (bands are contiguous: the next one).  A block that is fill throughout goes out as ONE 16-byte store, a block an interval's edge or the
+// tensor's end cuts element by element, fill elements only, a covered block is not touched.  The table is read from global memory - a few words per lane,
+// most of them the same for the lanes of a wave; store-only otherwise, no LDS.
+template <typename E, bool MASK, typename Idx>
+__device__ __forceinline__ void compose_cover_blocks(const hipdec::CanvasCover& cv, HIPDEC_GLOBAL E* base, uint32_t f0, uint32_t f1, uint32_t f2)
+{
+  constexpr int N = 16 / (int)sizeof(E), PER = 4 / (int)sizeof(E);
+  constexpr uint32_t kAll = N == 16 ? 0xffffu : (N == 8 ? 0xffu : 0xfu);
+  constexpr int kNone = 0x7fffffff;                                   // the cursor behind a band's last interval: no column reaches it
+  const bool nhwc = !MASK && cv.m.nhwc;
+  const int W = cv.m.W, H = cv.m.H, nb = cv.n_bands;
+  const HIPDEC_GLOBAL int32_t* edge = (const HIPDEC_GLOBAL int32_t*)(uintptr_t)cv.table;
+  const HIPDEC_GLOBAL int32_t* first = edge + nb + 1;
+  const HIPDEC_GLOBAL int32_t* iv = first + nb + 1;
+  const Idx px = (Idx)W * (Idx)H, total = MASK ? px : px * 3;
+  const uintptr_t addr = (uintptr_t)base;
+  const bool aligned = (addr & (sizeof(E) - 1)) == 0;                 // (an output that is not even element-aligned takes element stores throughout)
+  const uint32_t lead = (uint32_t)((addr & 15) / sizeof(E));          // elements between the 16-byte boundary below the canvas and its first element
+  HIPDEC_GLOBAL E* origin = base - lead;
+  const Idx nblocks = (total + lead + (Idx)(N - 1)) / (Idx)N;
+  for (Idx j = (Idx)blockIdx.x * 256u + threadIdx.x; j < nblocks; j += (Idx)gridDim.x * 256u) {
+    const Idx v0 = j * (Idx)N;
+    const uint32_t skip = v0 < (Idx)lead ? lead - (uint32_t)v0 : 0u;  // (block 0 only: its elements in front of the canvas)
+    Idx e = v0 + skip - lead;
+    int c, y, x;
+    if (nhwc) {
+      const Idx pix = e / 3u, row = pix / (Idx)W;
+      c = (int)(e - pix * 3u); y = (int)row; x = (int)(pix - row * (Idx)W);
+    } else {
+      const Idx pl = e / px, r = e - pl * px, row = r / (Idx)W;
+      c = (int)pl; y = (int)row; x = (int)(r - row * (Idx)W);
+    }
+    int b = 0;                                                        // the band of y: the last one whose first row is not below it
+    for (int hi = nb - 1; b < hi;) {
+      const int mid = (b + hi + 1) >> 1;
+      if (edge[mid] <= y) b = mid; else hi = mid - 1;
+    }
+    int next = edge[b + 1], k = first[b], kend = first[b + 1];
+    for (int hi = kend; k < hi;) {                                    // the first interval that ends right of x
+      const int mid = (k + hi) >> 1;
+      if (iv[2 * mid + 1] <= x) k = mid + 1; else hi = mid;
+    }
+    int cx0 = k < kend ? iv[2 * k] : kNone, cx1 = k < kend ? iv[2 * k + 1] : kNone;   // x < cx1 holds from here on
+    uint32_t w[4] = {0u, 0u, 0u, 0u}, bits = 0u;
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+      if ((uint32_t)i >= skip && e < total) {
+        const bool in = x >= cx0;
+        const uint32_t el = MASK ? (in ? 0u : 1u) : (c == 0 ? f0 : (c == 1 ? f1 : f2));
+        w[i / PER] |= el << (8u * (uint32_t)sizeof(E) * (uint32_t)(i % PER));
+        if (MASK || !in) bits |= 1u << i;
+        e++;
+        bool step = true;
+        if (nhwc) { step = ++c == 3; if (step) c = 0; }
+        if (step) {
+          if (++x == W) {
+            x = 0;
+            if (++y == H) { y = 0; c++; b = 0; next = edge[1]; }      // the next plane (NHWC and the mask: the canvas' end, nothing follows)
+            else if (y == next) { b++; next = edge[b + 1]; }
+            k = first[b]; kend = first[b + 1];
+            cx0 = k < kend ? iv[2 * k] : kNone; cx1 = k < kend ? iv[2 * k + 1] : kNone;
+          } else if (x == cx1) {                                      // (merged intervals: the next one starts right of x)
+            k++;
+            cx0 = k < kend ? iv[2 * k] : kNone; cx1 = k < kend ? iv[2 * k + 1] : kNone;
+          }
+        }
+      }
+    }
+    HIPDEC_GLOBAL E* d = origin + v0;
+    if (bits == kAll && aligned) {
+      uint4 v; v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+      *(HIPDEC_GLOBAL uint4*)d = v;
+    } else if (bits) {
+#pragma unroll
+      for (int i = 0; i < N; i++)
+        if ((bits >> i) & 1u) d[i] = (E)(w[i / PER] >> (8u * (uint32_t)sizeof(E) * (uint32_t)(i % PER)));
+    }
+  }
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void k_compose_cover(const hipdec::CanvasCover* __restrict__ cs)
+{
+  typedef typename TensorElem<DT>::T E;
+  const hipdec::CanvasCover cv = cs[blockIdx.z];   // wave-uniform: scalar loads into SGPRs
+  const bool small = (uint64_t)cv.m.W * (uint64_t)cv.m.H * 3ull < (1ull << 31);
+  if (cv.m.margin) {
+    const uint32_t f0 = canvas_fill_elem<DT>(cv.m, cv.m.value[0], cv.m.scale[0], cv.m.bias[0]),
+                   f1 = canvas_fill_elem<DT>(cv.m, cv.m.value[1], cv.m.scale[1], cv.m.bias[1]),
+                   f2 = canvas_fill_elem<DT>(cv.m, cv.m.value[2], cv.m.scale[2], cv.m.bias[2]);
+    if (small) compose_cover_blocks<E, false, uint32_t>(cv, (HIPDEC_GLOBAL E*)cv.m.o0, f0, f1, f2);
+    else compose_cover_blocks<E, false, uint64_t>(cv, (HIPDEC_GLOBAL E*)cv.m.o0, f0, f1, f2);
+  }
+  if (cv.m.mask) {
+    if (small) compose_cover_blocks<uint8_t, true, uint32_t>(cv, (HIPDEC_GLOBAL uint8_t*)cv.m.mask, 0u, 0u, 0u);
+    else compose_cover_blocks<uint8_t, true, uint64_t>(cv, (HIPDEC_GLOBAL uint8_t*)cv.m.mask, 0u, 0u, 0u);
+  }
+}
+
 // ---- warped tensor output (include/heif_hipdec.h hipdec_tensor_warp): k_warp_nearest / _bilinear / _bicubic
 #include "warp_kernels.h"
 
@@ -2191,7 +2297,7 @@ int record_tensor(const ColorParams& p)
   }
   t_tensor.on = false;   // taken
   t_captured_tensor.push_back(CapturedTensor{tp, sizeof(Pix) == 2, r.oriented ? 1 : 0, r.code, (uint64_t)r.pitch, r.plane_rows, r.resample, r.patch, r.merge, r.tpatch > 1 ? r.tpatch : 1,
-                                             r.oriented && !r.resample && !r.patch && r.strided_box ? 1 : 0, r.oriented && !r.patch && r.framed ? 1 : 0,
+                                             r.oriented && !r.resample && !r.patch && r.strided_box ? 1 : 0, r.oriented && !r.patch ? r.framed : 0,
                                              {r.frame_vis[0], r.frame_vis[1], r.frame_vis[2], r.frame_vis[3]}});
   return 0;
   }
@@ -2422,7 +2528,8 @@ struct FrameTileCount {
     tiles += hit; skipped += all - hit;
     max_x = hx > max_x ? hx : max_x; max_y = hy > max_y ? hy : max_y;
   }
-  void commit() const { g_framed_tiles += tiles; g_framed_skipped += skipped; }
+  // (composed: the pieces of a composed call - framed 2 - are hipdec_composed_stats', counted by the call)
+  void commit(bool composed) const { if (!composed) { g_framed_tiles += tiles; g_framed_skipped += skipped; } }
 };
 
 // the oriented form of color_tensor_launch: entries of all codes and (RGB form) sizes share the launch, so the grid covers the largest of each extent
@@ -2504,7 +2611,7 @@ int oriented_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
   });
   if (rc) return rc;
   g_oriented_entries += (uint64_t)caps.size(); g_oriented_quarter += quarter;
-  frame_tiles.commit();
+  frame_tiles.commit(caps[0].framed == 2);
   return 0;
 }
 
@@ -2575,7 +2682,7 @@ int resample_launch(std::vector<CapturedTensor>& caps, ColorBatchState& st, int 
   });
   if (rc) return rc;
   if (caps[0].oriented) { g_oriented_entries += (uint64_t)caps.size(); g_oriented_quarter += quarter; }
-  frame_tiles.commit();
+  frame_tiles.commit(caps[0].framed == 2);
   return 0;
 }
 }  // namespace
@@ -2640,6 +2747,47 @@ int canvas_margin_launch(ColorBatchState& st, const CanvasMargin* blocks, int n,
     dim3 block(256), grid((unsigned)(gx < 65536 ? gx : 65536), 1, (unsigned)count);
     if (dispatch_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((k_canvas_margin<decltype(dt)::value>), grid, block, 0, s, dev); })) return 0;
     return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "placed output: unknown dtype %d", dtype);
+  });
+}
+
+// ---- composed tensor output: the fill and the masks of all canvases of a call as ONE launch of k_compose_cover; the cover tables travel behind the
+// per-canvas blocks in the same upload (the blocks hold addresses inside it, as the resampling blocks do)
+std::atomic<uint64_t> g_composed_calls{0}, g_composed_entries{0}, g_composed_pieces{0}, g_composed_hidden{0}, g_composed_cover_launches{0};
+void composed_note_call(uint64_t entries, uint64_t pieces, uint64_t hidden)
+{
+  g_composed_calls++; g_composed_entries += entries; g_composed_pieces += pieces; g_composed_hidden += hidden;
+}
+
+int canvas_cover_launch(ColorBatchState& st, const CanvasCover* blocks, int n, const int32_t* words, size_t n_words, int dtype, hipStream_t s)
+{
+  bool any = false;
+  uint64_t max_elems = 0;
+  for (int i = 0; i < n; i++) {
+    if (!blocks[i].m.margin && !blocks[i].m.mask) continue;
+    any = true;
+    const uint64_t elems = 3ull * (uint64_t)blocks[i].m.W * (uint64_t)blocks[i].m.H;
+    max_elems = elems > max_elems ? elems : max_elems;
+  }
+  if (!any) return 0;
+  const size_t blocks_bytes = ((size_t)n * sizeof(CanvasCover) + 15) & ~(size_t)15;
+  const size_t bytes = blocks_bytes + n_words * sizeof(int32_t);
+  std::vector<uint8_t> host(bytes);
+  if (int rc = blocks_reserve(st, bytes)) return rc;   // (the blocks below hold addresses inside it)
+  const int32_t* words_dev = (const int32_t*)((const uint8_t*)st.dev + blocks_bytes);
+  for (int i = 0; i < n; i++) {
+    CanvasCover c = blocks[i];
+    c.table = (uint64_t)(uintptr_t)(words_dev + c.table);
+    memcpy(host.data() + (size_t)i * sizeof(CanvasCover), &c, sizeof(c));
+  }
+  if (n_words) memcpy(host.data() + blocks_bytes, words, n_words * sizeof(int32_t));
+  if (int rc = blocks_upload(st, host, s)) return rc;
+  const uint64_t per = dtype == TD_U8 ? 16 : (dtype == TD_F32 ? 4 : 8);   // (as canvas_margin_launch: a lane owns one 16-byte block at a time)
+  const uint64_t gx = (max_elems / per + 2 + 255) / 256;
+  return launch_z_chunks(0, (size_t)n, "cover kernel launch", &g_composed_cover_launches, [&](size_t first, size_t count) {
+    const CanvasCover* dev = (const CanvasCover*)st.dev + first;
+    dim3 block(256), grid((unsigned)(gx < 65536 ? gx : 65536), 1, (unsigned)count);
+    if (dispatch_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL((k_compose_cover<decltype(dt)::value>), grid, block, 0, s, dev); })) return 0;
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "composed output: unknown dtype %d", dtype);
   });
 }
 
@@ -3180,6 +3328,15 @@ void hipdec_framed_stats(uint64_t* calls, uint64_t* entries, uint64_t* tiles, ui
   if (entries) *entries = g_framed_entries.load();
   if (tiles) *tiles = g_framed_tiles.load();
   if (tiles_skipped) *tiles_skipped = g_framed_skipped.load();
+}
+
+void hipdec_composed_stats(uint64_t* calls, uint64_t* entries, uint64_t* pieces, uint64_t* hidden_entries, uint64_t* cover_launches)
+{
+  if (calls) *calls = g_composed_calls.load();
+  if (entries) *entries = g_composed_entries.load();
+  if (pieces) *pieces = g_composed_pieces.load();
+  if (hidden_entries) *hidden_entries = g_composed_hidden.load();
+  if (cover_launches) *cover_launches = g_composed_cover_launches.load();
 }
 
 void hipdec_placed_stats(uint64_t* calls, uint64_t* entries, uint64_t* margin_launches)

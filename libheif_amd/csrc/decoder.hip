@@ -834,7 +834,7 @@ int tensor_window(const char* who, const hipdec_tensor_entry* e, int idx, int w,
 int tensor_record_entry(const char* who, const uint8_t* y, size_t ys, const uint8_t* cb, size_t cbs, const uint8_t* cr, size_t crs, int w, int h, int bits, int cf,
                         const hipdec_nclx* nclx, const hipdec_nclx* nclx_after_sdr, const hipdec_tensor_desc* d, int left, int top, int rw, int rh, int flip, void* elem0,
                         int orientation = -1, size_t pitch = 0, int plane_rows = 0, int patch = 0, int merge = 1, int tpatch = 1, bool* strided_box = nullptr,
-                        const int* frame_vis = nullptr)   // frame_vis: a framed entry's visible part (placed_entry)
+                        const int* frame_vis = nullptr, bool composed = false)   // frame_vis: a framed entry's visible part (placed_entry), a composed entry's piece
 {
   if (int rc = tensor_check_resample_depth(who, d, bits)) return rc;
   TensorRequest rq;
@@ -858,7 +858,7 @@ int tensor_record_entry(const char* who, const uint8_t* y, size_t ys, const uint
   rq.tpatch = tpatch;
   if (strided_box) *strided_box = *strided_box && rq.oriented && !rq.resample && !patch && d->filter == HIPDEC_SCALE_BOX && (rq.code == HIPDEC_ORIENT_0 || rq.code == HIPDEC_ORIENT_MIRROR);
   rq.strided_box = strided_box && *strided_box;
-  if (frame_vis) { rq.framed = 1; for (int k = 0; k < 4; k++) rq.frame_vis[k] = frame_vis[k]; }
+  if (frame_vis) { rq.framed = composed ? 2 : 1; for (int k = 0; k < 4; k++) rq.frame_vis[k] = frame_vis[k]; }
   rq.plane_rows = plane_rows ? plane_rows : d->height;   // (d->height: the displayed rows)
   rq.sH = cf == 1 || cf == 2 ? 1 : 0; rq.sV = cf == 1 ? 1 : 0;
   rq.left = left; rq.top = top; rq.rw = rw; rq.rh = rh; rq.flip = flip; rq.nhwc = d->layout == HIPDEC_TENSOR_NHWC;
@@ -918,7 +918,9 @@ int check_orientations(const char* who, const char* what, const int* orientation
 
 // ---- placed tensor output (hipdec_batch_to_tensor_placed / hipdec_album_to_tensor_placed): what the two forms share
 // framed (hipdec_batch_to_tensor_framed / hipdec_album_to_tensor_framed): a rectangle may leave the canvas, and the k_frame_* kernels store its visible part
-struct PlacedArgs { const hipdec_tensor_place* places; const hipdec_tensor_fill* fill; void* mask; bool framed = false; };
+// composed (hipdec_batch_to_tensor_composed / hipdec_album_to_tensor_composed): `composed` with tiles on n_canvases canvases in place of the rectangles
+struct PlacedArgs { const hipdec_tensor_place* places; const hipdec_tensor_fill* fill; void* mask; bool framed = false;
+                    bool composed = false; const hipdec_tensor_tile* tiles = nullptr; int n_canvases = 0; };
 constexpr int kFrameReach = 1 << 24;   // |x|, |y| and the sides of a framed rectangle: sums and products of two stay far inside 64 bits
 
 // what the arguments alone decide (the description has passed tensor_check_desc)
@@ -1000,6 +1002,167 @@ void placed_entry(const hipdec_tensor_desc* d, const PlacedArgs& pa, int e, void
   for (int c = 0; c < 3; c++) { m->value[c] = pa.fill ? pa.fill->value[c] : 0.0f; m->scale[c] = d->scale[c]; m->bias[c] = d->bias[c]; }
 }
 
+// ---- composed tensor output (hipdec_batch_to_tensor_composed / hipdec_album_to_tensor_composed): what the two forms and hipdec_compose_visible_area share
+// A rectangle in canvas coordinates, half open.
+struct ComposeRect { int x0, y0, x1, y1; };
+// What the tiles alone decide, per call: the pieces every entry owns and the cover table of every canvas (hipdec_internal.h CanvasCover).
+struct ComposePlan {
+  std::vector<std::vector<ComposeRect>> pieces;   // per entry, disjoint, in canvas coordinates; empty: the entry is fully hidden
+  std::vector<int32_t> words;                     // the cover tables of all canvases
+  std::vector<size_t> table;                      // per canvas: its table's first word
+  std::vector<int> bands, intervals;              // per canvas
+  std::vector<uint8_t> uncovered;                 // per canvas: a pixel no region covers
+  uint64_t n_pieces = 0, hidden = 0;
+};
+
+// r without s: the rows of r above s, those below it, and what lies left and right of s in between - up to four disjoint rectangles, in that order
+void compose_subtract(const ComposeRect& r, const ComposeRect& s, std::vector<ComposeRect>* out)
+{
+  if (s.x0 >= r.x1 || s.x1 <= r.x0 || s.y0 >= r.y1 || s.y1 <= r.y0) { out->push_back(r); return; }
+  const int ya = std::max(r.y0, s.y0), yb = std::min(r.y1, s.y1);
+  if (r.y0 < ya) out->push_back({r.x0, r.y0, r.x1, ya});
+  if (yb < r.y1) out->push_back({r.x0, yb, r.x1, r.y1});
+  if (r.x0 < s.x0) out->push_back({r.x0, ya, s.x0, yb});
+  if (s.x1 < r.x1) out->push_back({s.x1, ya, r.x1, yb});
+}
+
+// The tiles of a call on canvases of W x H (positive): refusals name the entry; *plan is filled.  Nothing here reads a handle or touches a device.
+int compose_plan(const char* who, int W, int H, const hipdec_tensor_tile* tiles, int n_entries, int n_canvases, ComposePlan* plan)
+{
+  if (!tiles) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: no tiles", who);
+  if (n_entries < 1 || n_canvases < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: %d entries on %d canvases", who, n_entries, n_canvases);
+  std::vector<ComposeRect> region((size_t)n_entries);
+  std::vector<std::vector<int>> of((size_t)n_canvases);   // per canvas: its entries, ascending
+  auto far = [](const hipdec_tensor_place& p) {
+    return p.width > kFrameReach || p.height > kFrameReach || p.x > kFrameReach || p.x < -kFrameReach || p.y > kFrameReach || p.y < -kFrameReach;
+  };
+  for (int e = 0; e < n_entries; e++) {
+    const hipdec_tensor_tile& t = tiles[e];
+    const hipdec_tensor_place& pl = t.place;
+    if (t.canvas < 0 || t.canvas >= n_canvases) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: canvas %d of %d", who, e, t.canvas, n_canvases);
+    if (pl.width < 1 || pl.height < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: rectangle size %d x %d", who, e, pl.width, pl.height);
+    const bool whole = !t.clip.width && !t.clip.height;
+    if (!whole && (t.clip.width < 1 || t.clip.height < 1))
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: clip size %d x %d (0 x 0: the whole canvas)", who, e, t.clip.width, t.clip.height);
+    if (far(pl) || (!whole && far(t.clip)))
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: rectangle %d x %d at (%d, %d), clip %d x %d at (%d, %d): offsets and sides reach 2^24 at most", who, e,
+                       pl.width, pl.height, pl.x, pl.y, t.clip.width, t.clip.height, t.clip.x, t.clip.y);
+    ComposeRect r{std::max(pl.x, 0), std::max(pl.y, 0), std::min(pl.x + pl.width, W), std::min(pl.y + pl.height, H)};   // (below 2^25: no overflow)
+    if (!whole) { r.x0 = std::max(r.x0, t.clip.x); r.y0 = std::max(r.y0, t.clip.y); r.x1 = std::min(r.x1, t.clip.x + t.clip.width); r.y1 = std::min(r.y1, t.clip.y + t.clip.height); }
+    if (r.x0 >= r.x1 || r.y0 >= r.y1)
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: rectangle %d x %d at (%d, %d) and its clip share no pixel of the canvas of %d x %d", who, e, pl.width,
+                       pl.height, pl.x, pl.y, W, H);
+    region[(size_t)e] = r;
+    if (of[(size_t)t.canvas].size() == HIPDEC_COMPOSE_MAX_ENTRIES)
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: canvas %d has more than %d entries", who, e, t.canvas, HIPDEC_COMPOSE_MAX_ENTRIES);
+    of[(size_t)t.canvas].push_back(e);
+  }
+  plan->pieces.assign((size_t)n_entries, {});
+  plan->table.assign((size_t)n_canvases, 0); plan->bands.assign((size_t)n_canvases, 0); plan->intervals.assign((size_t)n_canvases, 0);
+  plan->uncovered.assign((size_t)n_canvases, 0);
+  plan->words.clear(); plan->n_pieces = 0; plan->hidden = 0;
+  std::vector<ComposeRect> cur, nxt;
+  std::vector<int> edges;
+  std::vector<std::pair<int, int>> spans;
+  for (int cv = 0; cv < n_canvases; cv++) {
+    const std::vector<int>& es = of[(size_t)cv];
+    for (size_t a = 0; a < es.size(); a++) {   // pieces: the region without the regions of the later entries
+      cur.assign(1, region[(size_t)es[a]]);
+      for (size_t j = a + 1; j < es.size() && !cur.empty(); j++) {
+        nxt.clear();
+        for (const ComposeRect& r : cur) compose_subtract(r, region[(size_t)es[j]], &nxt);
+        cur.swap(nxt);
+        if (cur.size() > HIPDEC_COMPOSE_MAX_PIECES) break;
+      }
+      plan->n_pieces += cur.size();
+      if (plan->n_pieces > HIPDEC_COMPOSE_MAX_PIECES)
+        return set_error(HIPDEC_ERR_LIMIT, "%s: entry %d: the call has more than %d pieces", who, es[a], HIPDEC_COMPOSE_MAX_PIECES);
+      if (cur.empty()) plan->hidden++;
+      plan->pieces[(size_t)es[a]] = cur;
+    }
+    // the cover table: bands between the distinct row edges, per band the merged column intervals of the regions that cross it
+    edges.assign({0, H});
+    for (int e : es) { edges.push_back(region[(size_t)e].y0); edges.push_back(region[(size_t)e].y1); }
+    std::sort(edges.begin(), edges.end());
+    edges.erase(std::unique(edges.begin(), edges.end()), edges.end());
+    const int nb = (int)edges.size() - 1;
+    const size_t t0 = plan->words.size();
+    plan->table[(size_t)cv] = t0; plan->bands[(size_t)cv] = nb;
+    plan->words.resize(t0 + 2 * ((size_t)nb + 1));
+    for (int k = 0; k <= nb; k++) plan->words[t0 + (size_t)k] = edges[(size_t)k];
+    uint64_t covered = 0;
+    int n_iv = 0;
+    for (int k = 0; k < nb; k++) {
+      plan->words[t0 + (size_t)nb + 1 + (size_t)k] = n_iv;
+      spans.clear();
+      for (int e : es) if (region[(size_t)e].y0 <= edges[(size_t)k] && edges[(size_t)k] < region[(size_t)e].y1) spans.emplace_back(region[(size_t)e].x0, region[(size_t)e].x1);
+      std::sort(spans.begin(), spans.end());
+      for (size_t i = 0; i < spans.size();) {
+        int x0 = spans[i].first, x1 = spans[i].second;
+        for (i++; i < spans.size() && spans[i].first <= x1; i++) x1 = std::max(x1, spans[i].second);   // (abutting intervals merge as well)
+        plan->words.push_back(x0); plan->words.push_back(x1);
+        covered += (uint64_t)(x1 - x0) * (uint64_t)(edges[(size_t)k + 1] - edges[(size_t)k]);
+        n_iv++;
+      }
+    }
+    plan->words[t0 + 2 * (size_t)nb + 1] = n_iv;
+    plan->intervals[(size_t)cv] = n_iv;
+    plan->uncovered[(size_t)cv] = covered < (uint64_t)W * (uint64_t)H;
+    if (plan->words.size() * sizeof(int32_t) > kComposeTableBytes)
+      return set_error(HIPDEC_ERR_LIMIT, "%s: the cover tables of this call exceed %zu bytes", who, (size_t)kComposeTableBytes);
+  }
+  return 0;
+}
+
+// a piece in the displayed coordinates of its entry's sample (x0, y0, x1, y1): the window of a framed block
+void compose_piece_window(const ComposeRect& r, const hipdec_tensor_place& pl, int* vis)
+{
+  vis[0] = r.x0 - pl.x; vis[1] = r.y0 - pl.y; vis[2] = r.x1 - pl.x; vis[3] = r.y1 - pl.y;
+}
+
+// what the arguments of a composed call alone decide, after tensor_check_desc: the tiles, the samples' sizes, the fill
+int composed_check(const char* who, const hipdec_tensor_desc* d, const PlacedArgs& pa, int n_entries, ComposePlan* plan)
+{
+  if (int rc = compose_plan(who, d->width, d->height, pa.tiles, n_entries, pa.n_canvases, plan)) return rc;
+  for (int e = 0; e < n_entries; e++) {
+    hipdec_tensor_desc sample = *d;   // what the oriented call refuses for a tensor of the rectangle's size
+    sample.width = pa.tiles[e].place.width; sample.height = pa.tiles[e].place.height;
+    size_t bytes = 0;
+    if (tensor_check_desc(who, &sample, 1, &bytes))
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: rectangle size %d x %d: the sample is too large", who, e, sample.width, sample.height);
+  }
+  return placed_check(who, d, pa, n_entries);   // (no places: the fill)
+}
+
+// entry e of a composed call: *sample is the description of the sample in its rectangle, *elem0 where the rectangle's first element would lie in its canvas
+void composed_entry(const hipdec_tensor_desc* d, const PlacedArgs& pa, int e, void* out_dev, size_t canvas_bytes, hipdec_tensor_desc* sample, void** elem0)
+{
+  const hipdec_tensor_place& pl = pa.tiles[e].place;
+  const size_t k = d->layout == HIPDEC_TENSOR_NHWC ? 3 : 1;
+  *sample = *d;
+  sample->width = pl.width; sample->height = pl.height;
+  *elem0 = (uint8_t*)out_dev + (size_t)pa.tiles[e].canvas * canvas_bytes + ((int64_t)pl.y * (int64_t)d->width + (int64_t)pl.x) * (int64_t)(k * tensor_elem_bytes(d->dtype));
+}
+
+// the fill and the masks of a composed call: ONE launch of k_compose_cover (color.hip) over the canvases' cover tables
+int composed_cover(ColorBatchState& st, const hipdec_tensor_desc* d, const PlacedArgs& pa, const ComposePlan& plan, void* out_dev, size_t canvas_bytes, hipStream_t s)
+{
+  std::vector<CanvasCover> blocks((size_t)pa.n_canvases);
+  for (int cv = 0; cv < pa.n_canvases; cv++) {
+    CanvasCover& c = blocks[(size_t)cv];
+    memset(&c, 0, sizeof(c));
+    c.m.o0 = (uint8_t*)out_dev + (size_t)cv * canvas_bytes;
+    c.m.mask = pa.mask ? (uint8_t*)pa.mask + (size_t)cv * (size_t)d->width * (size_t)d->height : nullptr;
+    c.m.W = d->width; c.m.H = d->height;
+    c.m.nhwc = d->layout == HIPDEC_TENSOR_NHWC;
+    c.m.domain = pa.fill ? pa.fill->domain : HIPDEC_FILL_COMPONENT;
+    c.m.margin = plan.uncovered[(size_t)cv];
+    for (int ch = 0; ch < 3; ch++) { c.m.value[ch] = pa.fill ? pa.fill->value[ch] : 0.0f; c.m.scale[ch] = d->scale[ch]; c.m.bias[ch] = d->bias[ch]; }
+    c.table = (uint64_t)plan.table[(size_t)cv]; c.n_bands = plan.bands[(size_t)cv]; c.n_intervals = plan.intervals[(size_t)cv];
+  }
+  return canvas_cover_launch(st, blocks.data(), pa.n_canvases, plan.words.data(), plan.words.size(), d->dtype, s);
+}
+
 // ---- packed tensor output (hipdec_batch_to_tensor_packed / hipdec_album_to_tensor_packed): what the two forms and hipdec_tensor_packed_layout share
 struct PackedArgs { const hipdec_tensor_sample* samples; int patch, merge; };
 
@@ -1079,10 +1242,14 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
   hipdec_tensor_desc unit;
   PackedArgs pk{nullptr, 0, 1};
   if (ps) if (int rc = packed_check_desc("to_tensor_packed", desc, &unit)) return rc;
-  if (int rc = tensor_check_desc("to_tensor", ps ? &unit : desc, n_entries, &bytes)) return rc;
+  const bool composed = pa && pa->composed;             // (bytes: n_canvases canvases)
+  ComposePlan plan;
+  if (composed && n_entries < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor_composed: %d entries", n_entries);
+  if (int rc = tensor_check_desc("to_tensor", ps ? &unit : desc, composed ? pa->n_canvases : n_entries, &bytes)) return rc;
   if (oriented) if (int rc = check_orientations("to_tensor_oriented", "entry", orientations, n_entries)) return rc;
   const bool framed = pa && pa->framed && pa->places;   // (without rectangles every sample is its canvas: the oriented kernels)
-  if (pa) if (int rc = placed_check(pa->framed ? "to_tensor_framed" : "to_tensor_placed", desc, *pa, n_entries)) return rc;
+  if (composed) { if (int rc = composed_check("to_tensor_composed", desc, *pa, n_entries, &plan)) return rc; }
+  else if (pa) if (int rc = placed_check(pa->framed ? "to_tensor_framed" : "to_tensor_placed", desc, *pa, n_entries)) return rc;
   if (ps) { if (int rc = packed_check("to_tensor_packed", desc, ps->samples, ps->patches, n_entries, out_bytes, &pk)) return rc; }
   else if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
   // (everything above is decided without reading the handle)
@@ -1098,10 +1265,14 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
   for (int e = 0; framed && b->max_pixels && e < n_entries; e++)
     if ((uint64_t)pa->places[e].width * (uint64_t)pa->places[e].height > b->max_pixels)
       return set_error(HIPDEC_ERR_LIMIT, "to_tensor_framed: entry %d: rectangle of %d x %d pixels exceeds max_image_size_pixels", e, pa->places[e].width, pa->places[e].height);
+  for (int e = 0; composed && b->max_pixels && e < n_entries; e++)
+    if ((uint64_t)pa->tiles[e].place.width * (uint64_t)pa->tiles[e].place.height > b->max_pixels)
+      return set_error(HIPDEC_ERR_LIMIT, "to_tensor_composed: entry %d: rectangle of %d x %d pixels exceeds max_image_size_pixels", e, pa->tiles[e].place.width,
+                       pa->tiles[e].place.height);
   return guarded("to_tensor", [&]() -> int {
     hipStream_t s = follow_stream(b, stream);
-    const size_t entry_bytes = bytes / (size_t)n_entries;
-    std::vector<CanvasMargin> margins(pa ? (size_t)n_entries : 0);
+    const size_t entry_bytes = bytes / (size_t)(composed ? pa->n_canvases : n_entries);   // (composed: a canvas)
+    std::vector<CanvasMargin> margins(pa && !composed ? (size_t)n_entries : 0);
     color_tensor_begin();
     for (int e = 0; e < n_entries; e++) {
       const int i = entries ? entries[e].item : e;
@@ -1118,15 +1289,22 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
       int plane_rows = 0;
       int vis[4];
       if (pa) {
-        if (!rc) rc = placed_check_component(pa->framed ? "to_tensor_framed" : "to_tensor_placed", desc, *pa, e, b->wide ? I.bit_depth_luma : 8);
-        placed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0, &margins[(size_t)e], vis);
+        if (!rc) rc = placed_check_component(composed ? "to_tensor_composed" : (pa->framed ? "to_tensor_framed" : "to_tensor_placed"), desc, *pa, e, b->wide ? I.bit_depth_luma : 8);
+        if (composed) composed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0);
+        else placed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0, &margins[(size_t)e], vis);
         pitch = (size_t)desc->width * (desc->layout == HIPDEC_TENSOR_NHWC ? 3 : 1); plane_rows = desc->height;
       }
       if (ps) packed_entry(desc, pk, e, out_dev, &sample, &elem0);   // (its own size, dense pitch and plane: the defaults of the sample's description)
-      if (!rc) rc = tensor_record_entry("to_tensor", b->arena + P.off_out[0], P.out_stride[0], b->arena + P.off_out[1], P.out_stride[1], b->arena + P.off_out[2], P.out_stride[2],
-                                        P.out_width, P.out_height, b->wide ? I.bit_depth_luma : 8, P.chroma_format_idc, &nclx, &nclx, &sample, left, top, rw, rh,
-                                        entries ? entries[e].flip : 0, elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows, pk.patch, pk.merge, 1, nullptr,
-                                        framed ? vis : nullptr);
+      // one request; a composed entry: one per piece it owns (none when it is hidden), the piece as the window of the framed kernels
+      const size_t n_req = composed ? plan.pieces[(size_t)e].size() : 1;
+      if (!rc && composed) rc = tensor_check_resample_depth("to_tensor_composed", desc, b->wide ? I.bit_depth_luma : 8);   // (a hidden entry is refused as a visible one)
+      for (size_t q = 0; !rc && q < n_req; q++) {
+        if (composed) compose_piece_window(plan.pieces[(size_t)e][q], pa->tiles[e].place, vis);
+        rc = tensor_record_entry("to_tensor", b->arena + P.off_out[0], P.out_stride[0], b->arena + P.off_out[1], P.out_stride[1], b->arena + P.off_out[2], P.out_stride[2],
+                                 P.out_width, P.out_height, b->wide ? I.bit_depth_luma : 8, P.chroma_format_idc, &nclx, &nclx, &sample, left, top, rw, rh,
+                                 entries ? entries[e].flip : 0, elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows, pk.patch, pk.merge, 1, nullptr,
+                                 framed || composed ? vis : nullptr, composed);
+      }
       if (rc) { color_tensor_abort(); return rc; }
     }
     const size_t slot = b->runs ? (b->runs - 1) % (b->ev.size() / kEv) : 0;
@@ -1134,13 +1312,15 @@ int batch_to_tensor_impl(hipdec_batch* b, const hipdec_tensor_desc* desc, const 
     HIPDEC_CHECK_HIP(hipEventRecord(ev[6], s));
     // (resampled entries are not hipdec_batch_tensor_block's blocks: they go with the oriented ones)
     int rc = color_tensor_launch(ps ? b->color_packed : (oriented || resample_filter(desc->filter) ? b->color_oriented : b->color_tensor), desc->filter, desc->dtype, s);
-    if (!rc && pa) rc = canvas_margin_launch(b->color_margin, margins.data(), n_entries, desc->dtype, s);   // (disjoint elements: no order between the two but the stream's)
+    if (!rc && composed) rc = composed_cover(b->color_margin, desc, *pa, plan, out_dev, entry_bytes, s);
+    else if (!rc && pa) rc = canvas_margin_launch(b->color_margin, margins.data(), n_entries, desc->dtype, s);   // (disjoint elements: no order between the two but the stream's)
     HIPDEC_CHECK_HIP(hipEventRecord(ev[7], s));
     if (!rc && b->runs) b->colour_timed[slot] = 1;
     b->mark_done(s);
     if (!rc) { g_tensor_calls++; g_tensor_entries += (uint64_t)n_entries; }
-    if (!rc && pa && !pa->framed) placed_note_call((uint64_t)n_entries);
+    if (!rc && pa && !pa->framed && !composed) placed_note_call((uint64_t)n_entries);
     if (!rc && pa && pa->framed) framed_note_call((uint64_t)n_entries);
+    if (!rc && composed) composed_note_call((uint64_t)n_entries, plan.n_pieces, plan.hidden);
     if (!rc && ps) packed_note_call((uint64_t)n_entries, pk.patch > 0);
     return rc;
   });
@@ -1362,6 +1542,14 @@ int hipdec_batch_to_tensor_framed(hipdec_batch* b, const hipdec_tensor_desc* des
   return batch_to_tensor_impl(b, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, &pa);
 }
 
+int hipdec_batch_to_tensor_composed(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                    const hipdec_tensor_tile* tiles, const hipdec_tensor_fill* fill, void* mask_dev, int n_entries, int n_canvases, void* out_dev,
+                                    size_t out_bytes, void* stream)
+{
+  const PlacedArgs pa{nullptr, fill, mask_dev, false, true, tiles, n_canvases};
+  return batch_to_tensor_impl(b, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, &pa);
+}
+
 int hipdec_batch_to_tensor_warped(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
                                   const hipdec_warp_desc* warp, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill, int n_entries, void* out_dev,
                                   size_t out_bytes, void* stream)
@@ -1450,6 +1638,60 @@ int hipdec_resize_crop_place(int src_width, int src_height, int resize, int crop
   };
   out->x = offset(w, crop_width); out->y = offset(h, crop_height);
   out->width = (int)w; out->height = (int)h;
+  return 0;
+}
+
+// the pixels every entry of a composed call owns: the areas of its pieces
+int hipdec_compose_visible_area(int width, int height, const hipdec_tensor_tile* tiles, int n_entries, int n_canvases, uint64_t* area)
+{
+  if (!area || width < 1 || height < 1 || width > kFrameReach || height > kFrameReach)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "compose_visible_area: canvas %d x %d", width, height), -1;
+  return guarded("compose_visible_area", [&]() -> int {
+    ComposePlan plan;
+    if (compose_plan("compose_visible_area", width, height, tiles, n_entries, n_canvases, &plan)) return -1;
+    for (int e = 0; e < n_entries; e++) {
+      uint64_t a = 0;
+      for (const ComposeRect& r : plan.pieces[(size_t)e]) a += (uint64_t)(r.x1 - r.x0) * (uint64_t)(r.y1 - r.y0);
+      area[e] = a;
+    }
+    return 0;
+  }) ? -1 : 0;
+}
+
+// YOLOv5's mosaic-4: the four samples meet at the centre, each clipped to its quadrant
+int hipdec_mosaic_tiles(int canvas_w, int canvas_h, int xc, int yc, const int* widths, const int* heights, int canvas, hipdec_tensor_tile* out)
+{
+  if (!out || !widths || !heights || canvas < 0 || canvas_w < 1 || canvas_h < 1 || canvas_w > kFrameReach || canvas_h > kFrameReach || xc <= 0 || xc >= canvas_w ||
+      yc <= 0 || yc >= canvas_h)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "mosaic_tiles: canvas %d of %d x %d, centre (%d, %d)", canvas, canvas_w, canvas_h, xc, yc), -1;
+  for (int k = 0; k < 4; k++)
+    if (widths[k] < 1 || heights[k] < 1 || widths[k] > kFrameReach || heights[k] > kFrameReach)
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "mosaic_tiles: sample %d of %d x %d (1 .. 2^24 each way)", k, widths[k], heights[k]), -1;
+  for (int k = 0; k < 4; k++) {
+    const bool right = k & 1, low = k >> 1;
+    out[k].canvas = canvas;
+    out[k].place = hipdec_tensor_place{right ? xc : xc - widths[k], low ? yc : yc - heights[k], widths[k], heights[k]};
+    out[k].clip = hipdec_tensor_place{right ? xc : 0, low ? yc : 0, right ? canvas_w - xc : xc, low ? canvas_h - yc : yc};
+  }
+  return 0;
+}
+
+// a contact sheet: entry k letterboxed (centred) into cell k, row-major
+int hipdec_sheet_tiles(int cols, int rows, int cell_w, int cell_h, int gap, const int* widths, const int* heights, int n, int upscale, int canvas, hipdec_tensor_tile* out)
+{
+  if (!out || !widths || !heights || canvas < 0 || cols < 1 || rows < 1 || cell_w < 1 || cell_h < 1 || gap < 0 || n < 1 || (int64_t)n > (int64_t)cols * rows)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "sheet_tiles: %d samples in %d x %d cells of %d x %d, gap %d, canvas %d", n, cols, rows, cell_w, cell_h, gap, canvas), -1;
+  const int64_t sheet_w = (int64_t)cols * cell_w + (int64_t)(cols - 1) * gap, sheet_h = (int64_t)rows * cell_h + (int64_t)(rows - 1) * gap;
+  if (sheet_w > kFrameReach || sheet_h > kFrameReach)
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "sheet_tiles: a sheet of %lld x %lld: sides reach 2^24 at most", (long long)sheet_w, (long long)sheet_h), -1;
+  for (int k = 0; k < n; k++) {
+    const int64_t cx = (int64_t)(k % cols) * ((int64_t)cell_w + gap), cy = (int64_t)(k / cols) * ((int64_t)cell_h + gap);
+    hipdec_tensor_place pl;
+    if (hipdec_letterbox_place(widths[k], heights[k], cell_w, cell_h, upscale, 1, &pl)) return -1;   // (its message stands)
+    out[k].canvas = canvas;
+    out[k].place = hipdec_tensor_place{(int)(cx + pl.x), (int)(cy + pl.y), pl.width, pl.height};
+    out[k].clip = hipdec_tensor_place{(int)cx, (int)cy, cell_w, cell_h};
+  }
   return 0;
 }
 

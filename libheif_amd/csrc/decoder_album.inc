@@ -324,10 +324,14 @@ int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const 
   hipdec_tensor_desc unit;
   PackedArgs pk{nullptr, 0, 1};
   if (ps) if (int rc = packed_check_desc("album_to_tensor_packed", desc, &unit)) return rc;
-  if (int rc = tensor_check_desc("album_to_tensor", ps ? &unit : desc, n_entries, &bytes)) return rc;
+  const bool composed = pa && pa->composed;
+  ComposePlan plan;
+  if (composed && n_entries < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_tensor_composed: %d entries", n_entries);
+  if (int rc = tensor_check_desc("album_to_tensor", ps ? &unit : desc, composed ? pa->n_canvases : n_entries, &bytes)) return rc;
   if (oriented) if (int rc = check_orientations("album_to_tensor_oriented", "entry", orientations, n_entries)) return rc;
   const bool framed = pa && pa->framed && pa->places;
-  if (pa) if (int rc = placed_check(pa->framed ? "album_to_tensor_framed" : "album_to_tensor_placed", desc, *pa, n_entries)) return rc;
+  if (composed) { if (int rc = composed_check("album_to_tensor_composed", desc, *pa, n_entries, &plan)) return rc; }
+  else if (pa) if (int rc = placed_check(pa->framed ? "album_to_tensor_framed" : "album_to_tensor_placed", desc, *pa, n_entries)) return rc;
   if (ps) { if (int rc = packed_check("album_to_tensor_packed", desc, ps->samples, ps->patches, n_entries, out_bytes, &pk)) return rc; }
   else if (out_bytes < bytes) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "album_to_tensor: out_bytes %zu is smaller than the tensor of %zu bytes", out_bytes, bytes);
   // (everything above is decided without reading the handle)
@@ -343,11 +347,15 @@ int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const 
   for (int e = 0; framed && a->max_pixels && e < n_entries; e++)
     if ((uint64_t)pa->places[e].width * (uint64_t)pa->places[e].height > a->max_pixels)
       return set_error(HIPDEC_ERR_LIMIT, "album_to_tensor_framed: entry %d: rectangle of %d x %d pixels exceeds max_image_size_pixels", e, pa->places[e].width, pa->places[e].height);
+  for (int e = 0; composed && a->max_pixels && e < n_entries; e++)
+    if ((uint64_t)pa->tiles[e].place.width * (uint64_t)pa->tiles[e].place.height > a->max_pixels)
+      return set_error(HIPDEC_ERR_LIMIT, "album_to_tensor_composed: entry %d: rectangle of %d x %d pixels exceeds max_image_size_pixels", e, pa->tiles[e].place.width,
+                       pa->tiles[e].place.height);
   return guarded("album_to_tensor", [&]() -> int {
     hipdec_batch* b = a->batch.get();
     hipStream_t s = follow_stream(b, stream);
-    const size_t entry_bytes = bytes / (size_t)n_entries;
-    std::vector<CanvasMargin> margins(pa ? (size_t)n_entries : 0);
+    const size_t entry_bytes = bytes / (size_t)(composed ? pa->n_canvases : n_entries);
+    std::vector<CanvasMargin> margins(pa && !composed ? (size_t)n_entries : 0);
     color_tensor_begin();
     for (int e = 0; e < n_entries; e++) {
       const int p = entries ? entries[e].item : e;
@@ -363,21 +371,31 @@ int album_to_tensor_impl(hipdec_album* a, const hipdec_tensor_desc* desc, const 
       int plane_rows = 0;
       int vis[4];
       if (pa) {
-        if (!rc) rc = placed_check_component(pa->framed ? "album_to_tensor_framed" : "album_to_tensor_placed", desc, *pa, e, S.wide ? I.bit_depth_luma : 8);
-        placed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0, &margins[(size_t)e], vis);
+        if (!rc) rc = placed_check_component(composed ? "album_to_tensor_composed" : (pa->framed ? "album_to_tensor_framed" : "album_to_tensor_placed"), desc, *pa, e,
+                                             S.wide ? I.bit_depth_luma : 8);
+        if (composed) composed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0);
+        else placed_entry(desc, *pa, e, out_dev, entry_bytes, &sample, &elem0, &margins[(size_t)e], vis);
         pitch = (size_t)desc->width * (desc->layout == HIPDEC_TENSOR_NHWC ? 3 : 1); plane_rows = desc->height;
       }
       if (ps) packed_entry(desc, pk, e, out_dev, &sample, &elem0);
-      if (!rc) rc = tensor_record_entry("album_to_tensor", S.plane[0], S.stride[0], S.plane[1], S.stride[1], S.plane[2], S.stride[2], S.width, S.height,
-                                        S.wide ? I.bit_depth_luma : 8, S.chroma_format_idc, &nclx, &nclx, &sample, left, top, rw, rh, entries ? entries[e].flip : 0,
-                                        elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows, pk.patch, pk.merge, 1, nullptr, framed ? vis : nullptr);
+      const size_t n_req = composed ? plan.pieces[(size_t)e].size() : 1;   // (as batch_to_tensor_impl: a composed entry records one request per piece)
+      if (!rc && composed) rc = tensor_check_resample_depth("album_to_tensor_composed", desc, S.wide ? I.bit_depth_luma : 8);
+      for (size_t q = 0; !rc && q < n_req; q++) {
+        if (composed) compose_piece_window(plan.pieces[(size_t)e][q], pa->tiles[e].place, vis);
+        rc = tensor_record_entry("album_to_tensor", S.plane[0], S.stride[0], S.plane[1], S.stride[1], S.plane[2], S.stride[2], S.width, S.height,
+                                 S.wide ? I.bit_depth_luma : 8, S.chroma_format_idc, &nclx, &nclx, &sample, left, top, rw, rh, entries ? entries[e].flip : 0,
+                                 elem0, oriented ? (orientations ? orientations[e] : 0) : -1, pitch, plane_rows, pk.patch, pk.merge, 1, nullptr,
+                                 framed || composed ? vis : nullptr, composed);
+      }
       if (rc) { color_tensor_abort(); return rc; }
     }
     int rc = color_tensor_launch(ps ? a->color_packed : (oriented || resample_filter(desc->filter) ? a->color_oriented : a->color_tensor), desc->filter, desc->dtype, s);
-    if (!rc && pa) rc = canvas_margin_launch(a->color_margin, margins.data(), n_entries, desc->dtype, s);
+    if (!rc && composed) rc = composed_cover(a->color_margin, desc, *pa, plan, out_dev, entry_bytes, s);
+    else if (!rc && pa) rc = canvas_margin_launch(a->color_margin, margins.data(), n_entries, desc->dtype, s);
     b->mark_done(s);
-    if (!rc && pa && !pa->framed) placed_note_call((uint64_t)n_entries);
+    if (!rc && pa && !pa->framed && !composed) placed_note_call((uint64_t)n_entries);
     if (!rc && pa && pa->framed) framed_note_call((uint64_t)n_entries);
+    if (!rc && composed) composed_note_call((uint64_t)n_entries, plan.n_pieces, plan.hidden);
     if (!rc && ps) packed_note_call((uint64_t)n_entries, pk.patch > 0);
     return rc;
   });
@@ -423,6 +441,14 @@ int hipdec_album_to_tensor_framed(hipdec_album* a, const hipdec_tensor_desc* des
                                   void* stream)
 {
   const PlacedArgs pa{places, fill, mask_dev, true};
+  return album_to_tensor_impl(a, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, &pa);
+}
+
+int hipdec_album_to_tensor_composed(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                    const hipdec_tensor_tile* tiles, const hipdec_tensor_fill* fill, void* mask_dev, int n_entries, int n_canvases, void* out_dev,
+                                    size_t out_bytes, void* stream)
+{
+  const PlacedArgs pa{nullptr, fill, mask_dev, false, true, tiles, n_canvases};
   return album_to_tensor_impl(a, desc, entries, orientations, true, n_entries, out_dev, out_bytes, stream, &pa);
 }
 

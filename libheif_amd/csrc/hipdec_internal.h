@@ -104,7 +104,8 @@ struct TensorRequest { int ow, oh, sH, sV, left, top, rw, rh, flip, nhwc; float 
                        int patch, merge;
                        int tpatch;        /* clips (hipdec_clips_to_tensor_packed): frames per token, a token is 3 * tpatch * patch * patch elements (0 / 1: a still's) */
                        int strided_box;   /* clips: a box entry whose folded code is 0 or 4 goes to k_clip_box - k_tensor_box's stage, the oriented store - not k_oriented_box */
-                       int framed;        /* the (oriented) block goes to the k_frame_* kernels, which store inside frame_vis only (FrameWindow below) */
+                       int framed;        /* the (oriented) block goes to the k_frame_* kernels, which store inside frame_vis only (FrameWindow below);
+                                             2: a piece of a composed call - the same block, its pieces of work are not hipdec_framed_stats' */
                        int frame_vis[4]; };
 // Framed tensor output (color.hip k_frame_*, include/heif_hipdec.h hipdec_batch_to_tensor_framed): the part of an entry's sample that lies on its canvas.
 // A request with `framed` set carries the window in displayed coordinates of the sample (frame_vis: x0, y0, x1, y1, half open, not empty); its `out` is
@@ -142,6 +143,23 @@ struct CanvasMargin {
 };
 // launches when an entry has a margin or a mask (nothing otherwise); dtype: hipdec_tensor_dtype
 int canvas_margin_launch(ColorBatchState& st, const CanvasMargin* blocks, int n, int dtype, hipStream_t s);
+// Composed tensor output (color.hip k_compose_cover, include/heif_hipdec.h hipdec_batch_to_tensor_composed): several entries share a canvas, and everything
+// no entry's region covers - the fill element and the mask - goes out in ONE launch for all canvases of a call.  One block per canvas: `m` is the margin
+// block of the placed call without its rectangle (o0, mask, W, H, nhwc, domain, value, scale, bias; margin: the canvas has a pixel no region covers), and
+// the covered pixels are the canvas' COVER TABLE of n_bands row bands, int32 words behind the blocks in the same upload:
+//   edge[0 .. n_bands]        ascending rows, edge[0] = 0 and edge[n_bands] = H: band b is the rows edge[b] .. edge[b + 1] - 1
+//   first[0 .. n_bands]       band b's intervals are first[b] .. first[b + 1] - 1
+//   x0, x1 per interval       the covered columns x0 .. x1 - 1 of the band: sorted, disjoint, and merged (x1 of one is below x0 of the next)
+// `table` is the table's first word: the host records its index among the call's words, canvas_cover_launch turns it into the device address.
+struct CanvasCover {
+  CanvasMargin m;
+  uint64_t table;
+  int n_bands, n_intervals;
+};
+constexpr size_t kComposeTableBytes = 1u << 20;   // the cover tables of one call (HIPDEC_COMPOSE_TABLE_BYTES)
+// launches when a canvas has an uncovered pixel or a mask (nothing otherwise); words: the tables of all canvases
+int canvas_cover_launch(ColorBatchState& st, const CanvasCover* blocks, int n, const int32_t* words, size_t n_words, int dtype, hipStream_t s);
+void composed_note_call(uint64_t entries, uint64_t pieces, uint64_t hidden);   // hipdec_composed_stats
 void placed_note_call(uint64_t entries);   // hipdec_placed_stats
 void framed_note_call(uint64_t entries);   // hipdec_framed_stats (its tile counts: the launches of the k_frame_* kernels, color.hip)
 void packed_note_call(uint64_t entries, bool patches);   // hipdec_packed_stats

@@ -91,6 +91,14 @@ def _bind(lib):
     lib.hipdec_resize_crop_place.argtypes = [ci, ci, ci, ci, ci, C.POINTER(TensorPlace)]
     lib.hipdec_framed_stats.restype = None
     lib.hipdec_framed_stats.argtypes = [C.POINTER(C.c_uint64)] * 4
+    composed = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), C.POINTER(ci), C.POINTER(TensorTile), C.POINTER(TensorFill), vp, ci, ci, vp, sz, vp]
+    lib.hipdec_batch_to_tensor_composed.argtypes = composed
+    lib.hipdec_album_to_tensor_composed.argtypes = composed
+    lib.hipdec_compose_visible_area.argtypes = [ci, ci, C.POINTER(TensorTile), ci, ci, C.POINTER(C.c_uint64)]
+    lib.hipdec_mosaic_tiles.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(TensorTile)]
+    lib.hipdec_sheet_tiles.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), ci, ci, ci, C.POINTER(TensorTile)]
+    lib.hipdec_composed_stats.restype = None
+    lib.hipdec_composed_stats.argtypes = [C.POINTER(C.c_uint64)] * 5
     packed = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), C.POINTER(ci), C.POINTER(TensorSample), C.POINTER(TensorPatches), ci, vp, sz, vp]
     lib.hipdec_batch_to_tensor_packed.argtypes = packed
     lib.hipdec_album_to_tensor_packed.argtypes = packed
@@ -172,6 +180,11 @@ class TensorEntry(C.Structure):
 class TensorPlace(C.Structure):
     """hipdec_tensor_place"""
     _fields_ = [("x", C.c_int), ("y", C.c_int), ("width", C.c_int), ("height", C.c_int)]
+
+
+class TensorTile(C.Structure):
+    """hipdec_tensor_tile"""
+    _fields_ = [("canvas", C.c_int), ("place", TensorPlace), ("clip", TensorPlace)]
 
 
 class TensorFill(C.Structure):
@@ -555,6 +568,98 @@ def framed_stats():
     v = [C.c_uint64() for _ in range(4)]
     lib.hipdec_framed_stats(*[C.byref(x) for x in v])
     return tuple(x.value for x in v)
+
+
+def tensor_tiles(tiles, n=None):
+    """a ctypes array of hipdec_tensor_tile from (canvas, place, clip) tuples - place and clip (x, y, width, height), clip None or (0, 0, 0, 0) for the whole
+    canvas - or TensorTile objects"""
+    tiles = list(tiles)
+    if n is not None and len(tiles) != n:
+        raise ValueError("%d tiles for %d entries" % (len(tiles), n))
+    arr = (TensorTile * len(tiles))()
+    for k, t in enumerate(tiles):
+        if isinstance(t, TensorTile):
+            arr[k] = t
+            continue
+        canvas, place, clip = t
+        arr[k] = TensorTile(int(canvas), TensorPlace(*(int(v) for v in place)), TensorPlace(*(int(v) for v in (clip if clip is not None else (0, 0, 0, 0)))))
+    return arr
+
+
+def _tiles_out(arr):
+    return [(t.canvas, (t.place.x, t.place.y, t.place.width, t.place.height), (t.clip.x, t.clip.y, t.clip.width, t.clip.height)) for t in arr]
+
+
+def mosaic_tiles(canvas_size, center, sizes, canvas=0):
+    """the four (canvas, place, clip) tiles of YOLOv5's mosaic-4 (hipdec_mosaic_tiles; host only): four DISPLAYED, already resized samples of
+    sizes[k] = (width, height) around center = (xc, yc) on a canvas of canvas_size = (width, height) - sample 0 above left of the centre, 1 above right,
+    2 below left, 3 below right, each clipped to its quadrant.  The `tiles` of a to_tensor_composed call (fill=114 is the usual grey)."""
+    sizes = [(int(w), int(h)) for w, h in sizes]
+    if len(sizes) != 4:
+        raise ValueError("mosaic_tiles takes four sizes")
+    out = (TensorTile * 4)()
+    if _bind(load_library()).hipdec_mosaic_tiles(int(canvas_size[0]), int(canvas_size[1]), int(center[0]), int(center[1]), (C.c_int * 4)(*[s[0] for s in sizes]),
+                                                 (C.c_int * 4)(*[s[1] for s in sizes]), int(canvas), out) != 0:
+        raise ValueError("mosaic_tiles(%r, %r, %r)" % (tuple(canvas_size), tuple(center), sizes))
+    return _tiles_out(out)
+
+
+def sheet_tiles(grid, cell, sizes, gap=0, upscale=True, canvas=0):
+    """the (canvas, place, clip) tiles of a contact sheet (hipdec_sheet_tiles; host only): grid = (cols, rows) cells of cell = (width, height) with `gap`
+    pixels between them, the DISPLAYED sample k of sizes[k] = (width, height) letterboxed (centred) into cell k, row-major, and clipped to it.  The canvas of
+    the to_tensor_composed call is sheet_size(grid, cell, gap)."""
+    sizes = [(int(w), int(h)) for w, h in sizes]
+    n = len(sizes)
+    out = (TensorTile * max(n, 1))()
+    if _bind(load_library()).hipdec_sheet_tiles(int(grid[0]), int(grid[1]), int(cell[0]), int(cell[1]), int(gap), (C.c_int * max(n, 1))(*[s[0] for s in sizes]),
+                                                (C.c_int * max(n, 1))(*[s[1] for s in sizes]), n, int(bool(upscale)), int(canvas), out) != 0:
+        raise ValueError("sheet_tiles(%r, %r, %d sizes, gap %r)" % (tuple(grid), tuple(cell), n, gap))
+    return _tiles_out(out)[:n]
+
+
+def sheet_size(grid, cell, gap=0):
+    """(width, height) of the sheet sheet_tiles lays out"""
+    return grid[0] * cell[0] + (grid[0] - 1) * gap, grid[1] * cell[1] + (grid[1] - 1) * gap
+
+
+def cutmix_tiles(size, boxes):
+    """CutMix over len(boxes) canvases of size = (width, height): (tiles, order) with two tiles per canvas - the base sample whole-canvas, then its partner
+    at the canvas' size clipped to boxes[k] = (x, y, width, height) - and order[e] = (canvas, role), role 0 the base and 1 the partner: the entry list the
+    tiles imply is the base's entry followed by the partner's, canvas by canvas.  compose_visible_area(size, tiles)[2 * k] / (width * height) is lambda."""
+    w, h = int(size[0]), int(size[1])
+    tiles, order = [], []
+    for k, box in enumerate(boxes):
+        tiles += [(k, (0, 0, w, h), (0, 0, 0, 0)), (k, (0, 0, w, h), tuple(int(v) for v in box))]
+        order += [(k, 0), (k, 1)]
+    return tiles, order
+
+
+def compose_visible_area(size, tiles, n_canvases=None):
+    """the pixels every entry of a to_tensor_composed call owns on canvases of size = (width, height) (hipdec_compose_visible_area; host only)"""
+    arr = tensor_tiles(tiles)
+    n = len(arr)
+    nc = (max(t.canvas for t in arr) + 1 if n else 0) if n_canvases is None else int(n_canvases)
+    area = (C.c_uint64 * max(n, 1))()
+    if _bind(load_library()).hipdec_compose_visible_area(int(size[0]), int(size[1]), arr, n, nc, area) != 0:
+        raise ValueError("compose_visible_area: %s" % _bind(load_library()).hipdec_last_error().decode())
+    return [int(a) for a in area[:n]]
+
+
+def composed_stats():
+    """(composed to_tensor calls, their entries, pieces recorded, fully hidden entries, launches of the cover kernel) since load (hipdec_composed_stats)"""
+    lib = _bind(load_library())
+    v = [C.c_uint64() for _ in range(5)]
+    lib.hipdec_composed_stats(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def _to_tensor_composed(self, lib_call, size, tiles, entries, n_canvases, orientations, fill, fill_domain, mask, filter, dtype, layout, mean, std, scale, bias, out,
+                        stream):
+    n = self.n if entries is None else len(entries)
+    tarr = tensor_tiles(tiles, n)
+    nc = (max(t.canvas for t in tarr) + 1 if n else 0) if n_canvases is None else int(n_canvases)
+    call = lambda h, desc, arr, codes, _places, f, mask_ptr, n, ptr, room, stream: lib_call(h, desc, arr, codes, tarr, f, mask_ptr, n, nc, ptr, room, stream)
+    return _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations, (None, fill, fill_domain, mask), canvases=nc)
 
 
 def packed_layout(sizes, patch=0, merge=1):
@@ -971,10 +1076,12 @@ def fit_within(width, height, size):
     return width * size // height, size
 
 
-def _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations=None, placed=None):
+def _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations=None, placed=None, canvases=None):
     """Batch.to_tensor / Album.to_tensor: the description, the output buffer (DeviceBuffer or torch.Tensor) and the stream, then `call` (the oriented
-    entry point when `orientations` is given; the placed one with placed = (places, fill, fill_domain, mask))"""
+    entry point when `orientations` is given; the placed one with placed = (places, fill, fill_domain, mask)); canvases: the samples of the tensor and
+    of the mask where they are not one per entry (to_tensor_composed)"""
     n = self.n if entries is None else len(entries)
+    n_out = n if canvases is None else canvases
     self._tensor_mask = None      # (the mask of THIS call, or none: tensor_mask_to_host() never hands back an earlier call's)
     last_mask = None
     if placed is not None:
@@ -992,7 +1099,7 @@ def _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias,
     max_value = (1 << d0["bit_depth_luma"]) - 1 if (dtype != "uint8" and d0["bit_depth_luma"] > 8) else 255
     sc, bi = tensor_scale_bias(mean, std, scale, bias, max_value)
     desc = tensor_desc(size, dtype, layout, filter, sc, bi)
-    shape = tensor_shape(n, size, layout)
+    shape = tensor_shape(n_out, size, layout)
     nbytes = int(np.prod(shape)) * np.dtype(_TENSOR_NUMPY[dtype]).itemsize
     arr = None if entries is None else tensor_entries(entries)
     host_wait = False
@@ -1021,7 +1128,7 @@ def _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias,
                 ts.synchronize()
                 host_wait = True
     if placed is not None and mask is not None and mask is not False:
-        mshape = (n, int(size[1]), int(size[0]))
+        mshape = (n_out, int(size[1]), int(size[0]))
         if mask is True:
             if isinstance(out, DeviceBuffer):
                 mask = DeviceBuffer(max(int(np.prod(mshape)), 1))
@@ -1292,6 +1399,18 @@ class Batch:
             return _to_tensor(self, self._lib.hipdec_batch_to_tensor_oriented, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream, orientations)
         return _to_tensor(self, self._lib.hipdec_batch_to_tensor, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
 
+    def to_tensor_composed(self, size, tiles, entries=None, n_canvases=None, orientations=None, fill=None, fill_domain="component", mask=None, filter=SCALE_BOX,
+                           dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, out=None, stream=None):
+        """asynchronous: SEVERAL entries per canvas - mosaic, CutMix, contact sheets - as ONE tensor of n_canvases canvases of size = (width, height)
+        (hipdec_batch_to_tensor_composed).  tiles: one (canvas, place, clip) per entry - the canvas it belongs to, the rectangle of its resized,
+        displayed sample in canvas coordinates (it may leave the canvas) and the rectangle of the canvas it may write (None or all zeros: the whole canvas);
+        mosaic_tiles(), sheet_tiles() and cutmix_tiles() make them.  Later entries lie on top; pixels nobody owns hold `fill` (fill / fill_domain as in
+        to_tensor(places=)), and mask - a DeviceBuffer, a uint8 torch.Tensor of shape (n_canvases, height, width) or True - is 1 there.  n_canvases None:
+        the largest canvas index + 1.  Inside what an entry owns the canvas holds what to_tensor(place size, ..., orientations=) writes for it.  `out`,
+        `stream`, tensor_to_host() and tensor_mask_to_host() as in to_tensor.  One launch of the picture kernels and at most one of the cover kernel."""
+        return _to_tensor_composed(self, self._lib.hipdec_batch_to_tensor_composed, size, tiles, entries, n_canvases, orientations, fill, fill_domain, mask, filter,
+                                   dtype, layout, mean, std, scale, bias, out, stream)
+
     def to_tensor_warped(self, size, maps, entries=None, src_size=None, warp_filter=SCALE_BILINEAR, fill=0, fill_domain="component", orientations=None,
                          filter=SCALE_BILINEAR, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, out=None, stream=None):
         """asynchronous: to_tensor with one affine warp per entry, Pillow-exact (hipdec_batch_to_tensor_warped).  Entry e is first resized as
@@ -1558,6 +1677,12 @@ class Album:
 
     tensor_to_host = Batch.tensor_to_host
     tensor_mask_to_host = Batch.tensor_mask_to_host
+
+    def to_tensor_composed(self, size, tiles, entries=None, n_canvases=None, orientations=None, fill=None, fill_domain="component", mask=None, filter=SCALE_BOX,
+                           dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, out=None, stream=None):
+        """Batch.to_tensor_composed over the composed photos (hipdec_album_to_tensor_composed)"""
+        return _to_tensor_composed(self, self._lib.hipdec_album_to_tensor_composed, size, tiles, entries, n_canvases, orientations, fill, fill_domain, mask, filter,
+                                   dtype, layout, mean, std, scale, bias, out, stream)
 
     def to_tensor_warped(self, size, maps, entries=None, src_size=None, warp_filter=SCALE_BILINEAR, fill=0, fill_domain="component", orientations=None,
                          filter=SCALE_BILINEAR, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, out=None, stream=None):
