@@ -947,7 +947,7 @@ HIPDEC_API int hipdec_clip_packed_layout(const hipdec_clip_desc* clip, const hip
  * that Pillow always takes the paths above and the fixed-point sums cannot wrap); and for the call: src_width or src_height < 1 or >= 32768, an unknown
  * warp filter or BOX, a non-zero `reserved`, a fill the placed call refuses or a component fill above 255, src_bytes or out_bytes too small.  More than
  * 2^31 - 1 output tiles (64 x 16 pixels) in a call: HIPDEC_ERR_LIMIT.
- * Not part of it: perspective and quad transforms; expand (pass a larger size); a mask (the point-wise RandAugment operations are the photo stage below,
+ * Not part of it: perspective and quad transforms (hipdec_tensor_project below); expand (pass a larger size); a mask (the point-wise RandAugment operations are the photo stage below,
  * hipdec_tensor_photo: chain the two through a U8 / NHWC buffer); a clips entry point (repeat
  * the map for the T frames of a clip and use hipdec_tensor_warp); Lanczos; warping straight from the full-size picture in one resampling. */
 typedef struct hipdec_tensor_map { double m[6]; } hipdec_tensor_map;
@@ -970,6 +970,66 @@ HIPDEC_API int hipdec_album_to_tensor_warped(hipdec_album* a, const hipdec_tenso
 HIPDEC_API int hipdec_rotate_map(double angle, int width, int height, hipdec_tensor_map* out);
 /* counters since load: launches of k_warp - one per call that wrote anything - and the entries they wrote */
 HIPDEC_API void hipdec_warp_stats(uint64_t* calls, uint64_t* entries);
+
+/* ---- projective tensor output: Pillow-exact PERSPECTIVE and QUAD transforms of the resized 8-bit picture, normalised, in one call ----------------------------
+ * torchvision's RandomPerspective and F.perspective, the keystone jitter of OCR / document / scene-text loaders (PERSPECTIVE) and the rectification of a
+ * photographed page from its four corners (QUAD) are PIL.Image.transform(size, PERSPECTIVE | QUAD, data, resample, fillcolor) applied to the already resized
+ * 8-bit picture.  The projective stage does exactly that to 8-bit interleaved RGB samples in device memory - per sample one map and one fill - and writes the
+ * normalised tensor the other tensor calls write.  Bit-equal to Pillow, no tolerance.
+ *
+ * THE STAGE (hipdec_tensor_project).  S, sw, sh, FLOOR, COORD and "outside" as in hipdec_tensor_warp above.  A map is eight doubles a = maps[e].a[0 .. 7] and
+ * a kind.  For output pixel (x, y) of the desc->width x desc->height sample let xc = (double)x + 0.5 and yc = (double)y + 0.5.  Every written operator is one
+ * IEEE double operation with one rounding, evaluated left to right in this order; no fused multiply-add; the division is the IEEE division.
+ *  HIPDEC_PROJECT_PERSPECTIVE: xin = (a0 * xc + a1 * yc + a2) / (a6 * xc + a7 * yc + 1.0),  yin = (a3 * xc + a4 * yc + a5) / (a6 * xc + a7 * yc + 1.0);
+ *    a is Pillow's PERSPECTIVE data as given (hipdec_perspective_map makes it from four point pairs).
+ *  HIPDEC_PROJECT_QUAD:        xin = a0 + a1 * xc + a2 * yc + a3 * xc * yc,  yin = a4 + a5 * xc + a6 * yc + a7 * xc * yc;
+ *    a is what Pillow's Python layer makes of the four corners (hipdec_quad_map).
+ *  warp->filter HIPDEC_SCALE_NEAREST: sx = COORD(xin), sy = COORD(yin); outside if sx < 0 || sx >= sw || sy < 0 || sy >= sh, else V = S[sy][sx].  This is
+ *    Pillow's generic per-pixel path - NOT the fixed-point path or the running-sum tables of the AFFINE call, which hipdec_tensor_warp states: a PERSPECTIVE
+ *    map with a6 = a7 = 0 and NEAREST need not give hipdec_tensor_warp's bytes for m = a[0 .. 5] (Pillow's own two methods differ there).
+ *  HIPDEC_SCALE_BILINEAR / HIPDEC_SCALE_BICUBIC: from (xin, yin) on exactly the statements of hipdec_tensor_warp - outside if xin < 0 || xin >= sw || yin < 0
+ *    || yin >= sh, else xin -= 0.5, yin -= 0.5, FLOOR, dx, dy, the clamped columns, the rows used only where they exist, L and B, the truncation or the clamp
+ *    to 0 .. 255.  A PERSPECTIVE map with a6 = a7 = 0 therefore gives hipdec_tensor_warp's bytes for m = a[0 .. 5]: a division by exactly 1.0 is exact.
+ *  HIPDEC_SCALE_BOX is refused.  warp is the hipdec_warp_desc of the warped call: the source size and the filter.  Entries of one call may mix the kinds.
+ * Float stage, dtypes, layouts, fill (hipdec_tensor_fill, component or element domain; NULL: component 0), src_dev / src_bytes and n == 0: as in
+ * hipdec_tensor_warp.  With a U8 / NHWC output the stage chains with hipdec_tensor_warp, hipdec_tensor_photo, hipdec_tensor_augment and hipdec_tensor_recipe.
+ *
+ * THE DECODE-SIDE FORMS (hipdec_batch_to_tensor_projected, hipdec_album_to_tensor_projected): the warped forms with this stage.  Sample e of the intermediate
+ * is what hipdec_batch_to_tensor_oriented writes for entry e and orientations[e] with dtype U8, layout NHWC, size src_width x src_height and desc->filter;
+ * then the stage above.  A float dtype from a source above 8 bits is HIPDEC_ERR_UNSUPPORTED.  The intermediate is the one the handle keeps for its warped
+ * calls.  The inner resize counts in hipdec_tensor_stats and hipdec_oriented_stats; the call counts in hipdec_project_stats, not in hipdec_warp_stats.
+ *
+ * Launches: the existing resize launch (decode-side forms), then ALL entries through ONE launch of k_project, whatever their number, kinds and maps.
+ * Asynchronous on `stream`.  Refused with HIPDEC_ERR_INVALID_ARGUMENT before any device is touched, `out_dev` untouched, naming `entry %d`: a kind other than
+ * 0 or 1; a non-zero `reserved`; a non-finite coefficient; |a[i]| >= 32000; at a corner of [0, width] x [0, height] a mapped coordinate of magnitude >= 32000
+ * or, for PERSPECTIVE, a denominator a6 * cx + a7 * cy + 1.0 below 1.0 / 1048576.  The corners decide for every pixel centre: the denominator is linear, a
+ * linear-fractional map over a region of positive denominator and a bilinear map take their extremes at the vertices, and the floor of 2^-20 keeps rounding
+ * from turning a positive denominator into zero - so Pillow sees no NaN and no integer overflow and never leaves the paths stated above.  And for the call:
+ * everything hipdec_tensor_warp refuses of the desc, the warp desc, the fill, n, the byte counts; more than 2^31 - 1 tiles: HIPDEC_ERR_LIMIT.
+ * Not part of it: a projective step inside recipe chains; MESH; a mask; expand; a clips entry point (repeat the map for the T frames of a clip). */
+#define HIPDEC_PROJECT_PERSPECTIVE 0
+#define HIPDEC_PROJECT_QUAD        1
+typedef struct hipdec_tensor_projection { double a[8]; int kind; int reserved; } hipdec_tensor_projection;
+HIPDEC_API int hipdec_tensor_project(const void* src_dev, size_t src_bytes, const hipdec_warp_desc* warp, const hipdec_tensor_projection* maps,
+                                     const hipdec_tensor_fill* fill, const hipdec_tensor_desc* desc, int n, void* out_dev, size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_batch_to_tensor_projected(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                                const hipdec_warp_desc* warp, const hipdec_tensor_projection* maps, const hipdec_tensor_fill* fill,
+                                                int n_entries, void* out_dev, size_t out_bytes, void* stream);
+HIPDEC_API int hipdec_album_to_tensor_projected(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                                const hipdec_warp_desc* warp, const hipdec_tensor_projection* maps, const hipdec_tensor_fill* fill,
+                                                int n_entries, void* out_dev, size_t out_bytes, void* stream);
+/* Host only.  The PERSPECTIVE map that sends endpoints[k] (output coordinates) to startpoints[k] (source coordinates), k = 0 .. 3, x, y pairs - the library's
+ * statement of torchvision's _get_perspective_coeffs (torchvision is not installed where the library is tested, and not pinned): per pair the rows
+ * [ex, ey, 1, 0, 0, 0, -sx * ex, -sx * ey | sx] and [0, 0, 0, ex, ey, 1, -sy * ex, -sy * ey | sy], the 8 x 8 system solved in double by Gaussian elimination
+ * with partial pivoting.  A singular system, a non-finite point or a NULL argument: HIPDEC_ERR_INVALID_ARGUMENT. */
+HIPDEC_API int hipdec_perspective_map(const double startpoints[8], const double endpoints[8], hipdec_tensor_projection* out);
+/* Host only.  The QUAD map of Image.transform((width, height), QUAD, corners) as Pillow's Python layer computes it, operator for operator: corners = (nw, sw,
+ * se, ne) as x, y pairs in source coordinates, As = 1.0 / width, At = 1.0 / height (the OUTPUT size); a0 = nw.x, a1 = (ne.x - nw.x) * As,
+ * a2 = (sw.x - nw.x) * At, a3 = (se.x - sw.x - ne.x + nw.x) * As * At; a4 .. a7 the same in y.  A non-finite corner, a non-positive size or a NULL argument:
+ * HIPDEC_ERR_INVALID_ARGUMENT. */
+HIPDEC_API int hipdec_quad_map(const double corners[8], int width, int height, hipdec_tensor_projection* out);
+/* counters since load: launches of k_project - one per call that wrote anything - and the entries they wrote */
+HIPDEC_API void hipdec_project_stats(uint64_t* calls, uint64_t* entries);
 
 /* ---- photometric tensor output: Pillow-exact ColorJitter / RandAugment colour operations on the resized 8-bit picture, normalised --------------------------
  * ColorJitter (brightness, contrast, saturation), RandomGrayscale, the colour half of RandAugment / AutoAugment / TrivialAugment (Brightness, Color,
@@ -1159,7 +1219,7 @@ HIPDEC_API int hipdec_gaussian_box(double radius, int* r, uint32_t* ww, uint32_t
  * NULL, a non-zero op.reserved, and of the record: a non-finite coefficient, |m[i]| >= 32000, a corner of [0, w] x [0, h] whose mapped coordinate has
  * magnitude >= 32000 (hipdec_tensor_warp's bounds), a filter other than NEAREST, BILINEAR, BICUBIC, a fill component outside 0 .. 255.  hipdec_tensor_photo
  * and hipdec_tensor_augment keep refusing opcode 32 as an unknown op.
- * Not part of it: perspective and quad maps; a step that changes the size; a mask; element-domain fills; timm's SolarizeAdd and the *Increasing magnitude
+ * Not part of it: perspective and quad maps inside a chain (hipdec_tensor_project is a stage of its own); a step that changes the size; a mask; element-domain fills; timm's SolarizeAdd and the *Increasing magnitude
  * schedules; samplers and magnitude tables (drawing stays with the caller); a clips entry point; staging source tiles in LDS. */
 #define HIPDEC_RECIPE_AFFINE 32          /* value: integer index into the call's affines, 0 .. n_affines - 1 */
 typedef struct hipdec_recipe_affine {

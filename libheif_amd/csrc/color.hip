@@ -18,6 +18,7 @@
 #include "hipdec_internal.h"
 #include "color_device.h"
 #include "warp_host.h"
+#include "project_host.h"
 #define PHOTO_FN __host__ __device__ inline
 #include "photo_lut.h"
 #include "augment_lut.h"
@@ -1500,6 +1501,8 @@ __global__ __launch_bounds__(256) void k_compose_cover(const hipdec::CanvasCover
 
 // ---- warped tensor output (include/heif_hipdec.h hipdec_tensor_warp): k_warp_nearest / _bilinear / _bicubic
 #include "warp_kernels.h"
+// ---- projective tensor output (include/heif_hipdec.h hipdec_tensor_project): k_project_nearest / _bilinear / _bicubic
+#include "project_kernels.h"
 
 // ---- photometric tensor output (include/heif_hipdec.h hipdec_tensor_photo): k_photo_hist, k_photo_apply
 #include "photo_kernels.h"
@@ -2794,7 +2797,8 @@ int canvas_cover_launch(ColorBatchState& st, const CanvasCover* blocks, int n, c
 // ---- warped tensor output: what the arguments alone decide, the per-entry table, ONE launch of k_warp_* for all entries of a call
 std::atomic<uint64_t> g_warp_calls{0}, g_warp_entries{0};
 
-int warp_check(const char* who, const hipdec_warp_desc* w, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill, const hipdec_tensor_desc* d, int n)
+// what the warp desc, the fill and the presence of the maps decide (the warped and the projected calls)
+static int warp_check_call(const char* who, const hipdec_warp_desc* w, const void* maps, const hipdec_tensor_fill* fill, const hipdec_tensor_desc* d, int n)
 {
   if (!w || (!maps && n > 0)) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
   if (w->src_width < 1 || w->src_height < 1 || w->src_width >= 32768 || w->src_height >= 32768)
@@ -2815,6 +2819,19 @@ int warp_check(const char* who, const hipdec_warp_desc* w, const hipdec_tensor_m
         return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: element fill %g of channel %d is not an integer in 0 .. 255", who, (double)v, c);
     }
   }
+  return 0;
+}
+
+static int warp_check_tiles(const char* who, const hipdec_tensor_desc* d, int n)
+{
+  const uint64_t tiles = (uint64_t)((d->width + kWarpTC - 1) / kWarpTC) * (uint64_t)((d->height + kWarpTR - 1) / kWarpTR);
+  if (tiles * (uint64_t)(n > 0 ? n : 1) > 0x7fffffffull) return set_error(HIPDEC_ERR_LIMIT, "%s: %d entries of %d x %d are more than 2^31 - 1 tiles", who, n, d->width, d->height);
+  return 0;
+}
+
+int warp_check(const char* who, const hipdec_warp_desc* w, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill, const hipdec_tensor_desc* d, int n)
+{
+  if (int rc = warp_check_call(who, w, maps, fill, d, n)) return rc;
   for (int e = 0; e < n; e++) {
     int which = 0;
     switch (warp_map_check(maps[e].m, d->width, d->height, &which)) {
@@ -2826,9 +2843,7 @@ int warp_check(const char* who, const hipdec_warp_desc* w, const hipdec_tensor_m
                          (which & 1) ? d->width : 0, (which & 2) ? d->height : 0);
     }
   }
-  const uint64_t tiles = (uint64_t)((d->width + kWarpTC - 1) / kWarpTC) * (uint64_t)((d->height + kWarpTR - 1) / kWarpTR);
-  if (tiles * (uint64_t)(n > 0 ? n : 1) > 0x7fffffffull) return set_error(HIPDEC_ERR_LIMIT, "%s: %d entries of %d x %d are more than 2^31 - 1 tiles", who, n, d->width, d->height);
-  return 0;
+  return warp_check_tiles(who, d, n);
 }
 
 // the state's device memory is about to be rewritten or handed back: not before the last launch that read it has passed
@@ -2923,6 +2938,79 @@ int warp_launch(WarpState& st, const void* src_dev, const hipdec_warp_desc* w, c
   HIPDEC_CHECK_HIP(hipEventRecord(st.done, s));
   st.last = s;
   g_warp_calls++; g_warp_entries += (uint64_t)n;
+  return 0;
+}
+
+// ---- projective tensor output: warp_check's refusals and those of the maps (project_host.h), the per-entry table, ONE launch of k_project_* per call
+std::atomic<uint64_t> g_project_calls{0}, g_project_entries{0};
+static_assert((int)HIPDEC_PROJECT_PERSPECTIVE == (int)PROJECT_PERSPECTIVE && (int)HIPDEC_PROJECT_QUAD == (int)PROJECT_QUAD, "project_host.h restates the kinds");
+
+int project_check(const char* who, const hipdec_warp_desc* w, const hipdec_tensor_projection* maps, const hipdec_tensor_fill* fill, const hipdec_tensor_desc* d, int n)
+{
+  if (int rc = warp_check_call(who, w, maps, fill, d, n)) return rc;
+  for (int e = 0; e < n; e++) {
+    const hipdec_tensor_projection& m = maps[e];
+    if (m.kind != HIPDEC_PROJECT_PERSPECTIVE && m.kind != HIPDEC_PROJECT_QUAD)
+      return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: map kind %d (perspective 0, quad 1)", who, e, m.kind);
+    if (m.reserved) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: map.reserved is %d, not 0", who, e, m.reserved);
+    int which = 0;
+    switch (project_map_check(m.a, m.kind, d->width, d->height, &which)) {
+      case 0: break;
+      case 1: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: map coefficient %d is not finite", who, e, which);
+      case 2: return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: map coefficient %d is %g (magnitude 32000 or more)", who, e, which, m.a[which]);
+      case 3:
+        return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: corner (%d, %d) of the output maps to a coordinate of magnitude 32000 or more", who, e,
+                         (which & 1) ? d->width : 0, (which & 2) ? d->height : 0);
+      default:
+        return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "%s: entry %d: the denominator at corner (%d, %d) of the output is below 2^-20", who, e,
+                         (which & 1) ? d->width : 0, (which & 2) ? d->height : 0);
+    }
+  }
+  return warp_check_tiles(who, d, n);
+}
+
+int project_launch(WarpState& st, const void* src_dev, const hipdec_warp_desc* w, const hipdec_tensor_projection* maps, const hipdec_tensor_fill* fill,
+                   const hipdec_tensor_desc* d, int n, void* out_dev, hipStream_t s)
+{
+  if (n <= 0) return 0;
+  const int sw = w->src_width, sh = w->src_height, ow = d->width, oh = d->height;
+  const size_t src_entry = (size_t)sw * (size_t)sh * 3, out_entry = (size_t)ow * (size_t)oh * 3 * (d->dtype == TD_U8 ? 1 : (d->dtype == TD_F32 ? 4 : 2));
+  const size_t bytes = (size_t)n * sizeof(ProjectEntry);
+  std::vector<uint8_t> host(bytes);
+  if (int rc = warp_state_order(st, s, st.table.dev_bytes < bytes)) return rc;
+  if (int rc = blocks_reserve(st.table, bytes)) return rc;
+  for (int e = 0; e < n; e++) {
+    ProjectEntry E;
+    memset(&E, 0, sizeof(E));
+    E.src = (const uint8_t*)src_dev + (size_t)e * src_entry;
+    E.o0 = (uint8_t*)out_dev + (size_t)e * out_entry;
+    for (int i = 0; i < 8; i++) E.a[i] = maps[e].a[i];
+    E.kind = maps[e].kind;
+    E.domain = fill ? fill->domain : HIPDEC_FILL_COMPONENT;
+    for (int c = 0; c < 3; c++) E.value[c] = fill ? fill->value[c] : 0.0f;
+    memcpy(host.data() + (size_t)e * sizeof(ProjectEntry), &E, sizeof(E));
+  }
+  if (int rc = blocks_upload(st.table, host, s)) return rc;
+  WarpCall c;
+  memset(&c, 0, sizeof(c));
+  c.sw = sw; c.sh = sh; c.ow = ow; c.oh = oh; c.nhwc = d->layout == HIPDEC_TENSOR_NHWC;
+  c.tiles_x = (uint32_t)((ow + kWarpTC - 1) / kWarpTC);
+  c.tiles = c.tiles_x * (uint32_t)((oh + kWarpTR - 1) / kWarpTR);
+  for (int k = 0; k < 3; k++) { c.scale[k] = d->scale[k]; c.bias[k] = d->bias[k]; }
+  const ProjectEntry* dev = (const ProjectEntry*)st.table.dev;
+  dim3 block(256), grid((unsigned)((uint64_t)c.tiles * (uint64_t)n));   // (project_check: below 2^31)
+  if (!dispatch_dtype(d->dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (w->filter == HIPDEC_SCALE_NEAREST) hipLaunchKernelGGL((k_project_nearest<DT>), grid, block, 0, s, dev, c);
+        else if (w->filter == HIPDEC_SCALE_BILINEAR) hipLaunchKernelGGL((k_project_bilinear<DT>), grid, block, 0, s, dev, c);
+        else hipLaunchKernelGGL((k_project_bicubic<DT>), grid, block, 0, s, dev, c);
+      })) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_project: unknown dtype %d", d->dtype);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_error(HIPDEC_ERR_DEVICE, "project kernel launch: %s", hipGetErrorString(e));
+  if (!st.done) HIPDEC_CHECK_HIP(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+  HIPDEC_CHECK_HIP(hipEventRecord(st.done, s));
+  st.last = s;
+  g_project_calls++; g_project_entries += (uint64_t)n;
   return 0;
 }
 
@@ -3480,6 +3568,68 @@ int hipdec_tensor_warp(const void* src_dev, size_t src_bytes, const hipdec_warp_
     int dev = 0;
     HIPDEC_CHECK_HIP(hipGetDevice(&dev));
     return warp_launch(states[dev], src_dev, warp, maps, fill, desc, n, out_dev, stream ? (hipStream_t)stream : default_stream());
+  });
+}
+
+void hipdec_project_stats(uint64_t* calls, uint64_t* entries)
+{
+  if (calls) *calls = g_project_calls.load();
+  if (entries) *entries = g_project_entries.load();
+}
+
+int hipdec_perspective_map(const double startpoints[8], const double endpoints[8], hipdec_tensor_projection* out)
+{
+  if (!startpoints || !endpoints || !out) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "perspective_map: bad arguments");
+  hipdec_tensor_projection p;
+  memset(&p, 0, sizeof(p));
+  p.kind = HIPDEC_PROJECT_PERSPECTIVE;
+  if (!project_perspective_map(startpoints, endpoints, p.a))
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "perspective_map: the system of the four point pairs is singular or not finite");
+  *out = p;
+  return 0;
+}
+
+int hipdec_quad_map(const double corners[8], int width, int height, hipdec_tensor_projection* out)
+{
+  if (!corners || !out || width < 1 || height < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "quad_map: bad arguments (size %d x %d)", width, height);
+  for (int i = 0; i < 8; i++)
+    if (!std::isfinite(corners[i])) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "quad_map: corner value %d is not finite", i);
+  memset(out, 0, sizeof(*out));
+  out->kind = HIPDEC_PROJECT_QUAD;
+  project_quad_map(corners, width, height, out->a);
+  return 0;
+}
+
+// the stage alone; its table lives in a state the process keeps per device, as hipdec_tensor_warp's does
+int hipdec_tensor_project(const void* src_dev, size_t src_bytes, const hipdec_warp_desc* warp, const hipdec_tensor_projection* maps, const hipdec_tensor_fill* fill,
+                          const hipdec_tensor_desc* desc, int n, void* out_dev, size_t out_bytes, void* stream)
+{
+  static std::mutex mu;
+  static std::map<int, WarpState> states;   // by device: the table is device memory
+  if (!desc || n < 0) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_project: bad arguments");
+  if (desc->width < 1 || desc->height < 1) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_project: output size %d x %d", desc->width, desc->height);
+  if (desc->dtype < HIPDEC_TENSOR_U8 || desc->dtype > HIPDEC_TENSOR_BF16) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_project: unknown dtype %d", desc->dtype);
+  if (desc->layout != HIPDEC_TENSOR_NCHW && desc->layout != HIPDEC_TENSOR_NHWC) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_project: unknown layout %d", desc->layout);
+  if (desc->dtype != HIPDEC_TENSOR_U8)
+    for (int c = 0; c < 3; c++)
+      if (!std::isfinite(desc->scale[c]) || !std::isfinite(desc->bias[c])) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_project: scale / bias of channel %d is not finite", c);
+  if (int rc = project_check("tensor_project", warp, maps, fill, desc, n)) return rc;
+  const uint64_t es = desc->dtype == HIPDEC_TENSOR_U8 ? 1 : (desc->dtype == HIPDEC_TENSOR_F32 ? 4 : 2);
+  const uint64_t need_src = 3ull * (uint64_t)warp->src_width * (uint64_t)warp->src_height * (uint64_t)n;   // (below 2^63: sizes below 2^15, n below 2^31)
+  const uint64_t per_out = 3ull * (uint64_t)desc->width * (uint64_t)desc->height * es;
+  if ((uint64_t)desc->width * (uint64_t)desc->height > (1ull << 40) || (n > 0 && per_out > (~0ull) / (uint64_t)n))
+    return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_project: tensor too large");
+  if (src_bytes < need_src) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_project: src_bytes %zu is smaller than the %d samples of %llu bytes", src_bytes, n, (unsigned long long)need_src);
+  if (out_bytes < per_out * (uint64_t)n) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_project: out_bytes %zu is smaller than the tensor of %llu bytes", out_bytes, (unsigned long long)(per_out * (uint64_t)n));
+  if (n == 0) return 0;
+  if (!src_dev || !out_dev) return set_error(HIPDEC_ERR_INVALID_ARGUMENT, "tensor_project: bad arguments");
+  // (everything above is decided without a device)
+  if (int rc = ensure_init()) return rc;
+  return guarded("tensor_project", [&]() -> int {
+    std::lock_guard<std::mutex> lock(mu);
+    int dev = 0;
+    HIPDEC_CHECK_HIP(hipGetDevice(&dev));
+    return project_launch(states[dev], src_dev, warp, maps, fill, desc, n, out_dev, stream ? (hipStream_t)stream : default_stream());
   });
 }
 

@@ -1351,6 +1351,19 @@ struct WarpStage {
   }
 };
 
+struct ProjectStage {   // the warp stage with a PERSPECTIVE or QUAD map per entry; the handle's state is the warped calls'
+  const hipdec_warp_desc* warp; const hipdec_tensor_projection* maps; const hipdec_tensor_fill* fill;
+  int src_width() const { return warp->src_width; }
+  int src_height() const { return warp->src_height; }
+  int check(const char* who, const hipdec_tensor_desc* d, int n) const { return project_check(who, warp, maps, fill, d, n); }
+  int depth(const char* who, const hipdec_tensor_desc* d, int e, int bits) const { return WarpStage{warp, nullptr, fill}.depth(who, d, e, bits); }
+  int scratch(hipdec_batch* b, size_t bytes, hipStream_t s, void** out) const { return warp_scratch(b->warp, bytes, s, out); }
+  int launch(hipdec_batch* b, const void* src, const hipdec_tensor_desc* d, int n, void* out_dev, hipStream_t s) const
+  {
+    return project_launch(b->warp, src, warp, maps, fill, d, n, out_dev, s);
+  }
+};
+
 struct PhotoStage {   // the photo stage and the augment stage: what the ChainView admits is what differs
   const hipdec_photo_desc* photo; ChainView chains;
   int src_width() const { return photo->src_width; }
@@ -1555,6 +1568,13 @@ int hipdec_batch_to_tensor_warped(hipdec_batch* b, const hipdec_tensor_desc* des
                                   size_t out_bytes, void* stream)
 {
   return batch_to_tensor_two_stage("to_tensor_warped", b, WarpStage{warp, maps, fill}, desc, entries, orientations, n_entries, out_dev, out_bytes, stream);
+}
+
+int hipdec_batch_to_tensor_projected(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                     const hipdec_warp_desc* warp, const hipdec_tensor_projection* maps, const hipdec_tensor_fill* fill, int n_entries, void* out_dev,
+                                     size_t out_bytes, void* stream)
+{
+  return batch_to_tensor_two_stage("to_tensor_projected", b, ProjectStage{warp, maps, fill}, desc, entries, orientations, n_entries, out_dev, out_bytes, stream);
 }
 
 int hipdec_batch_to_tensor_photo(hipdec_batch* b, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,

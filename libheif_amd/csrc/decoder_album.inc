@@ -466,6 +466,13 @@ int hipdec_album_to_tensor_warped(hipdec_album* a, const hipdec_tensor_desc* des
   return album_to_tensor_two_stage("album_to_tensor_warped", a, WarpStage{warp, maps, fill}, desc, entries, orientations, n_entries, out_dev, out_bytes, stream);
 }
 
+int hipdec_album_to_tensor_projected(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
+                                     const hipdec_warp_desc* warp, const hipdec_tensor_projection* maps, const hipdec_tensor_fill* fill, int n_entries, void* out_dev,
+                                     size_t out_bytes, void* stream)
+{
+  return album_to_tensor_two_stage("album_to_tensor_projected", a, ProjectStage{warp, maps, fill}, desc, entries, orientations, n_entries, out_dev, out_bytes, stream);
+}
+
 int hipdec_album_to_tensor_photo(hipdec_album* a, const hipdec_tensor_desc* desc, const hipdec_tensor_entry* entries, const int* orientations,
                                  const hipdec_photo_desc* photo, const hipdec_photo_chain* chains, int n_entries, void* out_dev, size_t out_bytes, void* stream)
 {

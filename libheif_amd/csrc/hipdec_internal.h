@@ -180,6 +180,12 @@ int warp_scratch(WarpState& st, size_t bytes, hipStream_t s, void** out);   // t
 int warp_launch(WarpState& st, const void* src_dev, const hipdec_warp_desc* w, const hipdec_tensor_map* maps, const hipdec_tensor_fill* fill,
                 const hipdec_tensor_desc* d, int n, void* out_dev, hipStream_t s);
 void warp_state_free(WarpState& st);
+// Projective tensor output (color.hip k_project, include/heif_hipdec.h hipdec_tensor_project): the warped output's structure with a PERSPECTIVE or QUAD map per
+// entry.  project_check is host-only; project_launch uploads n records with one copy and launches once.  The state is a WarpState - a handle's is the one its
+// warped calls use (table, intermediate, event).
+int project_check(const char* who, const hipdec_warp_desc* w, const hipdec_tensor_projection* maps, const hipdec_tensor_fill* fill, const hipdec_tensor_desc* d, int n);
+int project_launch(WarpState& st, const void* src_dev, const hipdec_warp_desc* w, const hipdec_tensor_projection* maps, const hipdec_tensor_fill* fill,
+                   const hipdec_tensor_desc* d, int n, void* out_dev, hipStream_t s);
 
 // Photometric tensor output (color.hip k_photo_hist / k_photo_apply, include/heif_hipdec.h hipdec_tensor_photo): n dense U8 / NHWC samples through a chain
 // of up to four operations each.  What the arguments alone decide (chain_check) is host-only; chain_launch builds one table of records per chain step,

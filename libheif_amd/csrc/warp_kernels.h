@@ -79,13 +79,60 @@ __device__ __forceinline__ double warp_cubic(double v1, double v2, double v3, do
   return p1 + d * (p2 + d * (p3 + d * p4));
 }
 
+// the inside test of the BILINEAR / BICUBIC statements
+__device__ __forceinline__ bool warp_inside(int sw, int sh, double xin, double yin) { return !(xin < 0.0 || xin >= (double)sw || yin < 0.0 || yin >= (double)sh); }
+
 // xin, yin of output pixel (x, y); false: outside
 __device__ __forceinline__ bool warp_map_pixel(const hipdec::WarpEntry& E, const WarpCall& c, int x, int y, double& xin, double& yin)
 {
   const double xc = (double)x + 0.5, yc = (double)y + 0.5;
   xin = E.m[0] * xc + E.m[1] * yc + E.m[2];
   yin = E.m[3] * xc + E.m[4] * yc + E.m[5];
-  return !(xin < 0.0 || xin >= (double)c.sw || yin < 0.0 || yin >= (double)c.sh);
+  return warp_inside(c.sw, c.sh, xin, yin);
+}
+
+// The sampling half of the BILINEAR / BICUBIC statements, from an inside (xin, yin) on: V[k], the 8-bit component values.  Stated once: k_warp_*,
+// k_recipe_affine_* (through warp_pixel) and k_project_* (project_kernels.h) call it.
+template <int FILTER>
+__device__ __forceinline__ void warp_sample(const HIPDEC_GLOBAL uint8_t* src, int sw, int sh, double xin, double yin, int (&V)[3])
+{
+  xin -= 0.5; yin -= 0.5;
+  const int ix = warp_floor_d(xin), iy = warp_floor_d(yin);
+  const double dx = xin - (double)ix, dy = yin - (double)iy;
+  if (FILTER == HIPDEC_SCALE_BILINEAR) {
+    const int x0 = clip_i(ix, sw - 1), x1 = clip_i(ix + 1, sw - 1), y0 = clip_i(iy, sh - 1);
+    const bool second = iy + 1 >= 0 && iy + 1 < sh;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const double v1 = warp_lerp((double)warp_src(src, sw, x0, y0, k), (double)warp_src(src, sw, x1, y0, k), dx);
+      double v2 = v1;
+      if (second) v2 = warp_lerp((double)warp_src(src, sw, x0, iy + 1, k), (double)warp_src(src, sw, x1, iy + 1, k), dx);
+      V[k] = (int)warp_lerp(v1, v2, dy);
+    }
+    return;
+  }
+  // bicubic: columns ix - 1 .. ix + 2 clamped; row iy - 1 clamped, rows iy .. iy + 2 used only where they exist
+  int xs[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) xs[j] = clip_i(ix - 1 + j, sw - 1);
+  const int yfirst = clip_i(iy - 1, sh - 1);
+#pragma unroll 1
+  for (int k = 0; k < 3; k++) {
+    double r[4];
+    r[0] = warp_cubic((double)warp_src(src, sw, xs[0], yfirst, k), (double)warp_src(src, sw, xs[1], yfirst, k), (double)warp_src(src, sw, xs[2], yfirst, k),
+                      (double)warp_src(src, sw, xs[3], yfirst, k), dx);
+#pragma unroll
+    for (int j = 1; j < 4; j++) {
+      const int yy = iy - 1 + j;
+      r[j] = r[j - 1];
+      if (yy >= 0 && yy < sh)
+        r[j] = warp_cubic((double)warp_src(src, sw, xs[0], yy, k), (double)warp_src(src, sw, xs[1], yy, k), (double)warp_src(src, sw, xs[2], yy, k),
+                          (double)warp_src(src, sw, xs[3], yy, k), dx);
+    }
+    const double v = warp_cubic(r[0], r[1], r[2], r[3], dy);
+    const int val = v <= 0.0 ? 0 : (v >= 255.0 ? 255 : (int)v);
+    V[0] = k == 0 ? val : V[0]; V[1] = k == 1 ? val : V[1]; V[2] = k == 2 ? val : V[2];   // (selects: a runtime index would put V into scratch memory)
+  }
 }
 
 // FILTER: hipdec_scale_filter.  V[k]: the 8-bit component values of output pixel (x, y); false: the pixel is outside and holds the fill
@@ -110,43 +157,7 @@ __device__ __forceinline__ bool warp_pixel(const hipdec::WarpEntry& E, const War
   }
   double xin, yin;
   if (!warp_map_pixel(E, c, x, y, xin, yin)) return false;
-  xin -= 0.5; yin -= 0.5;
-  const int ix = warp_floor_d(xin), iy = warp_floor_d(yin);
-  const double dx = xin - (double)ix, dy = yin - (double)iy;
-  if (FILTER == HIPDEC_SCALE_BILINEAR) {
-    const int x0 = clip_i(ix, sw - 1), x1 = clip_i(ix + 1, sw - 1), y0 = clip_i(iy, sh - 1);
-    const bool second = iy + 1 >= 0 && iy + 1 < sh;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      const double v1 = warp_lerp((double)warp_src(src, sw, x0, y0, k), (double)warp_src(src, sw, x1, y0, k), dx);
-      double v2 = v1;
-      if (second) v2 = warp_lerp((double)warp_src(src, sw, x0, iy + 1, k), (double)warp_src(src, sw, x1, iy + 1, k), dx);
-      V[k] = (int)warp_lerp(v1, v2, dy);
-    }
-    return true;
-  }
-  // bicubic: columns ix - 1 .. ix + 2 clamped; row iy - 1 clamped, rows iy .. iy + 2 used only where they exist
-  int xs[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) xs[j] = clip_i(ix - 1 + j, sw - 1);
-  const int yfirst = clip_i(iy - 1, sh - 1);
-#pragma unroll 1
-  for (int k = 0; k < 3; k++) {
-    double r[4];
-    r[0] = warp_cubic((double)warp_src(src, sw, xs[0], yfirst, k), (double)warp_src(src, sw, xs[1], yfirst, k), (double)warp_src(src, sw, xs[2], yfirst, k),
-                      (double)warp_src(src, sw, xs[3], yfirst, k), dx);
-#pragma unroll
-    for (int j = 1; j < 4; j++) {
-      const int yy = iy - 1 + j;
-      r[j] = r[j - 1];
-      if (yy >= 0 && yy < sh)
-        r[j] = warp_cubic((double)warp_src(src, sw, xs[0], yy, k), (double)warp_src(src, sw, xs[1], yy, k), (double)warp_src(src, sw, xs[2], yy, k),
-                          (double)warp_src(src, sw, xs[3], yy, k), dx);
-    }
-    const double v = warp_cubic(r[0], r[1], r[2], r[3], dy);
-    const int val = v <= 0.0 ? 0 : (v >= 255.0 ? 255 : (int)v);
-    V[0] = k == 0 ? val : V[0]; V[1] = k == 1 ? val : V[1]; V[2] = k == 2 ? val : V[2];   // (selects: a runtime index would put V into scratch memory)
-  }
+  warp_sample<FILTER>(src, sw, sh, xin, yin, V);
   return true;
 }
 

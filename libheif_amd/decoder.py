@@ -114,6 +114,16 @@ def _bind(lib):
         lib.hipdec_rotate_map.argtypes = [C.c_double, ci, ci, C.POINTER(TensorMap)]
         lib.hipdec_warp_stats.restype = None
         lib.hipdec_warp_stats.argtypes = [C.POINTER(C.c_uint64)] * 2
+    if hasattr(lib, "hipdec_tensor_project"):  # (likewise: the projective stage)
+        lib.hipdec_tensor_project.argtypes = [vp, sz, C.POINTER(WarpDesc), C.POINTER(TensorProjection), C.POINTER(TensorFill), C.POINTER(TensorDesc), ci, vp, sz, vp]
+        projected = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), C.POINTER(ci), C.POINTER(WarpDesc), C.POINTER(TensorProjection), C.POINTER(TensorFill), ci,
+                     vp, sz, vp]
+        lib.hipdec_batch_to_tensor_projected.argtypes = projected
+        lib.hipdec_album_to_tensor_projected.argtypes = projected
+        lib.hipdec_perspective_map.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(TensorProjection)]
+        lib.hipdec_quad_map.argtypes = [C.POINTER(C.c_double), ci, ci, C.POINTER(TensorProjection)]
+        lib.hipdec_project_stats.restype = None
+        lib.hipdec_project_stats.argtypes = [C.POINTER(C.c_uint64)] * 2
     if hasattr(lib, "hipdec_tensor_photo"):    # (likewise: an older branch's library has no photo stage)
         lib.hipdec_tensor_photo.argtypes = [vp, sz, C.POINTER(PhotoDesc), C.POINTER(PhotoChain), C.POINTER(TensorDesc), ci, vp, sz, vp]
         photo = [vp, C.POINTER(TensorDesc), C.POINTER(TensorEntry), C.POINTER(ci), C.POINTER(PhotoDesc), C.POINTER(PhotoChain), ci, vp, sz, vp]
@@ -210,6 +220,11 @@ class TensorMap(C.Structure):
 class WarpDesc(C.Structure):
     """hipdec_warp_desc"""
     _fields_ = [("src_width", C.c_int), ("src_height", C.c_int), ("filter", C.c_int), ("reserved", C.c_int)]
+
+
+class TensorProjection(C.Structure):
+    """hipdec_tensor_projection: PIL's PERSPECTIVE data, or the eight coefficients of its QUAD method, and the kind"""
+    _fields_ = [("a", C.c_double * 8), ("kind", C.c_int), ("reserved", C.c_int)]
 
 
 class PhotoOp(C.Structure):
@@ -853,6 +868,85 @@ def _to_tensor_warped(self, lib_call, size, maps, entries, src_size, warp_filter
     return _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
 
 
+# the projective stage (hipdec_tensor_project): PIL.Image.transform(size, PERSPECTIVE | QUAD, ...) on the 8-bit picture, bit for bit
+PROJECT_PERSPECTIVE, PROJECT_QUAD = 0, 1
+PROJECT_KINDS = {"perspective": PROJECT_PERSPECTIVE, "quad": PROJECT_QUAD}
+
+
+def tensor_projections(maps, n=None):
+    """a ctypes array of hipdec_tensor_projection.  A map is a sequence of eight numbers - PIL's PERSPECTIVE data -, a (kind, eight numbers) pair with kind
+    PROJECT_PERSPECTIVE / PROJECT_QUAD or "perspective" / "quad" (QUAD: the coefficients quad_map() makes, not the corners), or a TensorProjection"""
+    maps = list(maps)
+    if n is not None and len(maps) != n:
+        raise ValueError("%d maps for %d entries" % (len(maps), n))
+    arr = (TensorProjection * max(len(maps), 1))()
+    for k, m in enumerate(maps):
+        if isinstance(m, TensorProjection):
+            arr[k] = m
+            continue
+        m = tuple(m)
+        kind = PROJECT_PERSPECTIVE
+        if len(m) == 2:
+            kind, m = m
+            if isinstance(kind, str):
+                if kind.lower() not in PROJECT_KINDS:
+                    raise ValueError("unknown kind of map %r" % (kind,))
+                kind = PROJECT_KINDS[kind.lower()]
+        a = [float(v) for v in m]
+        if len(a) != 8:
+            raise ValueError("a projective map has eight coefficients, not %d" % len(a))
+        arr[k] = TensorProjection((C.c_double * 8)(*a), int(kind), 0)
+    return arr
+
+
+def perspective_map(startpoints, endpoints):
+    """The TensorProjection (PERSPECTIVE) that reads output point endpoints[k] from source point startpoints[k], k = 0 .. 3, each an (x, y) pair - the
+    library's statement of torchvision's _get_perspective_coeffs(startpoints, endpoints), computed by the C helper hipdec_perspective_map (an 8 x 8 system
+    in float64, Gaussian elimination with partial pivoting).  NOT pinned to torchvision, which is not installed where this library is tested.  Four
+    collinear or repeated points raise HipDecError."""
+    lib = _bind(load_library())
+    sp = [float(v) for p in startpoints for v in p]
+    ep = [float(v) for p in endpoints for v in p]
+    if len(sp) != 8 or len(ep) != 8:
+        raise ValueError("perspective_map takes four (x, y) start points and four end points")
+    out = TensorProjection()
+    check(lib.hipdec_perspective_map((C.c_double * 8)(*sp), (C.c_double * 8)(*ep), C.byref(out)))
+    return out
+
+
+def quad_map(corners, size):
+    """The TensorProjection (QUAD) of PIL.Image.transform(size, QUAD, corners): corners = (nw, sw, se, ne), each an (x, y) pair in source coordinates - or the
+    eight numbers flat, as Pillow takes them - and size = (width, height) of the OUTPUT.  Computed by the C helper hipdec_quad_map with Pillow's own
+    arithmetic, coefficient for coefficient."""
+    lib = _bind(load_library())
+    c = list(corners)
+    c = [float(v) for v in c] if len(c) == 8 else [float(v) for p in c for v in p]
+    if len(c) != 8:
+        raise ValueError("quad_map takes four (x, y) corners: nw, sw, se, ne")
+    out = TensorProjection()
+    check(lib.hipdec_quad_map((C.c_double * 8)(*c), int(size[0]), int(size[1]), C.byref(out)))
+    return out
+
+
+def project_stats():
+    """(launches of the projective kernel - one per projected call that wrote anything -, the entries they wrote) since load"""
+    lib = _bind(load_library())
+    a, b = C.c_uint64(), C.c_uint64()
+    lib.hipdec_project_stats(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def _to_tensor_projected(self, lib_call, size, maps, entries, src_size, warp_filter, fill, fill_domain, orientations, filter, dtype, layout, mean, std, scale,
+                         bias, out, stream):
+    n = self.n if entries is None else len(entries)
+    wd = warp_desc(size if src_size is None else src_size, warp_filter)
+    marr = tensor_projections(maps, n)
+    f = None if fill is None else tensor_fill(fill, fill_domain)
+    codes = None if orientations is None else _orientation_array(orientations, n)
+    call = lambda h, desc, arr, n_, ptr, room, stream_: lib_call(h, desc, arr, codes, C.byref(wd), marr, f, n_, ptr, room, stream_)
+    return _to_tensor(self, call, size, entries, dtype, layout, mean, std, scale, bias, filter, out, stream)
+
+
 # hipdec_photo_opcode: the photometric operations (PIL.ImageEnhance.* / PIL.ImageOps.* on the 8-bit picture, bit for bit)
 PHOTO_BRIGHTNESS, PHOTO_COLOR, PHOTO_CONTRAST, PHOTO_SHARPNESS, PHOTO_POSTERIZE, PHOTO_SOLARIZE, PHOTO_INVERT, PHOTO_AUTOCONTRAST, PHOTO_EQUALIZE = range(1, 10)
 PHOTO_MAX_OPS = 4
@@ -1422,6 +1516,17 @@ class Batch:
         return _to_tensor_warped(self, self._lib.hipdec_batch_to_tensor_warped, size, maps, entries, src_size, warp_filter, fill, fill_domain, orientations,
                                  filter, dtype, layout, mean, std, scale, bias, out, stream)
 
+    def to_tensor_projected(self, size, maps, entries=None, src_size=None, warp_filter=SCALE_BILINEAR, fill=0, fill_domain="component", orientations=None,
+                            filter=SCALE_BILINEAR, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, out=None, stream=None):
+        """asynchronous: to_tensor with one PERSPECTIVE or QUAD transform per entry, Pillow-exact (hipdec_batch_to_tensor_projected).  Entry e is first
+        resized as to_tensor(src_size, entries, dtype="uint8", layout="NHWC", filter=filter, orientations=orientations) resizes it - src_size defaults to
+        `size` - and that 8-bit picture then goes through PIL.Image.transform(size, PERSPECTIVE | QUAD, maps[e], warp_filter, fillcolor=fill) bit for bit,
+        normalised as to_tensor normalises.  maps: per entry eight numbers (PERSPECTIVE data), a (kind, eight numbers) pair, or what perspective_map() /
+        quad_map() return; the entries of a call may mix the kinds.  Everything else as in to_tensor_warped.  One resize launch and one projective launch
+        per call."""
+        return _to_tensor_projected(self, self._lib.hipdec_batch_to_tensor_projected, size, maps, entries, src_size, warp_filter, fill, fill_domain,
+                                    orientations, filter, dtype, layout, mean, std, scale, bias, out, stream)
+
     def to_tensor_photo(self, size, chains, entries=None, filter=SCALE_BILINEAR, orientations=None, dtype="float16", layout="NCHW", mean=None, std=None,
                         scale=None, bias=None, out=None, stream=None):
         """asynchronous: to_tensor with one chain of photometric operations per entry, Pillow-exact (hipdec_batch_to_tensor_photo).  Entry e is first
@@ -1690,6 +1795,12 @@ class Album:
         return _to_tensor_warped(self, self._lib.hipdec_album_to_tensor_warped, size, maps, entries, src_size, warp_filter, fill, fill_domain, orientations,
                                  filter, dtype, layout, mean, std, scale, bias, out, stream)
 
+    def to_tensor_projected(self, size, maps, entries=None, src_size=None, warp_filter=SCALE_BILINEAR, fill=0, fill_domain="component", orientations=None,
+                            filter=SCALE_BILINEAR, dtype="float16", layout="NCHW", mean=None, std=None, scale=None, bias=None, out=None, stream=None):
+        """Batch.to_tensor_projected over the composed photos"""
+        return _to_tensor_projected(self, self._lib.hipdec_album_to_tensor_projected, size, maps, entries, src_size, warp_filter, fill, fill_domain,
+                                    orientations, filter, dtype, layout, mean, std, scale, bias, out, stream)
+
     def to_tensor_photo(self, size, chains, entries=None, filter=SCALE_BILINEAR, orientations=None, dtype="float16", layout="NCHW", mean=None, std=None,
                         scale=None, bias=None, out=None, stream=None):
         """Batch.to_tensor_photo over the composed photos"""
@@ -1747,12 +1858,8 @@ class _WarpStage:
     tensor_to_host = Batch.tensor_to_host
 
 
-def tensor_warp(src, size, maps, src_size=None, warp_filter=SCALE_BILINEAR, fill=0, fill_domain="component", dtype="float16", layout="NCHW", mean=None,
-                std=None, scale=None, bias=None, out=None, stream=None, to_host=False):
-    """asynchronous: the warp stage alone (hipdec_tensor_warp) over n = len(maps) dense 8-bit RGB samples in device memory: a uint8 torch.Tensor of shape
-    (n, src_height, src_width, 3), or a DeviceBuffer of n * src_height * src_width * 3 bytes with src_size = (src_width, src_height).  Sample e goes through
-    PIL.Image.transform(size, AFFINE, maps[e], warp_filter, fillcolor=fill) bit for bit and is normalised as to_tensor normalises; everything else as in
-    Batch.to_tensor_warped.  A clip's T frames share one map by repeating it T times.  Returns `out` (to_host=True: the NumPy array, after waiting)."""
+def _tensor_map_stage(lib_call, make_maps, src, size, maps, src_size, warp_filter, fill, fill_domain, dtype, layout, mean, std, scale, bias, out, stream, to_host):
+    """tensor_warp and tensor_project: the source, the maps, then the stage's call"""
     lib = _bind(load_library())
     maps = list(maps)
     n = len(maps)
@@ -1773,12 +1880,31 @@ def tensor_warp(src, size, maps, src_size=None, warp_filter=SCALE_BILINEAR, fill
         if out is None and stream is None and n > 0:
             out = torch.empty(tensor_shape(n, size, layout), dtype=getattr(torch, dtype), device=src.device)   # (written on torch's current stream, as src was)
     wd = warp_desc(src_size, warp_filter)
-    marr = tensor_maps(maps, n)
+    marr = make_maps(maps, n)
     f = None if fill is None else tensor_fill(fill, fill_domain)
     stage = _WarpStage(lib, n)
-    call = lambda h, desc, arr, n_, ptr, room, stream_: lib.hipdec_tensor_warp(sptr, sbytes, C.byref(wd), marr, f, desc, n_, ptr, room, stream_)
+    call = lambda h, desc, arr, n_, ptr, room, stream_: getattr(lib, lib_call)(sptr, sbytes, C.byref(wd), marr, f, desc, n_, ptr, room, stream_)
     out = _to_tensor(stage, call, size, None, dtype, layout, mean, std, scale, bias, 0, out, stream)
     return stage.tensor_to_host() if to_host else out
+
+
+def tensor_warp(src, size, maps, src_size=None, warp_filter=SCALE_BILINEAR, fill=0, fill_domain="component", dtype="float16", layout="NCHW", mean=None,
+                std=None, scale=None, bias=None, out=None, stream=None, to_host=False):
+    """asynchronous: the warp stage alone (hipdec_tensor_warp) over n = len(maps) dense 8-bit RGB samples in device memory: a uint8 torch.Tensor of shape
+    (n, src_height, src_width, 3), or a DeviceBuffer of n * src_height * src_width * 3 bytes with src_size = (src_width, src_height).  Sample e goes through
+    PIL.Image.transform(size, AFFINE, maps[e], warp_filter, fillcolor=fill) bit for bit and is normalised as to_tensor normalises; everything else as in
+    Batch.to_tensor_warped.  A clip's T frames share one map by repeating it T times.  Returns `out` (to_host=True: the NumPy array, after waiting)."""
+    return _tensor_map_stage("hipdec_tensor_warp", tensor_maps, src, size, maps, src_size, warp_filter, fill, fill_domain, dtype, layout, mean, std, scale, bias,
+                             out, stream, to_host)
+
+
+def tensor_project(src, size, maps, src_size=None, warp_filter=SCALE_BILINEAR, fill=0, fill_domain="component", dtype="float16", layout="NCHW", mean=None,
+                   std=None, scale=None, bias=None, out=None, stream=None, to_host=False):
+    """asynchronous: the projective stage alone (hipdec_tensor_project): tensor_warp with maps as Batch.to_tensor_projected takes them - sample e goes
+    through PIL.Image.transform(size, PERSPECTIVE | QUAD, maps[e], warp_filter, fillcolor=fill) bit for bit.  Everything else as tensor_warp; dtype "uint8"
+    with layout "NHWC" gives samples that tensor_warp, tensor_photo, tensor_augment, tensor_recipe and this call take again."""
+    return _tensor_map_stage("hipdec_tensor_project", tensor_projections, src, size, maps, src_size, warp_filter, fill, fill_domain, dtype, layout, mean, std,
+                             scale, bias, out, stream, to_host)
 
 
 def _tensor_chain_stage(lib_call, make_chains, src, chains, src_size, dtype, layout, mean, std, scale, bias, out, stream, to_host):
