@@ -15,7 +15,10 @@
 //     in VGPRs, so every ds_read is a broadcast and every ds_write stores the same dword from all lanes;
 //   * LDS instructions of one wave complete in order, so a read behind a write of the same variable sees it, and counted lgkmcnt waits are exact
 //     once the statement has drained what the compiler left in flight (the first wait of every statement is lgkmcnt(0));
-//   * range / value / bits_needed stay wave-uniform vector values as in the register-file build; the byte refill still reads the window register.
+//   * range / value / bits_needed stay wave-uniform vector values as in the register-file build;
+//   * the byte refill (HIPDEC_PARSE_LDS_WIN) adds the prefetched byte %[vbyte] and issues the broadcast read of the one behind it; no statement
+//     leaves with that read in flight (the compiler does not see it): inside a run the next bin's wait covers it, and a statement that ends
+//     behind a refill waits for it itself.  Without the switch the refill reads the window register as the register-file build does.
 #define PC_LDS_HEAD_Q   "v_lshrrev_b32 %[vt], 10, %[R]\n\tv_and_b32 %[vt], 24, %[vt]\n\t"
 // LPS tail: value -= R, renormalise by clz(lps), the variable after the LPS from tnext (valMps flips where its bit 16 is set), the bin flips
 #define PC_LDS_LPS                                                                                                                 \
@@ -31,7 +34,25 @@
   "v_xor_b32 %[vb], 1, %[vb]\n\t"                                                                                                   \
   "s_waitcnt lgkmcnt(0)\n\t"                                                                                                        \
   "v_xor_b32 %[vn], %[vn], %[vt]\n\t"
-// byte refill from the window register; branches to SLOW when the fast window is exhausted
+// byte refill; branches to SLOW when the fast window is exhausted
+#if HIPDEC_PARSE_LDS_WIN
+#define PC_LDS_REFILL(SLOW)                                                                                                        \
+  "s_cmp_lt_u32 %[pos], %[flim]\n\t"                                                                                                \
+  "s_cbranch_scc0 " SLOW "\n\t"                                                                                                     \
+  "v_lshl_add_u32 %[val], %[vbyte], %[bits], %[val]\n\t"                                                                            \
+  "v_add_u32 %[vpos], 1, %[vpos]\n\t"                                                                                               \
+  "s_add_u32 %[pos], %[pos], 1\n\t"                                                                                                 \
+  "ds_read_u8 %[vbyte], %[vpos] offset:%c[wwin]\n\t"                                                                                \
+  "v_add_u32 %[bits], -8, %[bits]\n\t"
+#define PC_LDS_WIN_WAIT "s_waitcnt lgkmcnt(0)\n\t"
+#define PC_LDS_WIN_STATE(s) [vbyte] "+v"((s).vbyte), [vpos] "+v"((s).vpos),
+#define PC_LDS_WIN_TEMPS(st, row)
+#define PC_LDS_WIN_IN(s) [wwin] "i"(__builtin_offsetof(Lds, wwin))
+#else
+#define PC_LDS_WIN_WAIT
+#define PC_LDS_WIN_STATE(s)
+#define PC_LDS_WIN_TEMPS(st, row) [st] "=&s"(st), [row] "=&s"(row),
+#define PC_LDS_WIN_IN(s) [win] "v"((s).win)
 #define PC_LDS_REFILL(SLOW)                                                                                                        \
   "s_cmp_lt_u32 %[pos], %[flim]\n\t"                                                                                                \
   "s_cbranch_scc0 " SLOW "\n\t"                                                                                                     \
@@ -44,6 +65,7 @@
   "s_and_b32 %[st], %[st], 0xff\n\t"                                                                                                \
   "v_lshl_add_u32 %[val], %[st], %[bits], %[val]\n\t"                                                                               \
   "v_add_u32 %[bits], -8, %[bits]\n\t"
+#endif
 // the part of a bin every statement shares: state in %[vst] (being loaded) -> range update, MPS / LPS decision.  Falls through on an MPS
 // with %[vn] = the variable after the MPS and VCC = "renormalise"; LPS_LABEL is taken for an LPS.
 #ifdef HIPDEC_EXP_BIN_LATENCY   // measurement build: ~64 cycles of pure latency per bin (is the pool latency- or issue-bound?)
@@ -69,7 +91,8 @@ PC_DEV uint32_t pc_lds_ctx_addr(CtxGroup grp, int lane) { return (uint32_t)__bui
 
 PC_DEV int decode_bin(PS& s, CtxRef grp, int ctx_lane)
 {
-  uint32_t r, st, row, flag;
+  uint32_t r, flag;
+  [[maybe_unused]] uint32_t st, row;
   uint32_t vst, vrow, vt, vl, vn, vr, vb;
   const uint32_t va = pc_lds_ctx_addr(grp, ctx_lane);   // (a literal for most call sites: the compiler materialises it with one move)
   uint32_t pos = pc_uni(s.pos);
@@ -89,16 +112,17 @@ PC_DEV int decode_bin(PS& s, CtxRef grp, int ctx_lane)
     "v_cmp_lt_i32_e32 vcc, -1, %[bits]\n\t"
     "s_cbranch_vccz 6f\n\t"
     PC_LDS_REFILL("3f")
+    PC_LDS_WIN_WAIT
     "s_branch 6f\n"
     "3:\n\t"
     "s_mov_b32 %[flag], 1\n"
     "6:\n\t"
     "ds_write_b32 %[va], %[vn]\n\t"
     "v_readfirstlane_b32 %[r], %[vb]\n\t"
-    : [R] "+v"(s.range), [val] "+v"(s.value), [bits] "+v"(s.bits_needed), [pos] "+s"(pos),
-      [r] "=&s"(r), [st] "=&s"(st), [row] "=&s"(row), [flag] "=&s"(flag),
+    : [R] "+v"(s.range), [val] "+v"(s.value), [bits] "+v"(s.bits_needed), [pos] "+s"(pos), PC_LDS_WIN_STATE(s)
+      [r] "=&s"(r), PC_LDS_WIN_TEMPS(st, row) [flag] "=&s"(flag),
       [vst] "=&v"(vst), [vrow] "=&v"(vrow), [vt] "=&v"(vt), [vl] "=&v"(vl), [vn] "=&v"(vn), [vr] "=&v"(vr), [vb] "=&v"(vb)
-    : [va] "v"(va), [win] "v"(s.win), [flim] "s"(flim), [m128] "v"(0xffffff80u), PC_LDS_OFFSETS
+    : [va] "v"(va), PC_LDS_WIN_IN(s), [flim] "s"(flim), [m128] "v"(0xffffff80u), PC_LDS_OFFSETS
     : "vcc", "scc", "memory");
   s.pos = pc_uni(pos);
   if (__builtin_expect(pc_uni(flag) != 0u, 0)) refill_byte(s);
@@ -147,7 +171,8 @@ PC_DEV uint32_t decode_sig_run(PS& s, const VReg& vctx, int n_start)
   asm volatile("v_mov_b32 %0, 0" : "=v"(vacc));
   int32_t j = __builtin_amdgcn_readfirstlane(n_start - 1);   // the position after the current one; the run ends when it leaves 0 .. 15
   for (;;) {
-    uint32_t flag, st, row, t;
+    uint32_t flag, t;
+    [[maybe_unused]] uint32_t st, row;
     uint32_t vst, vrow, vt, vl, vn, vr, vb, vca, vcb, vj;
     uint32_t pos = pc_uni(s.pos);
     const uint32_t flim = pc_uni(s.fast_limit);
@@ -161,11 +186,12 @@ PC_DEV uint32_t decode_sig_run(PS& s, const VReg& vctx, int n_start)
       PC_LDS_SIG_ITER("0", "vca", "vcb", "110f")
       PC_LDS_SIG_ITER("1", "vcb", "vca", "100b")
       "190:\n\t"
-      : [R] "+v"(s.range), [val] "+v"(s.value), [bits] "+v"(s.bits_needed), [pos] "+s"(pos), [j] "+s"(j), [vacc] "+v"(vacc),
-        [flag] "=&s"(flag), [st] "=&s"(st), [row] "=&s"(row), [t] "=&s"(t),
+      PC_LDS_WIN_WAIT
+      : [R] "+v"(s.range), [val] "+v"(s.value), [bits] "+v"(s.bits_needed), [pos] "+s"(pos), [j] "+s"(j), [vacc] "+v"(vacc), PC_LDS_WIN_STATE(s)
+        [flag] "=&s"(flag), PC_LDS_WIN_TEMPS(st, row) [t] "=&s"(t),
         [vst] "=&v"(vst), [vrow] "=&v"(vrow), [vt] "=&v"(vt), [vl] "=&v"(vl), [vn] "=&v"(vn), [vr] "=&v"(vr), [vb] "=&v"(vb),
         [vca] "=&v"(vca), [vcb] "=&v"(vcb), [vj] "=&v"(vj)
-      : [win] "v"(s.win), [flim] "s"(flim), [m128] "v"(0xffffff80u), PC_LDS_OFFSETS
+      : PC_LDS_WIN_IN(s), [flim] "s"(flim), [m128] "v"(0xffffff80u), PC_LDS_OFFSETS
       : "vcc", "scc", "memory");
     s.pos = pc_uni(pos);
     if (__builtin_expect(__builtin_amdgcn_readfirstlane((int)flag) != 0, 0)) refill_byte(s);
@@ -185,7 +211,8 @@ PC_DEV uint32_t decode_g1_run(PS& s, int base_lane, int n, int& g_io)
   const uint32_t vbase = pc_lds_ctx_addr(PS::ctxC, base_lane);
   asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, %2" : "=&v"(vgb), "=&v"(vg) : "s"((uint32_t)__builtin_amdgcn_readfirstlane(g_io)));
   for (;;) {
-    uint32_t flag, st, row;
+    uint32_t flag;
+    [[maybe_unused]] uint32_t st, row;
     uint32_t vst, vrow, vt, vl, vn, vr, vb, vc, vt2;
     uint32_t pos = pc_uni(s.pos);
     const uint32_t flim = pc_uni(s.fast_limit);
@@ -228,11 +255,12 @@ PC_DEV uint32_t decode_g1_run(PS& s, int base_lane, int n, int& g_io)
       "s_add_u32 %[m], %[m], -1\n\t"
       "s_mov_b32 %[flag], 1\n"
       "290:\n\t"
-      : [R] "+v"(s.range), [val] "+v"(s.value), [bits] "+v"(s.bits_needed), [pos] "+s"(pos), [m] "+s"(m), [vgb] "+v"(vgb), [vg] "+v"(vg),
-        [flag] "=&s"(flag), [st] "=&s"(st), [row] "=&s"(row),
+      PC_LDS_WIN_WAIT
+      : [R] "+v"(s.range), [val] "+v"(s.value), [bits] "+v"(s.bits_needed), [pos] "+s"(pos), [m] "+s"(m), [vgb] "+v"(vgb), [vg] "+v"(vg), PC_LDS_WIN_STATE(s)
+        [flag] "=&s"(flag), PC_LDS_WIN_TEMPS(st, row)
         [vst] "=&v"(vst), [vrow] "=&v"(vrow), [vt] "=&v"(vt), [vl] "=&v"(vl), [vn] "=&v"(vn), [vr] "=&v"(vr), [vb] "=&v"(vb), [vc] "=&v"(vc),
         [vt2] "=&v"(vt2)
-      : [vbase] "v"(vbase), [win] "v"(s.win), [flim] "s"(flim), [m128] "v"(0xffffff80u), PC_LDS_OFFSETS
+      : [vbase] "v"(vbase), PC_LDS_WIN_IN(s), [flim] "s"(flim), [m128] "v"(0xffffff80u), PC_LDS_OFFSETS
       : "vcc", "scc", "memory");
     s.pos = pc_uni(pos);
     if (__builtin_expect(__builtin_amdgcn_readfirstlane((int)flag) != 0, 0)) refill_byte(s);
@@ -254,7 +282,8 @@ PC_DEV int decode_unary_ctx_run(PS& s, CtxRef grp, int base_lane, int shift_, in
   uint32_t vsh;
   asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, %2" : "=&v"(vi), "=&v"(vsh) : "s"((uint32_t)__builtin_amdgcn_readfirstlane(shift_)));
   for (;;) {
-    uint32_t flag, st, row;
+    uint32_t flag;
+    [[maybe_unused]] uint32_t st, row;
     uint32_t vst, vrow, vt, vl, vn, vr, vb, vc;
     uint32_t pos = pc_uni(s.pos);
     const uint32_t flim = pc_uni(s.fast_limit);
@@ -300,10 +329,11 @@ PC_DEV int decode_unary_ctx_run(PS& s, CtxRef grp, int base_lane, int shift_, in
       "306:\n\t"
       "s_mov_b32 %[flag], 3\n"
       "390:\n\t"
-      : [R] "+v"(s.range), [val] "+v"(s.value), [bits] "+v"(s.bits_needed), [pos] "+s"(pos), [i] "+s"(i), [vi] "+v"(vi),
-        [flag] "=&s"(flag), [st] "=&s"(st), [row] "=&s"(row),
+      PC_LDS_WIN_WAIT
+      : [R] "+v"(s.range), [val] "+v"(s.value), [bits] "+v"(s.bits_needed), [pos] "+s"(pos), [i] "+s"(i), [vi] "+v"(vi), PC_LDS_WIN_STATE(s)
+        [flag] "=&s"(flag), PC_LDS_WIN_TEMPS(st, row)
         [vst] "=&v"(vst), [vrow] "=&v"(vrow), [vt] "=&v"(vt), [vl] "=&v"(vl), [vn] "=&v"(vn), [vr] "=&v"(vr), [vb] "=&v"(vb), [vc] "=&v"(vc)
-      : [vbase] "v"(vbase), [vsh] "v"(vsh), [mx] "s"(mx), [win] "v"(s.win), [flim] "s"(flim), [m128] "v"(0xffffff80u), PC_LDS_OFFSETS
+      : [vbase] "v"(vbase), [vsh] "v"(vsh), [mx] "s"(mx), PC_LDS_WIN_IN(s), [flim] "s"(flim), [m128] "v"(0xffffff80u), PC_LDS_OFFSETS
       : "vcc", "scc", "memory");
     s.pos = pc_uni(pos);
     i = pc_uni(i);

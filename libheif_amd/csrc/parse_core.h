@@ -25,7 +25,7 @@
 //     26.4 SALU + 26.1 VALU + 8 branch per pixel (profiles/r02l_pmc_parse_b512_after_valu_state.txt); round 3's hand-scheduled
 //     statements for the bins: 23.4 + 21.9 + 7.3 (profiles/r03b_pmc_parse_b512.txt).
 //   * the 64 lanes do the data-parallel side jobs (context init, window loads and emulation-prevention scan, map fills, per-sub-
-//     block context selection and level finalisation, coefficient block flush, WPP context save / restore).
+//     block context selection and level finalisation, level stores and zero fill, WPP context save / restore).
 //
 // The same source compiles for the device (parse_kernel.hip) and, with HIPDEC_HOST_EMU, as a
 // lane-emulating host build used ONLY by the CPU tests (tests/emu) to check the parser's logic
@@ -120,6 +120,9 @@ PC_DEV uint32_t pc_mul24(uint32_t a, uint32_t b) { return __umul24(a, b); }     
 #ifndef HIPDEC_PARSE_LDS_MAPS
 #define HIPDEC_PARSE_LDS_MAPS HIPDEC_PARSE_LDS_CTX   // 1: the CTB's five unit maps live in LDS as well (see "LDS-resident unit maps" below)
 #endif
+#ifndef HIPDEC_PARSE_LDS_WIN
+#define HIPDEC_PARSE_LDS_WIN HIPDEC_PARSE_LDS_CTX    // 1: the bitstream window lives in LDS and the next unread byte is prefetched (see "LDS-resident window" below)
+#endif
 #ifndef HIPDEC_PARSE_LEAN_GLUE
 #define HIPDEC_PARSE_LEAN_GLUE HIPDEC_PARSE_LDS_CTX   // 1: residual_coding's glue between the bins in its shorter form (see "lean glue" in residual_coding)
 #endif
@@ -131,7 +134,6 @@ namespace hipdec {
 namespace pcore {
 
 struct Lds {
-  alignas(16) int16_t coef[32 * 32];  // coefficient block being parsed (zero outside the parse of a block)
   alignas(16) uint32_t park[SAVE_DWORDS];   // staging image of a parked row's record (save_row_state / load_row_state)
 #if HIPDEC_PARSE_LDS_CTX
   // LDS-resident contexts (round 6).  Measured on MI355X (profiles/r06_issue_model_*.txt): a VALU instruction that touches the scalar register
@@ -154,6 +156,14 @@ struct Lds {
   // use at 32 one-wave workgroups per CU.
   uint32_t umap[5 * 64];
 #endif
+#if HIPDEC_PARSE_LDS_WIN
+  // LDS-resident window: the 256-byte bitstream window and the prefetched next one, in the two halves of a 512-byte ring - byte p of the stream
+  // sits at ring index p & 511, so a contiguous advance only loads the half that fell free.  The decoder keeps the next unread byte (PS::vbyte)
+  // and its ring index (PS::vpos) as wave-uniform vector values: a refill adds the byte it already holds and issues one broadcast ds_read_u8 for
+  // the one behind it, instead of v_readlane + wait state + scalar shift and mask.  Two dwords of slack: the prefetch behind the last byte of the
+  // upper half, and decode_remaining_v's look at the byte after, read (and never use) index 512 / 513.
+  uint32_t wwin[128 + 2];
+#endif
 };
 #if HIPDEC_PARSE_LDS_MAPS
 struct UMap { int base; };             // a unit map is a byte range of Lds::umap ...
@@ -175,7 +185,7 @@ typedef VReg& CtxRef;                  // ... or a 64-lane register
 // everything here is wave-uniform unless it is a VReg
 struct PS {
 #ifdef HIPDEC_PARSE_CYCLES   // measurement build (tools/ab_variant.sh cyc -DHIPDEC_PARSE_CYCLES): where does a row's time go?  printed per row
-  unsigned long long c_resid = 0, c_flush = 0, c_wait = 0, c_cu = 0, c_pub = 0; uint32_t n_resid = 0;
+  unsigned long long c_resid = 0, c_wait = 0, c_cu = 0, c_pub = 0; uint32_t n_resid = 0;
 #endif
   // ---- arithmetic decoder: range / value / bits_needed are wave-uniform values kept in VECTOR registers (UReg), so the
   //      decoder's arithmetic issues on the SIMD's VALU while the CU-shared scalar pipe keeps the syntax control flow
@@ -193,7 +203,12 @@ struct PS {
   VReg ctxA, ctxB, ctxC;
   VReg t_lps, t_next;
 #endif
-  VReg win, win_next;
+  VReg win, win_next;                           // (LDS-resident window: only load_window's temporaries)
+#if HIPDEC_PARSE_LDS_WIN
+  // the byte at `pos` and its index in Lds::wwin's ring, valid while pos < fast_limit; every slow read re-primes both (win_prime), and a resumed row
+  // or a fresh substream starts with fast_limit = 0, i.e. with a slow read
+  UReg vbyte = 0, vpos = 0;
+#endif
 #if HIPDEC_PARSE_LDS_MAPS
   static constexpr UMap m_size{0}, m_flags{256}, m_ipm{512}, m_ipmc{768}, m_qp{1024};
 #else
@@ -293,6 +308,20 @@ PC_DEV void load_window(PS& s, uint32_t base, uint32_t first_pos)
 {
   const bool contiguous = base == s.win_base + 256u;
   uint32_t tail;             // the two bytes in front of the window
+#if HIPDEC_PARSE_LDS_WIN
+  uint32_t* const cur = s.L->wwin + ((base >> 2) & 64u);           // the ring half of this window ...
+  uint32_t* const nxt = s.L->wwin + (((base >> 2) & 64u) ^ 64u);   // ... and of the one behind it (which still holds the one in front)
+  if (contiguous) {
+    uint32_t last = 0;
+    PC_VEC_BEGIN last = nxt[63]; PC_L(s.win) = cur[lane]; PC_VEC_END
+    tail = pc_uni(last) >> 16;
+  } else {
+    tail = base >= 4u ? pc_uni(*(const uint32_t*)(s.bs + base - 4u)) >> 16 : 0x0101u;
+    PC_VEC_BEGIN PC_L(s.win) = *(const uint32_t*)(s.bs + base + 4u * (uint32_t)lane); cur[lane] = PC_L(s.win); PC_VEC_END
+  }
+  PC_VEC_BEGIN PC_L(s.win_next) = *(const uint32_t*)(s.bs + base + 256u + 4u * (uint32_t)lane); nxt[lane] = PC_L(s.win_next); PC_VEC_END
+  PC_LDS_SYNC();   // (the byte reads that follow look at what other lanes stored)
+#else
   if (contiguous) {
     tail = pc_rdlane(s.win, 63) >> 16;
     PC_VEC_BEGIN PC_L(s.win) = PC_L(s.win_next); PC_VEC_END
@@ -301,6 +330,7 @@ PC_DEV void load_window(PS& s, uint32_t base, uint32_t first_pos)
     PC_VEC_BEGIN PC_L(s.win) = *(const uint32_t*)(s.bs + base + 4u * (uint32_t)lane); PC_VEC_END
   }
   PC_VEC_BEGIN PC_L(s.win_next) = *(const uint32_t*)(s.bs + base + 256u + 4u * (uint32_t)lane); PC_VEC_END
+#endif
   s.win_base = base;
   VReg cand;
   PC_VEC_BEGIN
@@ -318,16 +348,35 @@ PC_DEV void load_window(PS& s, uint32_t base, uint32_t first_pos)
     if (first_pos == base) s.zeros = (tail & 0xffffu) == 0 ? 2 : ((tail >> 8) == 0 ? 1 : 0);
   }
 }
+#if HIPDEC_PARSE_LDS_WIN
+// ring byte `idx` as a wave-uniform vector value (a broadcast read; the compiler places its wait where the value is used)
+PC_DEV UReg win_byte(PS& s, UReg idx)
+{
+  return ((const uint8_t*)s.L->wwin)[idx];
+}
+PC_DEV void win_prime(PS& s) { s.vpos = pc_vec(s.pos & 511u); s.vbyte = win_byte(s, s.vpos); }        // behind every slow read
+PC_DEV void win_advance(PS& s) { s.pos++; s.vpos += 1u; s.vbyte = win_byte(s, s.vpos); }               // the fast path: consume vbyte, prefetch
+#endif
 PC_DEV uint32_t fetch_byte(PS& s, uint32_t pos)
 {
   if ((pos & ~255u) != s.win_base) load_window(s, pos & ~255u, pos);
+#if HIPDEC_PARSE_LDS_WIN
+  return pc_uni(win_byte(s, pc_vec(pos & 511u)));
+#else
   return (pc_rdlane(s.win, (int)((pos >> 2) & 63u)) >> ((pos & 3u) * 8u)) & 255u;
+#endif
 }
 PC_DEV uint32_t read_byte(PS& s)
 {
   if (__builtin_expect(s.pos < s.fast_limit, 1)) {   // inside a window without emulation-prevention candidates, before the end
+#if HIPDEC_PARSE_LDS_WIN
+    const UReg b = s.vbyte;
+    win_advance(s);
+    return pc_uni(b);
+#else
     const uint32_t p = s.pos++;
     return (pc_rdlane(s.win, (int)((p >> 2) & 63u)) >> ((p & 3u) * 8u)) & 255u;
+#endif
   }
   uint32_t b;
   for (;;) {   // (a loop so that the window fetch is emitted once per call site)
@@ -338,6 +387,9 @@ PC_DEV uint32_t read_byte(PS& s)
     s.zeros = b == 0 ? s.zeros + 1 : 0;
     break;
   }
+#if HIPDEC_PARSE_LDS_WIN
+  win_prime(s);
+#endif
   return b;
 }
 // the same byte as a wave-uniform VECTOR value: the arithmetic decoder adds it to its (vector-resident) window, so position masking, shift and
@@ -345,10 +397,16 @@ PC_DEV uint32_t read_byte(PS& s)
 PC_DEV UReg read_byte_v(PS& s)
 {
   if (__builtin_expect(s.pos < s.fast_limit, 1)) {
+#if HIPDEC_PARSE_LDS_WIN
+    const UReg b = s.vbyte;
+    win_advance(s);
+    return b;
+#else
     const uint32_t p = s.pos++;
     const uint32_t dw = pc_rdlane(s.win, (int)(p >> 2));     // (v_readlane takes the lane from bits 5:0 of the select)
     const UReg sh = (pc_vec(p) & 3u) << 3;
     return ((UReg)dw >> sh) & 255u;
+#endif
   }
   return pc_vec(read_byte(s));
 }
@@ -451,6 +509,9 @@ PC_DEV int decode_bin_cxx(PS& s, VReg& grp, int ctx_lane)
 #if HIPDEC_PARSE_LDS_CTX
 #include "parse_bins_lds_gfx950.h"
 #else
+#if HIPDEC_PARSE_LDS_WIN
+#error "HIPDEC_PARSE_LDS_WIN: the register-file statements (parse_bins_gfx950.h) read the window register"
+#endif
 #include "parse_bins_gfx950.h"
 #endif
 #else
@@ -617,24 +678,24 @@ PC_DEV void set_qp_y(PS& s)
   s.cur_qp_y = ((s.qpy_pred + s.cu_qp_delta_val + 52 + 2 * off) % (52 + off)) - off;
 }
 
-// ---- coefficient block staging (LDS block -> TU-contiguous int16 in HBM) -------------------------
-struct alignas(16) Coef8 { int16_t v[8]; };
+// ---- coefficient blocks (TU-contiguous int16 in HBM, raster n x n) ---------------------------------
+// residual_coding stores the 16 levels of every sub-block it parses (zeros included) straight at their raster places in the block; what is left
+// are the sub-blocks whose coded_sub_block_flag is 0 (and the ones behind the last position): zero_uncoded_sub_blocks() fills them once per block,
+// one lane per sub-block with four 8-byte row stores, from the bitmap of the stored ones (bit ys * 8 + xs).  A block whose sub-blocks were all
+// stored - every 4x4 block, most small ones - skips it with one wave-uniform compare.
 struct alignas(8) Coef4 { int16_t v[4]; };
-PC_DEV void flush_coef(PS& s, int16_t* dst, int n2)
+PC_DEV void zero_uncoded_sub_blocks(int16_t* dst, int log2n, uint64_t stored)
 {
-  PC_LDS_SYNC();
+  const int lg = log2n - 2;
+  const uint64_t full = lg == 3 ? ~0ull : (lg == 2 ? 0x0f0f0f0full : (lg == 1 ? 0x0303ull : 1ull));
+  if (stored == full) return;
   PC_VEC_BEGIN
-    if (n2 >= 64) {
-      for (int i = lane * 8; i < n2; i += 512) {
-        *(Coef8*)&dst[i] = *(const Coef8*)&s.L->coef[i];
-        *(Coef8*)&s.L->coef[i] = Coef8{{0, 0, 0, 0, 0, 0, 0, 0}};
-      }
-    } else if (lane < 4) {  // 4x4: 32 bytes
-      *(Coef4*)&dst[lane * 4] = *(const Coef4*)&s.L->coef[lane * 4];
-      *(Coef4*)&s.L->coef[lane * 4] = Coef4{{0, 0, 0, 0}};
+    const int xs = lane & ((1 << lg) - 1), ys = lane >> lg;
+    if (lane < (1 << (2 * lg)) && !((stored >> (ys * 8 + xs)) & 1u)) {
+      const uint32_t o = (uint32_t)(((ys << 2) << log2n) + (xs << 2));
+      for (uint32_t r = 0; r < 4u; r++) *(Coef4*)(dst + (o + (r << log2n))) = Coef4{{0, 0, 0, 0}};
     }
   PC_VEC_END
-  PC_LDS_SYNC();
 }
 
 // ---- 7.3.8.11 residual_coding ----------------------------------------------------------------
@@ -656,8 +717,13 @@ PC_DEV UReg decode_remaining_v(PS& s, UReg rice)
 {
   if (__builtin_expect(s.pos < s.fast_limit, 1)) {
     const uint32_t p = s.pos;
+#if HIPDEC_PARSE_LDS_WIN
+    const UReg byte = s.vbyte;
+    const UReg byte2 = win_byte(s, s.vpos + 1u);                    // the byte after: the next prefetched byte if this one is taken, the 9 .. 16-bin form's second byte
+#else
     const uint32_t dw = pc_rdlane(s.win, (int)(p >> 2));
     const UReg byte = ((UReg)dw >> ((pc_vec(p) & 3u) << 3)) & 255u;
+#endif
     const UReg bn = s.bits_needed;                                  // -8 .. -1
     const UReg v8 = (s.value << 8) + (byte << (bn + 8u));           // what 8 steps of 9.3.4.3.4 would have shifted in (the refill always happens within 8)
     const UReg scaled = s.range;
@@ -677,7 +743,11 @@ PC_DEV UReg decode_remaining_v(PS& s, UReg rice)
         const UReg bn2 = bn + len;
         const bool took = pc_any((int32_t)bn2 >= 0);
         UReg vl = s.value << len;
+#if HIPDEC_PARSE_LDS_WIN
+        if (took) { vl += byte << bn2; s.pos = p + 1u; s.vpos += 1u; s.vbyte = byte2; }
+#else
         if (took) { vl += byte << bn2; s.pos = p + 1u; }
+#endif
         s.value = vl - pc_mul24(q >> (8u - len), scaled);
         s.bits_needed = took ? bn2 - 8u : bn2;
         PC_COUNT(0);
@@ -686,8 +756,10 @@ PC_DEV UReg decode_remaining_v(PS& s, UReg rice)
       // codes of 9 .. 16 bins (escape codes of large levels: the first coefficients of a busy sub-block, before cRiceParam has grown): the next 8
       // bins are a second division of the first one's remainder extended by the byte after (both bytes only looked at)
       if (__builtin_expect(s.pos + 1u < s.fast_limit, 1)) {
+#if !HIPDEC_PARSE_LDS_WIN
         const uint32_t dw2 = pc_rdlane(s.win, (int)((p + 1u) >> 2));   // (the window register holds 256 bytes: p + 1 < fast_limit stays inside it)
         const UReg byte2 = ((UReg)dw2 >> ((pc_vec(p + 1u) & 3u) << 3)) & 255u;
+#endif
         const UReg r8 = v8 - pc_mul24(q, scaled);                      // remainder after the first 8 bins (bits_needed is back at bn)
         const UReg v16 = (r8 << 8) + (byte2 << (bn + 8u));
         UReg q2 = (UReg)((float)v16 * pc_rcp((float)scaled));
@@ -709,6 +781,9 @@ PC_DEV UReg decode_remaining_v(PS& s, UReg rice)
             UReg vl = r8 << m;
             if (took2) vl += byte2 << bn3;
             s.pos = p + (took2 ? 2u : 1u);
+#if HIPDEC_PARSE_LDS_WIN
+            if (took2) { s.vpos += 2u; s.vbyte = win_byte(s, s.vpos); } else { s.vpos += 1u; s.vbyte = byte2; }
+#endif
             s.value = vl - pc_mul24(q2 >> (8u - m), scaled);
             s.bits_needed = took2 ? bn3 - 8u : bn3;
             PC_COUNT(1);
@@ -733,8 +808,8 @@ PC_DEV void scan_sb(PS& s, int lg, int scan_idx, int i, int& xs, int& ys)
   else { const uint32_t v = (pc_rdlane(s.t_next, i) >> 8) & 63u; xs = (int)(v & 7u); ys = (int)(v >> 3); }
 }
 
-// returns transform_skip_flag; coefficients go to L->coef (raster, n x n)
-PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
+// returns transform_skip_flag; the block's n x n levels go to dst (raster): all of them are written, the zeros too
+PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode, int16_t* dst)
 {
   const int n = 1 << log2n;
   int ts = 0;
@@ -754,7 +829,7 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
     else if (pred_mode >= 22 && pred_mode <= 30) scan_idx = 1;
   }
   if (scan_idx == 2) { const int t = last_x; last_x = last_y; last_y = t; }
-  if (last_x >= n || last_y >= n) { s.err = DEV_ERR_SYNTAX; return ts; }
+  if (last_x >= n || last_y >= n) { s.err = DEV_ERR_SYNTAX; zero_uncoded_sub_blocks(dst, log2n, 0); return ts; }
   const uint64_t scan4 = scan_idx == 0 ? PC_DIAG4 : (scan_idx == 1 ? PC_HORZ4 : PC_VERT4);
 
   // locate the last position in scan order — sub-block (last_x >> 2, last_y >> 2), position inside it — through the inverse scans
@@ -821,7 +896,6 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
       PC_GLUE(coded ? 17 : 16); if (nb & 2u) PC_GLUE(18); if (nb & 0x100u) PC_GLUE(19); if (!nb) PC_GLUE(20);
     } else coded = 1;
     if (!coded) continue;
-    csbf |= 1ull << pos;
     const uint32_t pat = log2n == 2 ? 0u : (nb == 0u ? PC_SIGPAT0 : (nb == 2u ? PC_SIGPAT1 : (nb == 0x100u ? PC_SIGPAT2 : PC_SIGPAT3)));
     const int sig_off = sig_base - (pos ? 0 : sig_dc);
     const int xs = pos, ys = 0;   // (only their union is looked at below)
@@ -836,7 +910,6 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
       PC_GLUE(coded ? 17 : 16); if (right) PC_GLUE(18); if (below) PC_GLUE(19); if (!(right | below)) PC_GLUE(20);
     } else coded = 1;
     if (!coded) continue;
-    csbf |= 1ull << (ys * 8 + xs);
     // per-sub-block sig_coeff_flag context selection: pattern word + constant offset
     uint32_t pat;
     int sig_off;
@@ -874,7 +947,14 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
       if (infer_dc && !sig) sig = 1u;
       else sig |= (uint32_t)decode_bin(s, s.ctxB, B_SIG_COEFF + (int)pc_rdlane(vctx, 0));
     }
+    // (only the DC sub-block can be parsed without a significant position - the others' is inferred -, and nothing looks at its own flag: the
+    //  bitmap is set behind this test and so says which sub-blocks are STORED below, which is what zero_uncoded_sub_blocks() needs)
     if (!sig) continue;
+#if HIPDEC_PARSE_LEAN_GLUE
+    csbf |= 1ull << pos;
+#else
+    csbf |= 1ull << (ys * 8 + xs);
+#endif
     // greater1 / greater2 flags
 #if HIPDEC_PARSE_LEAN_GLUE
     const int ctx_set = ((i == 0 || c_idx > 0) ? 0 : 2) + g1_zero;
@@ -972,12 +1052,13 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode)
       // a level outside -32768 .. 32767 (a > 32768, or 32768 without the sign): the largest a - neg of the block is looked at ONCE, behind the last
       // sub-block (a ballot per sub-block was 0.4 wave-instructions per pixel)
       { const uint32_t m = a ? a - neg : 0u; PC_L(vovf) = m > PC_L(vovf) ? m : PC_L(vovf); }   // (lanes 16 .. 63 hold a = 0)
-      if (lane < 16 && a) {
+      if (lane < 16) {   // all 16 positions: a is 0 where the position is not significant
         const uint32_t r = (uint32_t)(scan4 >> (k * 4)) & 15u;
-        s.L->coef[sb_base + (int)(r >> 2) * n + (int)(r & 3u)] = (int16_t)(neg ? -(int32_t)a : (int32_t)a);
+        dst[(uint32_t)sb_base + ((r >> 2) << log2n) + (r & 3u)] = (int16_t)(neg ? -(int32_t)a : (int32_t)a);
       }
     PC_VEC_END
   }
+  zero_uncoded_sub_blocks(dst, log2n, csbf);
   {
     VReg vbad;
     PC_VEC_BEGIN PC_L(vbad) = PC_L(vovf) > 32767u ? 1u : 0u; PC_VEC_END
@@ -1062,13 +1143,13 @@ PC_DEV void pcm_coding_unit(PS& s, int zb, int log2cb, int16_t* coef_y, int16_t*
     const int c = cfi == 2 ? (k + 1) >> 1 : k, t = cfi == 2 ? ((k + 1) & 1) : 0;   // 4:2:2: k = 0 luma, 1 / 2 Cb upper / lower, 3 / 4 Cr
     const int lg = (c && cfi != 3) ? log2cb - 1 : log2cb, n2 = 1 << (2 * lg);
     const int depth = (int)((s.pcm >> (c ? 16 : 8)) & 255u), shift = (c ? s.bit_depth_chroma : s.bit_depth_luma) - depth;
+    int16_t* const dst = c == 0 ? coef_y + zb * 16 : (c == 1 ? coef_cb : coef_cr) + zb * (cfi == 3 ? 16 : (cfi == 2 ? 8 : 4)) + t * n2;   // (t only counts for chroma)
     for (int i = 0; i < n2; i++) {
       while (nacc < depth) { acc = (acc << 8) | read_byte(s); nacc += 8; }
       const uint32_t v = (acc >> (nacc - depth)) & ((1u << depth) - 1u);
       nacc -= depth;
-      PC_VEC_BEGIN if (lane == 0) s.L->coef[i] = (int16_t)(v << shift); PC_VEC_END
+      PC_VEC_BEGIN if (lane == 0) dst[i] = (int16_t)(v << shift); PC_VEC_END
     }
-    flush_coef(s, c == 0 ? coef_y + zb * 16 : (c == 1 ? coef_cb : coef_cr) + zb * (cfi == 3 ? 16 : (cfi == 2 ? 8 : 4)) + t * n2, n2);
   }
   cabac_restart(s);
   fill_tu_maps(s, zb, n_units, (uint32_t)(UF_PCM | (s.cu_tq_bypass ? UF_BYPASS : 0)), 1u, (uint32_t)((log2cb << 4) | log2cb));
@@ -1280,8 +1361,7 @@ PC_DEV void inter_coding_unit(PS& s, int zb, int log2cb, int cu_skip, int16_t* c
         const int c = c422 ? (k == 0 ? 0 : 1 + ((k - 1) & 1)) : k, low = c422 && k >= 3;
         const int lg = c == 0 ? t : tc;
         int16_t* dst = c == 0 ? coef_y + zu * 16 : (c == 1 ? coef_cb : coef_cr) + zc * c_mult + (low << (2 * lg));
-        ts_bits |= (uint32_t)residual_coding(s, lg, c, 1 /* not intra: the up-right diagonal scan */) << k;
-        flush_coef(s, dst, 1 << (2 * lg));
+        ts_bits |= (uint32_t)residual_coding(s, lg, c, 1 /* not intra: the up-right diagonal scan */, dst) << k;
       }
       fill_tu_maps(s, zu, tu_units,
                    (uint32_t)((cbf_luma ? UF_CBF_LUMA : 0) | ((do_chroma && cbf_cb) ? UF_CBF_CB : 0) | ((do_chroma && cbf_cr) ? UF_CBF_CR : 0) | bypass |
@@ -1478,13 +1558,9 @@ PC_DEV void coding_unit(PS& s, int zb /*unit z-index of the CU inside the CTB*/,
 #ifdef HIPDEC_PARSE_CYCLES
       const unsigned long long pc_t0 = __builtin_readcyclecounter();
 #endif
-      ts_bits |= (uint32_t)residual_coding(s, lg, c, c == 0 ? luma_mode : chroma_mode) << k;
+      ts_bits |= (uint32_t)residual_coding(s, lg, c, c == 0 ? luma_mode : chroma_mode, dst) << k;
 #ifdef HIPDEC_PARSE_CYCLES
-      const unsigned long long pc_t1 = __builtin_readcyclecounter();
-#endif
-      flush_coef(s, dst, 1 << (2 * lg));
-#ifdef HIPDEC_PARSE_CYCLES
-      { const unsigned long long pc_t2 = __builtin_readcyclecounter(); s.c_resid += pc_t1 - pc_t0; s.c_flush += pc_t2 - pc_t1; s.n_resid++; }
+      { const unsigned long long pc_t1 = __builtin_readcyclecounter(); s.c_resid += pc_t1 - pc_t0; s.n_resid++; }
 #endif
     }
     const int ts_y = (int)(ts_bits & 1u), ts_cb = (int)((ts_bits >> 1) & 1u), ts_cr = (int)((ts_bits >> 2) & 1u);
@@ -2084,8 +2160,8 @@ PC_DEV int parse_substream(const ParseArgs& A, uint32_t sub_idx, int same_wave_d
   }
 #if defined(HIPDEC_PARSE_CYCLES) && !defined(HIPDEC_HOST_EMU)
   if (threadIdx.x == 0 && sub_pic == 0)
-    printf("cyc sub %u ctbs %u total %llu wait %llu cu %llu resid %llu flush %llu nresid %u\n", sub_idx, num_ctbs, __builtin_readcyclecounter() - pc_row0, s.c_wait, s.c_cu, s.c_resid,
-           s.c_flush, s.n_resid);
+    printf("cyc sub %u ctbs %u total %llu wait %llu cu %llu resid %llu nresid %u\n", sub_idx, num_ctbs, __builtin_readcyclecounter() - pc_row0, s.c_wait, s.c_cu, s.c_resid,
+           s.n_resid);   // (resid includes the level stores and the zero fill: there is no separate flush any more)
 #endif
   if (s.err) pc_report(A.status, s.err | (int32_t)(sub_idx << 8));
   return s.err;

@@ -18,8 +18,6 @@ namespace hipdec {
     uint32_t t = 0;                                                                                       \
     if (lane == 0) t = atomicAdd(A.ticket, 1u);                                                           \
     const uint32_t wave_idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);                           \
-    for (int i = lane * 8; i < 32 * 32; i += 512) *(uint4*)&lds.coef[i] = make_uint4(0, 0, 0, 0);         \
-    __syncthreads();                                                                                      \
     if (wave_idx >= A.num_waves) return;                                                                  \
     pcore::parse_wave(A, wave_idx, &lds);                                                                 \
 

@@ -21,8 +21,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HIPDEC_TP_OC
   uint32_t t = 0;
   if (lane == 0) t = atomicAdd(A.ticket, 1u);
   const uint32_t wave_idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-  for (int i = lane * 8; i < 32 * 32; i += 512) *(uint4*)&lds.coef[i] = make_uint4(0, 0, 0, 0);
-  __syncthreads();
   if (wave_idx >= A.num_waves) return;
   // the hand-scheduled statements address Lds by byte offsets from LDS address 0: it is the kernel's only __shared__ object
   if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) pcore::Lds*)&lds != 0u) { pcore::pc_report(A.status, DEV_ERR_SYNTAX | (int32_t)0x40000000); return; }

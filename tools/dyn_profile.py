@@ -141,7 +141,8 @@ if os.environ.get("BY_ELEMENT"):
                ("residual_coding", r"VReg vbad;", "overflow check"),
                ("coding_unit", r"^PC_DEV void coding_unit", "coding_unit"),
                ("coding_unit", r"// ---- transform tree ----", "transform-tree glue (cbf, split, destination, map arguments)")]
-    FUNCS = {"scan_sb": "sub-block loop control and csbf", "flush_coef": "level assembly and store",
+    FUNCS = {"scan_sb": "sub-block loop control and csbf", "zero_uncoded_sub_blocks": "level assembly and store",
+             "win_byte": "byte reading", "win_prime": "byte reading", "win_advance": "byte reading",
              "fill_tu_maps": "transform-tree glue (cbf, split, destination, map arguments)", "parse_cu_qp_delta": "coding_unit", "derive_qp_pred": "coding_unit",
              "set_qp_y": "coding_unit", "left_cb_log2": "coding_unit", "up_cb_log2": "coding_unit",
              "read_byte_v": "byte reading", "read_byte": "byte reading", "refill_byte": "byte reading", "load_window": "byte reading", "fetch_byte": "byte reading",
