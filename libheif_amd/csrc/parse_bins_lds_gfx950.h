@@ -89,12 +89,13 @@
 #define PC_LDS_OFFSETS [tlps] "i"(__builtin_offsetof(Lds, tlps)), [tnext] "i"(__builtin_offsetof(Lds, tnext)), [vctx] "i"(__builtin_offsetof(Lds, vctx))
 PC_DEV uint32_t pc_lds_ctx_addr(CtxGroup grp, int lane) { return (uint32_t)__builtin_offsetof(Lds, ctx) + 4u * (uint32_t)(grp.base + lane); }
 
-PC_DEV int decode_bin(PS& s, CtxRef grp, int ctx_lane)
+// one context-coded bin; va: the LDS byte address of its context variable, wave-uniform (a literal for most call sites - the compiler materialises it
+// with one move - or a vector value read from a table)
+PC_DEV int decode_bin_at(PS& s, uint32_t va)
 {
   uint32_t r, flag;
   [[maybe_unused]] uint32_t st, row;
   uint32_t vst, vrow, vt, vl, vn, vr, vb;
-  const uint32_t va = pc_lds_ctx_addr(grp, ctx_lane);   // (a literal for most call sites: the compiler materialises it with one move)
   uint32_t pos = pc_uni(s.pos);
   const uint32_t flim = pc_uni(s.fast_limit);
   asm volatile(
@@ -128,15 +129,23 @@ PC_DEV int decode_bin(PS& s, CtxRef grp, int ctx_lane)
   if (__builtin_expect(pc_uni(flag) != 0u, 0)) refill_byte(s);
   return (int)pc_uni(r);
 }
+PC_DEV int decode_bin(PS& s, CtxRef grp, int ctx_lane) { return decode_bin_at(s, pc_lds_ctx_addr(grp, ctx_lane)); }
 
 // sig_coeff_flag of the scan positions n_start .. 1 of one sub-block (bit k of the result = position k).  The context variables' addresses of the 16
-// positions are in Lds::vctx (residual_coding stores them beside computing vctx); the run reads the next position's address while it decodes the
-// current one and collects the bins in a vector register: ONE crossing to the scalar side per run.
+// positions are in Lds::vctx (residual_coding stores them beside computing vctx) or, with HIPDEC_PARSE_TU_TABLES, in a row of 16-bit addresses whose
+// own LDS byte address the caller gives (a row of Lds::sigrow); the run reads the next position's address while it decodes the current one and
+// collects the bins in a vector register: ONE crossing to the scalar side per run.
+#if HIPDEC_PARSE_TU_TABLES
+#define PC_LDS_SIG_ROW_IN [srow] "s"(srow),
+#define PC_LDS_SIG_NEXT(CB) "v_add_u32 %[vj], -2, %[vj]\n\tds_read_u16 %[" CB "], %[vj]\n\t"
+#else
+#define PC_LDS_SIG_ROW_IN
+#define PC_LDS_SIG_NEXT(CB) "v_add_u32 %[vj], -4, %[vj]\n\tds_read_b32 %[" CB "], %[vj] offset:%c[vctx]\n\t"
+#endif
 #define PC_LDS_SIG_ITER(P, CA, CB, NEXT)                                                                                           \
   "1" P "0:\n\t"                                                                                                                    \
   "ds_read_b32 %[vst], %[" CA "]\n\t"                                                                                               \
-  "v_add_u32 %[vj], -4, %[vj]\n\t"                                                                                                  \
-  "ds_read_b32 %[" CB "], %[vj] offset:%c[vctx]\n\t"                                                                                \
+  PC_LDS_SIG_NEXT(CB)                                                                                                               \
   PC_LDS_HEAD_Q                                                                                                                     \
   "s_waitcnt lgkmcnt(1)\n\t"                                                                                                        \
   PC_LDS_CORE("1" P "1f")                                                                                                           \
@@ -164,9 +173,15 @@ PC_DEV int decode_bin(PS& s, CtxRef grp, int ctx_lane)
   "s_mov_b32 %[flag], 1\n\t"                                                                                                        \
   "s_branch 190f\n"
 
+#if HIPDEC_PARSE_TU_TABLES
+PC_DEV uint32_t decode_sig_run_row(PS& s, uint32_t row_addr, int n_start)
+{
+  const uint32_t srow = pc_uni(row_addr);
+#else
 PC_DEV uint32_t decode_sig_run(PS& s, const VReg& vctx, int n_start)
 {
   (void)vctx;
+#endif
   uint32_t vacc = 0;
   asm volatile("v_mov_b32 %0, 0" : "=v"(vacc));
   int32_t j = __builtin_amdgcn_readfirstlane(n_start - 1);   // the position after the current one; the run ends when it leaves 0 .. 15
@@ -177,11 +192,18 @@ PC_DEV uint32_t decode_sig_run(PS& s, const VReg& vctx, int n_start)
     uint32_t pos = pc_uni(s.pos);
     const uint32_t flim = pc_uni(s.fast_limit);
     asm volatile(
+#if HIPDEC_PARSE_TU_TABLES
+      "s_lshl1_add_u32 %[t], %[j], %[srow]\n\t"
+      "s_mov_b32 %[flag], 0\n\t"
+      "v_add_u32_e64 %[vj], %[t], 2\n\t"                        // LDS byte address of the current position's entry in the row
+      "ds_read_u16 %[vca], %[vj]\n\t"
+#else
       "s_lshl_b32 %[t], %[j], 2\n\t"
       "s_add_u32 %[t], %[t], 4\n\t"
       "s_mov_b32 %[flag], 0\n\t"
       "v_mov_b32 %[vj], %[t]\n\t"                               // byte offset of the current position inside vctx
       "ds_read_b32 %[vca], %[vj] offset:%c[vctx]\n\t"
+#endif
       "s_waitcnt lgkmcnt(0)\n\t"
       PC_LDS_SIG_ITER("0", "vca", "vcb", "110f")
       PC_LDS_SIG_ITER("1", "vcb", "vca", "100b")
@@ -191,7 +213,7 @@ PC_DEV uint32_t decode_sig_run(PS& s, const VReg& vctx, int n_start)
         [flag] "=&s"(flag), PC_LDS_WIN_TEMPS(st, row) [t] "=&s"(t),
         [vst] "=&v"(vst), [vrow] "=&v"(vrow), [vt] "=&v"(vt), [vl] "=&v"(vl), [vn] "=&v"(vn), [vr] "=&v"(vr), [vb] "=&v"(vb),
         [vca] "=&v"(vca), [vcb] "=&v"(vcb), [vj] "=&v"(vj)
-      : PC_LDS_WIN_IN(s), [flim] "s"(flim), [m128] "v"(0xffffff80u), PC_LDS_OFFSETS
+      : PC_LDS_SIG_ROW_IN PC_LDS_WIN_IN(s), [flim] "s"(flim), [m128] "v"(0xffffff80u), PC_LDS_OFFSETS
       : "vcc", "scc", "memory");
     s.pos = pc_uni(pos);
     if (__builtin_expect(__builtin_amdgcn_readfirstlane((int)flag) != 0, 0)) refill_byte(s);

@@ -126,6 +126,18 @@ PC_DEV uint32_t pc_mul24(uint32_t a, uint32_t b) { return __umul24(a, b); }     
 #ifndef HIPDEC_PARSE_LEAN_GLUE
 #define HIPDEC_PARSE_LEAN_GLUE HIPDEC_PARSE_LDS_CTX   // 1: residual_coding's glue between the bins in its shorter form (see "lean glue" in residual_coding)
 #endif
+#ifndef HIPDEC_PARSE_TU_TABLES
+#define HIPDEC_PARSE_TU_TABLES HIPDEC_PARSE_LDS_CTX   // 1: residual_coding takes what only depends on the block's kind from tables (see "TU tables" in residual_coding)
+#endif
+#if HIPDEC_PARSE_TU_TABLES && !(HIPDEC_PARSE_LDS_CTX && HIPDEC_PARSE_LEAN_GLUE)
+#error "HIPDEC_PARSE_TU_TABLES: the sig-context rows live in LDS beside the context variables, and the row arithmetic is the lean glue's"
+#endif
+#ifndef HIPDEC_PARSE_TU_DESC
+#define HIPDEC_PARSE_TU_DESC HIPDEC_PARSE_TU_TABLES   // (the second step of the TU tables, apart for measurements: the per-block descriptor and the sub-block scans)
+#endif
+#if HIPDEC_PARSE_TU_DESC && !HIPDEC_PARSE_TU_TABLES
+#error "HIPDEC_PARSE_TU_DESC: the descriptor holds addresses of the sig-context rows"
+#endif
 #ifndef HIPDEC_PARSE_INTER
 #define HIPDEC_PARSE_INTER 0            // 1: the build that also parses P slices (sequence tracks; parse_kernel_inter.hip, the CPU emulation)
 #endif
@@ -133,6 +145,7 @@ PC_DEV uint32_t pc_mul24(uint32_t a, uint32_t b) { return __umul24(a, b); }     
 namespace hipdec {
 namespace pcore {
 
+#define PC_SIG_ROWS (HIPDEC_PARSE_CHROMA_GENERAL ? PC_SIG_ROWS_ALL : PC_SIG_ROWS_420)
 struct Lds {
   alignas(16) uint32_t park[SAVE_DWORDS];   // staging image of a parked row's record (save_row_state / load_row_state)
 #if HIPDEC_PARSE_LDS_CTX
@@ -164,7 +177,30 @@ struct Lds {
   // upper half, and decode_remaining_v's look at the byte after, read (and never use) index 512 / 513.
   uint32_t wwin[128 + 2];
 #endif
+#if HIPDEC_PARSE_TU_TABLES
+  // TU tables: the sig_coeff_flag context rows of parse_tables.h (pc_make_sig_rows), copied once per wave (load_tu_tables): 46 rows of 16 LDS byte
+  // addresses, 16 bits each, for the 4:0:0 / 4:2:0 build - 3536 + 1472 = 5008 B of the 5120 -, 54 where 4:4:4 pictures are parsed (the host
+  // emulation).  Constants: no task writes them, so a row resumed on another wave, or behind other tasks on this one, finds them as they were.
+  // Lds::vctx above is no longer written by the parser: it stays as the scratch row of decode_sig_run's form with run-time contexts.
+  uint16_t sigrow[PC_SIG_ROWS * 16];
+#endif
+#if HIPDEC_PARSE_TU_DESC
+  uint8_t sbscan[PC_SBSCAN_BYTES];    // the sub-block scans of parse_tables.h (pc_make_sbscan), 92 B: 5100 B in all
+#endif
 };
+#if HIPDEC_PARSE_LDS_CTX
+#define PC_LDS_CTX_B_ADDR ((uint32_t)__builtin_offsetof(Lds, ctx) + 4u * (64u + (uint32_t)B_SIG_COEFF))   /* LDS byte address of context variable B_SIG_COEFF + 0 */
+#endif
+#if HIPDEC_PARSE_TU_TABLES
+static_assert(pc_sig_rows_match(PC_LDS_CTX_B_ADDR), "sig_coeff_flag context rows against 9.3.4.2.5 as residual_coding derived it");
+static_assert(__builtin_offsetof(Lds, sigrow) % 4 == 0 && sizeof(Lds) < 65536, "sig rows are copied by dwords and hold 16-bit LDS addresses");
+PC_CONST SigRowTable c_sig_rows = pc_make_sig_rows(PC_LDS_CTX_B_ADDR);
+#endif
+#if HIPDEC_PARSE_TU_DESC
+static_assert(sizeof(Lds) < (1u << 13) && __builtin_offsetof(Lds, sbscan) % 4 == 0, "the descriptor holds 13-bit LDS addresses; the scans are copied by dwords");
+PC_CONST TuDescTable c_tu_desc = pc_make_tu_desc((uint32_t)__builtin_offsetof(Lds, sigrow));
+PC_CONST SbScanTable c_sbscan = pc_make_sbscan();
+#endif
 #if HIPDEC_PARSE_LDS_MAPS
 struct UMap { int base; };             // a unit map is a byte range of Lds::umap ...
 typedef UMap MapRef;
@@ -240,6 +276,17 @@ struct PS {
 #endif
 };
 enum : uint32_t { TOOL_SDH = 1, TOOL_TS = 2, TOOL_CUQPD = 4, TOOL_TQBYPASS = 8 };
+#if HIPDEC_PARSE_LDS_CTX
+static_assert(PS::ctxB.base == 64, "PC_LDS_CTX_B_ADDR");
+#endif
+#if HIPDEC_PARSE_TU_TABLES
+// the 16-bit word at LDS byte address `addr` as a wave-uniform vector value (a broadcast read; the compiler places its wait where the value is used)
+PC_DEV UReg pc_lds_u16(PS& s, uint32_t addr) { return *(const uint16_t*)((const uint8_t*)s.L + addr); }
+PC_DEV UReg pc_lds_u8(PS& s, uint32_t addr) { return *((const uint8_t*)s.L + addr); }
+// LDS byte address of a sub-block's sig-context row: the block's first row (rows) or the first of its DC sub-block (rows_dc; pos = ys * 8 + xs of the
+// sub-block), one row up with the right neighbour coded (nb bit 1), two with the lower one (nb bit 8)
+PC_DEV uint32_t tu_sig_row(uint32_t rows, uint32_t rows_dc, uint32_t nb, int pos) { return (pos ? rows : rows_dc) + (((nb << 4) | (nb >> 2)) & 96u); }
+#endif
 
 PC_DEV uint32_t interleave4(uint32_t x, uint32_t y)  // z-index of unit (x,y), x,y < 16
 {
@@ -442,9 +489,10 @@ PC_DEV void refill_byte(PS& s) { s.value += read_byte_v(s) << s.bits_needed; s.b
 #if HIPDEC_PARSE_LDS_CTX
 // the C++ form over the LDS-resident contexts (host emulation of this build, -DHIPDEC_PARSE_CXX_BINS on the device): same arithmetic as below with
 // the variable's low half scaled by four
-PC_DEV int decode_bin_cxx(PS& s, CtxRef grp, int ctx_lane)
+// (the context variable is named by its LDS byte address, as in the hand-scheduled statements)
+PC_DEV int decode_bin_cxx_at(PS& s, uint32_t ctx_addr)
 {
-  uint32_t* const cv = &s.L->ctx[grp.base + ctx_lane];
+  uint32_t* const cv = (uint32_t*)((uint8_t*)s.L + ctx_addr);
   const uint32_t st = pc_uni(*cv);
   const uint32_t row = pc_uni(s.L->tlps[(st & 0xfcu) >> 2]);
   const UReg lps = (row >> ((s.range >> 10) & 24u)) & 255u;
@@ -471,6 +519,7 @@ PC_DEV int decode_bin_cxx(PS& s, CtxRef grp, int ctx_lane)
   if (__builtin_expect(pc_any((int32_t)s.bits_needed >= 0), 0)) refill_byte(s);
   return bin;
 }
+PC_DEV int decode_bin_cxx(PS& s, CtxRef grp, int ctx_lane) { return decode_bin_cxx_at(s, (uint32_t)__builtin_offsetof(Lds, ctx) + 4u * (uint32_t)(grp.base + ctx_lane)); }
 #else
 PC_DEV int decode_bin_cxx(PS& s, VReg& grp, int ctx_lane)
 {
@@ -532,12 +581,36 @@ PC_DEV uint32_t decode_g1_run(PS& s, int base_lane, int n, int& g)
   }
   return gb;
 }
+#if HIPDEC_PARSE_LDS_CTX
+PC_DEV int decode_bin_at(PS& s, UReg ctx_addr) { return decode_bin_cxx_at(s, pc_uni(ctx_addr)); }
+#endif
+#if HIPDEC_PARSE_TU_TABLES
+PC_DEV uint32_t decode_sig_run_row(PS& s, uint32_t row, int n_start)
+{
+  uint32_t sig = 0;
+  int k = n_start;
+  do sig |= (uint32_t)decode_bin_at(s, pc_uni(*(const uint16_t*)((const uint8_t*)s.L + row + 2u * (uint32_t)k))) << k; while (--k > 0);
+  return sig;
+}
+#else
 PC_DEV uint32_t decode_sig_run(PS& s, const VReg& vctx, int n_start)
 {
   uint32_t sig = 0;
   int k = n_start;
   do sig |= (uint32_t)decode_bin(s, s.ctxB, (int)pc_rdlane(vctx, k)) << k; while (--k > 0);
   return sig;
+}
+#endif
+#endif
+#if HIPDEC_PARSE_TU_TABLES
+// the run over contexts that are only known at run time, one per lane of vctx (the test probe of the arithmetic decoder): their addresses go to
+// the scratch row Lds::vctx, and the run reads that row as it reads a row of the table
+PC_DEV uint32_t decode_sig_run(PS& s, const VReg& vctx, int n_start)
+{
+  PC_LDS_SYNC();
+  PC_VEC_BEGIN if (lane < 16) ((uint16_t*)s.L->vctx)[lane] = (uint16_t)(PC_LDS_CTX_B_ADDR + 4u * PC_L(vctx)); PC_VEC_END
+  PC_LDS_SYNC();
+  return decode_sig_run_row(s, (uint32_t)__builtin_offsetof(Lds, vctx), n_start);
 }
 #endif
 
@@ -644,6 +717,22 @@ PC_DEV void load_tables(PS& s)
     PC_VEC_BEGIN PC_L(s.t_next) |= PC_L(inv) << 24; PC_VEC_END
   }
 }
+
+#if HIPDEC_PARSE_TU_TABLES
+// the sig_coeff_flag context rows into LDS, dword by dword (parse_wave: once per wave)
+PC_DEV void load_tu_tables(Lds* L)
+{
+  const uint32_t* const src = (const uint32_t*)c_sig_rows.a;
+  uint32_t* const dst = (uint32_t*)L->sigrow;
+  PC_VEC_BEGIN
+    for (int k = lane; k < PC_SIG_ROWS * 8; k += 64) dst[k] = src[k];
+#if HIPDEC_PARSE_TU_DESC
+    if (lane < PC_SBSCAN_BYTES / 4) ((uint32_t*)L->sbscan)[lane] = ((const uint32_t*)c_sbscan.a)[lane];
+#endif
+  PC_VEC_END
+  PC_LDS_SYNC();
+}
+#endif
 
 // ---- neighbour helpers over the z-ordered maps ---------------------------------------------------
 // log2 CB size of the unit left of / above unit (ux, uy) of the current CTB, or 0 if unavailable
@@ -808,29 +897,63 @@ PC_DEV void scan_sb(PS& s, int lg, int scan_idx, int i, int& xs, int& ys)
   else { const uint32_t v = (pc_rdlane(s.t_next, i) >> 8) & 63u; xs = (int)(v & 7u); ys = (int)(v >> 3); }
 }
 
+// 7.4.9.11: scanIdx from the intra prediction mode, for 4x4 and 8x8 luma blocks, 4x4 chroma blocks and (ChromaArrayType 3) 8x8 chroma blocks
+PC_DEV int tu_scan_idx(PS& s, int log2n, int c_idx, int pred_mode)
+{
+  int scan_idx = 0;
+  if (log2n == 2 || (log2n == 3 && (c_idx == 0 || pc_is444(s)))) {
+    if (pred_mode >= 6 && pred_mode <= 14) scan_idx = 2;
+    else if (pred_mode >= 22 && pred_mode <= 30) scan_idx = 1;
+  }
+  return scan_idx;
+}
 // returns transform_skip_flag; the block's n x n levels go to dst (raster): all of them are written, the zeros too
 PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode, int16_t* dst)
 {
   const int n = 1 << log2n;
   int ts = 0;
+#if HIPDEC_PARSE_TU_DESC
+  // TU tables, the block's descriptor (parse_tables.h: pc_make_tu_desc): one 16-byte scalar load by the block's kind, issued in front of
+  // transform_skip_flag and the last-position prefixes, whose first wait covers it.  A scalar load and not a broadcast LDS read: the 384 B do not
+  // fit beside the sig-context rows below the 5120 B of LDS, a 16-byte row arrives in the SGPRs where its fields are used, and four dwords
+  // need no aligned tuple of eight.  Not in it: the inverse scans of the last position - as dwords 4 .. 7 they moved SGPR spills into the sub-block
+  // loop (profiles/parse_tu_tables.txt), so last_pos / last_sb are derived below as before and the inverse 8x8 scan keeps its half of PS::t_next -
+  // and the chroma offsets of the coded_sub_block_flag / greater1 / greater2 contexts, which are c_idx itself.
+  const int scan_idx_d = tu_scan_idx(s, log2n, c_idx, pred_mode);
+  typedef uint32_t u32x4 __attribute__((vector_size(16)));   // (one s_load_dwordx4)
+  const u32x4 desc = *(const u32x4*)c_tu_desc.w[(uint32_t)pc_tu_kind(log2n, c_idx, scan_idx_d)];
+  const uint32_t d0 = desc[0], d1 = desc[1], d2 = desc[2], d3 = desc[3];
+#endif
   if ((s.tools & TOOL_TS) && !s.cu_tq_bypass && log2n <= 2) ts = decode_bin(s, s.ctxA, A_TRANSFORM_SKIP + (c_idx ? 1 : 0));
+#if HIPDEC_PARSE_TU_DESC
+  const int ctx_offset = (int)(d1 & 31u), ctx_shift = (int)((d1 >> 5) & 3u), c_max = (int)((d1 >> 7) & 15u);
+#else
   int ctx_offset, ctx_shift;
   if (c_idx == 0) { ctx_offset = 3 * (log2n - 2) + ((log2n - 1) >> 2); ctx_shift = (log2n + 1) >> 2; }
   else { ctx_offset = 15; ctx_shift = log2n - 2; }
   const int c_max = (log2n << 1) - 1;
+#endif
   const int px = decode_unary_ctx_run(s, s.ctxA, A_LAST_X + ctx_offset, ctx_shift, c_max);
   const int py = decode_unary_ctx_run(s, s.ctxA, A_LAST_Y + ctx_offset, ctx_shift, c_max);
   int last_x = px, last_y = py;
   if (px > 3) last_x = (1 << ((px >> 1) - 1)) * (2 + (px & 1)) + decode_bypass_bits(s, (px >> 1) - 1);
   if (py > 3) last_y = (1 << ((py >> 1) - 1)) * (2 + (py & 1)) + decode_bypass_bits(s, (py >> 1) - 1);
+#if HIPDEC_PARSE_TU_DESC
+  const int scan_idx = scan_idx_d;
+#else
   int scan_idx = 0;
   if (log2n == 2 || (log2n == 3 && (c_idx == 0 || pc_is444(s)))) {   // 7.4.9.11: 8x8 chroma blocks too with ChromaArrayType 3
     if (pred_mode >= 6 && pred_mode <= 14) scan_idx = 2;
     else if (pred_mode >= 22 && pred_mode <= 30) scan_idx = 1;
   }
+#endif
   if (scan_idx == 2) { const int t = last_x; last_x = last_y; last_y = t; }
   if (last_x >= n || last_y >= n) { s.err = DEV_ERR_SYNTAX; zero_uncoded_sub_blocks(dst, log2n, 0); return ts; }
+#if HIPDEC_PARSE_TU_DESC
+  const uint64_t scan4 = (uint64_t)d2 | ((uint64_t)d3 << 32);
+#else
   const uint64_t scan4 = scan_idx == 0 ? PC_DIAG4 : (scan_idx == 1 ? PC_HORZ4 : PC_VERT4);
+#endif
 
   // locate the last position in scan order — sub-block (last_x >> 2, last_y >> 2), position inside it — through the inverse scans
   const int lg = log2n - 2;  // log2 of the sub-block grid width
@@ -860,6 +983,7 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode, int16_t* 
   // cu_transquant_bypass unit; 24 cu_qp_delta parsed; 26 a block with a level of 32767 and up that passes the range check; 27 / 28 4:2:2 / 4:4:4
   if (ts) PC_GLUE(0);
   PC_GLUE(c_idx ? 3 + log2n : log2n - 1);
+  if (c_idx && log2n == 4) PC_GLUE(15);   // chroma 16x16 (3 + log2n is counter 7 there)
   if (log2n <= 3) PC_GLUE((log2n == 2 ? 7 : 10) + scan_idx);
   if (lg > 0 && last_sb == 0) PC_GLUE(13);
   if (lg > 0 && last_sb == (1 << (2 * lg)) - 1) PC_GLUE(14);
@@ -871,8 +995,24 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode, int16_t* 
   // from ONE number per sub-block - its position ys * 8 + xs in the coded_sub_block_flag bitmap
   int g1_zero = 0;   // the previous sub-block with greater1 flags left greater1Ctx at 0 (9.3.4.2.6: its successor's ctxSet is one up)
   const int sdh = (s.tools & TOOL_SDH) != 0 && !s.cu_tq_bypass;
+#if HIPDEC_PARSE_TU_TABLES
+  // TU tables: the sig_coeff_flag contexts of a sub-block's 16 scan positions are a row of Lds::sigrow (parse_tables.h: which rows there are, and
+  // why so few) - the block's group here, the neighbours' flags and the DC step per sub-block -, read by the run where it read what the 64 lanes
+  // had computed and stored for every sub-block.  Position 0 of a DC sub-block has the component's first context: entry 0 of its 4x4 row.
+#if HIPDEC_PARSE_TU_DESC
+  const uint32_t sig_rows = d0 & 0xffffu, sig_rows_dc = d0 >> 16, sig_dc0 = d1 >> 18;
+  const uint32_t sb_scan = (uint32_t)__builtin_offsetof(Lds, sbscan) + ((d1 >> 11) & 127u);   // LDS byte address of the block's sub-block scan
+#else
+  const uint32_t sig_rows = (uint32_t)__builtin_offsetof(Lds, sigrow) + (uint32_t)PC_SIG_ROW_BYTES *
+      (uint32_t)(log2n == 2 ? (c_idx ? 3 : 0) + scan_idx
+                            : (c_idx == 0 ? (log2n == 3 ? 6 + 8 * scan_idx : 30) : (log2n == 3 ? ((HIPDEC_PARSE_CHROMA_GENERAL && scan_idx) ? 42 + 4 * scan_idx : 38) : 42)));
+  const uint32_t sig_rows_dc = sig_rows + ((c_idx == 0 && log2n > 2) ? (uint32_t)PC_SIG_DC_STEP : 0u);
+  const uint32_t sig_dc0 = (uint32_t)__builtin_offsetof(Lds, sigrow) + (c_idx ? 3u * PC_SIG_ROW_BYTES : 0u);
+#endif
+#else
   const int sig_dc = (c_idx == 0 && log2n > 2) ? 3 : 0;   // luma blocks above 4x4: the DC sub-block's contexts lie 3 below the others'
   const int sig_base = log2n == 2 ? (c_idx ? 27 : 0) : (c_idx == 0 ? 3 + (log2n == 3 ? (scan_idx == 0 ? 9 : 15) : 21) : 27 + (log2n == 3 ? 9 : 12));
+#endif
 #else
   int g1_carry = 1, first_sb_with_g1 = 1;
   const int sdh = (s.tools & TOOL_SDH) != 0;
@@ -883,10 +1023,14 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode, int16_t* 
     int infer_dc = 0, coded;
 #if HIPDEC_PARSE_LEAN_GLUE
     int pos;   // ys * 8 + xs (see scan_sb)
+#if HIPDEC_PARSE_TU_DESC
+    pos = (int)pc_uni(pc_lds_u8(s, sb_scan + (uint32_t)i));   // one path for every grid: a broadcast byte read of the block's scan
+#else
     if (lg == 3) pos = (int)((pc_rdlane(s.t_next, i) >> 8) & 63u);
     else if (lg == 2) { const uint32_t v = (uint32_t)(PC_DIAG4 >> (i * 4)) & 15u; pos = (int)((v & 3u) | ((v & 12u) << 1)); }
     else if (lg == 1) pos = scan_idx == 1 ? ((i & 1) | ((i & 2) << 2)) : ((i >> 1) | ((i & 1) << 3));
     else pos = 0;
+#endif
     // the flags of the right (bit 1) and lower (bit 8) neighbours with one 64-bit shift: rows and columns outside the block are never set, the
     // row below row 7 is shifted out, and only column 7's right neighbour would be the next row's column 0
     const uint32_t nb = (uint32_t)(csbf >> pos) & ((pos & 7) == 7 ? 0x100u : 0x102u);
@@ -896,9 +1040,15 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode, int16_t* 
       PC_GLUE(coded ? 17 : 16); if (nb & 2u) PC_GLUE(18); if (nb & 0x100u) PC_GLUE(19); if (!nb) PC_GLUE(20);
     } else coded = 1;
     if (!coded) continue;
+#if HIPDEC_PARSE_TU_TABLES
+    // (a 4x4 block's only sub-block has no neighbours: nb is 0 there)
+    const uint32_t sig_row = tu_sig_row(sig_rows, sig_rows_dc, nb, pos);
+    const UReg va0 = pc_lds_u16(s, pos ? sig_row : sig_dc0);   // position 0's context: issued here, waited for behind the run
+#else
     const uint32_t pat = log2n == 2 ? 0u : (nb == 0u ? PC_SIGPAT0 : (nb == 2u ? PC_SIGPAT1 : (nb == 0x100u ? PC_SIGPAT2 : PC_SIGPAT3)));
     const int sig_off = sig_base - (pos ? 0 : sig_dc);
     const int xs = pos, ys = 0;   // (only their union is looked at below)
+#endif
 #else
     int xs, ys;
     scan_sb(s, lg, scan_idx, i, xs, ys);
@@ -921,6 +1071,7 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode, int16_t* 
       else sig_off = 27 + ((log2n == 3) ? 9 : 12);
     }
 #endif
+#if !HIPDEC_PARSE_TU_TABLES
     // sig_coeff_flag contexts of the 16 scan positions, one per lane (vector), then the serial bin loop
     VReg vctx;
     {
@@ -937,15 +1088,24 @@ PC_DEV int residual_coding(PS& s, int log2n, int c_idx, int pred_mode, int16_t* 
 #endif
       PC_VEC_END
     }
+#endif
     uint32_t sig = 0;  // bit k = sig_coeff_flag at scan position k
     int n_start = 15;
     if (i == last_sb) { sig = 1u << last_pos; n_start = last_pos - 1; }
     if (n_start > 0) {
+#if HIPDEC_PARSE_TU_TABLES
+      sig |= decode_sig_run_row(s, sig_row, n_start);
+#else
       sig |= decode_sig_run(s, vctx, n_start);
+#endif
     }
     if (n_start >= 0) {   // position 0: inferred significant when the sub-block was signalled coded and nothing else is
       if (infer_dc && !sig) sig = 1u;
+#if HIPDEC_PARSE_TU_TABLES
+      else sig |= (uint32_t)decode_bin_at(s, va0);
+#else
       else sig |= (uint32_t)decode_bin(s, s.ctxB, B_SIG_COEFF + (int)pc_rdlane(vctx, 0));
+#endif
     }
     // (only the DC sub-block can be parsed without a significant position - the others' is inferred -, and nothing looks at its own flag: the
     //  bitmap is set behind this test and so says which sub-blocks are STORED below, which is what zero_uncoded_sub_blocks() needs)
@@ -1923,7 +2083,9 @@ PC_DEV int parse_substream(const ParseArgs& A, uint32_t sub_idx, int same_wave_d
     PC_L(s.p_left) = 0; PC_L(s.up) = 0; PC_L(s.sao) = 0; PC_L(s.sao_left) = 0;
 #if HIPDEC_PARSE_LDS_CTX
     for (int g = 0; g < 3; g++) s.L->ctx[g * 64 + lane] = 0;
+#if !HIPDEC_PARSE_TU_TABLES
     if (lane < 16) s.L->vctx[lane] = (uint32_t)__builtin_offsetof(Lds, ctx);
+#endif
 #else
     PC_L(s.ctxA) = 0; PC_L(s.ctxB) = 0; PC_L(s.ctxC) = 0;
 #endif
@@ -2193,6 +2355,9 @@ PC_DEV void parse_wave(const ParseArgs& A, uint32_t wave_idx, Lds* lds)
       }
     }
   }
+#if HIPDEC_PARSE_TU_TABLES
+  load_tu_tables(lds);   // once per wave, in front of its first task: constants of the standard, never written again
+#endif
 #if defined(HIPDEC_POOL_TRACE) && !defined(HIPDEC_HOST_EMU)
   unsigned long long tr_start = 0, tr_last = 0, tr_idle = 0, tr_tasks = 0, tr_busy = 0, tr_now0 = wall_clock64();
 #endif

@@ -130,5 +130,135 @@ constexpr uint32_t pc_sigpat(int prev_csbf)
 constexpr uint32_t PC_SIGPAT0 = pc_sigpat(0), PC_SIGPAT1 = pc_sigpat(1), PC_SIGPAT2 = pc_sigpat(2), PC_SIGPAT3 = pc_sigpat(3);
 static_assert(PC_SIGPAT0 == 0x00010516u && PC_SIGPAT1 == 0x000055AAu && PC_SIGPAT2 == 0x06060606u && PC_SIGPAT3 == 0xAAAAAAAAu, "sig patterns");
 
+// ---- sig_coeff_flag context rows (HIPDEC_PARSE_TU_TABLES) -----------------------------------------
+// sigCtx (9.3.4.2.5, before the B_SIG_COEFF base) of scan position k of a 4x4 sub-block, as residual_coding derives it per sub-block: the block's
+// log2 size, luma / chroma, scan index, the coded_sub_block_flag of the right / lower neighbour, "this is the block's DC sub-block"
+constexpr uint32_t pc_sig_ctx(int log2n, int c_idx, int scan_idx, int right, int below, int dc_sb, int k)
+{
+  const uint64_t scan4 = scan_idx == 0 ? PC_DIAG4 : (scan_idx == 1 ? PC_HORZ4 : PC_VERT4);
+  const uint32_t r = (uint32_t)(scan4 >> (k * 4)) & 15u;
+  if (log2n == 2) return (c_idx ? 27u : 0u) + (uint32_t)((PC_CTXIDXMAP4 >> (r * 4)) & 15u);
+  if (dc_sb && r == 0) return c_idx ? 27u : 0u;
+  const uint32_t pat = pc_sigpat(right | (below << 1));
+  const uint32_t off = c_idx == 0 ? (dc_sb ? 0u : 3u) + (log2n == 3 ? (scan_idx == 0 ? 9u : 15u) : 21u) : 27u + (log2n == 3 ? 9u : 12u);
+  return off + ((pat >> (r * 2)) & 3u);
+}
+// That value depends on less than its arguments: a 4x4 block has one sub-block without neighbours; luma 16x16 and 32x32 blocks share their contexts, and
+// so do chroma 16x16 and 32x32; above 8x8 only the diagonal scan occurs; a chroma block's DC sub-block differs from its others in position 0 alone,
+// which the parser takes from a constant.  What is left are PC_SIG_ROWS_420 = 46 rows of 16 positions for 4:0:0 / 4:2:0 pictures (8x8 chroma blocks
+// are scanned diagonally there, 7.4.9.11) and 8 more for the horizontal and vertical scan of 8x8 chroma blocks (ChromaArrayType 3):
+//   0 .. 5    4x4 blocks: 3 * chroma + scan index
+//   6 .. 29   luma 8x8: 6 + 8 * scan index + 4 * DC + right + 2 * below
+//   30 .. 37  luma 16x16 / 32x32: 30 + 4 * DC + right + 2 * below
+//   38 .. 41  chroma 8x8, diagonal: 38 + right + 2 * below           42 .. 45  chroma 16x16 / 32x32: 42 + right + 2 * below
+//   46 .. 53  chroma 8x8, horizontal / vertical: 46 + 4 * (scan index - 1) + right + 2 * below
+enum : int { PC_SIG_ROWS_420 = 46, PC_SIG_ROWS_ALL = 54, PC_SIG_ROW_BYTES = 32, PC_SIG_DC_STEP = 4 * PC_SIG_ROW_BYTES };
+// first row of a block's group (right = below = 0, not the DC sub-block) ...
+constexpr int pc_sig_row_group(int log2n, int c_idx, int scan_idx)
+{
+  if (log2n == 2) return (c_idx ? 3 : 0) + scan_idx;
+  if (c_idx == 0) return log2n == 3 ? 6 + 8 * scan_idx : 30;
+  return log2n == 3 ? (scan_idx == 0 ? 38 : 46 + 4 * (scan_idx - 1)) : 42;
+}
+// ... and the step to the rows of its DC sub-block, in bytes
+constexpr int pc_sig_dc_step(int log2n, int c_idx) { return (c_idx == 0 && log2n > 2) ? PC_SIG_DC_STEP : 0; }
+// the row's entries are what the sig_coeff_flag run reads instead of computing them: the LDS byte address of the context variable of every scan
+// position, 16 bits each.  ctx_b_addr: the LDS byte address of context variable B_SIG_COEFF + 0 (the including file knows its LDS layout)
+struct alignas(4) SigRowTable { uint16_t a[PC_SIG_ROWS_ALL * 16]; };
+constexpr SigRowTable pc_make_sig_rows(uint32_t ctx_b_addr)
+{
+  SigRowTable t = {};
+  for (int c_idx = 0; c_idx < 2; c_idx++)
+    for (int log2n = 2; log2n <= 5; log2n++)
+      for (int scan_idx = 0; scan_idx < (log2n <= 3 ? 3 : 1); scan_idx++)
+        for (int nbp = 0; nbp < (log2n == 2 ? 1 : 4); nbp++)
+          for (int dc = 0; dc < 2; dc++) {
+            if (dc && pc_sig_dc_step(log2n, c_idx) == 0 && log2n > 2) continue;   // (a chroma block's DC sub-block reads the rows of the others)
+            if (log2n == 2 && !dc) continue;                                      // (a 4x4 block's only sub-block is its DC sub-block)
+            const int row = pc_sig_row_group(log2n, c_idx, scan_idx) + nbp + (dc && log2n > 2 ? PC_SIG_DC_STEP / PC_SIG_ROW_BYTES : 0);
+            for (int k = 0; k < 16; k++) t.a[row * 16 + k] = (uint16_t)(ctx_b_addr + 4u * pc_sig_ctx(log2n, c_idx, scan_idx, nbp & 1, nbp >> 1, dc, k));
+          }
+  return t;
+}
+// the table against the per-sub-block derivation it replaces, by the row arithmetic the parser does at run time: group + 32 * right + 64 * below +
+// the DC step, position 0 of a DC sub-block from entry 0 of the component's 4x4 row
+constexpr bool pc_sig_rows_match(uint32_t ctx_b_addr)
+{
+  const SigRowTable t = pc_make_sig_rows(ctx_b_addr);
+  for (int c_idx = 0; c_idx < 2; c_idx++)
+    for (int log2n = 2; log2n <= 5; log2n++)
+      for (int scan_idx = 0; scan_idx < (log2n <= 3 ? 3 : 1); scan_idx++)
+        for (int nbp = 0; nbp < (log2n == 2 ? 1 : 4); nbp++)
+          for (int dc = (log2n == 2 ? 1 : 0); dc < 2; dc++) {
+            const int row_bytes = pc_sig_row_group(log2n, c_idx, scan_idx) * PC_SIG_ROW_BYTES + (nbp & 1) * 32 + (nbp >> 1) * 64 + (dc ? pc_sig_dc_step(log2n, c_idx) : 0);
+            if (row_bytes % PC_SIG_ROW_BYTES || row_bytes / PC_SIG_ROW_BYTES >= PC_SIG_ROWS_ALL) return false;
+            if (!(c_idx && log2n == 3 && scan_idx) && row_bytes / PC_SIG_ROW_BYTES >= PC_SIG_ROWS_420) return false;
+            for (int k = 0; k < 16; k++) {
+              const int at = (k == 0 && dc) ? pc_sig_row_group(2, c_idx, 0) * 16 : row_bytes / 2 + k;
+              if (t.a[at] != ctx_b_addr + 4u * pc_sig_ctx(log2n, c_idx, scan_idx, nbp & 1, nbp >> 1, dc, k)) return false;
+            }
+          }
+  return true;
+}
+
+
+// ---- transform-block descriptor and sub-block scans (HIPDEC_PARSE_TU_DESC) --------------------------
+// What residual_coding sets up per transform block is a function of the block's kind alone: log2 size, luma / chroma, scan index (7.4.9.11: 1 and 2
+// only occur up to 8x8; those kinds above are never looked up)
+enum : int { PC_TU_KINDS = 24 };
+constexpr int pc_tu_kind(int log2n, int c_idx, int scan_idx) { return ((c_idx ? 4 : 0) + log2n - 2) * 3 + scan_idx; }
+// 6.5.3: the up-right diagonal scan of an n x n array, entry k = x | y << shift of the k-th position
+struct DiagScan { uint8_t a[64]; };
+constexpr DiagScan pc_diag_scan(int n, int shift)
+{
+  DiagScan d = {};
+  int i = 0, x = 0, y = 0;
+  for (;;) {
+    while (y >= 0) { if (x < n && y < n) d.a[i++] = (uint8_t)(x | (y << shift)); y--; x++; }
+    y = x; x = 0;
+    if (i >= n * n) break;
+  }
+  return d;
+}
+static_assert(pc_diag_scan(4, 2).a[3] == ((PC_DIAG4 >> 12) & 15u) && pc_diag_scan(4, 2).a[9] == ((PC_DIAG4 >> 36) & 15u) && pc_diag_scan(4, 2).a[15] == 15, "6.5.3 against PC_DIAG4");
+// the scan of a block's sub-blocks as bytes ys << 3 | xs (the bit of the sub-block in the coded_sub_block_flag bitmap), one run per grid: 1x1; 2x2
+// diagonal (= vertical), 2x2 horizontal; 4x4 and 8x8 diagonal (blocks above 8x8 are scanned diagonally)
+enum : int { PC_SBSCAN_1 = 0, PC_SBSCAN_2D = 4, PC_SBSCAN_2H = 8, PC_SBSCAN_4 = 12, PC_SBSCAN_8 = 28, PC_SBSCAN_BYTES = 92 };
+struct alignas(4) SbScanTable { uint8_t a[PC_SBSCAN_BYTES]; };
+constexpr SbScanTable pc_make_sbscan()
+{
+  SbScanTable t = {};
+  for (int i = 0; i < 4; i++) { t.a[PC_SBSCAN_2D + i] = (uint8_t)((i >> 1) | ((i & 1) << 3)); t.a[PC_SBSCAN_2H + i] = (uint8_t)((i & 1) | ((i >> 1) << 3)); }
+  for (int i = 0; i < 16; i++) t.a[PC_SBSCAN_4 + i] = pc_diag_scan(4, 3).a[i];
+  for (int i = 0; i < 64; i++) t.a[PC_SBSCAN_8 + i] = pc_diag_scan(8, 3).a[i];
+  return t;
+}
+constexpr int pc_sbscan_of(int log2n, int scan_idx) { return log2n == 2 ? PC_SBSCAN_1 : (log2n == 3 ? (scan_idx == 1 ? PC_SBSCAN_2H : PC_SBSCAN_2D) : (log2n == 4 ? PC_SBSCAN_4 : PC_SBSCAN_8)); }
+// one descriptor per kind, four dwords:
+//   w0  15:0 LDS byte address of the block's first sig-context row, 31:16 of the first row of its DC sub-block
+//   w1  4:0 ctxOffset and 6:5 ctxShift of last_sig_coeff_x / y_prefix (9.3.4.2.3), 10:7 their cMax (2 * log2 size - 1), 17:11 the sub-block scan's
+//       offset in SbScanTable, 30:18 the LDS byte address of the row whose entry 0 is the context of position 0 of a DC sub-block
+//   w2, w3  the 4x4 scan inside a sub-block, nibble k = x | y << 2 of scan position k
+// sigrow_addr: the LDS byte address of row 0 of the sig-context rows
+struct alignas(16) TuDescTable { uint32_t w[PC_TU_KINDS][4]; };
+constexpr TuDescTable pc_make_tu_desc(uint32_t sigrow_addr)
+{
+  TuDescTable t = {};
+  for (int c_idx = 0; c_idx < 2; c_idx++)
+    for (int log2n = 2; log2n <= 5; log2n++)
+      for (int scan_idx = 0; scan_idx < (log2n <= 3 ? 3 : 1); scan_idx++) {
+        uint32_t* const w = t.w[pc_tu_kind(log2n, c_idx, scan_idx)];
+        const uint32_t rows = sigrow_addr + (uint32_t)(pc_sig_row_group(log2n, c_idx, scan_idx) * PC_SIG_ROW_BYTES);
+        w[0] = rows | ((rows + (uint32_t)pc_sig_dc_step(log2n, c_idx)) << 16);
+        const uint32_t ctx_offset = c_idx == 0 ? (uint32_t)(3 * (log2n - 2) + ((log2n - 1) >> 2)) : 15u;
+        const uint32_t ctx_shift = c_idx == 0 ? (uint32_t)((log2n + 1) >> 2) : (uint32_t)(log2n - 2);
+        const uint32_t dc0 = sigrow_addr + (uint32_t)(pc_sig_row_group(2, c_idx, 0) * PC_SIG_ROW_BYTES);
+        w[1] = ctx_offset | (ctx_shift << 5) | ((uint32_t)(2 * log2n - 1) << 7) | ((uint32_t)pc_sbscan_of(log2n, scan_idx) << 11) | (dc0 << 18);
+        const uint64_t scan4 = scan_idx == 0 ? PC_DIAG4 : (scan_idx == 1 ? PC_HORZ4 : PC_VERT4);
+        w[2] = (uint32_t)scan4; w[3] = (uint32_t)(scan4 >> 32);
+      }
+  return t;
+}
+
 }  // namespace pcore
 }  // namespace hipdec

@@ -132,7 +132,7 @@ if os.environ.get("BY_ELEMENT"):
     ANCHORS = [("residual_coding", r"^PC_DEV int residual_coding", "transform_skip, last_x / last_y prefix and suffix"),
                ("residual_coding", r"int scan_idx = 0;", "last-position lookup"),
                ("residual_coding", r"uint64_t csbf = 0;", "sub-block loop control and csbf"),
-               ("residual_coding", r"per-sub-block sig_coeff_flag context selection|const uint32_t pat = log2n == 2", "sig-context setup"),
+               ("residual_coding", r"per-sub-block sig_coeff_flag context selection|const uint32_t pat = log2n == 2|const uint32_t sig_row = ", "sig-context setup"),
                ("residual_coding", r"^#else", "sub-block loop control and csbf"),
                ("residual_coding", r"sig_coeff_flag contexts of the 16 scan positions", "sig-context setup"),
                ("residual_coding", r"// greater1 / greater2 flags", "greater1 / greater2 glue"),
@@ -142,6 +142,9 @@ if os.environ.get("BY_ELEMENT"):
                ("coding_unit", r"^PC_DEV void coding_unit", "coding_unit"),
                ("coding_unit", r"// ---- transform tree ----", "transform-tree glue (cbf, split, destination, map arguments)")]
     FUNCS = {"scan_sb": "sub-block loop control and csbf", "zero_uncoded_sub_blocks": "level assembly and store",
+             "pc_lds_u16": "sig-context setup", "tu_sig_row": "sig-context setup", "pc_lds_u8": "sub-block loop control and csbf",
+             "tu_scan_idx": "last-position lookup",
+             "load_tu_tables": "CTB loop, quadtree, SAO, publish",
              "win_byte": "byte reading", "win_prime": "byte reading", "win_advance": "byte reading",
              "fill_tu_maps": "transform-tree glue (cbf, split, destination, map arguments)", "parse_cu_qp_delta": "coding_unit", "derive_qp_pred": "coding_unit",
              "set_qp_y": "coding_unit", "left_cb_log2": "coding_unit", "up_cb_log2": "coding_unit",
