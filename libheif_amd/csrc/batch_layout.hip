@@ -357,7 +357,7 @@ int layout_core(BatchLayout& b, const size_t* sizes, std::string& err_out)
     P.off_u_ipm = off; off = align_up(off + nunits, 256);
     P.off_u_ipmc = off; off = align_up(off + nunits, 256);
     P.off_u_qp = off; off = align_up(off + nunits, 256);
-    // reconstruction plan (k_recon_plan): worst case one luma block per 4x4 unit and one chroma block per 8x8 luma area
+    // reconstruction plan (k_recon_plan): worst case one luma block per 4x4 unit and one chroma block per 8x8 luma area, 16 B each (5 % of the picture's arena)
     P.off_plan = P.off_plan_cnt = 0;
     if (!P.is_inter && P.chroma_format_idc < 2) {
       P.off_plan = off; off = align_up(off + (nunits + nunits / 4) * sizeof(PlanRecord), 256);

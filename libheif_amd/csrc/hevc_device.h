@@ -178,12 +178,20 @@ struct PicParams {
 //   w0: bits 0..3 / 4..7 the block's x / y inside the CTB in units of 4 component samples, 8..10 log2 of its size, 11 its reference samples are smoothed
 //       (8.4.4.2.3: luma blocks from 8x8 up, by mode), 12..16 NL, 17..21 NT, 22 the above region is available, 23 the above-left sample is, 24..31 the z index of
 //       the block's first 4x4 luma unit (a quad of 4x4 luma blocks: of the quad) - the residual sits at that index
-//   w1: bits 0..7 the intra mode of the component(s) (as the unit map carries it), 8..15 the u_flags byte of the unit the block's flags come from
+//   w1: bits 0..7 the intra mode of the component(s) (as the unit map carries it), 8..15 the u_flags byte of the unit the block's flags come from (the wave
+//       takes its plane's cbf | PCM bits out of it: the halves of the chroma pair differ there), and what k_recon_plan has worked out from w0 / the mode so
+//       that the wavefront does not: 16..27 the block's offset in its LDS tile ((y << log2 of the CTB size in component samples) + x, in samples), 28..30 its
+//       prediction class (PK_*), 31 some reference sample is missing (the substitution process 8.4.4.2.2 runs)
+//   w2, w3: low / high half of the availability mask of the first 64 reference samples in scan order (left column bottom-up, corner, top row): what
+//       plan_mask(V, n, 0) gives from the counts below; the chroma pair's lists keep the scan positions their lane passes cover (e < 32 below 16x16)
 //   Availability of the neighbouring samples (8.4.4.2.2, constrained intra prediction off) in units of 4 component samples: NL samples of the left
 //   column are available counted from the block's top edge downward (left, then below-left: 0 .. 2 * size / 4); NT samples of the top row counted
 //   rightward from the block's left edge if the above region is available, else from its right edge (above-right only: a slice that starts in the CTB row above)
-struct PlanRecord { uint32_t w0, w1; };
-static_assert(sizeof(PlanRecord) == 8, "PlanRecord layout");
+struct PlanRecord { uint32_t w0, w1, w2, w3; };
+static_assert(sizeof(PlanRecord) == 16, "PlanRecord layout");
+// prediction classes of a block (PlanRecord::w1 bits 28..30): which sample loop reconstructs it.  PK_PURE_EDGE: modes 10 / 26 of a luma block below 32x32 (the
+// boundary filter of 8.4.4.2.6 applies); PK_POS: angular with intraPredAngle >= 0 (no tap is projected from the other arm); PK_NEG: angular, negative angle
+enum : int { PK_PLANAR = 0, PK_DC = 1, PK_PURE_EDGE = 2, PK_POS = 3, PK_NEG = 4 };
 
 struct CtbInfo {
   uint16_t slice_idx;   // index into the picture's SliceParams

@@ -18,8 +18,9 @@
 //     word per 4x4 unit, a bitmap of the units decoded so far), so gathering, substitution, smoothing and
 //     prediction never touch HBM; the finished CTB leaves LDS once with row-contiguous stores.
 //   * which blocks a CTB holds and which of their neighbouring samples are available does not depend on samples: for intra pictures with 4:0:0 / 4:2:0
-//     sampling k_recon_plan works it out for all CTBs at once in front of the wavefront, which then reads 8-byte records by scalar loads and needs neither
-//     the unit words nor the bitmap (P / B and 4:2:2 / 4:4:4 pictures keep them: the `_inter` builds).
+//     sampling k_recon_plan works it out for all CTBs at once in front of the wavefront, which then reads 16-byte records by scalar loads and needs neither
+//     the unit words nor the bitmap (P / B and 4:2:2 / 4:4:4 pictures keep them: the `_inter` builds).  A record also carries what follows from the
+//     block's geometry and mode alone: the availability mask of its first 64 reference samples, its offset in the tile and the class of its sample loop.
 //   * the kernel is VALU-issue bound (a 4x4 block uses 16 of the lanes but costs whole wave instructions), so the
 //     block path avoids quarter-rate multiplies (v_mul_i32_i24), constant-memory tables (packed immediates) and
 //     anything that waits on global memory besides the prefetched residual.
@@ -103,7 +104,19 @@ struct ReconLds {
 // Availability of a block's neighbouring samples as the plan carries it (PlanRecord, hevc_device.h), in units of 4 component samples: nl samples of
 // the left column counted from the block's top edge downward, nt of the top row counted rightward from the block's left edge (above != 0) or from its
 // right edge, the above-left sample; smooth: 8.4.4.2.3 applies to the block (size and mode).  Unused (zero) in the builds that walk the bitmap.
-struct PlanAvail { int nl, nt, above, corner, smooth; };
+// m0: the mask of the reference samples e < 64 (PlanRecord w2 / w3); toff: the block's offset in the tile; kind: PK_*; subst: a reference sample is missing.
+// w0: the record's first word - the counts stay packed in it until a block form needs them (plan_counts).
+struct PlanAvail { int nl, nt, above, corner, smooth; uint64_t m0; int toff, kind, subst; uint32_t w0; };
+// The class of a block's sample loop (PK_*, hevc_device.h) from its mode; edge: the DC / horizontal / vertical boundary filters apply (luma below 32x32).
+// A mode without an entry in the angle table counts as angle 0, as the table reads.
+__host__ __device__ __forceinline__ int block_kind(int mode, int edge)
+{
+  if (mode == 0) return PK_PLANAR;
+  if (mode == 1) return PK_DC;
+  const int mm = mode & 63;
+  if (mm > 10 && mm < 26) return PK_NEG;
+  return (edge && (mm == 10 || mm == 26 || mm < 2 || mm > 34)) ? PK_PURE_EDGE : PK_POS;
+}
 // bits [lo, lo + len) of a 64-bit word, clipped to it (lo may be negative)
 __device__ __forceinline__ uint64_t bit_run(int lo, int len)
 {
@@ -120,6 +133,13 @@ __device__ __forceinline__ uint64_t plan_mask(const PlanAvail& V, int n, int j)
 }
 // the last sample of the top row (e = 4n, handled apart by the forms whose passes end before it): available when the top run reaches it
 __device__ __forceinline__ int plan_last(const PlanAvail& V, int n) { return V.nt == (V.above ? n >> 1 : n >> 2); }
+// the counts of a record's w0 (PlanRecord, hevc_device.h)
+__device__ __forceinline__ PlanAvail plan_counts(uint32_t w0)
+{
+  PlanAvail V{};
+  V.nl = (int)((w0 >> 12) & 31u); V.nt = (int)((w0 >> 17) & 31u); V.above = (int)((w0 >> 22) & 1u); V.corner = (int)((w0 >> 23) & 1u); V.smooth = (int)((w0 >> 11) & 1u);
+  return V;
+}
 
 constexpr uint32_t UM_OUTSIDE = 16u, UM_INVALID = 32u;   // unit-word bits 4 / 5 (ReconLds::m_unit): the unit lies outside the picture / carries an impossible transform size
 
@@ -175,13 +195,15 @@ __device__ __forceinline__ uint32_t plan_load32(const uint32_t* p)
   return *p;
 #endif
 }
-__device__ __forceinline__ uint2 plan_load64(const PlanRecord* p)
+// a whole record: one 16-byte scalar load (records are 16-byte aligned)
+__device__ __forceinline__ PlanRecord plan_load128(const PlanRecord* p)
 {
 #ifndef HIPDEC_HOST_EMU
-  const uint64_t v = *(const __attribute__((address_space(4))) uint64_t*)(uintptr_t)p;
-  return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 v = *(const __attribute__((address_space(4))) u32x4*)(uintptr_t)p;
+  return PlanRecord{v.x, v.y, v.z, v.w};
 #else
-  return make_uint2(p->w0, p->w1);
+  return *p;
 #endif
 }
 
@@ -267,7 +289,8 @@ __device__ __forceinline__ void reconstruct_block(ReconLds<Pix, PLAN>& L, const 
     const int px = is_left ? -1 : e - n2 - 1, py = is_left ? n2 - 1 - e : -1;
     const int X = xb + px, Y = yb + py;
     int a = 0;
-    if constexpr (PLAN) { m[j] = plan_mask(V, n, j); a = (int)((m[j] >> lane) & 1u); }
+    // (the plan's mask covers pass 0; the second pass of a 32x32 block and the extra sample come from the counts, and only when something is missing)
+    if constexpr (PLAN) { m[j] = j == 0 ? V.m0 : (V.subst ? plan_mask(plan_counts(V.w0), n, 1) : ~0ull); a = (int)((m[j] >> lane) & 1u); }
     else if (e < N) a = (int)((L.avrow[(Y >> C.ush) + 1] >> ((X >> C.ush) + 1)) & 1u);
     if (a) {
       const Pix* src = Y < 0 ? &top[X + 1] : (X < 0 ? &L.left[Y] : &tile[(Y << lg_ctbc) + X]);
@@ -280,15 +303,14 @@ __device__ __forceinline__ void reconstruct_block(ReconLds<Pix, PLAN>& L, const 
   const int has_x = n >= 16;
   if (has_x) {
     const int X = xb + n2 - 1, Y = yb - 1;
-    if constexpr (PLAN) ax = plan_last(V, n);
+    if constexpr (PLAN) ax = V.subst ? plan_last(plan_counts(V.w0), n) : 1;
     else ax = (int)((L.avrow[(Y >> C.ush) + 1] >> ((X >> C.ush) + 1)) & 1u);
     if (ax && lane == 0) ref0[N - 1] = (uint16_t)(Y < 0 ? top[X + 1] : tile[(Y << lg_ctbc) + X]);
   }
   lds_sync();
-  // ---- substitution process, only where something is missing (wave-uniform) ----
-  const int n_av = __popcll(m[0]) + __popcll(m[1]) + (has_x ? ax : 0);
-  if (n_av != N) {
-    if (n_av == 0) {
+  // ---- substitution process, only where something is missing (wave-uniform; the plan says so) ----
+  if (PLAN ? V.subst != 0 : __popcll(m[0]) + __popcll(m[1]) + (has_x ? ax : 0) != N) {
+    if ((m[0] | m[1]) == 0 && !(has_x && ax)) {
       const uint16_t half = (uint16_t)(1 << (C.bit_depth - 1));
       for (int e = lane; e < N; e += 64) ref0[e] = half;
     } else {
@@ -333,31 +355,30 @@ __device__ __forceinline__ void reconstruct_block(ReconLds<Pix, PLAN>& L, const 
         const int c0 = ref[n2], tl = ref[0], tm = ref[n], rt = ref[N - 1], rm = ref[n2 + n];  // corner, p[-1][63], p[-1][31], p[63][-1], p[31][-1]
         int a1 = c0 + rt - 2 * rm, a2 = c0 + tl - 2 * tm;
         a1 = a1 < 0 ? -a1 : a1; a2 = a2 < 0 ? -a2 : a2;
-        strong = a1 < (1 << (C.bit_depth - 5)) && a2 < (1 << (C.bit_depth - 5));
+        // (every lane has read the same five samples: the decision is wave-uniform, and a scalar branch keeps the two filters apart)
+        strong = __builtin_amdgcn_readfirstlane((int)(a1 < (1 << (C.bit_depth - 5)) && a2 < (1 << (C.bit_depth - 5))));
       }
-      // in place: every lane filters its (at most three) samples into registers, then all write back
-      int fv[3] = {0, 0, 0};
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const int e = lane + 64 * j;
-        if (64 * j >= N) continue;      // wave-uniform
-        if (e < N) {
-          int v;
-          if (e == 0 || e == N - 1) v = ref0[e];
-          else if (strong) {
-            if (e == n2) v = ref0[n2];
-            else if (e < n2) { const int y = 63 - e; v = ((63 - y) * ref0[n2] + (y + 1) * ref0[0] + 32) >> 6; }
-            else { const int x = e - n2 - 1; v = ((63 - x) * ref0[n2] + (x + 1) * ref0[N - 1] + 32) >> 6; }
-          } else v = (ref0[e - 1] + 2 * ref0[e] + ref0[e + 1] + 2) >> 2;
-          fv[j] = v;
-        }
-      }
-      lds_sync();
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const int e = lane + 64 * j;
-        if (64 * j >= N) continue;
-        if (e < N) ref0[e] = (uint16_t)fv[j];
+      // in place: every lane filters its samples into registers, then all write back.  n >= 16 here: the first pass is full (e = lane < N - 1), a second one
+      // exists for 32x32 only (e = 64 + lane, all inside), and the two ends e = 0 and e = N - 1 stay as they are - the sample beyond the passes is always an end
+      if (strong) {
+        // 32x32: bi-linear between the corner (e = 64) and the far end of the sample's arm, by the distance from the corner (0 / 64 give the corner / the end).
+        // Only the corner and the two ends are read and the filter leaves all three as they are: written in place, one value at a time
+        const int c0 = ref0[n2];
+        const int f0 = (mul24(lane, c0) + mul24(64 - lane, (int)ref0[0]) + 32) >> 6;            // e = lane: the left arm
+        const int f1 = (mul24(64 - lane, c0) + mul24(lane, (int)ref0[N - 1]) + 32) >> 6;       // e = 64 + lane: the corner and the top arm
+        lds_sync();
+        ref0[lane] = (uint16_t)f0;
+        ref0[lane + 64] = (uint16_t)f1;
+      } else {
+        const bool two = n == 32;
+        const int e1 = lane + 64;
+        const int c = ref0[lane];
+        const int f0 = lane == 0 ? c : (ref0[lane - 1] + 2 * c + ref0[lane + 1] + 2) >> 2;
+        int f1 = 0;
+        if (two) f1 = (ref0[e1 - 1] + 2 * ref0[e1] + ref0[e1 + 1] + 2) >> 2;
+        lds_sync();
+        ref0[lane] = (uint16_t)f0;
+        if (two) ref0[e1] = (uint16_t)f1;
       }
       lds_sync();
     }
@@ -365,64 +386,91 @@ __device__ __forceinline__ void reconstruct_block(ReconLds<Pix, PLAN>& L, const 
 #define RL(k) ((int)ref[n2 - (k)])
 #define RT(k) ((int)ref[n2 + (k)])
   // ---- prediction 8.4.4.2.4 - 8.4.4.2.6, residual add, store into the tile ----
+  // n >= 16 here: a pass is 64 samples = `rows` whole rows of the block; a lane keeps its column x and moves down by `rows` per pass, so the row terms and
+  // the tile address are carried from pass to pass, not recomputed from the sample index
   const int edge = C.luma && n < 32;  // DC / horizontal / vertical boundary smoothing
+  const int kind = PLAN ? V.kind : block_kind(mode, edge);
   const int iters = nn > 64 ? nn >> 6 : 1;
-  Pix* dst0 = &tile[(yb << lg_ctbc) + xb];
-  if (mode == 0) {
+  const int rows = 64 >> log2n;
+  const int dstep = rows << lg_ctbc;
+#define PUT_SAMPLE() do { if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0); /* a PCM unit's "residual" is the sample itself */ \
+                          *dst = (Pix)v; dst += dstep; } while (0)
+  if (kind == PK_PLANAR) {
     const int tr = RT(n + 1), bl = RL(n + 1);
+    Pix* dst0 = &tile[(PLAN ? V.toff : (yb << lg_ctbc) + xb)];
     for (int it = 0; it < iters; it++) {
       const int idx = lane + 64 * it, x = idx & (n - 1), y = idx >> log2n;
-      if (idx < nn) {
-        int v = (mul24(n - 1 - x, RL(y + 1)) + mul24(x + 1, tr) + mul24(n - 1 - y, RT(x + 1)) + mul24(y + 1, bl) + n) >> (log2n + 1);
-        if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0);   // a PCM unit's "residual" is the sample itself
-        dst0[(y << lg_ctbc) + x] = (Pix)v;
-      }
+      int v = (mul24(n - 1 - x, RL(y + 1)) + mul24(x + 1, tr) + mul24(n - 1 - y, RT(x + 1)) + mul24(y + 1, bl) + n) >> (log2n + 1);
+      if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0);
+      dst0[(y << lg_ctbc) + x] = (Pix)v;
       NEXT_RES(it);
     }
-  } else if (mode == 1) {
+  } else if (kind == PK_DC) {
     int part = lane < n ? RT(lane + 1) + RL(lane + 1) : 0;
     for (int o = 16; o > 0; o >>= 1) part += __shfl_xor(part, o);      // n <= 32 lanes carry a term: lanes 0..31 hold the sum
     const int dc_val = (__builtin_amdgcn_readfirstlane(part) + n) >> (log2n + 1);
+    Pix* dst0 = &tile[(PLAN ? V.toff : (yb << lg_ctbc) + xb)];
     for (int it = 0; it < iters; it++) {
       const int idx = lane + 64 * it, x = idx & (n - 1), y = idx >> log2n;
-      if (idx < nn) {
-        int v = dc_val;
-        if (edge) {
-          if (x == 0 && y == 0) v = (RL(1) + 2 * dc_val + RT(1) + 2) >> 2;
-          else if (y == 0) v = (RT(x + 1) + 3 * dc_val + 2) >> 2;
-          else if (x == 0) v = (RL(y + 1) + 3 * dc_val + 2) >> 2;
-        }
-        if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0);   // a PCM unit's "residual" is the sample itself
-        dst0[(y << lg_ctbc) + x] = (Pix)v;
+      int v = dc_val;
+      if (edge) {
+        if (x == 0 && y == 0) v = (RL(1) + 2 * dc_val + RT(1) + 2) >> 2;
+        else if (y == 0) v = (RT(x + 1) + 3 * dc_val + 2) >> 2;
+        else if (x == 0) v = (RL(y + 1) + 3 * dc_val + 2) >> 2;
       }
+      if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0);
+      dst0[(y << lg_ctbc) + x] = (Pix)v;
       NEXT_RES(it);
     }
   } else {
+    const int x = lane & (n - 1), y0 = lane >> log2n;
+    Pix* dst = &tile[(PLAN ? V.toff : (yb << lg_ctbc) + xb) + (y0 << lg_ctbc) + x];
     // angular: with the roles of the two reference arms swapped for the horizontal modes (2..17) both families read
     // main(k) = ref[2n + s k], side(k) = ref[2n - s k]  (s = +1 vertical, -1 horizontal)
     const int vertical = mode >= 18;
     const int s = vertical ? 1 : -1;
-    const int32_t ae = k_angles.v[mode & 63];                // modes 11..25 point up-left: negative angle, taps projected with invAngle
-    const int angle = (int)(int8_t)(ae & 255), inv_angle = ae >> 16;
-    const int pure = edge && angle == 0;                     // pure vertical / horizontal (modes 26 / 10) with boundary smoothing
-    for (int it = 0; it < iters; it++) {
-      const int idx = lane + 64 * it, x = idx & (n - 1), y = idx >> log2n;
-      if (idx < nn) {
-        const int a = vertical ? x : y, b = vertical ? y : x;   // along / across the main arm
-        const int t = mul24(b + 1, angle), i_idx = t >> 5, i_fact = t & 31;
-        const int k0 = a + i_idx + 1, k1 = k0 + 1;
-        // taps with a negative index come from the other arm, projected with invAngle (24-bit multiplies: full rate)
-        const int p0 = -((mul24(k0, inv_angle) + 128) >> 8), p1 = -((mul24(k1, inv_angle) + 128) >> 8);
-        const int r0 = ref[n2 + mul24(s, k0 >= 0 ? k0 : p0)];
-        const int r1 = ref[n2 + mul24(s, k1 >= 0 ? k1 : p1)];
-        int v = (mul24(32 - i_fact, r0) + mul24(i_fact, r1) + 16) >> 5;      // i_fact == 0 gives r0
-        if (pure && a == 0) v = clip3(0, maxv, (int)ref[n2 + s] + (((int)ref[n2 - mul24(s, b + 1)] - (int)ref[n2]) >> 1));
-        if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0);   // a PCM unit's "residual" is the sample itself
-        dst0[(y << lg_ctbc) + x] = (Pix)v;
+    const uint16_t* refm = ref + n2;
+    int a = vertical ? x : y0, b1 = (vertical ? y0 : x) + 1;   // along the main arm / across it (+ 1): one is the lane's column, the other advances with the rows
+    const int da = vertical ? 0 : rows, db = vertical ? rows : 0;
+    if (kind == PK_PURE_EDGE) {
+      // pure vertical / horizontal (modes 26 / 10) with boundary smoothing: a copy of the main arm, the first row / column filtered with the other arm
+      const int c0 = refm[0], m1 = refm[s];
+      for (int it = 0; it < iters; it++, a += da, b1 += db) {
+        int v = refm[mul24(s, a + 1)];
+        if (a == 0) v = clip3(0, maxv, m1 + (((int)refm[-mul24(s, b1)] - c0) >> 1));
+        PUT_SAMPLE();
+        NEXT_RES(it);
       }
-      NEXT_RES(it);
+    } else {
+      const int32_t ae = k_angles.v[mode & 63];                // modes 11..25 point up-left: negative angle, taps projected with invAngle
+      const int angle = (int)(int8_t)(ae & 255), inv_angle = ae >> 16;
+      int t = mul24(b1, angle);                                // (across + 1) * intraPredAngle: advances by a wave-uniform step
+      const int dt = db * angle;
+      if (kind == PK_NEG) {
+        for (int it = 0; it < iters; it++, a += da, t += dt) {
+          const int i_idx = t >> 5, i_fact = t & 31;
+          const int k0 = a + i_idx + 1, k1 = k0 + 1;
+          // taps with a negative index come from the other arm, projected with invAngle (24-bit multiplies: full rate)
+          const int p0 = -((mul24(inv_angle, k0) + 128) >> 8), p1 = -((mul24(inv_angle, k1) + 128) >> 8);
+          const int r0 = refm[mul24(s, k0 >= 0 ? k0 : p0)];
+          const int r1 = refm[mul24(s, k1 >= 0 ? k1 : p1)];
+          int v = ((r0 << 5) + mul24(i_fact, r1 - r0) + 16) >> 5;      // i_fact == 0 gives r0
+          PUT_SAMPLE();
+          NEXT_RES(it);
+        }
+      } else {
+        // angle >= 0: both taps lie on the main arm (k0 >= 1)
+        for (int it = 0; it < iters; it++, a += da, t += dt) {
+          const int i_fact = t & 31, e0 = mul24(s, a + (t >> 5) + 1);
+          const int r0 = refm[e0], r1 = refm[e0 + s];
+          int v = ((r0 << 5) + mul24(i_fact, r1 - r0) + 16) >> 5;      // i_fact == 0 gives r0
+          PUT_SAMPLE();
+          NEXT_RES(it);
+        }
+      }
     }
   }
+#undef PUT_SAMPLE
 #undef RL
 #undef RT
 #undef NEXT_RES
@@ -455,12 +503,12 @@ __device__ __forceinline__ void reconstruct_block_reg(ReconLds<Pix, PLAN>& L, co
   const int X = xb + (is_left ? -1 : e - n2 - 1), Y = yb + (is_left ? n2 - 1 - e : -1);
   int a = 0;
   uint64_t m;
-  if constexpr (PLAN) { m = plan_mask(V, n, 0); a = (int)((m >> lane) & 1u); }
+  if constexpr (PLAN) { m = V.m0; a = (int)((m >> lane) & 1u); }
   else if (e < N) a = (int)((L.avrow[(Y >> C.ush) + 1] >> ((X >> C.ush) + 1)) & 1u);
   int r = 0;
   if (a) r = (int)(Y < 0 ? top[X + 1] : (X < 0 ? L.left[Y] : tile[(Y << lg_ctbc) + X]));
   if constexpr (!PLAN) m = __ballot(a);
-  if (m != (1ull << N) - 1ull) {   // (wave-uniform) substitution
+  if (PLAN ? V.subst != 0 : m != (1ull << N) - 1ull) {   // (wave-uniform) substitution
     if (m == 0) r = 1 << (C.bit_depth - 1);
     else {
       const int first = __ffsll((long long)m) - 1;
@@ -481,11 +529,12 @@ __device__ __forceinline__ void reconstruct_block_reg(ReconLds<Pix, PLAN>& L, co
   // ref[k] for a lane-varying k: __shfl(r, k); left column p[-1][k-1] = ref[2n - k], top row p[k-1][-1] = ref[2n + k]
   const int idx = lane & (nn - 1), x = idx & (n - 1), y = idx >> LG;   // (lanes >= nn compute on a copy of a block sample and store nothing)
   const int edge = C.luma;   // DC / horizontal / vertical boundary smoothing (n < 32)
+  const int kind = PLAN ? V.kind : block_kind(mode, edge);
   int v;
-  if (mode == 0) {
+  if (kind == PK_PLANAR) {
     const int tr = __shfl(r, n2 + n + 1), bl = __shfl(r, n2 - n - 1), rl = __shfl(r, n2 - (y + 1)), rt = __shfl(r, n2 + (x + 1));
     v = (mul24(n - 1 - x, rl) + mul24(x + 1, tr) + mul24(n - 1 - y, rt) + mul24(y + 1, bl) + n) >> (LG + 1);
-  } else if (mode == 1) {
+  } else if (kind == PK_DC) {
     // sum of p[-1][0 .. n-1] and p[0 .. n-1][-1]: the lanes e in [n, 2n) and (2n, 3n]
     int part = ((e >= n && e < n2) || (e > n2 && e <= n2 + n)) ? r : 0;
     for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
@@ -500,22 +549,27 @@ __device__ __forceinline__ void reconstruct_block_reg(ReconLds<Pix, PLAN>& L, co
   } else {
     const int vertical = mode >= 18;
     const int s = vertical ? 1 : -1;
-    const int32_t ae = k_angles.v[mode & 63];
-    const int angle = (int)(int8_t)(ae & 255), inv_angle = ae >> 16;
     const int a_ = vertical ? x : y, b_ = vertical ? y : x;   // along / across the main arm
-    const int t = mul24(b_ + 1, angle), i_idx = t >> 5, i_fact = t & 31;
-    const int k0 = a_ + i_idx + 1, k1 = k0 + 1;
-    const int p0 = -((mul24(k0, inv_angle) + 128) >> 8), p1 = -((mul24(k1, inv_angle) + 128) >> 8);
-    const int r0 = __shfl(r, n2 + mul24(s, k0 >= 0 ? k0 : p0));
-    const int r1 = __shfl(r, n2 + mul24(s, k1 >= 0 ? k1 : p1));
-    v = (mul24(32 - i_fact, r0) + mul24(i_fact, r1) + 16) >> 5;
-    if (edge && angle == 0) {   // pure vertical / horizontal (modes 26 / 10) with boundary smoothing (wave-uniform)
+    if (kind == PK_PURE_EDGE) {   // pure vertical / horizontal (modes 26 / 10) with boundary smoothing: the main arm copied, its first row / column filtered
+      const int r0 = __shfl(r, n2 + mul24(s, a_ + 1));
       const int c0 = __shfl(r, n2), m1 = __shfl(r, n2 + s), o1 = __shfl(r, n2 - mul24(s, b_ + 1));
-      if (a_ == 0) v = clip3(0, maxv, m1 + ((o1 - c0) >> 1));
+      v = a_ == 0 ? clip3(0, maxv, m1 + ((o1 - c0) >> 1)) : r0;
+    } else {
+      const int32_t ae = k_angles.v[mode & 63];
+      const int angle = (int)(int8_t)(ae & 255), inv_angle = ae >> 16;
+      const int t = mul24(b_ + 1, angle), i_idx = t >> 5, i_fact = t & 31;
+      const int k0 = a_ + i_idx + 1, k1 = k0 + 1;
+      int e0 = mul24(s, k0), e1 = e0 + s;
+      if (kind == PK_NEG) {   // taps with a negative index come from the other arm, projected with invAngle
+        const int p0 = -((mul24(k0, inv_angle) + 128) >> 8), p1 = -((mul24(k1, inv_angle) + 128) >> 8);
+        e0 = mul24(s, k0 >= 0 ? k0 : p0); e1 = mul24(s, k1 >= 0 ? k1 : p1);
+      }
+      const int r0 = __shfl(r, n2 + e0), r1 = __shfl(r, n2 + e1);
+      v = ((r0 << 5) + mul24(i_fact, r1 - r0) + 16) >> 5;
     }
   }
   if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0);   // a PCM unit's "residual" is the sample itself
-  if (lane < nn) tile[((yb + y) << lg_ctbc) + xb + x] = (Pix)v;
+  if (lane < nn) tile[(PLAN ? V.toff : (yb << lg_ctbc) + xb) + (y << lg_ctbc) + x] = (Pix)v;
   // ---- the block's units are decoded now ----
   if constexpr (!PLAN) {
     const int k = n >> C.ush;    // units per side (>= 1)
@@ -553,7 +607,7 @@ __device__ __forceinline__ void reconstruct_chroma_pair(ReconLds<Pix, PLAN>& L, 
   // ---- reference samples: e = l + 32 j for J = 1 (2 for 16x16) passes; blocks from 8x8 up have the extra sample e = 4n ----
   const int J = n == 16 ? 2 : 1;
   uint64_t m0 = 0;        // availability over e < 64 (identical in both halves: taken from the Cb lanes)
-  if constexpr (PLAN) m0 = plan_mask(V, n, 0) & (J == 2 ? ~0ull : 0xffffffffull);
+  if constexpr (PLAN) m0 = V.m0;   // (the plan keeps the positions the passes cover: e < 32 J)
   int av[2] = {0, 0};
 #pragma unroll
   for (int j = 0; j < 2; j++) {
@@ -576,14 +630,13 @@ __device__ __forceinline__ void reconstruct_chroma_pair(ReconLds<Pix, PLAN>& L, 
   const int has_x = n >= 8;
   if (has_x) {
     const int X = xb + n2 - 1, Y = yb - 1;
-    if constexpr (PLAN) ax = plan_last(V, n);
+    if constexpr (PLAN) ax = V.subst ? plan_last(plan_counts(V.w0), n) : 1;
     else ax = (int)((L.avrow[(Y >> ushy) + 1] >> ((X >> 1) + 1)) & 1u);
     if (ax && l == 0) ref0[N - 1] = (uint16_t)(Y < 0 ? top[X + 1] : tile[(Y << lg_ctbc) + X]);
   }
   lds_sync();
-  const int n_av = __popcll(m0) + (has_x ? ax : 0);
-  if (n_av != N) {
-    if (n_av == 0) {
+  if (PLAN ? V.subst != 0 : __popcll(m0) + (has_x ? ax : 0) != N) {
+    if (m0 == 0 && !(has_x && ax)) {
       const uint16_t half = (uint16_t)(1 << (C.bit_depth - 1));
       for (int e = l; e < N; e += 32) ref0[e] = half;
     } else {
@@ -614,52 +667,72 @@ __device__ __forceinline__ void reconstruct_chroma_pair(ReconLds<Pix, PLAN>& L, 
   const uint16_t* ref = ref0;
 #define RL(k) ((int)ref[n2 - (k)])
 #define RT(k) ((int)ref[n2 + (k)])
-  Pix* dst0 = &tile[(yb << lg_ctbc) + xb];
-  if (mode == 0) {
-    const int tr = RT(n + 1), bl = RL(n + 1);
-    for (int it = 0; it < iters; it++) {
-      const int idx = l + 32 * it, x = idx & (n - 1), y = idx >> log2n;
-      if (idx < nn) {
-        int v = (mul24(n - 1 - x, RL(y + 1)) + mul24(x + 1, tr) + mul24(n - 1 - y, RT(x + 1)) + mul24(y + 1, bl) + n) >> (log2n + 1);
-        if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0);   // a PCM unit's "residual" is the sample itself
-        dst0[(y << lg_ctbc) + x] = (Pix)v;
-      }
+  // a pass is 32 samples per half = `rows` whole rows of the block (the plan's builds: n >= 8, every pass is full; a 4x4 block of the other builds is half
+  // a pass); a lane keeps its column and moves down by `rows` per pass: row terms and tile address are carried
+  const int kind = PLAN ? V.kind : block_kind(mode, 0);
+  const int rows = 32 >> log2n, x = l & (n - 1), y0 = l >> log2n;
+  const bool whole = PLAN || l < nn;
+  Pix* dst = &tile[(PLAN ? V.toff : (yb << lg_ctbc) + xb) + (y0 << lg_ctbc) + x];
+  const int dstep = rows << lg_ctbc;
+#define PUT_SAMPLE() do { if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0); /* a PCM unit's "residual" is the sample itself */ \
+                          if (whole) *dst = (Pix)v; \
+                          dst += dstep; } while (0)
+  if (kind == PK_PLANAR) {
+    const int tr = RT(n + 1), bl = RL(n + 1), rtx = RT(x + 1);
+    const int fx = mul24(x + 1, tr) + n, wx = n - 1 - x;   // the column's terms
+    for (int it = 0, y = y0; it < iters; it++, y += rows) {
+      int v = (mul24(wx, whole ? RL(y + 1) : 0) + fx + mul24(n - 1 - y, rtx) + mul24(y + 1, bl)) >> (log2n + 1);
+      PUT_SAMPLE();
       NEXT_RES(it);
     }
-  } else if (mode == 1) {
+  } else if (kind == PK_DC) {
     int part = l < n ? RT(l + 1) + RL(l + 1) : 0;
     for (int o = 16; o > 0; o >>= 1) part += __shfl_xor(part, o);      // every lane of a half ends up with its half's sum
     const int dc_val = (part + n) >> (log2n + 1);
     for (int it = 0; it < iters; it++) {
-      const int idx = l + 32 * it, x = idx & (n - 1), y = idx >> log2n;
-      if (idx < nn) {
-        int v = dc_val;
-        if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0);   // a PCM unit's "residual" is the sample itself
-        dst0[(y << lg_ctbc) + x] = (Pix)v;
-      }
+      int v = dc_val;
+      PUT_SAMPLE();
       NEXT_RES(it);
     }
   } else {
     const int vertical = mode >= 18;
     const int s = vertical ? 1 : -1;
+    const uint16_t* refm = ref + n2;
     const int32_t ae = k_angles.v[mode & 63];
     const int angle = (int)(int8_t)(ae & 255), inv_angle = ae >> 16;
-    for (int it = 0; it < iters; it++) {
-      const int idx = l + 32 * it, x = idx & (n - 1), y = idx >> log2n;
-      if (idx < nn) {
-        const int a = vertical ? x : y, b = vertical ? y : x;
-        const int t = mul24(b + 1, angle), i_idx = t >> 5, i_fact = t & 31;
+    int a = vertical ? x : y0;                                 // along the main arm
+    const int b1 = (vertical ? y0 : x) + 1;                    // across it (+ 1)
+    const int da = vertical ? 0 : rows, dt = (vertical ? rows : 0) * angle;
+    int t = mul24(b1, angle);
+    if (kind == PK_NEG) {
+      for (int it = 0; it < iters; it++, a += da, t += dt) {
+        const int i_idx = t >> 5, i_fact = t & 31;
         const int k0 = a + i_idx + 1, k1 = k0 + 1;
-        const int p0 = -((mul24(k0, inv_angle) + 128) >> 8), p1 = -((mul24(k1, inv_angle) + 128) >> 8);
-        const int r0 = ref[n2 + mul24(s, k0 >= 0 ? k0 : p0)];
-        const int r1 = ref[n2 + mul24(s, k1 >= 0 ? k1 : p1)];
-        int v = (mul24(32 - i_fact, r0) + mul24(i_fact, r1) + 16) >> 5;
-        if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0);   // a PCM unit's "residual" is the sample itself
-        dst0[(y << lg_ctbc) + x] = (Pix)v;
+        const int p0 = -((mul24(inv_angle, k0) + 128) >> 8), p1 = -((mul24(inv_angle, k1) + 128) >> 8);
+        int v = 0;
+        if (whole) {
+          const int r0 = refm[mul24(s, k0 >= 0 ? k0 : p0)];
+          const int r1 = refm[mul24(s, k1 >= 0 ? k1 : p1)];
+          v = ((r0 << 5) + mul24(i_fact, r1 - r0) + 16) >> 5;
+        }
+        PUT_SAMPLE();
+        NEXT_RES(it);
       }
-      NEXT_RES(it);
+    } else {
+      // angle >= 0: both taps lie on the main arm (k0 >= 1)
+      for (int it = 0; it < iters; it++, a += da, t += dt) {
+        const int i_fact = t & 31, e0 = mul24(s, a + (t >> 5) + 1);
+        int v = 0;
+        if (whole) {
+          const int r0 = refm[e0], r1 = refm[e0 + s];
+          v = ((r0 << 5) + mul24(i_fact, r1 - r0) + 16) >> 5;
+        }
+        PUT_SAMPLE();
+        NEXT_RES(it);
+      }
     }
   }
+#undef PUT_SAMPLE
 #undef RL
 #undef RT
 #undef NEXT_RES
@@ -688,12 +761,12 @@ __device__ __forceinline__ void reconstruct_chroma_pair_reg4(ReconLds<Pix, PLAN>
   const int X = xb + (is_left ? -1 : e - n2 - 1), Y = yb + (is_left ? n2 - 1 - e : -1);
   int a = 0;
   uint32_t m;
-  if constexpr (PLAN) { m = (uint32_t)plan_mask(V, n, 0); a = (int)((m >> l) & 1u); }
+  if constexpr (PLAN) { m = (uint32_t)V.m0; a = (int)((m >> l) & 1u); }
   else if (e < N) a = (int)((L.avrow[(Y >> ushy) + 1] >> ((X >> 1) + 1)) & 1u);
   int r = 0;
   if (a) r = (int)(Y < 0 ? top[X + 1] : (X < 0 ? left[Y] : tile[(Y << lg_ctbc) + X]));
   if constexpr (!PLAN) m = (uint32_t)__ballot(a);   // availability is the same in both halves: the Cb lanes' bits
-  if (m != (1u << N) - 1u) {
+  if (PLAN ? V.subst != 0 : m != (1u << N) - 1u) {
     if (m == 0) r = 1 << (C.bit_depth - 1);
     else {
       const int first = __ffsll((long long)m) - 1;
@@ -703,11 +776,12 @@ __device__ __forceinline__ void reconstruct_chroma_pair_reg4(ReconLds<Pix, PLAN>
     }
   }
   const int idx = l & (nn - 1), x = idx & (n - 1), y = idx >> LG;
+  const int kind = PLAN ? V.kind : block_kind(mode, 0);
   int v;
-  if (mode == 0) {
+  if (kind == PK_PLANAR) {
     const int tr = __shfl(r, hb + n2 + n + 1), bl = __shfl(r, hb + n2 - n - 1), rl = __shfl(r, hb + n2 - (y + 1)), rt = __shfl(r, hb + n2 + (x + 1));
     v = (mul24(n - 1 - x, rl) + mul24(x + 1, tr) + mul24(n - 1 - y, rt) + mul24(y + 1, bl) + n) >> (LG + 1);
-  } else if (mode == 1) {
+  } else if (kind == PK_DC) {
     int part = ((e >= n && e < n2) || (e > n2 && e <= n2 + n)) ? r : 0;
     for (int o = 16; o > 0; o >>= 1) part += __shfl_xor(part, o);      // every lane of a half ends up with its half's sum
     v = (part + n) >> (LG + 1);
@@ -719,13 +793,16 @@ __device__ __forceinline__ void reconstruct_chroma_pair_reg4(ReconLds<Pix, PLAN>
     const int a_ = vertical ? x : y, b_ = vertical ? y : x;
     const int t = mul24(b_ + 1, angle), i_idx = t >> 5, i_fact = t & 31;
     const int k0 = a_ + i_idx + 1, k1 = k0 + 1;
-    const int p0 = -((mul24(k0, inv_angle) + 128) >> 8), p1 = -((mul24(k1, inv_angle) + 128) >> 8);
-    const int r0 = __shfl(r, hb + n2 + mul24(s, k0 >= 0 ? k0 : p0));
-    const int r1 = __shfl(r, hb + n2 + mul24(s, k1 >= 0 ? k1 : p1));
-    v = (mul24(32 - i_fact, r0) + mul24(i_fact, r1) + 16) >> 5;
+    int e0 = mul24(s, k0), e1 = e0 + s;
+    if (kind == PK_NEG) {   // taps with a negative index come from the other arm, projected with invAngle
+      const int p0 = -((mul24(k0, inv_angle) + 128) >> 8), p1 = -((mul24(k1, inv_angle) + 128) >> 8);
+      e0 = mul24(s, k0 >= 0 ? k0 : p0); e1 = mul24(s, k1 >= 0 ? k1 : p1);
+    }
+    const int r0 = __shfl(r, hb + n2 + e0), r1 = __shfl(r, hb + n2 + e1);
+    v = ((r0 << 5) + mul24(i_fact, r1 - r0) + 16) >> 5;
   }
   if (cbf) v = (cbf & UF_PCM) ? rp0 : clip3(0, maxv, v + rp0);   // a PCM unit's "residual" is the sample itself
-  if (l < nn) tile[((yb + y) << lg_ctbc) + xb + x] = (Pix)v;
+  if (l < nn) tile[(PLAN ? V.toff : (yb << lg_ctbc) + xb) + (y << lg_ctbc) + x] = (Pix)v;
   if constexpr (!PLAN) {
     const int k = n >> 1, rows = n >> ushy;    // units per row of the block, unit rows (4:2:2: a 4x4 block is two units wide and one tall)
     if (lane < (rows > 0 ? rows : 1)) lds_or(&L.avrow[(yb >> ushy) + 1 + lane], ((1ull << k) - 1ull) << ((xb >> 1) + 1));
@@ -911,14 +988,17 @@ __device__ __forceinline__ void recon_rows(const ReconArgs& A, const ReconWave& 
       const PlanRecord* recs = (const PlanRecord*)(A.arena + P.off_plan) + (size_t)ctb_rs * (size_t)(units + (units >> 2)) + (DUAL ? units : 0);
       const uint32_t counts = plan_load32((const uint32_t*)(A.arena + P.off_plan_cnt) + ctb_rs);
       const int count = (int)(DUAL ? counts >> 16 : counts & 0xffffu);
-      uint2 nx = plan_load64(recs);    // (slot 0 always exists)
+      PlanRecord nx = plan_load128(recs);    // (slot 0 always exists)
       for (int i = 0; i < count; i++) {
-        const uint32_t w0 = nx.x, w1 = nx.y;
-        nx = plan_load64(recs + (i + 1 < count ? i + 1 : i));
+        const uint32_t w0 = nx.w0, w1 = nx.w1;
+        PlanAvail V;
+        V.m0 = (uint64_t)nx.w2 | ((uint64_t)nx.w3 << 32);
+        nx = plan_load128(recs + (i + 1 < count ? i + 1 : i));
         const int xb = (int)(w0 & 15u) << 2, yb = (int)((w0 >> 4) & 15u) << 2, lg = (int)((w0 >> 8) & 7u), z = (int)(w0 >> 24);
         const int mode = (int)(w1 & 255u), fl = (int)((w1 >> 8) & 255u);
-        PlanAvail V;
-        V.nl = (int)((w0 >> 12) & 31u); V.nt = (int)((w0 >> 17) & 31u); V.above = (int)((w0 >> 22) & 1u); V.corner = (int)((w0 >> 23) & 1u); V.smooth = (int)((w0 >> 11) & 1u);
+        V.toff = (int)((w1 >> 16) & 0xfffu); V.kind = (int)((w1 >> 28) & 7u); V.subst = (int)(w1 >> 31);
+        V.nl = V.nt = V.above = V.corner = 0; V.w0 = w0;   // (the counts stay in w0: only blocks above 8x8 read them, and only when a reference sample is missing)
+        V.smooth = (int)((w0 >> 11) & 1u);
         if (!DUAL) {
           if (lg == 2) reconstruct_block_reg<Pix, 2, PLAN>(L, C, top, xb, yb, mode, fl & (cbf_bit | UF_PCM), res_base + z * 16, V);
           else if (lg == 3) reconstruct_block_reg<Pix, 3, PLAN>(L, C, top, xb, yb, mode, fl & (cbf_bit | UF_PCM), res_base + z * 16, V);
@@ -1050,8 +1130,9 @@ namespace {
 // luma units for the luma list, 8x8 luma areas for the chroma list); rem_x / rem_y: grid units from the CTB's origin to the right / bottom picture edge.
 // z indices of the neighbouring squares by arithmetic on the interleaved form: x lives in the even bits, y in the odd ones; a subtraction borrows across
 // the other coordinate's (masked-off) bits, an addition carries across them once they are filled with ones.
+// lg_ctbc: log2 of the CTB size in component samples; pair: a record of the chroma pair's list (no boundary filters; lane passes of 32 scan positions).
 __device__ __forceinline__ PlanRecord plan_record(int gx, int gy, int gk, int gside, uint32_t gz, int rem_x, int rem_y, uint32_t avail, int lg, uint32_t z,
-                                                  uint32_t mode, uint32_t flags, int smooth)
+                                                  uint32_t mode, uint32_t flags, int smooth, int lg_ctbc, bool pair)
 {
   constexpr uint32_t MX = 0x55555555u, MY = 0xaaaaaaaau;
   const uint32_t zx = gz & MX, zy = gz & MY, dx = (uint32_t)(gk * gk), dy = 2u * dx;   // gk in interleaved form, as an x / a y step
@@ -1074,7 +1155,16 @@ __device__ __forceinline__ PlanRecord plan_record(int gx, int gy, int gk, int gs
   PlanRecord r;
   r.w0 = (uint32_t)gx | ((uint32_t)gy << 4) | ((uint32_t)lg << 8) | ((uint32_t)(smooth ? 1 : 0) << 11) | ((uint32_t)nl << 12) | ((uint32_t)nt << 17) |
          ((uint32_t)(above ? 1 : 0) << 22) | ((uint32_t)(corner ? 1 : 0) << 23) | (z << 24);
-  r.w1 = mode | (flags << 8);
+  // what the wavefront would derive from the above, block by block on its scalar pipe: the mask of the first lane pass(es), the tile offset, the loop class
+  PlanAvail V;
+  V.nl = nl; V.nt = nt; V.above = above ? 1 : 0; V.corner = corner ? 1 : 0; V.smooth = 0;
+  const int n = 1 << lg;
+  uint64_t m0 = plan_mask(V, n, 0);
+  if (pair && n < 16) m0 &= 0xffffffffull;
+  const uint32_t subst = (nl == 2 * gk && nt == 2 * gk && above && corner) ? 0u : 1u;
+  const uint32_t toff = ((uint32_t)gy << (lg_ctbc + 2)) + ((uint32_t)gx << 2);
+  r.w1 = mode | (flags << 8) | (toff << 16) | ((uint32_t)block_kind((int)mode, !pair && n < 32) << 28) | (subst << 31);
+  r.w2 = (uint32_t)m0; r.w3 = (uint32_t)(m0 >> 32);
   return r;
 }
 }  // namespace
@@ -1150,12 +1240,12 @@ __global__ __launch_bounds__(64) void k_recon_plan(ReconArgs A)
         constexpr uint64_t k8 = smooth_mode_mask(8), k16 = smooth_mode_mask(16), k32 = smooth_mode_mask(32);
         const uint32_t m = (md >> (8 * k)) & 63u;
         const uint64_t filtered_modes = tb == 3u ? k8 : (tb == 4u ? k16 : k32);
-        recs[slot_l++] = plan_record(ux, uy, n, side, z, rem_x, rem_y, avail, (int)tb, z, m, f, tb > 2u && ((filtered_modes >> m) & 1ull));
+        recs[slot_l++] = plan_record(ux, uy, n, side, z, rem_x, rem_y, avail, (int)tb, z, m, f, tb > 2u && ((filtered_modes >> m) & 1ull), log2_ctb, false);
       }
       if ((k == 0 || k == 3) && ((emit_c >> k) & 1u)) {
         const int quad = tb == 2u;
         recs[units + slot_c++] = plan_record(ux >> 1, uy >> 1, quad ? 1 : n >> 1, side >> 1, z >> 2, (rem_x + 1) >> 1, (rem_y + 1) >> 1, avail,
-                                             quad ? 2 : (int)tb - 1, quad ? (z & ~3u) : z, (mc >> (8 * k)) & 255u, f, 0);
+                                             quad ? 2 : (int)tb - 1, quad ? (z & ~3u) : z, (mc >> (8 * k)) & 255u, f, 0, log2_ctb - 1, true);
       }
     }
     if (lane == 0) { plan_cnt[2 * ctb_rs] = (uint16_t)n_l; plan_cnt[2 * ctb_rs + 1] = (uint16_t)n_c; }
